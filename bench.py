@@ -8,16 +8,19 @@ plus one aerial tile [1,3,224,224] through DBVanilla2D (ResNet18, GeM, MLP) -- S
 A STEP embeds `--batch` pairs per GPU, then all-gathers the query and database descriptors over
 RCCL (the eval path's exchange step); weak scaling: per-GPU work is fixed as N grows.
 Steps are replayed hipGraphs; by default TWO steps are in flight (step i on stream i % 2 with its own input batch, workspaces and
-outputs: one step's latency-bound tail runs beside the next step's first layers; --inflight 1 for one at a time, and the line
+outputs: one step's latency-bound tail runs beside the next step's first layers; --inflight 1 for one at a time; the --full line
 carries that figure too as config.ms_per_step_one_in_flight).  Every step embeds its whole batch; the timed region is K steps
 between barrier + synchronize pairs.
 Inputs are synthetic (seeded N(0,1) images, U(0,1) voxel stand-ins) and resident in HBM before
 the timed region; weights are seeded random init of the reference architecture.
 
-One JSON line on rank 0 (driver contract) with `roofline` (dominant kernel = the implicit-GEMM
-conv, timed live with events on the launch stream) and `cpu_baseline` (the CPU oracle = a port of
-the reference forward, on the host cores, bounded sample).  Also reports kNN queries/s at
-100k x 256 (the second half of BASELINE's metric string) under "knn".
+One JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times exactly --steps steps
+(one window), writes the last step's outputs if --dump-outputs is given, and prints the line.  --full
+adds everything else, as one run: the median of five windows, `roofline` (dominant kernel = the
+implicit-GEMM conv, timed live with events on the launch stream), `cpu_baseline` (the CPU oracle = a
+port of the reference forward, on the host cores, bounded sample), kNN queries/s at 100k x 256 (the
+second half of BASELINE's metric string) under "knn", the training, voxel-branch, NetVLAD and
+tight-mode legs, and the replay-equals-eager check.
 """
 import argparse
 import json
@@ -44,9 +47,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (roofline, kNN, training, voxel-branch, NetVLAD and "
+                         "tight-mode legs, CPU baselines, replay-equals-eager, one-in-flight time); off: only the headline step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the query and database embeddings of the last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--windows", type=int, default=None,
                     help="timed windows of --steps steps each (every one bracketed by barrier + synchronize); the line reports the "
-                         "MEDIAN window, config.windows carries all of them")
+                         "MEDIAN window, config.windows carries all of them (default: 1, with --full 5)")
     ap.add_argument("--batch", type=int, default=64, help="pairs per GPU per step (SURVEY.md 8(d): b in {16, 32, 64} per GPU)")
     ap.add_argument("--prec", type=int, default=0, choices=[0, 2, 3, 4],
                     help="MFMA precision of the convs: 0 (default) = the library default, Options().mfma_precision (4 = fp16 x fp16, "
@@ -62,8 +70,8 @@ def parse():
     ap.add_argument("--inflight", type=int, default=0, choices=[0, 1, 2, 3, 4],
                     help="0 = auto (2 on resident inputs, 1 with --h2d: under the upload the overlap buys nothing).  N > 1: N steps in flight -- step i replays its own captured graph on stream i %% N (own input batch, "
                          "workspaces and outputs), so the latency-bound tail of one step (vector programs, the last small launches) "
-                         "runs beside the next step's stem and layer 1; every step still embeds its whole batch.  The line also "
-                         "carries the same graph's time with one step in flight (config.ms_per_step_one_in_flight).  Applies to the "
+                         "runs beside the next step's stem and layer 1; every step still embeds its whole batch.  The --full line "
+                         "also carries the same graph's time with one step in flight (config.ms_per_step_one_in_flight).  Applies to the "
                          "graph-replayed step on resident inputs (not --h2d / --vox / --graph 0)")
     ap.add_argument("--qsplit", type=int, default=0, choices=[0, 1, 2, 4],
                     help="N > 1: the query batch is embedded as N equal sub-batches on N HIP streams (same work per step; "
@@ -92,7 +100,7 @@ def parse():
                          "stand-ins; prints its own line, with the stand-in step of the same run beside it")
     ap.add_argument("--vox-points", type=int, default=8000)
     ap.add_argument("--vox-leg", type=int, default=1, choices=[0, 1],
-                    help="1 (default): the line also carries `vox` = the same step end to end from coords / features (the sparse-voxel "
+                    help="1 (default): the --full line also carries `vox` = the same step end to end from coords / features (the sparse-voxel "
                          "branch inside MM.forward_q), four steps in flight, same models")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--train-steps", type=int, default=10,
@@ -113,7 +121,26 @@ def parse():
     ap.add_argument("--verbose", action="store_true", help="per-conv-launch table on stderr")
     ap.add_argument("--cpu-pairs", type=int, default=256, help="pairs in the bounded CPU sample (about 10 s of host work)")
     ap.add_argument("--cpu-knn-queries", type=int, default=512, help="queries of the bounded CPU kNN sample")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy; above 64 MB in all, the same seeded sample of rows of each."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    total = sum(v.numel() * 4 for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, v.shape[0] * DUMP_LIMIT_BYTES // total)
+            v = v[torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(path, name + ".npy"), v.numpy())
 
 
 def main():
@@ -407,8 +434,11 @@ def main():
     window_s = [timed_window() for _ in range(max(1, args.windows))]
     dt = sorted(window_s)[len(window_s) // 2]
     pairs_per_s = world * b * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # eq / ed hold what the last step() returned (a captured graph's static outputs): copied out before any later replay
+        dump_outputs(args.dump_outputs, {"query_embedding": eq, "database_embedding": ed})
     ms_one_in_flight = None
-    if flight is not None:       # the same graph with ONE step in flight (each replay waits for the previous one), same run
+    if flight is not None and args.full:       # the same graph with ONE step in flight (each replay waits for the previous one), same run
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         with torch.cuda.stream(cap_stream):
@@ -419,7 +449,7 @@ def main():
 
     # ---- the same step in the opt-in tight mode (F16W2), same run (the headline is the library default since round 5)
     library_default = None
-    if args.prec == 4 and flight is not None and not args.vox and not c2 and not args.u8 and args.default_prec_leg:
+    if args.full and args.prec == 4 and flight is not None and not args.vox and not c2 and not args.u8 and args.default_prec_leg:
         try:
             library_default = default_precision_leg(args, dev, [f_[3] for f_ in flight], world, b, pair, MM, DBVanilla2D, Options)
         except Exception as e:
@@ -429,7 +459,7 @@ def main():
     # ---- --vox: the same step with the voxel branch's outputs as dense stand-ins (what the headline line runs), same run, same
     # models, captured and timed the same way: what the branch adds
     vox_cmp = None
-    if args.vox and args.pair and ring is None:
+    if args.full and args.vox and args.pair and ring is None:
         with torch.cuda.stream(cap_stream):
             for _ in range(2):
                 embed(dq=data_standins)
@@ -456,7 +486,7 @@ def main():
     # ---- outside the timed region: the replayed hipGraph computes what the eager path computes (bit for bit: the same
     # kernels on the same buffers; None when the step was not a graph replay of resident inputs)
     replay_equals_eager = None
-    if graph is not None and ring is None:
+    if args.full and graph is not None and ring is None:
         replay_equals_eager = True
         for st_, g_, (oq_, od_), (dk, tk) in (flight if flight is not None else [(cap_stream, graph, (eq, ed), (data, tiles))]):
             with torch.cuda.stream(st_):
@@ -469,11 +499,11 @@ def main():
             replay_equals_eager = replay_equals_eager and bool(torch.equal(rq, xq) and torch.equal(rd, xd) and torch.isfinite(rq).all()
                                                                and float(rq.abs().sum()) > 0)
 
-    roofline = conv_roofline(args, embed, ops, rank, c2)
+    roofline = conv_roofline(args, embed, ops, rank, c2) if args.full else None
 
-    # ---- the step END TO END from coords (the sparse-voxel branch inside MM.forward_q) in the default line, same models
+    # ---- the step END TO END from coords (the sparse-voxel branch inside MM.forward_q) in the --full line, same models
     vox = None
-    if args.vox_leg and not args.vox and not c2 and not args.u8 and ring is None and graph is not None and args.pair:
+    if args.full and args.vox_leg and not args.vox and not c2 and not args.u8 and ring is None and graph is not None and args.pair:
         try:
             vox = vox_leg(args, embed, modelq, data_standins, b, qw, opt, dev, rank, world)
         except Exception as e:
@@ -515,8 +545,9 @@ def main():
                                   ("uint8 camera tiles" if args.u8 else "fp32 normalised panorama"),
                    "gmac_per_pair": round((bench_inputs.resnet_gmacs("resnet18", 3, 224, qw) + bench_inputs.resnet_gmacs(opt.dbimage_fe, 3, 224, 224)
                                            + 14 * (qw // 16) * 256 * 256 * 9 * 2) / 1e9, 3)},
-        "roofline": roofline,
     }
+    if args.full:
+        out["roofline"] = roofline
     if rccl is not None:
         out["rccl"] = rccl
     if vox_cmp is not None:
@@ -525,11 +556,11 @@ def main():
         out["vox"] = vox
 
     # ---- kNN queries/s at DB = 100k x 256 (query shard per rank, database replicated)
-    if not args.no_knn and not c2 and not args.vox:
+    if args.full and not args.no_knn and not c2 and not args.vox:
         out["knn"] = knn_measurement(args, opt, dev, rank, world, parallel, retrieval)
 
     # ---- secondary metric: training step = fwd + bwd + Adam, 1 query + 11 tiles per "query"
-    if args.train_steps > 0 and not c2 and not args.vox:
+    if args.full and args.train_steps > 0 and not c2 and not args.vox:
         try:
             out["train"] = train_measurement(args, opt, dev, rank, world, parallel, side=side)
         except Exception as e:      # never lose the headline line over the secondary metric
@@ -570,19 +601,19 @@ def main():
                     print(f"bench.py: training measurement with the voxel branch failed: {e!r}", file=sys.stderr)
 
     # ---- NetVLAD.forward on the matrix pipe (the other aggregator of SURVEY.md 8 row a9), this rank's clock
-    if rank == 0 and not c2 and not args.vox and not args.no_netvlad:
+    if args.full and rank == 0 and not c2 and not args.vox and not args.no_netvlad:
         try:
             out["netvlad"] = netvlad_leg(dev)
         except Exception as e:
             print(f"bench.py: NetVLAD leg failed: {e!r}", file=sys.stderr)
 
     # ---- CPU baseline: the oracle (a port of the reference forward) on the host cores, rank 0, N=1
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_measurement(args, opt, modelq, modeldb, data, tiles, b)
 
     # ---- "reference-dependency CPU" rows: torchdiffeq.odeint and faiss.IndexFlatL2 on
     # the same tensors IF the box's own site-packages have them (reference call sites network_mm/ffns.py:84-85, test.py:27-32)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["reference_deps"] = reference_dependency_rows(opt, args)
 
     if rank == 0:

@@ -35,7 +35,8 @@ def test_bench_gpus2_self_launch_on_one_gpu_over_gloo(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(AGP_DIST_BACKEND="gloo", AGP_LOCAL_DEVICE="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--no-knn", "--train-steps", "0", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-knn", "--train-steps", "0", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -58,3 +58,27 @@ def test_bench_parent_of_a_multi_rank_run_never_initialises_the_gpu():
         assert p.returncode not in (0, 2), (p.returncode, p.stderr[-800:])
         assert "needs a GPU" in p.stderr
         assert not any(ln.startswith("{") for ln in p.stdout.splitlines())
+
+
+def test_bench_plain_run_is_one_window_and_dumps_float32_within_the_limit(tmp_path, monkeypatch):
+    """A plain line times exactly --steps steps (one window; --full keeps five); --dump-outputs writes float32 .npy files and, above
+    the limit, the same seeded rows of every array."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert (a.steps, a.windows, a.full, a.dump_outputs) == (7, 1, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    assert bench.parse().windows == 5
+    q, d = torch.randn(64, 8).half(), torch.randn(64, 8)
+    bench.dump_outputs(str(tmp_path / "all"), {"q": q, "d": d})
+    got = np.load(tmp_path / "all" / "q.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, q.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 * 8 * 4)          # room for half of the rows
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), {"q": d, "d": d})
+    s = [np.load(tmp_path / run / f"{n}.npy") for run in ("s1", "s2") for n in ("q", "d")]
+    assert s[0].shape == (32, 8) and all(np.array_equal(s[0], x) for x in s[1:])
+    assert all(any(np.array_equal(r, x) for x in d.numpy()) for r in s[0])

@@ -12,4 +12,4 @@ for r in list(csv.DictReader(open(f)))[:9]:
     print(f"{r['Name'][:80]:80s} {int(r['Calls']):5d} avg {float(r['AverageNs'])/1e3:8.1f} us  {float(r['Percentage']):5.1f}%")
 PY
 rm -rf $R/gpurun_out/imgprof
-python3 bench.py --no-cpu-baseline --no-knn --train-steps 0 --default-prec-leg 0 --steps 40 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ms_per_step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'family', d['roofline']['conv_family']['frac'])"
+python3 bench.py --full --no-cpu-baseline --no-knn --train-steps 0 --default-prec-leg 0 --steps 40 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ms_per_step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'family', d['roofline']['conv_family']['frac'])"

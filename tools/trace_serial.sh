@@ -2,7 +2,7 @@
 # rocprofv3 kernel trace + stats of the serial (one stream, no graph) bench pass -> gpurun_out/<tag>_trace ; prints the per-kernel table
 tag=${1:-r06}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-ARGS="--no-cpu-baseline --no-knn --no-netvlad --vox-leg 0 --windows 1 --train-steps 0 --graph 0 --streams 1 --qsplit 1 --steps 40 --warmup 2"
+ARGS="--full --no-cpu-baseline --no-knn --no-netvlad --vox-leg 0 --windows 1 --train-steps 0 --graph 0 --streams 1 --qsplit 1 --steps 40 --warmup 2"
 mkdir -p $R/gpurun_out/${tag}_trace
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_trace -o t -- python3 $R/bench.py $ARGS > /dev/null 2>&1

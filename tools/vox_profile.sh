@@ -8,4 +8,4 @@ rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/$tag -o t -- pytho
 cd $R
 python3 tools/vox_timeline.py $(find gpurun_out/$tag -name "*kernel_trace.csv" | head -1) | tee gpurun_out/$tag/timeline.txt
 find $R/gpurun_out/$tag -name "*kernel_trace.csv" -size +40M -delete
-python3 bench.py --vox --no-cpu-baseline --no-knn --train-steps 0 --default-prec-leg 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('vox ms_per_step', d['ms_per_step'], 'one in flight', d['config'].get('ms_per_step_one_in_flight'))"
+python3 bench.py --full --vox --no-cpu-baseline --no-knn --train-steps 0 --default-prec-leg 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('vox ms_per_step', d['ms_per_step'], 'one in flight', d['config'].get('ms_per_step_one_in_flight'))"
