@@ -76,6 +76,15 @@ class DBVanilla2D(nn.Module):
         # (train_graph.bn_frozen) -- F.batch_norm(training=False) under autograd.
         train = self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
                                   and any(p.requires_grad for p in self.parameters()))
+        if not train:
+            return self._forward_db(data_dict, train, trunk_maps, out_rows, defer_head)
+        from .. import train_graph
+        # the opt-in fast modes (train_graph.py) for THIS model's forward only, as in MM.forward_q
+        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1):
+            return self._forward_db(data_dict, train, trunk_maps, out_rows, defer_head)
+
+    def _forward_db(self, data_dict, train, trunk_maps, out_rows, defer_head):
+        opt = self.opt
         db_map = data_dict['db_map']
         u8 = db_map.dtype == torch.uint8
         if u8:
@@ -96,10 +105,6 @@ class DBVanilla2D(nn.Module):
             raise NotImplementedError
         assert c == 3
         prec = 3 if train else opt.mfma_precision
-        if train:
-            from .. import train_graph
-            train_graph.FWD_F16 = opt.train_precision == 16      # the opt-in fast mode: one-product forward convs (train_graph.py)
-            train_graph.DGRAD_HI_ONLY = opt.train_dgrad_products == 1      # ... and one-product data gradients
         if (not train and torch.is_grad_enabled() and getattr(self, "_frozen_backbone", False) and prec == 4
                 and any(p.requires_grad for p in self.parameters())):
             prec = 2          # heads trained on frozen features: the tight mode, as in MM.forward_q

@@ -191,11 +191,17 @@ class MM(nn.Module):
         # (train_graph.bn_frozen), exactly F.batch_norm(training=False) under autograd.
         train = self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
                                   and any(p.requires_grad for p in self.parameters()))
+        if not train:
+            return self._forward_q(data_dict, train, image_maps, out_rows, rider)
+        from .. import train_graph
+        # the opt-in fast modes (train_graph.py): one-product forward convs, one-product data gradients -- for THIS model's
+        # forward only, the process-wide switches restored when it returns
+        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1):
+            return self._forward_q(data_dict, train, image_maps, out_rows, rider)
+
+    def _forward_q(self, data_dict, train, image_maps, out_rows, rider):
+        opt = self.opt
         prec = 3 if train else opt.mfma_precision       # training runs on split-bf16 maps (range + precision of gradients)
-        if train:
-            from .. import train_graph
-            train_graph.FWD_F16 = opt.train_precision == 16      # the opt-in fast mode: one-product forward convs (train_graph.py)
-            train_graph.DGRAD_HI_ONLY = opt.train_dgrad_products == 1      # ... and one-product data gradients
         if (not train and torch.is_grad_enabled() and getattr(self, "_frozen_backbone", False) and prec == 4
                 and any(p.requires_grad for p in self.parameters())):
             # fine-tuning the fusion path on FROZEN features (freeze_backbone): gradients of near-cancelling sums (a mixing weight's

@@ -83,8 +83,8 @@ class Options:
     # every forward and data-gradient conv, one fp16 product in the weight gradients; every parameter gradient within 1e-3 of
     # fp64 autograd (tests/test_gpu_train.py).  16 = the opt-in FAST mode: the forward of the 3x3 stride-1 convs as ONE
     # fp16 x fp16 product (train_graph.FWD_F16; fp32 master weights, fp64-finalised statistics, three-product data gradients);
-    # gradient error and cosine against the fp64 oracle: tests/test_gpu_train.py::test_fast_training_mode_gradients, timing:
-    # bench.py train.fast_mode.
+    # gradient error and cosine against the fp64 oracle: tests/test_gpu_train.py (FASTGRAD lines of
+    # test_resnet_trunk_training_gradients[fast] / [dgrad1] and the end-to-end tests' fast cases), timing: bench.py train.fast_mode.
     train_precision: int = 32
     # 3 (default) | 1 = opt-in: the data gradients of the 3x3 convs as ONE bf16 product of the hi planes (train_graph.DGRAD_HI_ONLY),
     # usually together with train_precision = 16; measured error: tests/test_gpu_train.py, timing: bench.py train.fast_mode
@@ -106,6 +106,17 @@ class Options:
     train_positives_dist_threshold: int = 10      # tools/options.py:45
     val_positive_dist_threshold: int = 25         # tools/options.py:44
 
+    def __post_init__(self):
+        self.validate()
+
+    def validate(self):
+        # the training modes are selected by value (train_precision == 16, train_dgrad_products == 1): anything else would
+        # silently give the tight mode
+        if self.train_precision not in (16, 32):
+            raise ValueError(f"train_precision {self.train_precision!r}: 32 (tight) | 16 (one-product forward convs)")
+        if self.train_dgrad_products not in (1, 3):
+            raise ValueError(f"train_dgrad_products {self.train_dgrad_products!r}: 3 (tight) | 1 (one-product data gradients)")
+
     def copy(self, **kw):
         d = {f.name: getattr(self, f.name) for f in fields(self)}
         d.update(kw)
@@ -121,6 +132,7 @@ def from_reference_opt(ns) -> Options:
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")
             setattr(o, f.name, v)
+    o.validate()
     return o
 
 

@@ -14,6 +14,7 @@ hand on halo-padded split-bf16 maps (ops.SplitMap):
 
 Parameter gradients are accumulated into `.grad` of the nn.Conv2d / nn.BatchNorm2d containers.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -47,6 +48,7 @@ WGRAD_F16_STEM = True
 # gradient keeps three products (a gradient map has no fp16 range without a scale per tensor), the weight gradient its one.
 # tools/grad_prec_emul.py prices this plan at 4.0-4.4 x the tight mode's 1e-3 gradient bar on a randomly initialised trunk
 # (train-mode BatchNorm amplifies the forward's rounding layer by layer): tests/test_gpu_train.py measures what it is.
+# Set with DGRAD_HI_ONLY through training_mode(), for one model's forward and restored after it.
 FWD_F16 = False
 # Options.train_dgrad_products = 1 (opt-in, on top of either mode; set where FWD_F16 is): the DATA gradient of every 3x3 conv
 # (stride 1, and the stride-2 entries' conv over the zero-upsampled gradient) as ONE bf16 product of the hi planes
@@ -60,6 +62,20 @@ DGRAD_HI_ONLY = False
 Y16_ONLY = True
 # FWD_F16 also for the stage entries (3x3 stride 2, 1x1 stride-2 downsample): A/B switch of tools/train_bench.py
 FWD_F16_ENTRIES = True
+
+
+@contextlib.contextmanager
+def training_mode(fwd_f16, dgrad_hi_only):
+    """FWD_F16 / DGRAD_HI_ONLY set for the forwards run inside the block and restored on exit (also on an exception): the mode
+    belongs to the model whose forward sets it (MM.forward_q, DBVanilla2D.forward_db), not to the process.  Only forwards read
+    the switches; a unit's data-gradient mode is kept with its saved state (ConvBNUnit._dgrad_hi_only)."""
+    global FWD_F16, DGRAD_HI_ONLY
+    before = (FWD_F16, DGRAD_HI_ONLY)
+    FWD_F16, DGRAD_HI_ONLY = bool(fwd_f16), bool(dgrad_hi_only)
+    try:
+        yield
+    finally:
+        FWD_F16, DGRAD_HI_ONLY = before
 
 
 def _L():

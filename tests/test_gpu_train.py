@@ -1,5 +1,7 @@
 """-m gpu parity tests of the training path (train-mode BatchNorm, conv dgrad/wgrad, pooling backward)
 against autograd through the fp64 CPU oracle.  Bar: 1e-3 relative (north star)."""
+import time
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -196,8 +198,9 @@ def test_stem_one_pass_weight_gradient_really_runs(dev, monkeypatch):
             assert torch.equal(g1[k], g3[k]), k
 
 
-@pytest.mark.parametrize("fe_type,hw,fast", [("resnet18", (64, 96), False), ("resnet50", (96, 96), False), ("resnet18", (64, 96), True),
-                                             ("resnet18", (64, 96), "dgrad1")])
+@pytest.mark.parametrize("fe_type,hw,fast", [("resnet18", (64, 96), False), ("resnet50", (96, 96), False),
+                                             pytest.param("resnet18", (64, 96), True, id="fast"),
+                                             pytest.param("resnet18", (64, 96), "dgrad1", id="dgrad1")])
 def test_resnet_trunk_training_gradients(dev, fe_type, hw, fast, monkeypatch):
     """fast: Options.train_precision = 16 (train_graph.FWD_F16) -- the forward of the 3x3 stride-1 convs as ONE fp16 x fp16 product;
     "dgrad1": that plus Options.train_dgrad_products = 1 (train_graph.DGRAD_HI_ONLY) -- the 3x3 data gradients as ONE bf16 product.
@@ -456,16 +459,36 @@ def trunk_pattern(trunk, slot=0):
     return pat
 
 
-def _compare_grads(model, params, run_oracle, perturb, min_checked, skip=(), must=(), batch_stats=True):
-    """Product .grad vs fp64 oracle autograd; tolerance max(TOL, 3x the oracle's own response to a 1e-5
-    relative input perturbation) -- see test_resnet_trunk_training_gradients."""
+# the training modes, as Options fields (the public switch: MM.forward_q / DBVanilla2D.forward_db enter train_graph.training_mode)
+MODES = {"tight": {}, "fast": dict(train_precision=16), "dgrad1": dict(train_precision=16, train_dgrad_products=1)}
+# fast modes: (rel-L2 bar, cosine bar) of every parameter gradient against fp64 autograd -- test_resnet_trunk_training_gradients'
+FAST_BARS = {"fast": (1e-2, 0.9999), "dgrad1": (2e-2, 0.9998)}
+# ... except for the parameters whose gradient is ONE cancelling sum over the batch and the channels: the GeM exponents (".p":
+# the gradient of (mean x^p)^(1/p) in p is a covariance of log x under the weights x^p) and the fusion ODE's fc biases: the
+# forward's fp16 rounding of the last maps (3e-3, FASTFWD) reaches them amplified by that cancellation.  Their bars are 2 x the
+# trunk's; measured (MI355X), the same in "fast" and "dgrad1" (so from the forward, not from the data gradients; the tight mode,
+# same kernels outside the convs, holds them at 1e-3): dbimage_pools.0.p 1.77e-2 (satellite), fuseblocktoshallow.blocks.2.blocks.0.
+# func.func.fc.bias / .weight 1.62e-2, cosine 0.99987 (next to the voxel branch: level 3 of the fusion over 3 queries)
+CANCELLING = (".p", "func.func.fc.bias", "func.func.fc.weight")
+FAST_BARS_CANCELLING = {"fast": (2e-2, 0.9998), "dgrad1": (4e-2, 0.9996)}
+# model outputs against the unconstrained fp64 oracle
+OUT_BARS = {"tight": 1e-3, "fast": 3e-3, "dgrad1": 3e-3}
+
+
+def _compare_grads(model, params, run_oracle, perturb, min_checked, skip=(), must=(), batch_stats=True, mode="tight"):
+    """Product .grad vs fp64 oracle autograd.  mode "tight": tolerance max(TOL, 3x the oracle's own response to a 1e-5
+    relative input perturbation) -- see test_resnet_trunk_training_gradients.  mode "fast" / "dgrad1" (Options.train_precision
+    = 16, and train_dgrad_products = 1): every parameter gradient within FAST_BARS[mode] of fp64 autograd in rel-L2 AND in
+    cosine -- the trunk test's bars; one FASTGRAD line (median and worst rel-L2, worst cosine) is printed."""
     def grads(pert):
         for v in params.values():
             v.grad = None
         run_oracle(pert).backward()
         return {k: v.grad.clone() for k, v in params.items() if v.grad is not None}
-    ref, refp = grads(False), grads(True)
-    bad, checked, seen = [], 0, set()
+    fast = mode != "tight"
+    ref = grads(False)
+    refp = None if fast else grads(True)             # (the fast bars are fixed: no perturbed oracle run)
+    bad, checked, seen, errs, coss = [], 0, set(), [], []
     for name, prm in model.named_parameters():
         if name not in ref or name.startswith(skip) or not prm.requires_grad:
             continue
@@ -481,39 +504,136 @@ def _compare_grads(model, params, run_oracle, perturb, min_checked, skip=(), mus
             continue
         r = ref[name].reshape(prm.grad.shape)
         err = rel_l2(prm.grad, r)
-        tol = max(TOL, 3 * rel_l2(refp[name].reshape(r.shape), r))
+        if fast:
+            tol, cbar = (FAST_BARS_CANCELLING if name.endswith(CANCELLING) else FAST_BARS)[mode]
+            g1, g2 = prm.grad.detach().double().cpu().flatten(), r.double().flatten()
+            cos = float((g1 @ g2) / (g1.norm() * g2.norm()).clamp_min(1e-300))
+            errs.append((err, name)); coss.append((cos, name))
+            if not cos >= cbar:
+                bad.append((name + " (1 - cosine)", 1 - cos, 1 - cbar))
+        else:
+            tol = max(TOL, 3 * rel_l2(refp[name].reshape(r.shape), r))
         if not err < tol:
             bad.append((name, err, tol))
         checked += 1
+    if fast:
+        errs.sort(); coss.sort()
+        print(f"FASTGRAD [{mode}] rel_l2 median {errs[len(errs) // 2][0]:.2e} ({errs[len(errs) // 2][1]}) worst {errs[-1][0]:.2e} "
+              f"({errs[-1][1]}); cosine worst {coss[0][0]:.6f} ({coss[0][1]}) over {checked} parameter tensors")
     print("GRADERR " + " ".join(f"{n}:{e:.1e}/{t:.1e}" for n, e, t in bad))
     assert not bad, bad[:6]
     assert checked >= min_checked, checked
     assert not [m for m in must if m not in seen], [m for m in must if m not in seen]
 
 
-@pytest.mark.parametrize("nlayers,bn_mode", [(1, "train"), (2, "train"), (1, "eval")])
-def test_mm_end_to_end_training_gradients(dev, nlayers, bn_mode):
+# Path census of the fast modes, derived once from the rules of ConvBNUnit.forward / reads_f16_plane_only: a unit's forward is ONE
+# fp16 product (its z one fp16 plane, saved[1].lo is None) when it is not the stem, is a 3x3 stride-1 conv or a stage entry (3x3
+# stride 2, 1x1 stride-2 downsample), has in and out channels divisible by 64 and its input map keeps an fp16 plane; a unit's output
+# is ONE fp16 plane (saved[2].lo is None) when its only reader is such a 3x3 stride-1 unit (a block's conv1 -> conv2).
+# ResNet18 "2_2_2" (64_128_256): every unit but the stem (the max-pooled stem output keeps the plane for l0.0.c0; every block output
+# keeps it for the next block's entries) ...
+TRUNK18_Z16 = frozenset(f"l{li}.{bi}.c{ci}" for li in range(3) for bi in range(2) for ci in range(2)) | {"l1.0.ds", "l2.0.ds"}
+TRUNK18_Y16 = frozenset(f"l{li}.{bi}.c0" for li in range(3) for bi in range(2))
+# ... the stage-2 BasicBlock (stage2fuse_blockadd.py, forward_map_train): its input is the trunk map plus the broadcast vector
+# (ops.bcast_add writes no fp16 plane), so its conv1 keeps three products; conv2 reads conv1's output, stored as one fp16 plane
+STG2_Z16 = frozenset({"t.c2"})
+STG2_Y16 = frozenset({"t.c1"})
+
+
+def _single_plane(units):
+    z16 = {n for n, u in units.items() if u.saved[1].lo is None}
+    y16 = {n for n, u in units.items() if u.saved[2] is not None and u.saved[2].lo is None}
+    return z16, y16
+
+
+def _fast_path_census(mode, trunks=(), blocks=()):
+    """trunks: (label, resnet trunk, slot prefix); blocks: (label, stage-2 BasicBlock).  In a fast mode exactly the expected units
+    ran in one-product form (a silent fall-back to three products fails); in the tight mode none.  Every 3x3 unit carries
+    the data-gradient mode of its forward (_dgrad_hi_only) -- set in "dgrad1" only."""
+    fast = mode != "tight"
+    units = []
+    for label, trunk, pre in trunks:
+        us = {n[len(pre):]: u for n, u in trunk._units.items() if n.startswith(pre)}
+        assert len(us) == 15, (label, sorted(us))
+        z16, y16 = _single_plane(us)
+        print(f"CENSUS [{mode}] {label} one-product z: {sorted(z16)}; one-plane outputs: {sorted(y16)}")
+        assert z16 == (TRUNK18_Z16 if fast else set()), (label, sorted(z16 ^ TRUNK18_Z16))
+        assert y16 == (TRUNK18_Y16 if fast else set()), (label, sorted(y16 ^ TRUNK18_Y16))
+        units += us.values()
+    for label, blk in blocks:
+        us = {u.tag: u for u in blk._units}
+        z16, y16 = _single_plane(us)
+        print(f"CENSUS [{mode}] {label} one-product z: {sorted(z16)}; one-plane outputs: {sorted(y16)}")
+        assert z16 == (STG2_Z16 if fast else set()) and y16 == (STG2_Y16 if fast else set()), (label, z16, y16)
+        units += us.values()
+    for u in units:       # (the switch as it stood at the unit's forward; its backward applies it to the 3x3 data gradients)
+        assert u._dgrad_hi_only == (mode == "dgrad1"), (u.tag, u._dgrad_hi_only)
+
+
+def _grads(model):
+    return {n: p.grad.detach().clone() for n, p in model.named_parameters() if p.grad is not None}
+
+
+def _assert_dgrad1_ran(grads, fast_grads, names):
+    """dgrad1 only: the same state and input in the "fast" mode (three-product data gradients) give conv weight gradients that
+    are NOT bit-equal -- the one-product data gradient ran.  `names`: the conv weights whose gradient passes a 3x3 data gradient."""
+    same = [n for n in names if torch.equal(grads[n], fast_grads[n])]
+    assert not same and len(names) > 0, same
+
+
+def _conv_weights(model, prefix, exclude=()):
+    return [n for n, p in model.named_parameters() if n.startswith(prefix) and p.dim() == 4 and n not in exclude]
+
+
+_MM_CASES = [pytest.param("tight", 1, "train", 4, (64, 128), id="1-train"), pytest.param("tight", 2, "train", 4, (64, 128), id="2-train"),
+             pytest.param("tight", 1, "eval", 4, (64, 128), id="1-eval")]
+_MM_CASES += [pytest.param(m, nl, bm, 4, (64, 128), id=f"{m}-{nl}-{bm}") for m in ("fast", "dgrad1")
+              for nl, bm in ((1, "train"), (2, "train"), (1, "eval"))]
+# the bench's query batch shape (two of its 224 x 1344 panoramas: layer 3 at 14 x 84, the stage-2 block there)
+_MM_CASES += [pytest.param("dgrad1", 1, "train", 2, (224, 1344), id="dgrad1-bench-2x224x1344")]
+
+
+@pytest.mark.parametrize("mode,nlayers,bn_mode,nq,hw", _MM_CASES)
+def test_mm_end_to_end_training_gradients(dev, mode, nlayers, bn_mode, nq, hw):
     """.train() MM: loss on the embedding and two auxiliary outputs -> every parameter's gradient
     (ResNet convs/BNs, GeM exponents, fusion path, stage-2 conv block and projections).  nlayers = 2: opt.stg2nlayers
     stacked stage-2 layers (reference stage2fuse_blockadd.py:190, layer i+1 reads layer i's map).
     bn_mode "eval": .eval() with gradients enabled -- fine-tuning on frozen BatchNorm statistics (F.batch_norm with
-    training=False under autograd): running statistics used and left untouched, constants of the backward."""
+    training=False under autograd): running statistics used and left untouched, constants of the backward.
+    mode "fast" / "dgrad1": the model built with Options(train_precision=16[, train_dgrad_products=1]) -- the step bench.py times
+    as train.fast_mode: every gradient at the trunk test's fast bars (_compare_grads), exactly the expected units in one-product
+    form (_fast_path_census), and under dgrad1 conv weight gradients that differ from the fast mode's on the same state and input."""
+    t0 = time.perf_counter()
     training = bn_mode == "train"
     from agplace_amd.network_mm.mm import MM
     from agplace_amd.options import Options
     from gpu_util import to_dev
-    opt = Options(stg2nlayers=nlayers)
+    opt = Options(stg2nlayers=nlayers, **MODES[mode])
     torch.manual_seed(21)
     model = randomize_bn(MM(opt=opt)).to(dev).train(training)
-    data = nets.synth_query(4, 64, 128, opt, seed=5)
+    state0 = {k: v.clone() for k, v in model.state_dict().items()}
+    data = nets.synth_query(nq, hw[0], hw[1], opt, seed=5)
+    ddev = to_dev(data, dev)
     g = torch.Generator().manual_seed(2)
-    G = [torch.randn(4, 256, generator=g) for _ in range(4)]
+    G = [torch.randn(nq, 256, generator=g) for _ in range(4)]
+
+    def step(m):
+        out = m(ddev, mode="q")
+        loss = (out["embedding"] * G[0].to(dev)).sum() + (out["stg2imagevec"] * G[1].to(dev)).sum() \
+            + (out["imagevec_org"] * G[2].to(dev)).sum() + (out["stg2fusevec"] * G[3].to(dev)).sum()
+        loss.backward()
+        return out
     before = model.image_fe.fe.bn1.running_mean.clone()
-    out = model(to_dev(data, dev), mode="q")
-    loss = (out["embedding"] * G[0].to(dev)).sum() + (out["stg2imagevec"] * G[1].to(dev)).sum() \
-        + (out["imagevec_org"] * G[2].to(dev)).sum() + (out["stg2fusevec"] * G[3].to(dev)).sum()
-    loss.backward()
+    out = step(model)
     assert torch.equal(before, model.image_fe.fe.bn1.running_mean) != training     # running stats updated in .train() only
+    _fast_path_census(mode, [("image_fe", model.image_fe.fe, "t.")],
+                      [(f"stg2fuseblock.ffnsimg.{li}", model.stg2fuseblock.ffnsimg[li]) for li in range(nlayers)])
+    if mode == "dgrad1":
+        twin = MM(opt=opt.copy(train_dgrad_products=3)).to(dev).train(training)
+        twin.load_state_dict(state0)
+        step(twin)
+        _assert_dgrad1_ran(_grads(model), _grads(twin), _conv_weights(model, "image_fe.fe.")
+                           + [f"stg2fuseblock.ffnsimg.{li}.conv1.weight" for li in range(nlayers)])
     params = {k: (v.double() if v.is_floating_point() else v) for k, v in cpu_state(model).items()}
     for k, v in params.items():
         if v.is_floating_point() and "running_" not in k and not k.endswith("_weight"):
@@ -537,7 +657,7 @@ def test_mm_end_to_end_training_gradients(dev, nlayers, bn_mode):
 
     free = nets.mm_forward_q(d64, params, opt, training=training)
     for k in ("embedding", "stg2imagevec", "imagevec_org", "shallowvec_org", "stg2fusevec"):
-        assert rel_l2(out[k], free[k]) < 1e-3, (k, rel_l2(out[k], free[k]))
+        assert rel_l2(out[k], free[k]) < OUT_BARS[mode], (k, rel_l2(out[k], free[k]))
     must = ["image_fe.fe.conv1.weight", "image_fe.fe.layer3.1.bn2.weight", "image_pool.p",
             "stg2fuseblock.poolimage.p", "stg2fuseblock.projsfuseimg.0.0.weight",
             "stg2fuseblock.ffnsimg.0.conv1.weight", "stg2fuseblock.ffnsimg.0.bn2.bias",
@@ -549,31 +669,61 @@ def test_mm_end_to_end_training_gradients(dev, nlayers, bn_mode):
     if not training:
         must += ["stg2fuseblock.ffnsimg.0.conv1.bias"]
     _compare_grads(model, params, run_oracle, noise, min_checked=65, skip=("image_fe.fe.fc.",), must=tuple(must),
-                   batch_stats=training)
+                   batch_stats=training, mode=mode)
+    print(f"WALL mm [{mode}-{nlayers}-{bn_mode} {nq}x{hw[0]}x{hw[1]}] {time.perf_counter() - t0:.1f} s")
 
 
-@pytest.mark.parametrize("variant,bn_mode", [(dict(), "train"), (dict(maptype="satellite_roadmap"), "train"),
-                                             (dict(maptype="satellite_roadmap", share_dbfe=True), "train"),
-                                             (dict(maptype="satellite_roadmap", share_dbfe=True), "eval")])
-def test_dbvanilla2d_end_to_end_training_gradients(dev, variant, bn_mode):
+_DB_CASES = [pytest.param("tight", dict(), "train", (2, 3, 64), id="variant0-train"),
+             pytest.param("tight", dict(maptype="satellite_roadmap"), "train", (2, 3, 64), id="variant1-train"),
+             pytest.param("tight", dict(maptype="satellite_roadmap", share_dbfe=True), "train", (2, 3, 64), id="variant2-train"),
+             pytest.param("tight", dict(maptype="satellite_roadmap", share_dbfe=True), "eval", (2, 3, 64), id="variant3-eval")]
+_DB_CASES += [pytest.param(m, v, "train", (2, 3, 64), id=f"{m}-{vid}-train") for m in ("fast", "dgrad1")
+              for vid, v in (("satellite", dict()), ("shared-roadmap", dict(maptype="satellite_roadmap", share_dbfe=True)))]
+# the bench's database batch shape: [2, 2, 1, 3, 256, 256] aerial tiles (layer 3 at 16 x 16)
+_DB_CASES += [pytest.param("dgrad1", dict(), "train", (2, 2, 256), id="dgrad1-bench-2x2x1x256")]
+
+
+@pytest.mark.parametrize("mode,variant,bn_mode,shape", _DB_CASES)
+def test_dbvanilla2d_end_to_end_training_gradients(dev, mode, variant, bn_mode, shape):
     """share_dbfe: ONE trunk over both map types (reference models_baseline/dbvanilla2d.py:69-72); its gradients are the
-    sum over the two applications.  bn_mode "eval": gradients through eval-mode (frozen-statistics) BatchNorm."""
+    sum over the two applications.  bn_mode "eval": gradients through eval-mode (frozen-statistics) BatchNorm.
+    mode "fast" / "dgrad1": Options(train_precision=16[, train_dgrad_products=1]) as in test_mm_end_to_end_training_gradients;
+    the census covers each trunk, or both slots ("t.", "t1.") of the shared one."""
+    t0 = time.perf_counter()
     training = bn_mode == "train"
     from agplace_amd.models_baseline.dbvanilla2d import DBVanilla2D
     from agplace_amd.options import Options
-    opt = Options(**variant)
+    opt = Options(**variant, **MODES[mode])
     torch.manual_seed(22)
     model = randomize_bn(DBVanilla2D(mode="db", dim=256, opt=opt)).to(dev).train(training)
+    state0 = {k: v.clone() for k, v in model.state_dict().items()}
     nmap = len(opt.maptype.split("_"))
-    db_map = torch.randn(2, 3, nmap, 3, 64, 64)
-    G = torch.randn(2, 3, 256)
-    out = model({"db_map": db_map.to(dev)}, mode="db")["embedding"]
-    (out * G.to(dev)).sum().backward()
+    b, ndb, hw = shape
+    db_map = torch.randn(b, ndb, nmap, 3, hw, hw)
+    G = torch.randn(b, ndb, 256)
+
+    def step(m):
+        out = m({"db_map": db_map.to(dev)}, mode="db")["embedding"]
+        (out * G.to(dev)).sum().backward()
+        return out
+    out = step(model)
+    shared = opt.share_dbfe is True
+    if shared:
+        trunks = [("dbimage_fes.0 slot 0", model.dbimage_fes[0].fe, "t."), ("dbimage_fes.0 slot 1", model.dbimage_fes[0].fe, "t1.")]
+    else:
+        trunks = [(f"dbimage_fes.{i}", model.dbimage_fes[i].fe, "t.") for i in range(nmap)]
+    _fast_path_census(mode, trunks)
+    if mode == "dgrad1":
+        twin = DBVanilla2D(mode="db", dim=256, opt=opt.copy(train_dgrad_products=3)).to(dev).train(training)
+        twin.load_state_dict(state0)
+        step(twin)
+        # (the last conv's weight gradient comes from the pooling alone: no data gradient in front of it)
+        _assert_dgrad1_ran(_grads(model), _grads(twin), [n for i in range(1 if shared else nmap) for n in _conv_weights(
+            model, f"dbimage_fes.{i}.fe.", exclude=(f"dbimage_fes.{i}.fe.layer3.1.conv2.weight",))])
     params = {k: (v.double() if v.is_floating_point() else v) for k, v in cpu_state(model).items()}
     for k, v in params.items():
         if v.is_floating_point() and "running_" not in k:
             v.requires_grad_(True)
-    shared = opt.share_dbfe is True
     patterns = [trunk_pattern(model.dbimage_fes[0 if shared else i].fe, slot=i if shared else 0) for i in range(nmap)]
     gp = torch.Generator().manual_seed(3)
     noise = 1 + 1e-5 * torch.randn(db_map.shape, generator=gp, dtype=torch.float64)
@@ -584,10 +734,12 @@ def test_dbvanilla2d_end_to_end_training_gradients(dev, variant, bn_mode):
         return (ref["embedding"] * G.double()).sum()
 
     free = nets.dbvanilla2d_forward_db({"db_map": db_map.double()}, params, opt, training=training)["embedding"]
-    assert rel_l2(out, free) < 1e-3
+    assert rel_l2(out, free) < OUT_BARS[mode], rel_l2(out, free)
     nfe = len(model.dbimage_fes)
     _compare_grads(model, params, run_oracle, noise, min_checked=48, skip=tuple(f"dbimage_fes.{i}.fe.fc." for i in range(nfe)),
-                   must=("dbimage_fes.0.fe.conv1.weight", "dbimage_pools.0.p", "dbimage_mlps.0.seq.0.weight"), batch_stats=training)
+                   must=("dbimage_fes.0.fe.conv1.weight", "dbimage_pools.0.p", "dbimage_mlps.0.seq.0.weight"), batch_stats=training,
+                   mode=mode)
+    print(f"WALL db [{mode}-{bn_mode} {b}x{ndb}x{nmap}x{hw}x{hw}] {time.perf_counter() - t0:.1f} s")
 
 
 def test_training_gradients_are_bit_repeatable(dev):
@@ -653,24 +805,222 @@ def test_adam_steps_reduce_a_matching_loss(dev):
     assert not torch.equal(w0, mq.image_fe.fe.layer2[0].conv1.weight)
 
 
-@pytest.mark.parametrize("bn_mode,ntd", [("train", 0), ("eval", 0), ("train", 1)])
-def test_mm_end_to_end_training_with_sparse_voxel_branch(dev, bn_mode, ntd):
+def _imagefe_step(fe, x, dev):
+    """One standalone training step of an ImageFE trunk (whatever mode the process-wide switches hold): its gradients."""
+    from agplace_amd import ops, train_graph
+    for q in fe.parameters():
+        q.grad = None
+    maps = fe.fe.forward_maps_train(x)
+    g = torch.Generator().manual_seed(1)
+    grads = []
+    for m in maps:
+        gm = ops.SplitMap.alloc(m.n, m.h, m.w, m.c, 1, 3, dev)
+        train_graph.pool_bwd(m, gm, gmean=torch.randn(m.n, m.c, generator=g).to(dev))
+        grads.append(gm)
+    fe.fe.backward_maps(grads)
+    return _grads(fe)
+
+
+def test_training_mode_is_per_model(dev):
+    """The training mode belongs to the model whose Options select it, not to the process: MM.forward_q / DBVanilla2D.forward_db
+    set train_graph's switches for their own forward only (train_graph.training_mode).  (a) a dgrad1 MM next to a tight
+    DBVanilla2D and (b) the modes swapped: forward q, forward db, one joint backward -- each model's gradients are bit-equal to
+    its gradients when it runs alone from the same state.  After a fast MM training forward the switches hold what they held
+    before, and a standalone ImageFE trunk step (which relies on them) gives the same bits as before that forward."""
+    from agplace_amd import train_graph
+    from agplace_amd.models_baseline.dbvanilla2d import DBVanilla2D
+    from agplace_amd.network.image_fe import ImageFE
+    from agplace_amd.network_mm.mm import MM
+    from agplace_amd.options import Options
+    from gpu_util import to_dev
+    base = Options()
+    torch.manual_seed(61)
+    sq = {k: v.clone() for k, v in randomize_bn(MM(opt=base)).state_dict().items()}
+    sd = {k: v.clone() for k, v in randomize_bn(DBVanilla2D("db", base.features_dim, opt=base), seed=1).state_dict().items()}
+
+    def build(cls, state, mode):
+        m = cls(opt=base.copy(**MODES[mode])) if cls is MM else cls("db", base.features_dim, opt=base.copy(**MODES[mode]))
+        m.load_state_dict(state)
+        return m.to(dev).train()
+    mq = {m: build(MM, sq, m) for m in ("tight", "dgrad1")}
+    mdb = {m: build(DBVanilla2D, sd, m) for m in ("tight", "dgrad1")}
+    data = to_dev(nets.synth_query(2, 64, 128, base, seed=8), dev)
+    db = {"db_map": torch.randn(2, 2, 1, 3, 64, 64, generator=torch.Generator().manual_seed(9)).to(dev)}
+    g = torch.Generator().manual_seed(2)
+    Gq, Gd = torch.randn(2, 256, generator=g).to(dev), torch.randn(2, 2, 256, generator=g).to(dev)
+
+    def run(q=None, d=None):
+        """forward q, then forward db, then ONE backward; every model reset to the same state first (parameters, running
+        statistics, num_batches_tracked)"""
+        for m, st in ((q, sq), (d, sd)):
+            if m is not None:
+                m.load_state_dict(st)
+                for p_ in m.parameters():
+                    p_.grad = None
+        loss = 0
+        if q is not None:
+            fq = q(data, mode="q")
+            loss = loss + (fq["embedding"] * Gq).sum() + (fq["stg2imagevec"] * Gq).sum()
+        if d is not None:
+            loss = loss + (d(db, mode="db")["embedding"] * Gd).sum()
+        loss.backward()
+        return _grads(q) if q is not None else None, _grads(d) if d is not None else None
+
+    for qm, dm in (("dgrad1", "tight"), ("tight", "dgrad1")):
+        jq, jd = run(mq[qm], mdb[dm])
+        aq, _ = run(q=mq[qm])
+        _, ad = run(d=mdb[dm])
+        assert len(jq) > 60 and jq.keys() == aq.keys() and jd.keys() == ad.keys()
+        diff = [n for n in jq if not torch.equal(jq[n], aq[n])] + [n for n in jd if not torch.equal(jd[n], ad[n])]
+        assert not diff, (qm, dm, diff[:8])
+    # the process-wide switches are left as they were; a trunk that relies on them runs in the same mode as before
+    torch.manual_seed(62)
+    fe = randomize_bn(ImageFE("resnet18", "2_2_2")).to(dev).train()
+    fe_state = {k: v.clone() for k, v in fe.state_dict().items()}
+    x = (torch.randn(3, 3, 64, 96, generator=torch.Generator().manual_seed(63)) * 1.5).to(dev)
+    switches = (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY)
+    g0 = _imagefe_step(fe, x, dev)
+    for m, inp, kind in ((mq["dgrad1"], data, "q"), (mdb["dgrad1"], db, "db")):
+        m(inp, mode=kind)
+        assert (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY) == switches, type(m).__name__
+        fe.load_state_dict(fe_state)
+        g1 = _imagefe_step(fe, x, dev)
+        diff = [n for n in g0 if not torch.equal(g0[n], g1[n])]
+        assert g0.keys() == g1.keys() and not diff, (type(m).__name__, diff[:8])
+
+
+# ------------------------------------------------------------------ Adam trajectory against the fp64 oracle
+TRAJ_STEPS, TRAJ_LR = 20, 1e-4
+
+
+@pytest.fixture(scope="module")
+def adam_oracle():
+    """The problem (2 queries at 64 x 128, database [2, 2, 1, 3, 64, 64], triplet loss with margin 1.5 so that the hinges stay
+    open over the run) and TRAJ_STEPS Adam steps of it through the oracle (oracle.nets + oracle.losses, plain autograd) in fp64 and
+    in fp32 -- the fp32 run is the drift of an ordinary fp32 PyTorch implementation, the control the product is measured against."""
+    from agplace_amd.models_baseline.dbvanilla2d import DBVanilla2D
+    from agplace_amd.network_mm.mm import MM
+    from agplace_amd.options import Options
+    from oracle import losses as olosses
+    opt = Options(train_batch_size=2, negs_num_per_query=2, margin=1.5)
+    torch.manual_seed(51)
+    mq, mdb = randomize_bn(MM(opt=opt)), randomize_bn(DBVanilla2D("db", opt.features_dim, opt=opt), seed=1)
+    pb = dict(opt=opt, sq=cpu_state(mq), sd=cpu_state(mdb),
+              names=[("q", n) for n, p_ in mq.named_parameters() if p_.requires_grad]
+              + [("db", n) for n, p_ in mdb.named_parameters() if p_.requires_grad],
+              data=nets.synth_query(2, 64, 128, opt, seed=52),
+              db=torch.randn(2, 2, len(opt.maptype.split("_")), 3, 64, 64, generator=torch.Generator().manual_seed(53)),
+              # rows: queries 0, 1, then the database tiles [query, tile] 2 = (0, 0), 3 = (0, 1), 4 = (1, 0), 5 = (1, 1)
+              trip=torch.tensor([[0, 2, 3], [0, 2, 4], [1, 4, 5], [1, 4, 2]]))
+
+    def run(dtype):
+        st = {w: {k: (v.to(dtype) if v.is_floating_point() else v).clone() for k, v in pb["s" + w[0]].items()} for w in ("q", "db")}
+        prm = [st[w][n].requires_grad_(True) for w, n in pb["names"]]
+        th0 = [p_.detach().clone() for p_ in prm]
+        d = {k: ([t.to(dtype) for t in v] if isinstance(v, list) else (v.to(dtype) if v.is_floating_point() else v))
+             for k, v in pb["data"].items()}
+        x = pb["db"].to(dtype)
+        optim = torch.optim.Adam(prm, lr=TRAJ_LR)
+        losses = []
+        for _ in range(TRAJ_STEPS):
+            optim.zero_grad(set_to_none=True)
+            q = nets.mm_forward_q(d, st["q"], opt, training=True)["embedding"]
+            e = nets.dbvanilla2d_forward_db({"db_map": x}, st["db"], opt, training=True)["embedding"]
+            loss = olosses.compute_loss(pb["trip"], torch.cat([q, e.reshape(-1, e.shape[-1])]), 2, 2, opt.margin)
+            loss.backward()
+            optim.step()
+            losses.append(float(loss.detach()))
+        return losses, {w + "." + n: (p_.detach() - t0).double() for (w, n), p_, t0 in zip(pb["names"], prm, th0)}
+    return pb, run(torch.float64), run(torch.float32)
+
+
+def _trajectory_error(losses, upd, ref):
+    """(largest relative loss deviation over the steps, median and worst per-tensor relative error of theta_20 - theta_0) against
+    the fp64 run `ref`.  Left out: the conv biases in front of batch-statistics BatchNorm (an analytically zero gradient, on
+    which Adam's normalised step follows rounding noise; BatchNorm removes them exactly) and tensors no gradient reaches."""
+    l64, u64 = ref
+    dev_ = max(abs(a - b) / abs(b) for a, b in zip(losses, l64))
+    errs = sorted((rel_l2(upd[n], u64[n]), n) for n in u64
+                  if not n.endswith(("conv1.bias", "conv2.bias")) and float(u64[n].abs().max()) > 0)
+    return dev_, errs[len(errs) // 2][0], errs[-1]
+
+
+# the fast modes' bars (loss deviation, update median, update worst): 1.5 x the values measured on an MI355X (the test's docstring)
+TRAJ_FAST_BARS = {"fast": (1.2e-3, 2.2e-1, 4.3e-1), "dgrad1": (2.3e-3, 2.2e-1, 4.9e-1)}
+
+
+@pytest.mark.parametrize("mode", ["tight", "fast", "dgrad1"])
+def test_adam_trajectory_matches_fp64_oracle(dev, mode, adam_oracle):
+    """TRAJ_STEPS Adam steps of query and database networks on one fixed batch (losses.compute_loss, triplet) against the same
+    steps through the fp64 oracle: the largest relative loss deviation over the steps and the per-tensor relative error of
+    the whole update theta_20 - theta_0 (median, worst).  A ReLU kink cannot be pinned over 20 steps, so the bars are relative
+    to an fp32 run of the oracle: the tight mode within 3 x that control; the fast modes within 1.5 x what they measured
+    (TRAJ_FAST_BARS).  The loss goes down in every mode.  Measured (MI355X): fp32 control 1.33e-3 / 4.23e-2 / 1.21e-1 (loss
+    deviation / update median / worst); tight 1.55e-3 / 8.76e-2 / 2.12e-1; fast 8.12e-4 / 1.48e-1 / 2.87e-1; dgrad1 1.55e-3 /
+    1.48e-1 / 3.25e-1.  Adam normalises each tensor's step, so a constant error factor on one gradient is invisible here: the
+    end-to-end gradient tests are the ones that catch it."""
+    from agplace_amd import losses as plosses
+    from agplace_amd.models_baseline.dbvanilla2d import DBVanilla2D
+    from agplace_amd.network_mm.mm import MM
+    from gpu_util import to_dev
+    t0 = time.perf_counter()
+    pb, ref, ctl = adam_oracle
+    opt = pb["opt"].copy(**MODES[mode])
+    mq, mdb = MM(opt=opt), DBVanilla2D("db", opt.features_dim, opt=opt)
+    mq.load_state_dict(pb["sq"]); mdb.load_state_dict(pb["sd"])
+    mq, mdb = mq.to(dev).train(), mdb.to(dev).train()
+    own = {"q": dict(mq.named_parameters()), "db": dict(mdb.named_parameters())}
+    prm = [own[w][n] for w, n in pb["names"]]
+    th0 = [p_.detach().clone() for p_ in prm]
+    data, db, trip = to_dev(pb["data"], dev), {"db_map": pb["db"].to(dev)}, pb["trip"].to(dev)
+    optim = torch.optim.Adam(prm, lr=TRAJ_LR)
+    losses = []
+    for _ in range(TRAJ_STEPS):
+        optim.zero_grad(set_to_none=True)
+        q = mq(data, mode="q")["embedding"]
+        e = mdb(db, mode="db")["embedding"]
+        loss = plosses.compute_loss(opt, None, trip, torch.cat([q, e.reshape(-1, e.shape[-1])]))
+        loss.backward()
+        optim.step()
+        losses.append(float(loss.detach()))
+    upd = {w + "." + n: (p_.detach() - t).double().cpu() for (w, n), p_, t in zip(pb["names"], prm, th0)}
+    got, fp32 = _trajectory_error(losses, upd, ref), _trajectory_error(*ctl, ref)
+    print(f"TRAJECTORY [{mode}] loss {losses[0]:.4f} -> {losses[-1]:.4f} (fp64 {ref[0][0]:.4f} -> {ref[0][-1]:.4f}); "
+          f"loss deviation {got[0]:.2e} (fp32 control {fp32[0]:.2e}); update rel-L2 median {got[1]:.2e} (control {fp32[1]:.2e}), "
+          f"worst {got[2][0]:.2e} {got[2][1]} (control {fp32[2][0]:.2e} {fp32[2][1]}); {time.perf_counter() - t0:.1f} s")
+    assert losses[-1] < losses[0] and ref[0][-1] < ref[0][0], losses
+    if mode == "tight":
+        bars = (3 * fp32[0], 3 * fp32[1], 3 * fp32[2][0])
+    else:
+        bars = TRAJ_FAST_BARS[mode]
+    for name, v, bar in zip(("loss deviation", "update median", "update worst"), (got[0], got[1], got[2][0]), bars):
+        assert bar is None or v <= bar, (name, v, bar)
+
+
+@pytest.mark.parametrize("mode,bn_mode,ntd", [pytest.param("tight", "train", 0, id="train-0"), pytest.param("tight", "eval", 0, id="eval-0"),
+                                              pytest.param("tight", "train", 1, id="train-1"),
+                                              pytest.param("fast", "train", 0, id="fast-train-0"),
+                                              pytest.param("dgrad1", "train", 0, id="dgrad1-train-0")])
+def test_mm_end_to_end_training_with_sparse_voxel_branch(dev, mode, bn_mode, ntd):
     """bn_mode "eval": the same through eval-mode (frozen-statistics) BatchNorm / MinkowskiBatchNorm.
     .train() MM from query_image + coords/features: gradients of every parameter -- image trunk, MinkFPN
     (sparse convs, MinkowskiBatchNorm, ECA), both GeM/MinkGeM exponents, fusion path, stage-2 image AND sparse
-    side -- against fp64 autograd through the oracle."""
+    side -- against fp64 autograd through the oracle.  mode "fast" / "dgrad1": the image side in a fast training mode
+    (Options(train_precision=16[, train_dgrad_products=1])) next to the voxel branch, at the fast bars (_compare_grads)."""
+    t0 = time.perf_counter()
     from agplace_amd.network_mm.mm import MM
     from agplace_amd.options import Options
     from gpu_util import to_dev
     from oracle import sparse as osp
     # ntd = 1: the voxel FPN's top-down path inside MM (equal voxel planes, see test_gpu_models.py)
-    opt = Options() if ntd == 0 else Options(mm_voxfe_ntd=ntd, mm_voxfe_planes="256_256_256")
+    opt = Options(**MODES[mode]) if ntd == 0 else Options(mm_voxfe_ntd=ntd, mm_voxfe_planes="256_256_256", **MODES[mode])
     torch.manual_seed(31)
     model = MM(opt=opt)
     params0 = nets.init_mm_params(opt, seed=21)
     model.load_reference_state_dict(params0)
     training = bn_mode == "train"
     model = model.to(dev).train(training)
+    state0 = {k: v.clone() for k, v in model.state_dict().items()}
     data = nets.synth_query(3, 64, 128, opt, seed=15)
     for k in ("vox_levels", "voxfeatvec", "stg2voxvec", "voxvec_fuse"):
         data.pop(k)
@@ -679,9 +1029,21 @@ def test_mm_end_to_end_training_with_sparse_voxel_branch(dev, bn_mode, ntd):
     g = torch.Generator().manual_seed(2)
     keys = ("embedding", "stg2imagevec", "stg2voxvec", "voxvec_org", "stg2fusevec")
     G = {k: torch.randn(3, 256, generator=g) for k in keys}
-    out = model(to_dev(data, dev), mode="q")
-    loss = sum((out[k] * G[k].to(dev)).sum() for k in keys)
-    loss.backward()
+
+    def step(m):
+        out = m(to_dev(data, dev), mode="q")
+        loss = sum((out[k] * G[k].to(dev)).sum() for k in keys)
+        loss.backward()
+        return out
+    out = step(model)
+    _fast_path_census(mode, [("image_fe", model.image_fe.fe, "t.")], [("stg2fuseblock.ffnsimg.0", model.stg2fuseblock.ffnsimg[0])])
+    if mode == "dgrad1":
+        twin = MM(opt=opt.copy(train_dgrad_products=3))
+        twin.load_reference_state_dict(params0)
+        twin = twin.to(dev).train(training)
+        twin.load_state_dict(state0)
+        step(twin)
+        _assert_dgrad1_ran(_grads(model), _grads(twin), _conv_weights(model, "image_fe.fe.") + ["stg2fuseblock.ffnsimg.0.conv1.weight"])
     params = {k: (v.double() if v.is_floating_point() else v) for k, v in cpu_state(model).items()}
     for k, v in params.items():
         if v.is_floating_point() and "running_" not in k and not k.endswith("_weight"):
@@ -719,14 +1081,15 @@ def test_mm_end_to_end_training_with_sparse_voxel_branch(dev, bn_mode, ntd):
 
     free = nets.mm_forward_q(d64, params, opt, training=training)
     for k in keys:
-        assert rel_l2(out[k], free[k]) < 1e-3, (k, rel_l2(out[k], free[k]))
+        assert rel_l2(out[k], free[k]) < OUT_BARS[mode], (k, rel_l2(out[k], free[k]))
     _compare_grads(model, params, run_oracle, noise, min_checked=125, skip=("image_fe.fe.fc.",),
                    must=("image_fe.fe.conv1.weight", "vox_fe.conv0.kernel", "vox_fe.blocks.2.0.conv2.kernel",
                          "vox_fe.blocks.1.0.eca.conv.weight", "vox_fe.bns.0.bn.weight", "vox_pool.p",
                          *(("vox_fe.tconvs.0.kernel", "vox_fe.conv1x1s.1.kernel") if ntd else ()),
                          "stg2fuseblock.ffnsvox.0.conv1.kernel", "stg2fuseblock.ffnsvox.0.eca.conv.weight",
                          "stg2fuseblock.projsvoxfuse.0.0.kernel", "stg2fuseblock.projsfusevox.0.0.weight",
-                         "stg2fuseblock.poolvox.p", "fuseblocktoshallow.updimsvox.0.weight"), batch_stats=training)
+                         "stg2fuseblock.poolvox.p", "fuseblocktoshallow.updimsvox.0.weight"), batch_stats=training, mode=mode)
+    print(f"WALL mm+vox [{mode}-{bn_mode}-{ntd}] {time.perf_counter() - t0:.1f} s")
 
 
 def test_two_stream_training_step_gives_the_same_gradients(dev):

@@ -24,6 +24,45 @@ def test_options_defaults_match_reference_flags():
     assert a.odeint_method == "rk4" and a.final_type == ["imageorg", "stg2image"]
 
 
+def test_options_reject_unknown_training_modes():
+    """train_precision in {16, 32}, train_dgrad_products in {1, 3}: any other value is an error (it used to select the tight
+    mode without a word) -- at construction, in copy() and when adapting a reference namespace."""
+    for kw in (dict(train_precision=18), dict(train_precision=8), dict(train_precision="16"), dict(train_dgrad_products=2),
+               dict(train_dgrad_products=0), dict(train_precision=16, train_dgrad_products=4)):
+        with pytest.raises(ValueError):
+            Options(**kw)
+        with pytest.raises(ValueError):
+            Options().copy(**kw)
+    for tp in (16, 32):
+        for dp in (1, 3):
+            o = Options(train_precision=tp, train_dgrad_products=dp)
+            assert (o.train_precision, o.train_dgrad_products) == (tp, dp)
+            c = Options().copy(train_precision=tp, train_dgrad_products=dp)
+            assert (c.train_precision, c.train_dgrad_products) == (tp, dp) and c.maptype == o.maptype
+    a = from_reference_opt(types.SimpleNamespace(train_precision=16, train_dgrad_products=1, margin=0.2))
+    assert (a.train_precision, a.train_dgrad_products, a.margin) == (16, 1, 0.2)
+    assert from_reference_opt(types.SimpleNamespace(maptype="satellite_roadmap")).train_precision == 32
+    with pytest.raises(ValueError):
+        from_reference_opt(types.SimpleNamespace(train_precision=18))
+
+
+def test_training_mode_switch_is_scoped():
+    """train_graph.training_mode sets the fast-mode switches for the block only and restores them on exit, on an exception too
+    (MM.forward_q / DBVanilla2D.forward_db run their training forwards inside it)."""
+    from agplace_amd import train_graph
+    before = (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY)
+    with train_graph.training_mode(True, True):
+        assert (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY) == (True, True)
+        with train_graph.training_mode(True, False):
+            assert (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY) == (True, False)
+        assert (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY) == (True, True)
+    assert (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY) == before
+    with pytest.raises(RuntimeError):
+        with train_graph.training_mode(True, True):
+            raise RuntimeError("a failing forward")
+    assert (train_graph.FWD_F16, train_graph.DGRAD_HI_ONLY) == before
+
+
 def test_time_grid_equals_oracle_grid():
     for step in (0.1, 0.25, 0.3, 0.5, 1.0, 0.07):
         assert ops.ode_grid_dts(step) == ode.grid_dts(step).tolist()
