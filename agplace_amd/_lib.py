@@ -72,6 +72,8 @@ _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SIGNATURES = {
     "agp_version": (C.c_char_p, []),
     "agp_arch": (C.c_char_p, []),
+    "agp_range_flag_set": (_P, [_P]),
+    "agp_range_flag_get": (_P, []),
     "agp_split_f32": (_I, [_P, _P, _P, _L, _I, _P]),
     "agp_split_conv_weight": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "agp_split_conv_weight_both": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),

@@ -4,6 +4,15 @@
 extern "C" const char* agp_version(void) { return "agplace_hip 0.1.0"; }
 extern "C" const char* agp_arch(void) { return "gfx950"; }
 
+// The fp16 range guard's word of the calling host thread (include/agplace_hip.h); launchers read it through agp_range_flag_get.
+static thread_local uint32_t* t_range_flag = nullptr;
+extern "C" uint32_t* agp_range_flag_set(uint32_t* word) {
+    uint32_t* const prev = t_range_flag;
+    t_range_flag = word;
+    return prev;
+}
+extern "C" uint32_t* agp_range_flag_get(void) { return t_range_flag; }
+
 #if defined(AGP_TUNING)
 // Development build only (`make tuning`): the experiment switches that AGP_TUNE(key, default) reads, set by the A/B harnesses
 // under tools/ through this extra export.  The release library has neither the table nor the export: its AGP_TUNE is the

@@ -102,6 +102,68 @@ __device__ __forceinline__ u32x4 pack8_h_lo(const float* f, float lo) {
     return o;
 }
 __device__ __forceinline__ u32x4 pack8_h(const float* f) { return pack8_h_lo(f, -65504.f); }
+// ---- the fp16 range guard (include/agplace_hip.h: agp_range_flag_set).  A kernel that stores fp16 maps takes `bool RG` as a
+// template parameter and the bound word as its LAST argument (NULL when unguarded).  RangeTrack<false> holds nothing and every
+// call on it is empty, so the unguarded instantiation is the code it was before the guard existed.  RangeTrack<true> keeps per
+// lane the running maximum of the values its conversions clamp against +65504 (`hi`, v_max3_f32: two values per instruction,
+// the abs modifier free where the clamp is symmetric) and, where the lower bound is a runtime choice between -65504 and a folded
+// ReLU (0), the running minimum (`lo`); flush() ballots `beyond +-65504` over the wave and ONE lane ORs 1 into the word (a vector
+// atomic, relaxed, agent scope) -- no per-element atomics.  NaN compares false everywhere and is not reported.
+template <bool RG> struct RangeTrack {
+    float hi = 0.f, lo = 0.f;
+    __device__ __forceinline__ void sym2(float a, float b) {                 // clamp to [-65504, 65504]
+        if constexpr (RG) hi = __builtin_fmaxf(hi, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b)));
+    }
+    __device__ __forceinline__ void pos2(float a, float b) {                 // clamp to [0, 65504] (ReLU folded)
+        if constexpr (RG) hi = __builtin_fmaxf(hi, __builtin_fmaxf(a, b));
+    }
+    __device__ __forceinline__ void any2(float a, float b) {                 // clamp to [lo, 65504], lo known at flush()
+        if constexpr (RG) {
+            hi = __builtin_fmaxf(hi, __builtin_fmaxf(a, b));
+            lo = __builtin_fminf(lo, __builtin_fminf(a, b));
+        }
+    }
+    __device__ __forceinline__ void any8(const float* f) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) any2(f[2 * i], f[2 * i + 1]);
+    }
+    __device__ __forceinline__ void sym8(const float* f) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sym2(f[2 * i], f[2 * i + 1]);
+    }
+    // only where `fp16` holds (a map kernel whose output may also be a bf16 pair): in the unguarded form not even the test remains
+    __device__ __forceinline__ void sym8_if(bool fp16, const float* f) {
+        if constexpr (RG) {
+            if (fp16) sym8(f);
+        }
+    }
+    __device__ __forceinline__ void sym2_if(bool fp16, float a, float b) {
+        if constexpr (RG) {
+            if (fp16) sym2(a, b);
+        }
+    }
+    // clamp_lo: the lower bound any2() values were clamped to (0: ReLU, values below it are not saturation)
+    __device__ __forceinline__ void flush(uint32_t* word, float clamp_lo = -65504.f) {
+        if constexpr (RG) {
+            const bool bad = hi > 65504.f || (clamp_lo < 0.f && lo < -65504.f);
+            const uint64_t b = __builtin_amdgcn_ballot_w64(bad);
+            if (b && (int)(threadIdx.x & 63) == __builtin_ctzll(b))
+                __hip_atomic_fetch_or(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+};
+// The bound word reaches a guarded kernel as a TRAILING argument the unguarded instantiation does not have (a parameter pack
+// `RF... rf`, empty when unguarded): appending it to an argument struct, or appending a fixed argument, grows the kernel-argument
+// segment, and the compiler may then merge the scalar loads of the last fields differently (it did for igemm_kxr2, igemm_s2,
+// fblock64 and stem_walk) -- the unguarded code would change.
+__device__ __forceinline__ uint32_t* rg_word() { return nullptr; }
+__device__ __forceinline__ uint32_t* rg_word(uint32_t* w) { return w; }
+// Host: call fn(std::integral_constant<bool, RG>) with RG = (word != NULL) -- the launcher's one switch between the two forms.
+#include <type_traits>
+template <class F> static inline int agp_rg_dispatch(const uint32_t* word, F&& fn) {
+    return word ? fn(std::true_type{}) : fn(std::false_type{});
+}
+
 // element-wise maximum of eight packed NON-NEGATIVE fp16 values (post-ReLU maps): for such values the IEEE order is the
 // order of the bit patterns as signed 16-bit integers (-0 = 0x8000 sorts below everything), so v_pk_max_i16 is an exact
 // max that no floating-point mode (denormal flushing, NaN quieting) can touch; the max-pool stays in the storage format

@@ -76,9 +76,12 @@ struct Group {
 
 __device__ __forceinline__ int perm23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
-template <bool POOL, bool M16>
-__global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g) {
+// RG: the fp16 range guard (common.hpp RangeTrack) over BOTH conversions -- the intermediate map's into LDS and the output's.
+// rf: the bound word in the guarded instantiation (common.hpp rg_word), absent otherwise.
+template <bool POOL, bool M16, class... RF>
+__global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool RG = sizeof...(RF) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const XR = smem;
     char* const IR = smem + RING * ROWB;
@@ -304,11 +307,20 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g) {
             }
         }
     };
+    // the range guard: the values a lane stores as fp16, padding / dead columns (stored as zeros or not at all) left out
+    RangeTrack<RG> rg;
+    auto track16 = [&](const float* v, bool ok0, bool ok1) {
+        RangeTrack<RG> t0, t1;
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) { t0.pos2(v[e], v[e + 1]); t1.pos2(v[8 + e], v[9 + e]); }
+        rg.pos2(ok0 ? t0.hi : 0.f, ok1 ? t1.hi : 0.f);
+    };
     // conv1: intermediate rows R, R + 1 (a row that is not an image row is conv2's zero padding)
     auto write_ir = [&](int R, const Acc& acc, bool real) {
         char* const dst = IR + __builtin_amdgcn_readfirstlane((R & (RING - 1)) * ROWB);
         float v[16];
         bn(acc, v);
+        if constexpr (RG) track16(v, real && cin0, real && cin1);
         u32x4 o0 = pack8_h_lo(v, 0.f), o1 = pack8_h_lo(v + 8, 0.f);
         if (!(real && cin0)) o0 = u32x4{0u, 0u, 0u, 0u};
         if (!(real && cin1)) o1 = u32x4{0u, 0u, 0u, 0u};
@@ -358,6 +370,7 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g) {
         unpack8_h(r1, rf + 8);
 #pragma unroll
         for (int e = 0; e < 16; ++e) v[e] += rf[e];
+        if constexpr (RG) track16(v, real && sok0, real && sok1);
         u32x4 o0 = pack8_h_lo(v, 0.f), o1 = pack8_h_lo(v + 8, 0.f);
         // (LDS operations of one wave execute in order: the reads below see the writes above, and the next row's writes come
         // after these reads)
@@ -442,6 +455,7 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g) {
         if (!(dbg & 4)) __builtin_amdgcn_s_barrier();
     }
     if (role == 1) flush_pending();
+    rg.flush(rg_word(rf...), 0.f);
 #endif
 }
 
@@ -505,18 +519,24 @@ extern "C" int agp_bblock64_fwd_grouped(const agp_bblock64_desc* descs, int n, v
         g.wg_end[i] = wg;
     }
     const int form = descs[0].form == 0 ? 1 : 0;                // kernel template argument M16 (agp_bblock64_desc::form)
-    static std::atomic<uint64_t> attr_done[2][2];
-    const void* fn = pool ? (form ? (const void*)fblock64_kernel<true, true> : (const void*)fblock64_kernel<true, false>)
-                          : (form ? (const void*)fblock64_kernel<false, true> : (const void*)fblock64_kernel<false, false>);
-    const int lds = pool ? lds_bytes<true>() : lds_bytes<false>();
-    if (!agp_lds_attr(fn, lds, attr_done[pool][form])) return AGP_E_LAUNCH;
-    (void)hipGetLastError();
-    if (pool && form) hipLaunchKernelGGL((fblock64_kernel<true, true>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g);
-    else if (pool) hipLaunchKernelGGL((fblock64_kernel<true, false>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g);
-    else if (form) hipLaunchKernelGGL((fblock64_kernel<false, true>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL((fblock64_kernel<false, false>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g);
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    static std::atomic<uint64_t> attr_done[2][2][2];
+    uint32_t* const rflag = agp_range_flag_get();
+    // (RF...: the guarded instantiations take the word as one more argument, see common.hpp rg_word)
+    auto launch = [&](auto... rf) {
+        constexpr bool RG = sizeof...(rf) != 0;
+        const void* fn = pool ? (form ? (const void*)fblock64_kernel<true, true, decltype(rf)...> : (const void*)fblock64_kernel<true, false, decltype(rf)...>)
+                              : (form ? (const void*)fblock64_kernel<false, true, decltype(rf)...> : (const void*)fblock64_kernel<false, false, decltype(rf)...>);
+        const int lds = pool ? lds_bytes<true>() : lds_bytes<false>();
+        if (!agp_lds_attr(fn, lds, attr_done[RG][pool][form])) return AGP_E_LAUNCH;
+        (void)hipGetLastError();
+        if (pool && form) hipLaunchKernelGGL((fblock64_kernel<true, true, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
+        else if (pool) hipLaunchKernelGGL((fblock64_kernel<true, false, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
+        else if (form) hipLaunchKernelGGL((fblock64_kernel<false, true, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
+        else hipLaunchKernelGGL((fblock64_kernel<false, false, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
+        AGP_CHECK_LAUNCH();
+        return AGP_OK;
+    };
+    return rflag ? launch(rflag) : launch();
 }
 
 // mean_out[i][c] = (sum of image i's pair sums [pair][strip][c]) / (h w), fixed order: 16 slices of the entries per channel

@@ -46,8 +46,9 @@ constexpr int igemm_lds_bytes() {
 // The body is compiled in the device pass only: on the host pass hipcc (ROCm 7.2) silently
 // drops the stub of a kernel template whose body holds the 32x32x16 MFMA loop.
 #if defined(__HIP_DEVICE_COMPILE__)
-template <int WM, int WN, int BK, int NPREC, int EPI, int NST>
-__device__ __forceinline__ void igemm_body(const IgemmParams& p, const int bid) {
+// RG: the fp16 range guard (common.hpp RangeTrack) over the stored fp16 map, the bound word `rflag` (NPREC 2 / 4, EPI_CONV only).
+template <int WM, int WN, int BK, int NPREC, int EPI, int NST, bool RG = false>
+__device__ __forceinline__ void igemm_body(const IgemmParams& p, const int bid, uint32_t* rflag = nullptr) {
     constexpr int BM = WM * 64, BN = WN * 64, NW = WM * WN;
     constexpr int ROWB = BK * 2;          // bytes per LDS row
     constexpr int CPR = ROWB / 16;        // 16-B chunks per row
@@ -329,6 +330,7 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const int bid) 
     float st1[8], st2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { st1[e] = 0.f; st2[e] = 0.f; }
+    RangeTrack<RG> rg;
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm) {
         if (tm) __syncthreads();      // pass 0's reads are done before pass 1 overwrites the rows
@@ -367,6 +369,7 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const int bid) 
                 for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
             }
             if (p.dbg & 32) { if (v[0] == 1.2345678e30f) ohi[off] = 1; continue; }
+            rg.sym8(v);
             map_store8(ohi, olo, off, v);
             if constexpr (NPREC == 3) {
                 if (stats) {
@@ -376,6 +379,7 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const int bid) 
             }
         }
     }
+    rg.flush(rflag);
     if constexpr (NPREC == 3) {
         if (stats) {
             // lanes sharing a channel chunk (lane & 7) -> wave totals; the WM waves of a column block -> tile totals, fixed order
@@ -412,10 +416,10 @@ __device__ __forceinline__ void igemm_body(const IgemmParams& p, const int bid) 
 }
 #endif  // __HIP_DEVICE_COMPILE__
 
-template <int WM, int WN, int BK, int NPREC, int EPI, int NST>
-__global__ void __launch_bounds__(WM* WN * 64) igemm_kernel(IgemmParams p) {
+template <int WM, int WN, int BK, int NPREC, int EPI, int NST, bool RG = false>
+__global__ void __launch_bounds__(WM* WN * 64) igemm_kernel(IgemmParams p, uint32_t* rflag) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    igemm_body<WM, WN, BK, NPREC, EPI, NST>(p, blockIdx.x);
+    igemm_body<WM, WN, BK, NPREC, EPI, NST, RG>(p, blockIdx.x, rflag);
 #endif
 }
 
@@ -427,9 +431,10 @@ struct IgemmGroup {
     IgemmParams p[4];
     int start[5];
     int n;
+    uint32_t* rflag;           // the fp16 range guard's word (agp_range_flag_get), read by the RG = true instantiations only
 };
 
-template <int WM, int WN, int BK, int NPREC, int EPI, int NST>
+template <int WM, int WN, int BK, int NPREC, int EPI, int NST, bool RG = false>
 __global__ void __launch_bounds__(WM* WN * 64) igemm_group_kernel(IgemmGroup g) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int bid = blockIdx.x;
@@ -438,19 +443,20 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_group_kernel(IgemmGroup g) 
     for (int i = 1; i < 4; ++i)
         if (i < g.n && bid >= g.start[i]) prob = i;
     prob = __builtin_amdgcn_readfirstlane(prob);
-    igemm_body<WM, WN, BK, NPREC, EPI, NST>(g.p[prob], bid - g.start[prob]);
+    igemm_body<WM, WN, BK, NPREC, EPI, NST, RG>(g.p[prob], bid - g.start[prob], g.rflag);
 #endif
 }
 
 // Grouped launch of the fp16 single-product configuration (the only one the product groups): every problem must
 // satisfy CK % 32 == 0 and N % 128 == 0.
-template <int BK, int NST>
+template <int BK, int NST, bool RG = false>
 int launch_group_f16_cfg(IgemmParams* ps, int n, hipStream_t s) {
     constexpr int WM = 2, WN = 2, NPREC = 4;
     constexpr int lds = igemm_lds_bytes<WM, WN, BK, NPREC, NST>();
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr((const void*)igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     IgemmGroup g = {};
+    g.rflag = RG ? agp_range_flag_get() : nullptr;
     g.n = n;
     int grid = 0;
     for (int i = 0; i < n; ++i) {
@@ -463,7 +469,7 @@ int launch_group_f16_cfg(IgemmParams* ps, int n, hipStream_t s) {
         grid += p.mt_chunk * 8 * p.NT;
     }
     for (int i = n; i < 5; ++i) g.start[i] = grid;
-    AGP_LAUNCH((igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST>), dim3(grid), dim3(WM * WN * 64), lds, s, g);
+    AGP_LAUNCH((igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST, RG>), dim3(grid), dim3(WM * WN * 64), lds, s, g);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -477,24 +483,33 @@ int launch_group_f16(IgemmParams* ps, int n, hipStream_t s) {
     if (var == 1) return launch_group_f16_cfg<64, 2>(ps, n, s);
     if (var == 2) return launch_group_f16_cfg<32, 2>(ps, n, s);
 #endif
-    return launch_group_f16_cfg<32, 3>(ps, n, s);
+    return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) { return launch_group_f16_cfg<32, 3, decltype(rg)::value>(ps, n, s); });
 }
 
-template <int WM, int WN, int BK, int NPREC, int EPI, int NST>
-int launch_cfg(IgemmParams& p, hipStream_t s) {
+template <int WM, int WN, int BK, int NPREC, int EPI, int NST, bool RG = false>
+int launch_cfg_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s) {
     constexpr int lds = igemm_lds_bytes<WM, WN, BK, NPREC, NST>();
     static_assert(lds <= 160 * 1024, "LDS budget");
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_kernel<WM, WN, BK, NPREC, EPI, NST>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr((const void*)igemm_kernel<WM, WN, BK, NPREC, EPI, NST, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     constexpr int BM = WM * 64, BN = WN * 64;
     p.MT = (p.M + BM - 1) / BM;
     p.NT = (p.N + BN - 1) / BN;
     p.mt_chunk = (p.MT + 7) / 8;
     const int grid = p.mt_chunk * 8 * p.NT;
     const int splits = 1;
-    AGP_LAUNCH((igemm_kernel<WM, WN, BK, NPREC, EPI, NST>), dim3(grid, splits), dim3(WM * WN * 64), lds, s, p);
+    AGP_LAUNCH((igemm_kernel<WM, WN, BK, NPREC, EPI, NST, RG>), dim3(grid, splits), dim3(WM * WN * 64), lds, s, p, rflag);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
+}
+// the fp16 conv configurations have a guarded twin (fp16 maps); the bf16-pair and kNN ones store no fp16 map
+template <int WM, int WN, int BK, int NPREC, int EPI, int NST>
+int launch_cfg(IgemmParams& p, hipStream_t s) {
+    if constexpr (EPI == EPI_CONV && PrecT<NPREC>::F16) {
+        uint32_t* const rflag = agp_range_flag_get();
+        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_cfg_rg<WM, WN, BK, NPREC, EPI, NST, decltype(rg)::value>(p, rflag, s); });
+    }
+    return launch_cfg_rg<WM, WN, BK, NPREC, EPI, NST>(p, nullptr, s);
 }
 
 // Tuning hook (development build only): IGEMM_VARIANT selects an alternative tile / pipeline configuration.

@@ -36,8 +36,9 @@ constexpr int d16_lds_bytes() {
 // the 7x7 outputs of MaxPool2d(3, 2, 1) it fully contains are written.  The full-resolution stem map (4x the
 // pooled one, otherwise written once and read once) never exists; 27 % of the conv is recomputed at the
 // block seams.
-template <int NTW, int NPREC, int POOL = 0>
-__global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(IgemmParams p) {
+// RG: the fp16 range guard (common.hpp RangeTrack) over the stored fp16 map, the bound word `rflag` (NPREC 2 / 4 only).
+template <int NTW, int NPREC, int POOL = 0, bool RG = false>
+__global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(IgemmParams p, uint32_t* rflag) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = 256, BN = NTW * 16;
     constexpr int NPL = PrecT<NPREC>::XPL, WPL = PrecT<NPREC>::WPL;   // NPL: X planes held in registers
@@ -46,6 +47,7 @@ __global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(Igem
     constexpr int WI = BN / 64;                 // W LDS-DMA instructions per wave per plane
     constexpr int EROWB = BN * 4 + 16;          // epilogue row: BN fp32 + pad
     constexpr int LPP = BN / 8;                 // lanes per pixel in the epilogue read-back
+    RangeTrack<RG> rg;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -199,6 +201,8 @@ __global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(Igem
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = ok ? fmaxf(acc[nt][mt][e] * sc4[e] + sh4[e], 0.f) : 0.f;
                 const int px = (4 * wave + mt) * 16 + l15;
+                rg.sym2(v[0], v[1]);
+                rg.sym2(v[2], v[3]);
                 u32x2 pk = {pack2(f2h(v[0]), f2h(v[1])), pack2(f2h(v[2]), f2h(v[3]))};
                 *(u32x2*)(blk + px * PP + c0) = pk;
             }
@@ -225,6 +229,7 @@ __global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(Igem
             const size_t off = (size_t)pimg * p.o_sn + (size_t)oy * p.o_sh + (size_t)ox * p.o_sw + p.o_base + g * 8;
             *(u32x4*)(ohi + off) = pack8_h(best);
         }
+        rg.flush(rflag);
         return;
     }
 
@@ -282,6 +287,7 @@ __global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(Igem
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
             }
+            rg.sym8(v);
             map_store8(ohi, olo, off, v);
             if (stats) {
 #pragma unroll
@@ -321,6 +327,7 @@ __global__ void __launch_bounds__(256, (NTW == 4 ? 3 : 2)) igemm_d16_kernel(Igem
             p.stat_partial[(size_t)mt * 2 * p.N + p.N + n0 + tid] = b;
         }
     }
+    rg.flush(rflag);
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
@@ -501,29 +508,42 @@ int launch_stem_pool_lds(IgemmParams& p, const StemRaw& raw, hipStream_t s) {
     return AGP_OK;
 }
 
-template <int NTW, int NPREC>
-int launch_d16(IgemmParams& p, hipStream_t s) {
+template <int NTW, int NPREC, bool RG>
+int launch_d16_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s) {
     constexpr int lds = d16_lds_bytes<NTW, NPREC>();
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_d16_kernel<NTW, NPREC>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr((const void*)igemm_d16_kernel<NTW, NPREC, 0, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     p.MT = (p.M + 255) / 256;
     p.NT = (p.N + NTW * 16 - 1) / (NTW * 16);
     p.mt_chunk = (p.MT + 7) / 8;
-    AGP_LAUNCH((igemm_d16_kernel<NTW, NPREC>), dim3(p.mt_chunk * 8 * p.NT), dim3(256), lds, s, p);
+    AGP_LAUNCH((igemm_d16_kernel<NTW, NPREC, 0, RG>), dim3(p.mt_chunk * 8 * p.NT), dim3(256), lds, s, p, rflag);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
+template <int NTW, int NPREC>
+int launch_d16(IgemmParams& p, hipStream_t s) {
+    if constexpr (PrecT<NPREC>::F16) {
+        uint32_t* const rflag = agp_range_flag_get();
+        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_d16_rg<NTW, NPREC, decltype(rg)::value>(p, rflag, s); });
+    }
+    return launch_d16_rg<NTW, NPREC, false>(p, nullptr, s);
+}
 
 // fused stem + max-pool launch (fp16 maps, 64 output channels)
-template <int NPREC>
-int launch_d16_pool(IgemmParams& p, hipStream_t s) {
+template <int NPREC, bool RG>
+int launch_d16_pool_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s) {
     constexpr int lds = d16_lds_bytes<4, NPREC>() > 256 * 72 * 2 ? d16_lds_bytes<4, NPREC>() : 256 * 72 * 2;
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_d16_kernel<4, NPREC, 1>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr((const void*)igemm_d16_kernel<4, NPREC, 1, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     const int n = p.M / (p.pool_h1 * p.pool_w1);
-    AGP_LAUNCH((igemm_d16_kernel<4, NPREC, 1>), dim3(n * p.pool_ty * p.pool_tx), dim3(256), lds, s, p);
+    AGP_LAUNCH((igemm_d16_kernel<4, NPREC, 1, RG>), dim3(n * p.pool_ty * p.pool_tx), dim3(256), lds, s, p, rflag);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
+}
+template <int NPREC>
+int launch_d16_pool(IgemmParams& p, hipStream_t s) {
+    uint32_t* const rflag = agp_range_flag_get();
+    return agp_rg_dispatch(rflag, [&](auto rg) { return launch_d16_pool_rg<NPREC, decltype(rg)::value>(p, rflag, s); });
 }
 
 }  // namespace agp_igemm

@@ -73,9 +73,12 @@ constexpr int kxr_min_blocks() {
 // MF = MFMA shape: 32 = 32x32x16 (two K-steps per tap phase), 16 = 16x16x32 (one): same operand bytes and MFMA
 // cycles per phase, but the chip holds a higher clock under load with the 16x16x32 form (MI355X_MICROARCH.md,
 // DVFS item 7), and these kernels are clock-limited: the same launch runs 1.37x faster on all-zero operands.
-template <int BM, int BN, int WM, int WN, int NPREC, int RING, int MF = 32, bool LDS_EPI = false, bool Q8 = false>
-__global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>())) igemm_kxr_kernel(IgemmParams p) {
+// rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
+template <int BM, int BN, int WM, int WN, int NPREC, int RING, int MF = 32, bool LDS_EPI = false, bool Q8 = false, class... RF>
+__global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>())) igemm_kxr_kernel(IgemmParams p, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool RG = sizeof...(RF) != 0;
+    RangeTrack<RG> rg;
     static_assert(MF == 32 || (MF == 16 && RING >= 2), "the 16x16x32 form exists for the phase-pipelined loop only");
     static_assert(!Q8 || (NPREC == 2 && RING >= 2 && MF == 32), "Q8: the fp8 lo product of the F16W2 mode, phase-pipelined 32x32 loop only");
     constexpr int NW = WM * WN;
@@ -691,9 +694,11 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
+                rg.sym8(v);
                 *(u32x4*)(ohi + doff[tm] + 16 * j) = pack8_h(v);
             }
         }
+        rg.flush(rg_word(rf...));
         return;
     }
     // ---- epilogue (as igemm.hip), halo columns masked; one pass per 32-pixel tile row
@@ -780,6 +785,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                             for (int e = 0; e < 8; ++e) v[e] += r[e];
                         }
                     }
+                    rg.sym8(v);
                     map_store8(ohi, olo, cur.off, v);
                     float zz[8], zl[8];
                     if (bz_lo) { unpack8(cur.zh, zz); unpack8(cur.zl, zl); }
@@ -822,6 +828,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
             }
+            rg.sym8(v);
             map_store8(ohi, olo, off, v);
             if (stats) {
 #pragma unroll
@@ -829,6 +836,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
             }
         }
     }
+    rg.flush(rg_word(rf...));
     if (bstats) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) st2[e] *= p.bs_rstd[nglob + e];
@@ -885,11 +893,22 @@ int launch_kxr(IgemmParams& p, hipStream_t s) {
     constexpr int lds = kxr_lds_bytes<BM, BN, WM, WN, NPREC, RING>();
     static_assert(lds <= (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 3 ? 53 : (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 2 ? 80 : 160)) * 1024,
                   "LDS budget of the intended workgroups per CU");
-    static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
+    static std::atomic<uint64_t> attr_done{0}, attr_done_rg{0};
     p.MT = (p.M + BM - 1) / BM;
     p.NT = (p.N + BN - 1) / BN;
     p.mt_chunk = (p.MT + 7) / 8;
+    // fp16 maps (modes 2 / 4): the guarded twin while a range-guard word is bound (common.hpp RangeTrack)
+    if constexpr (PrecT<NPREC>::F16) {
+        if (uint32_t* const rflag = agp_range_flag_get()) {
+            if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>, lds, attr_done_rg))
+                return AGP_E_LAUNCH;
+            AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>), dim3(p.mt_chunk * 8 * p.NT),
+                       dim3(WM * WN * 64), lds, s, p, rflag);
+            AGP_CHECK_LAUNCH();
+            return AGP_OK;
+        }
+    }
+    if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
     AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>), dim3(p.mt_chunk * 8 * p.NT), dim3(WM * WN * 64), lds, s, p);
     AGP_CHECK_LAUNCH();
     return AGP_OK;

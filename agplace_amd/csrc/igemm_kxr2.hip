@@ -112,9 +112,11 @@ constexpr int kxr2_lds_bytes() { return (PF ? 3 : 2) * (BM + 16) * 64 + (PF ? 4 
 // bare MFMAs against 100-185 at the head of a phase, and in front of the MFMAs that time sits on the wave's chain); all fragment
 // reads of the phase come first (an LDS-DMA write may not pass an LDS read in program order), the last macro-step is peeled so
 // that the loop body has no branch (one scheduling region per phase).
-template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW_ = 4, bool SCH = false>
-__global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g) {
+// rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
+template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW_ = 4, bool SCH = false, class... RF>
+__global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool RG = sizeof...(RF) != 0;
     static_assert(!SCH || (!PF && !M16 && NW_ == 4), "scheduled variant: the plain loop of the four-wave 32x32x16 kernel");
     static_assert(!(M16 && PF), "the 16x16x32 variant is built without the fragment-prefetch pipeline");
     static_assert(!M16 || BM == 256, "16x16x32 variant: 256-row tiles");
@@ -640,6 +642,7 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g)
     const float* tb = tab + 8 * lh;
     bf16_t* const ohi = (bf16_t*)p.o_hi;
     const float relu_lo = p.relu ? 0.f : -65504.f;
+    RangeTrack<RG> rg;
     // LDS accesses in BATCHES (all reads of a step issued before the first use): written value by value the compiler
     // serialises ~10 dependent LDS round trips per tile row -- the census showed 3.8 us of epilogue per tile, not the stores.
     // (scale / shift are re-read per tile row in two halves: holding all 64 values would cost the third wave per SIMD)
@@ -697,6 +700,7 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g)
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] += r[e];
                 }
+                rg.any8(v);
                 outv[jj] = pack8_h_lo(v, relu_lo);         // ReLU folded into the fp16 saturation clamp (one med3 per value)
             }
         }
@@ -721,6 +725,7 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g)
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += r[e];
                     }
+                    rg.any8(v);
                     outv[2 * ph + u] = pack8_h_lo(v, relu_lo);
                 }
             }
@@ -770,6 +775,7 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g)
             if (ppp || pool_sq) o[pN] = psum[1];
         }
     }
+    rg.flush(rg_word(rf...), relu_lo);
 #if AGP_CENSUS
     if (census && tid == 0) {
         rec[4 + 3] = __builtin_amdgcn_s_memrealtime();          // epilogue issued
@@ -780,12 +786,13 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g)
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW = 4, bool SCH = false>
+template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW = 4, bool SCH = false, bool RG = false>
 int launch_kxr2(Kxr2Group& g, hipStream_t s) {
     constexpr int lds = kxr2_lds_bytes<BM, PF>();
     static_assert(lds * (MINB * 4 / NW) <= 160 * 1024, "LDS budget of the intended workgroups per CU");
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr(RG ? (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>
+                         : (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>, lds, attr_done)) return AGP_E_LAUNCH;
     int mt = 0;
     for (int i = 0; i < g.nprob; ++i) {
         mt += (g.p[i].M + BM - 1) / BM;
@@ -794,7 +801,12 @@ int launch_kxr2(Kxr2Group& g, hipStream_t s) {
     g.MT = mt;
     g.NT = (g.p[0].N + 63) / 64;
     g.mt_chunk = (g.MT + 7) / 8;
-    AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>), dim3(g.mt_chunk * 8 * g.NT), dim3(NW * 64), lds, s, g);
+    if constexpr (RG) {
+        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>), dim3(g.mt_chunk * 8 * g.NT), dim3(NW * 64), lds, s, g,
+                   agp_range_flag_get());
+    } else {
+        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>), dim3(g.mt_chunk * 8 * g.NT), dim3(NW * 64), lds, s, g);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -829,7 +841,10 @@ int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s) {
     if (!pool && var == 2) return launch_kxr2<256, 2>(g, s);
     if (!pool && var == 3) return launch_kxr2<256, 2, true>(g, s);
 #endif
-    if (pool)                           // (agp_conv2d_pool_blocks promises this tile shape)
-        return launch_kxr2<256, 3, false, true, false, 4, true>(g, s);
-    return launch_kxr2<256, 3, false, false, false, 4, true>(g, s);
+    return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) {
+        constexpr bool RG = decltype(rg)::value;
+        if (pool)                       // (agp_conv2d_pool_blocks promises this tile shape)
+            return launch_kxr2<256, 3, false, true, false, 4, true, RG>(g, s);
+        return launch_kxr2<256, 3, false, false, false, 4, true, RG>(g, s);
+    });
 }

@@ -38,6 +38,7 @@ struct KxrwGroup {
     // round 6, the launch's LAST round of workgroups as HALF tiles (128 rows): row tiles [MT_full, MT) of the global sequence are
     // not in the XCD-ordered part of the grid but follow it as 2 (MT - MT_full) NT blocks from block `half_bid0` on
     int MT_full, half_bid0;
+    uint32_t* rflag;           // the fp16 range guard's word (agp_range_flag_get), read by the RG = true instantiations only
 };
 
 template <int N> __device__ __forceinline__ void kw_wait() {
@@ -64,7 +65,7 @@ template <int TM_, int TN_> struct KwShape {
 };
 
 // One tile: rows [m0, m0 + 128 TM_) x columns [n0, n0 + 32 TN_) of problem g.p[pid].
-template <bool POOL, bool SCHED, int TM_, int TN_>
+template <bool POOL, bool SCHED, int TM_, int TN_, bool RG = false>
 __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, const int m0, const int n0) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using SH = KwShape<TM_, TN_>;
@@ -370,6 +371,7 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     const float* tb = tab + 8 * lh;
     bf16_t* const ohi = (bf16_t*)p.o_hi;
     const float relu_lo = p.relu ? 0.f : -65504.f;
+    RangeTrack<RG> rg;
     float psum[2][2] = {{0.f, 0.f}, {0.f, 0.f}};       // [channel half][stat]
     const float* const ppp = POOL ? p.pool_p : nullptr;
     const float pool_pw = ppp ? ppp[0] : 1.f, pool_eps = POOL ? p.pool_eps : 0.f;
@@ -403,6 +405,7 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] += r[e];
             }
+            rg.any8(v);
             outv[jj] = pack8_h_lo(v, relu_lo);
         }
 #pragma unroll
@@ -478,13 +481,14 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
             }
         }
     }
+    rg.flush(g.rflag, relu_lo);
 #endif
 }
 
 // block -> (problem, row tile, column tile).  XCD x owns a contiguous chunk of the global row tiles [0, MT_full); MIX: the blocks
 // from half_bid0 on are the HALF tiles (128 rows) of the row tiles [MT_full, MT) -- the launch's last, partial round of workgroups.
 // They carry the highest block ids, so they are dispatched last: the long tiles first, the short ones fill the end.
-template <bool POOL, bool SCHED = false, int TM_ = 2, int TN_ = 4, bool MIX = false>
+template <bool POOL, bool SCHED = false, int TM_ = 2, int TN_ = 4, bool MIX = false, bool RG = false>
 __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int BM = KwShape<TM_, TN_>::BM, BN = KwShape<TM_, TN_>::BN;
@@ -517,23 +521,23 @@ __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
         if (half) {
             const int m0 = mt * BM + sub * (BM / 2);
             if (m0 >= g.p[pid].M) return;                  // the second half of a problem's last, partial row tile
-            kxrw_tile<POOL, SCHED, 1, TN_>(g, pid, m0, n0);
+            kxrw_tile<POOL, SCHED, 1, TN_, RG>(g, pid, m0, n0);
             return;
         }
     }
-    kxrw_tile<POOL, SCHED, TM_, TN_>(g, pid, mt * BM, n0);
+    kxrw_tile<POOL, SCHED, TM_, TN_, RG>(g, pid, mt * BM, n0);
 #endif
 }
 
-template <bool POOL, bool SCHED, int TM_ = 2, int TN_ = 4, bool MIX = false>
+template <bool POOL, bool SCHED, int TM_ = 2, int TN_ = 4, bool MIX = false, bool RG = false>
 int launch_kxrw(KxrwGroup& g, hipStream_t s) {
     constexpr int lds = KwShape<TM_, TN_>::LDS;
     static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
     static_assert(!MIX || (TM_ == 2 && KwShape<1, TN_>::LDS + 3072 <= lds), "half tiles: their stage + the pooling scratch fit the full tile's LDS");
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr((const void*)igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     const int nblocks = g.mt_chunk * 8 * g.NT + (MIX ? 2 * (g.MT - g.MT_full) * g.NT : 0);
-    AGP_LAUNCH((igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX>), dim3(nblocks), dim3(256), lds, s, g);
+    AGP_LAUNCH((igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>), dim3(nblocks), dim3(256), lds, s, g);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -592,6 +596,10 @@ int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s) {
     }
     if (!sched) return pool ? launch_kxrw<true, false>(g, s) : launch_kxrw<false, false>(g, s);
 #endif
-    if (mix) return pool ? launch_kxrw<true, true, 2, 4, true>(g, s) : launch_kxrw<false, true, 2, 4, true>(g, s);
-    return pool ? launch_kxrw<true, true>(g, s) : launch_kxrw<false, true>(g, s);
+    g.rflag = agp_range_flag_get();
+    return agp_rg_dispatch(g.rflag, [&](auto rg) {
+        constexpr bool RG = decltype(rg)::value;
+        if (mix) return pool ? launch_kxrw<true, true, 2, 4, true, RG>(g, s) : launch_kxrw<false, true, 2, 4, true, RG>(g, s);
+        return pool ? launch_kxrw<true, true, 2, 4, false, RG>(g, s) : launch_kxrw<false, true, 2, 4, false, RG>(g, s);
+    });
 }

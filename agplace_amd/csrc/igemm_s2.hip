@@ -62,9 +62,11 @@ template <int TN> constexpr int s2_lds() {              // X double buffer, W ri
 // 4 = 128 x 128 tiles (71 KB: two per CU, 8 MFMAs per phase, the X blocks staged once per 128 channels).
 // SCH (the default; AGP_S2_SCHED=0 turns it off): a phase's LDS-DMA pieces are issued among its MFMAs instead of in front of them,
 // all of the phase's fragment reads first, the last macro-step peeled (see igemm_kxrw.hip).
-template <int TN, bool SCH = false>
-__global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group g) {
+// rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
+template <int TN, bool SCH = false, class... RF>
+__global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool RG = sizeof...(RF) != 0;
     constexpr int BM = S2_BM, BN = 32 * TN, NW = 4, ROWB = S2_ROWB;
     constexpr int S2_WTAP = BN * S2_ROWB;
     constexpr int NWP = TN / 2;                         // LDS-DMA instructions per wave for one W piece (BN rows of 64 B)
@@ -392,7 +394,8 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
     char* const strip = smem + wave * (32 * ERS);
     const int a_off = l31 * ERS + lh * 16;
     const int l_off = (lane / LPP) * ERS + (lane % LPP) * 16;
-    auto epilogue = [&](const f32x16* a, const float* tb0, bf16_t* out, float relu_lo) {
+    RangeTrack<RG> rg;
+    auto epilogue = [&](const f32x16* a, const float* tb0, bf16_t* out, float relu_lo, bool sym) {
         const float* tb = tb0 + 8 * lh;
         u32x4 outv[TN * 2];
 #pragma unroll
@@ -402,6 +405,8 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
             float v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = a[jj >> 1][8 * (jj & 1) + e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? h0[e & 3] : h1[e & 3]);
+            if (sym) rg.sym8(v);
+            else rg.any8(v);
             outv[jj] = pack8_h_lo(v, relu_lo);
         }
 #pragma unroll
@@ -415,8 +420,9 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
             if (eoff[i] >= 0) *(u32x4*)(out + eoff[i]) = lines[i];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     };
-    epilogue(acc, tab, (bf16_t*)p.o_hi, p.relu ? 0.f : -65504.f);
-    if (has_ds) epilogue(acc2, tab + 2 * BN, (bf16_t*)p.o2_hi, -65504.f);
+    epilogue(acc, tab, (bf16_t*)p.o_hi, p.relu ? 0.f : -65504.f, false);
+    if (has_ds) epilogue(acc2, tab + 2 * BN, (bf16_t*)p.o2_hi, -65504.f, true);
+    rg.flush(rg_word(rf...), p.relu ? 0.f : -65504.f);
 #endif
 }
 
@@ -452,9 +458,9 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
     g.mt_chunk = (g.MT + 7) / 8;
     const int wide = AGP_TUNE("S2_WIDE", 1);            // development build, 0: 64-channel tiles for every width
     const int sch = AGP_TUNE("S2_SCHED", 1);            // development build, 0: LDS-DMA pieces at the head of a phase
-    auto launch = [&](auto kern, int lds, std::atomic<uint64_t>& attr) -> int {
+    auto launch = [&](auto kern, int lds, std::atomic<uint64_t>& attr, auto... rf) -> int {
         if (!agp_lds_attr((const void*)kern, lds, attr)) return AGP_E_LAUNCH;
-        AGP_LAUNCH(kern, dim3(g.mt_chunk * 8 * g.NT), dim3(256), lds, s, g);
+        AGP_LAUNCH(kern, dim3(g.mt_chunk * 8 * g.NT), dim3(256), lds, s, g, rf...);
         return AGP_OK;
     };
     static std::atomic<uint64_t> a4s{0}, a2s{0};
@@ -466,12 +472,14 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
         else { g.NT = (ps[0].N + 63) / 64; rc = launch(igemm_s2_kernel<2, false>, s2_lds<2>(), a2); }
     } else
 #endif
-    if (wide && ps[0].N % 128 == 0) {
-        g.NT = ps[0].N / 128;
-        rc = launch(igemm_s2_kernel<4, true>, s2_lds<4>(), a4s);
-    } else {
-        g.NT = (ps[0].N + 63) / 64;
-        rc = launch(igemm_s2_kernel<2, true>, s2_lds<2>(), a2s);
+    {
+        static std::atomic<uint64_t> a4g{0}, a2g{0};
+        uint32_t* const rflag = agp_range_flag_get();
+        const bool w4 = wide && ps[0].N % 128 == 0;
+        g.NT = w4 ? ps[0].N / 128 : (ps[0].N + 63) / 64;
+        if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, true, uint32_t*>, s2_lds<4>(), a4g, rflag)
+                           : launch(igemm_s2_kernel<2, true, uint32_t*>, s2_lds<2>(), a2g, rflag);
+        else rc = w4 ? launch(igemm_s2_kernel<4, true>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2, true>, s2_lds<2>(), a2s);
     }
     (void)sch;
     if (rc != AGP_OK) return rc;

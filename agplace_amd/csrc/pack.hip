@@ -43,10 +43,13 @@ __global__ void split_f32_kernel(const float* __restrict__ x, bf16_t* __restrict
 }
 
 // one thread per (pixel, group of CG channels); CG = 4 (stem, cpad == 4) or 8
-template <int CG>
+// rf (here and in pack_nchw4_kernel / bcast_add_kernel): the fp16 range guard's word in the guarded instantiation (common.hpp
+// rg_word), absent otherwise; fp16 planes only (lo == NULL: a bf16 pair does not clamp)
+template <int CG, class... RF>
 __global__ void pack_kernel(const float* __restrict__ x, int64_t sn, int64_t sc, int64_t sh,
                             int64_t sw, int n, int c, int h, int w, int cpad, int pad,
-                            bf16_t* __restrict__ hi, bf16_t* __restrict__ lo) {
+                            bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
     const int groups = cpad / CG;
     const int64_t total = (int64_t)n * h * w * groups;
     const int hp = h + 2 * pad, wp = w + 2 * pad;
@@ -63,6 +66,7 @@ __global__ void pack_kernel(const float* __restrict__ x, int64_t sn, int64_t sc,
         for (int e = 0; e < CG; ++e) {
             const int ch = g * CG + e;
             const float v = ch < c ? src[ch * sc] : 0.f;
+            rg.sym2_if(!lo, v, 0.f);
             map_split1(v, lo != nullptr, hh[e], ll[e]);
         }
         const size_t off = (((size_t)im * hp + py + pad) * wp + px + pad) * cpad + g * CG;
@@ -79,15 +83,17 @@ __global__ void pack_kernel(const float* __restrict__ x, int64_t sn, int64_t sc,
             }
         }
     }
+    rg.flush(rg_word(rf...));
 }
 
 // Fast path of the stem input: fp32 NCHW planes with unit pixel stride, c <= 4 -> NHWC4.  One thread per FOUR pixels of a
 // row: one 16-byte load per channel plane, 32 contiguous output bytes, 32-bit index arithmetic with fast division
 // (the generic kernel does five 64-bit divisions per pixel and moves 12 + 8 bytes per thread).
+template <class... RF>
 __global__ __launch_bounds__(256) void pack_nchw4_kernel(const float* __restrict__ x, int64_t sn, int64_t sc, int64_t sh,
                                                          int n, int c, int h, int w, int pad, FastDiv dw4, FastDiv dh,
                                                          bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
-                                                         bf16_t* __restrict__ h16 = nullptr) {
+                                                         bf16_t* __restrict__ h16, RF... rf) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     const uint32_t w4 = dw4.d;
     if (t >= (uint32_t)n * h * w4) return;
@@ -97,6 +103,10 @@ __global__ __launch_bounds__(256) void pack_nchw4_kernel(const float* __restrict
     f32x4 v[4];
 #pragma unroll
     for (int ch = 0; ch < 4; ++ch) v[ch] = ch < c ? *(const f32x4*)(src + ch * sc) : f32x4{0.f, 0.f, 0.f, 0.f};
+    RangeTrack<sizeof...(RF) != 0> rg;
+    const bool f16 = !lo || h16;                         // an fp16 plane is written (the map, or the operand plane)
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) { rg.sym2_if(f16, v[ch][0], v[ch][1]); rg.sym2_if(f16, v[ch][2], v[ch][3]); }
     const int hp = h + 2 * pad, wp = w + 2 * pad;
     const size_t off = (((size_t)im * hp + py + pad) * wp + px + pad) * 4;
 #pragma unroll
@@ -112,6 +122,7 @@ __global__ __launch_bounds__(256) void pack_nchw4_kernel(const float* __restrict
             *(u32x2*)(h16 + off + 4 * k) = e;
         }
     }
+    rg.flush(rg_word(rf...));
 }
 
 __global__ void unpack_kernel(const bf16_t* __restrict__ hi, const bf16_t* __restrict__ lo, int n,
@@ -182,9 +193,11 @@ __global__ void maxpool_kernel(const bf16_t* __restrict__ ihi, const bf16_t* __r
     }
 }
 
+template <class... RF>
 __global__ void bcast_add_kernel(const bf16_t* __restrict__ ihi, const bf16_t* __restrict__ ilo,
                                  const float* __restrict__ vec, int n, int h, int w, int c, int pin,
-                                 bf16_t* __restrict__ ohi, bf16_t* __restrict__ olo, int pout) {
+                                 bf16_t* __restrict__ ohi, bf16_t* __restrict__ olo, int pout, RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
     const int groups = c / 8;
     const int64_t total = (int64_t)n * h * w * groups;
     const int hip_ = h + 2 * pin, wip = w + 2 * pin, hop = h + 2 * pout, wop = w + 2 * pout;
@@ -202,8 +215,10 @@ __global__ void bcast_add_kernel(const bf16_t* __restrict__ ihi, const bf16_t* _
         const float* ve = vec + (size_t)im * c + g * 8;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += ve[e];
+        rg.sym8_if(!olo, v);
         map_store8(ohi, olo, ooff, v);
     }
+    rg.flush(rg_word(rf...));
 }
 
 // uint8 HWC camera tiles -> normalised NHWC4 stem input, tiles concatenated along W:
@@ -415,8 +430,14 @@ extern "C" int agp_pack_f32_to_nhwc4_h16(const float* x, int64_t sn, int64_t sc,
           (int64_t)n * h * (w / 4) < (1ll << 31)))
         return AGP_E_UNSUPPORTED;
     const int64_t threads = (int64_t)n * h * (w / 4);
-    AGP_LAUNCH(pack_nchw4_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, n, c, h,
-               w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)h16);
+    if (uint32_t* const rf = agp_range_flag_get()) {
+        AGP_LAUNCH((pack_nchw4_kernel<uint32_t*>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc,
+                   sh, n, c, h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)h16,
+                   rf);
+    } else {
+        AGP_LAUNCH((pack_nchw4_kernel<>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, n, c,
+                   h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)h16);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -425,19 +446,37 @@ extern "C" int agp_pack_f32_to_nhwc(const float* x, int64_t sn, int64_t sc, int6
                                     int n, int c, int h, int w, int cpad, int pad, void* hi,
                                     void* lo, void* stream) {
     if (!x || !hi || cpad < c || n <= 0) return AGP_E_BADARG;
+    uint32_t* const rf = agp_range_flag_get();
     if (cpad == 4 && sw == 1 && c <= 4 && w % 4 == 0 && ((uintptr_t)x % 16) == 0 && sn % 4 == 0 && sc % 4 == 0 && sh % 4 == 0 &&
         (int64_t)n * h * (w / 4) < (1ll << 31)) {
         const int64_t threads = (int64_t)n * h * (w / 4);
-        AGP_LAUNCH(pack_nchw4_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, n, c,
-                   h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo);
+        if (rf) {
+            AGP_LAUNCH((pack_nchw4_kernel<uint32_t*>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn,
+                       sc, sh, n, c, h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo,
+                       (bf16_t*)nullptr, rf);
+        } else {
+            AGP_LAUNCH((pack_nchw4_kernel<>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh,
+                       n, c, h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo,
+                       (bf16_t*)nullptr);
+        }
     } else if (cpad == 4) {
-        AGP_LAUNCH(pack_kernel<4>, dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0,
-                           (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad, pad,
-                           (bf16_t*)hi, (bf16_t*)lo);
+        if (rf) {
+            AGP_LAUNCH((pack_kernel<4, uint32_t*>), dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc,
+                       sh, sw, n, c, h, w, cpad, pad, (bf16_t*)hi, (bf16_t*)lo, rf);
+        } else {
+            AGP_LAUNCH(pack_kernel<4>, dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0,
+                               (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad, pad,
+                               (bf16_t*)hi, (bf16_t*)lo);
+        }
     } else if (cpad % 8 == 0) {
-        AGP_LAUNCH(pack_kernel<8>, dim3(grid_for((int64_t)n * h * w * (cpad / 8), 256)),
-                           dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad,
-                           pad, (bf16_t*)hi, (bf16_t*)lo);
+        if (rf) {
+            AGP_LAUNCH((pack_kernel<8, uint32_t*>), dim3(grid_for((int64_t)n * h * w * (cpad / 8), 256)), dim3(256), 0, (hipStream_t)stream,
+                       x, sn, sc, sh, sw, n, c, h, w, cpad, pad, (bf16_t*)hi, (bf16_t*)lo, rf);
+        } else {
+            AGP_LAUNCH(pack_kernel<8>, dim3(grid_for((int64_t)n * h * w * (cpad / 8), 256)),
+                               dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad,
+                               pad, (bf16_t*)hi, (bf16_t*)lo);
+        }
     } else {
         return AGP_E_BADARG;
     }
@@ -502,9 +541,14 @@ extern "C" int agp_bcast_add_fwd(const void* in_hi, const void* in_lo, const flo
                                  int w, int c, int pin, void* out_hi, void* out_lo, int pout,
                                  void* stream) {
     if (!in_hi || !out_hi || !vec || c % 8 || n <= 0) return AGP_E_BADARG;
-    AGP_LAUNCH(bcast_add_kernel, dim3(grid_for((int64_t)n * h * w * (c / 8), 256)), dim3(256),
-                       0, (hipStream_t)stream, (const bf16_t*)in_hi, (const bf16_t*)in_lo, vec, n, h,
-                       w, c, pin, (bf16_t*)out_hi, (bf16_t*)out_lo, pout);
+    if (uint32_t* const rf = agp_range_flag_get()) {
+        AGP_LAUNCH((bcast_add_kernel<uint32_t*>), dim3(grid_for((int64_t)n * h * w * (c / 8), 256)), dim3(256), 0, (hipStream_t)stream,
+                   (const bf16_t*)in_hi, (const bf16_t*)in_lo, vec, n, h, w, c, pin, (bf16_t*)out_hi, (bf16_t*)out_lo, pout, rf);
+    } else {
+        AGP_LAUNCH((bcast_add_kernel<>), dim3(grid_for((int64_t)n * h * w * (c / 8), 256)), dim3(256),
+                           0, (hipStream_t)stream, (const bf16_t*)in_hi, (const bf16_t*)in_lo, vec, n, h,
+                           w, c, pin, (bf16_t*)out_hi, (bf16_t*)out_lo, pout);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }

@@ -8,10 +8,14 @@ namespace agp_sparse {
 
 // first layer (MinkFPN.conv0, kernel 5, Cin = 1): direct gather, fp32 weights
 //   out[i][co] = act( scale[co] * sum_k f[nbr[k][i]] * w[k][co] + shift[co] )
+// rf (here and in the kernels below): the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent
+// otherwise; fp16 outputs only (o_lo == NULL: a bf16 pair does not clamp)
+template <class... RF>
 __global__ void conv_cin1_kernel(const float* __restrict__ f, const int32_t* __restrict__ nbr, int64_t n_in, int64_t n_out,
                                  int ntaps, const float* __restrict__ w, int cout, const float* __restrict__ scale,
                                  const float* __restrict__ shift, int relu, bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo,
-                                 const int64_t* __restrict__ n_dev) {
+                                 const int64_t* __restrict__ n_dev, RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
     const int groups = cout / 8;
     const int64_t total = (n_dev ? min(n_out, *n_dev) : n_out) * groups;      // capacity mode: the valid rows only
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
@@ -33,8 +37,10 @@ __global__ void conv_cin1_kernel(const float* __restrict__ f, const int32_t* __r
             acc[e] = acc[e] * (scale ? scale[g * 8 + e] : 1.f) + (shift ? shift[g * 8 + e] : 0.f);
             if (relu) acc[e] = fmaxf(acc[e], 0.f);
         }
+        rg.sym8_if(!o_lo, acc);
         map_store8(o_hi, o_lo, (size_t)i * cout + g * 8, acc);
     }
+    rg.flush(rg_word(rf...));
 }
 
 // per-segment mean and GeM of a feature matrix: one block of 1024 threads per (segment, 64-channel chunk): 8 channel groups x
@@ -112,10 +118,12 @@ __global__ void eca_kernel(const float* __restrict__ mean, int nb, int c, const 
 }
 
 // out[i] = relu?( y[i] * scale[b(i)]? + add[b(i)]? + res[i]? )
+template <class... RF>
 __global__ void seg_affine_kernel(const bf16_t* __restrict__ y_hi, const bf16_t* __restrict__ y_lo, const int32_t* __restrict__ bidx,
                                   const float* __restrict__ scale, const float* __restrict__ add, const bf16_t* __restrict__ r_hi,
                                   const bf16_t* __restrict__ r_lo, int64_t n, int c, int relu, bf16_t* __restrict__ o_hi,
-                                  bf16_t* __restrict__ o_lo, const int64_t* __restrict__ n_dev) {
+                                  bf16_t* __restrict__ o_lo, const int64_t* __restrict__ n_dev, RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
     const int groups = c / 8;
     const int64_t total = (n_dev ? min(n, *n_dev) : n) * groups;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
@@ -143,8 +151,10 @@ __global__ void seg_affine_kernel(const bf16_t* __restrict__ y_hi, const bf16_t*
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
         }
+        rg.sym8_if(!o_lo, v);
         map_store8(o_hi, o_lo, off, v);
     }
+    rg.flush(rg_word(rf...));
 }
 
 // kernel map: nbr[k][i] = row of (out_keys[i] + dkey[k]) in the SORTED in_keys, n_in when absent.
@@ -219,12 +229,13 @@ __global__ void kernel_map_grid_kernel(const int64_t* __restrict__ in_keys, int6
 // channels and finds its neighbours itself.  z is the lowest key field, so the `ksize` z-neighbours of one (dx, dy) column
 // are adjacent in the sorted key array: one binary search per column, then a short forward scan -- ksize^2 searches per
 // row instead of ksize^3, and no [ksize^3][n] table (256 MB written and read back for 64 x 8000 voxels at kernel 5).
-template <int CO>
+template <int CO, class... RF>
 __global__ void __launch_bounds__(256) conv0_search_kernel(const int64_t* __restrict__ keys, int64_t cap, const int64_t* __restrict__ n_dev,
                                                            const float* __restrict__ f, int ksize, int stride, const float* __restrict__ w,
                                                            const float* __restrict__ scale, const float* __restrict__ shift, int relu,
                                                            bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo,
-                                                           const int64_t* __restrict__ seg_off) {
+                                                           const int64_t* __restrict__ seg_off, RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
     const int64_t n = n_dev ? min(cap, *n_dev) : cap;
     const int r = ksize / 2;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -262,9 +273,11 @@ __global__ void __launch_bounds__(256) conv0_search_kernel(const int64_t* __rest
                 o[e] = acc[g * 8 + e] * (scale ? scale[g * 8 + e] : 1.f) + (shift ? shift[g * 8 + e] : 0.f);
                 if (relu) o[e] = fmaxf(o[e], 0.f);
             }
+            rg.sym8_if(!o_lo, o);
             map_store8(o_hi, o_lo, (size_t)i * CO + g * 8, o);
         }
     }
+    rg.flush(rg_word(rf...));
 }
 
 // The same layer at AGP_PREC_F16 (one fp16 x fp16 product, fp32 accumulate: the precision the other layers of the branch run at)
@@ -278,12 +291,14 @@ __global__ void __launch_bounds__(256) conv0_search_kernel(const int64_t* __rest
 //      in the accumulator layout (W rows permuted so that a lane holds 8 consecutive channels: 16-byte stores).
 constexpr int C0_ROWS = 128;
 constexpr int C0_WK = 1536;                 // keys (+ features) of a tile's search window in LDS
-template <int CO>
+template <int CO, class... RF>
 __global__ void __launch_bounds__(256) conv0_mfma_kernel(const int64_t* __restrict__ keys, int64_t cap, const int64_t* __restrict__ n_dev,
                                                          const float* __restrict__ f, int ksize, int stride, const float* __restrict__ w,
                                                          const float* __restrict__ scale, const float* __restrict__ shift, int relu,
-                                                         bf16_t* __restrict__ o_hi, const int64_t* __restrict__ seg_off, int KP) {
+                                                         bf16_t* __restrict__ o_hi, const int64_t* __restrict__ seg_off, int KP, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    // guarded: the voxel features' conversion into the fp16 tile and the stored output (the weights are parameters, not a map)
+    RangeTrack<sizeof...(RF) != 0> rg;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int64_t s_win[2];
     const int ROWB = KP * 2 + 16;                              // bytes of a tile / weight line (padding: 16-lane groups on distinct banks)
@@ -394,7 +409,9 @@ __global__ void __launch_bounds__(256) conv0_mfma_kernel(const int64_t* __restri
                     const int dy = (int)((k >> 16) & 0xffff) - y0, dz = (int)(k & 0xffff) - z0;
                     if (dz < 0 || dz > 2 * r * stride) continue;                       // same x-plane, y in range, z outside the window
                     const int iy = dy / stride, iz = dz / stride;                      // (coordinates of a level are multiples of its stride)
-                    *(bf16_t*)(xs + row * ROWB + (ix + ksize * iy + k2 * iz) * 2) = f2h(feat_at(p_));
+                    const float fv = feat_at(p_);
+                    rg.sym2(fv, 0.f);
+                    *(bf16_t*)(xs + row * ROWB + (ix + ksize * iy + k2 * iz) * 2) = f2h(fv);
                 }
             }
         };
@@ -427,10 +444,12 @@ __global__ void __launch_bounds__(256) conv0_mfma_kernel(const int64_t* __restri
                     const int c = 16 * jj + 8 * lh + e;
                     v[e] = acc[jj >> 1][8 * (jj & 1) + e] * (scale ? scale[c] : 1.f) + (shift ? shift[c] : 0.f);
                 }
+                rg.any8(v);
                 *(u32x4*)(o_hi + (size_t)i * CO + 16 * jj + 8 * lh) = pack8_h_lo(v, relu_lo);
             }
         }
     }
+    rg.flush(rg_word(rf...), relu_lo);
 #endif
 }
 
@@ -654,8 +673,13 @@ extern "C" int agp_sparse_conv_cin1_fwd(const float* f, int64_t n_in, const int3
                                         int cout, const float* scale, const float* shift, int relu, void* out_hi, void* out_lo,
                                         const int64_t* n_dev, void* stream) {
     if (!f || !nbr || !w || !out_hi || n_out <= 0 || cout % 8 || ntaps <= 0) return AGP_E_BADARG;
-    AGP_LAUNCH(conv_cin1_kernel, dim3(grid_for(n_out * (cout / 8))), dim3(256), 0, (hipStream_t)stream, f, nbr, n_in, n_out, ntaps, w,
-               cout, scale, shift, relu, BF(out_hi), BF(out_lo), n_dev);
+    if (uint32_t* const rf = agp_range_flag_get()) {
+        AGP_LAUNCH((conv_cin1_kernel<uint32_t*>), dim3(grid_for(n_out * (cout / 8))), dim3(256), 0, (hipStream_t)stream, f, nbr, n_in,
+                   n_out, ntaps, w, cout, scale, shift, relu, BF(out_hi), BF(out_lo), n_dev, rf);
+    } else {
+        AGP_LAUNCH((conv_cin1_kernel<>), dim3(grid_for(n_out * (cout / 8))), dim3(256), 0, (hipStream_t)stream, f, nbr, n_in, n_out,
+                   ntaps, w, cout, scale, shift, relu, BF(out_hi), BF(out_lo), n_dev);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -672,24 +696,47 @@ extern "C" int agp_sparse_conv0_fwd(const int64_t* keys, int64_t cap, const int6
         const int lds = (C0_ROWS + cout) * (KP * 2 + 16) + C0_WK * 12;
         const int tiles = (int)((cap + C0_ROWS - 1) / C0_ROWS);
         const int grid = tiles < 1024 ? tiles : 1024;
+        uint32_t* const rf = agp_range_flag_get();
         if (cout == 32) {
-            AGP_LAUNCH(conv0_mfma_kernel<32>, dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
-                       BF(out_hi), seg_off, KP);
+            if (rf) {
+                AGP_LAUNCH((conv0_mfma_kernel<32, uint32_t*>), dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale,
+                               shift, relu, BF(out_hi), seg_off, KP, rf);
+            } else {
+                AGP_LAUNCH(conv0_mfma_kernel<32>, dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
+                            BF(out_hi), seg_off, KP);
+            }
         } else {
-            static std::atomic<uint64_t> attr_done{0};
-            if (!agp_lds_attr((const void*)conv0_mfma_kernel<64>, 96 * 1024, attr_done)) return AGP_E_LAUNCH;
-            AGP_LAUNCH(conv0_mfma_kernel<64>, dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
-                       BF(out_hi), seg_off, KP);
+            static std::atomic<uint64_t> attr_done{0}, attr_done_rg{0};
+            if (rf) {
+                if (!agp_lds_attr((const void*)conv0_mfma_kernel<64, uint32_t*>, 96 * 1024, attr_done_rg)) return AGP_E_LAUNCH;
+                AGP_LAUNCH((conv0_mfma_kernel<64, uint32_t*>), dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale,
+                           shift, relu, BF(out_hi), seg_off, KP, rf);
+            } else {
+                if (!agp_lds_attr((const void*)conv0_mfma_kernel<64>, 96 * 1024, attr_done)) return AGP_E_LAUNCH;
+                AGP_LAUNCH(conv0_mfma_kernel<64>, dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
+                           BF(out_hi), seg_off, KP);
+            }
         }
         AGP_CHECK_LAUNCH();
         return AGP_OK;
     }
+    uint32_t* const rf = agp_range_flag_get();
     if (cout == 32) {
-        AGP_LAUNCH(conv0_search_kernel<32>, dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
-                   BF(out_hi), BF(out_lo), seg_off);
+        if (rf) {
+            AGP_LAUNCH((conv0_search_kernel<32, uint32_t*>), dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w,
+                           scale, shift, relu, BF(out_hi), BF(out_lo), seg_off, rf);
+        } else {
+            AGP_LAUNCH(conv0_search_kernel<32>, dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift,
+                        relu, BF(out_hi), BF(out_lo), seg_off);
+        }
     } else {
-        AGP_LAUNCH(conv0_search_kernel<64>, dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
-                   BF(out_hi), BF(out_lo), seg_off);
+        if (rf) {
+            AGP_LAUNCH((conv0_search_kernel<64, uint32_t*>), dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w,
+                           scale, shift, relu, BF(out_hi), BF(out_lo), seg_off, rf);
+        } else {
+            AGP_LAUNCH(conv0_search_kernel<64>, dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift,
+                        relu, BF(out_hi), BF(out_lo), seg_off);
+        }
     }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
@@ -735,8 +782,13 @@ extern "C" int agp_seg_affine_fwd(const void* y_hi, const void* y_lo, const int3
                                   const void* r_hi, const void* r_lo, int64_t n, int c, int relu, void* o_hi, void* o_lo,
                                   const int64_t* n_dev, void* stream) {
     if (!y_hi || !bidx || !o_hi || n <= 0 || c % 8) return AGP_E_BADARG;
-    AGP_LAUNCH(seg_affine_kernel, dim3(grid_for(n * (c / 8))), dim3(256), 0, (hipStream_t)stream, CBF(y_hi), CBF(y_lo), bidx, scale,
-               add, CBF(r_hi), CBF(r_lo), n, c, relu, BF(o_hi), BF(o_lo), n_dev);
+    if (uint32_t* const rf = agp_range_flag_get()) {
+        AGP_LAUNCH((seg_affine_kernel<uint32_t*>), dim3(grid_for(n * (c / 8))), dim3(256), 0, (hipStream_t)stream, CBF(y_hi), CBF(y_lo),
+                   bidx, scale, add, CBF(r_hi), CBF(r_lo), n, c, relu, BF(o_hi), BF(o_lo), n_dev, rf);
+    } else {
+        AGP_LAUNCH((seg_affine_kernel<>), dim3(grid_for(n * (c / 8))), dim3(256), 0, (hipStream_t)stream, CBF(y_hi), CBF(y_lo), bidx,
+                   scale, add, CBF(r_hi), CBF(r_lo), n, c, relu, BF(o_hi), BF(o_lo), n_dev);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }

@@ -70,9 +70,12 @@ __device__ __forceinline__ uint32_t pack2_h_clamp(float a, float b, float hi) {
 // IN = 0: the packed NHWC4 halo-3 map (LDS-DMA).  IN = 1: the network's input itself, an fp32 [n][3][h][w] image with unit
 // column stride and 16-byte aligned rows (StemRaw; checked by the launcher), staged by LDS-DMA and converted to fp16 NHWC4 on
 // its way into the patch: no packed copy of the image is written or read.
-template <int IN>
-__global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRaw raw, WalkGeo g) {
+// RG: the fp16 range guard (common.hpp RangeTrack) over the conv map's stored values and, IN = 1, the image's conversion to fp16.
+// rf: the bound word in the guarded instantiation (common.hpp rg_word), absent otherwise.
+template <int IN, class... RF>
+__global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRaw raw, WalkGeo g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool RG = sizeof...(RF) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -204,6 +207,7 @@ __global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRa
         }
     };
     // the wave's staged rows -> fp16 NHWC4 pixels of patch buffer `buf` (pixel px of the patch = column 32 j - 3 + px)
+    RangeTrack<RG> rg;
     auto convert_raw = [&](int buf, int j) {
         if constexpr (IN == 2) {
 #pragma unroll
@@ -236,6 +240,8 @@ __global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRa
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         if ((gq == 0 && k == 0) || (gq == 9 && k == 3)) continue;      // pixels -1 and 38 of the patch do not exist
+                        rg.sym2(c0[k], c1[k]);
+                        rg.sym2(c2[k], 0.f);
                         *(u32x2*)(dst + k * 8) = u32x2{pack2(f2h(c0[k]), f2h(c1[k])), pack2(f2h(c2[k]), (bf16_t)0)};
                     }
                 }
@@ -350,6 +356,7 @@ __global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRa
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) hi_[mt] = (colok && ((rowok >> mt) & 1u)) ? 65504.f : 0.f;
         u32x2 r0[4];
+        RangeTrack<RG> rgm[4];              // per conv row: its seam-masked values (hi = 0) are not saturation
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             const f32x4 sc = *(const f32x4*)(ss + nt * 16 + 4 * lq), sh = *(const f32x4*)(ss + 64 + nt * 16 + 4 * lq);
@@ -359,12 +366,16 @@ __global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRa
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[nt][mt][e] * sc[e] + sh[e];
+                rgm[mt].pos2(v[0], v[1]);
+                rgm[mt].pos2(v[2], v[3]);
                 r[mt] = u32x2{pack2_h_clamp(v[0], v[1], hi_[mt]), pack2_h_clamp(v[2], v[3], hi_[mt])};
             }
             V[0][nt] = pkmax4_h(pkmax4_h(r[0], r[1]), r[2]);
             V[1][nt] = pkmax4_h(r[2], r[3]);
             r0[nt] = r[0];
         }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) rg.pos2(hi_[mt] > 0.f ? rgm[mt].hi : 0.f, 0.f);
         if (wave > 0) {
             char* ex = exch + ((j & 1) * 4 + wave) * SWK_EXCH + xo;
             *(u32x4*)ex = u32x4{r0[0][0], r0[0][1], r0[1][0], r0[1][1]};
@@ -380,6 +391,7 @@ __global__ void __launch_bounds__(256, 2) stem_walk_kernel(IgemmParams p, StemRa
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
     part2(j1 - 1);
+    rg.flush(rg_word(rf...), 0.f);
 #endif
 }
 
@@ -402,17 +414,23 @@ static WalkGeo walk_geo(int n, const IgemmParams& p) {
     return g;
 }
 
-template <int IN>
-static int launch_stem_walk(IgemmParams& p, const StemRaw& raw, hipStream_t s) {
+template <int IN, bool RG>
+static int launch_stem_walk(IgemmParams& p, const StemRaw& raw, uint32_t* rflag, hipStream_t s) {
     constexpr int lds = swk_lds<IN>();
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)stem_walk_kernel<IN>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr(RG ? (const void*)stem_walk_kernel<IN, uint32_t*> : (const void*)stem_walk_kernel<IN>, lds, attr_done))
+        return AGP_E_LAUNCH;
     const int n = p.M / (p.pool_h1 * p.pool_w1);
     WalkGeo g = walk_geo(n, p);
     const long long o_bytes = (long long)n * p.o_sn * 2;
     if (o_bytes >= 0xffffff00ll) return AGP_E_BADARG;
     g.o_bytes = (uint32_t)o_bytes;
-    AGP_LAUNCH(stem_walk_kernel<IN>, dim3(g.chunk * 8), dim3(256), lds, s, p, raw, g);
+    if constexpr (RG) {
+        AGP_LAUNCH((stem_walk_kernel<IN, uint32_t*>), dim3(g.chunk * 8), dim3(256), lds, s, p, raw, g, rflag);
+    } else {
+        (void)rflag;
+        AGP_LAUNCH((stem_walk_kernel<IN>), dim3(g.chunk * 8), dim3(256), lds, s, p, raw, g);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -439,16 +457,17 @@ bool agp_internal_stem_walk_reads_u8(const agp_igemm::StemRaw& raw, int n) {
 // 2: uint8 camera tiles (agp_internal_stem_walk_reads_u8 must hold)
 int agp_internal_stem_walk(agp_igemm::IgemmParams& p, int kind, agp_igemm::StemRaw raw, hipStream_t s) {
     using namespace agp_igemm;
-    if (kind == 0) return launch_stem_walk<0>(p, raw, s);
+    uint32_t* const rflag = agp_range_flag_get();
+    if (kind == 0) return agp_rg_dispatch(rflag, [&](auto rg) { return launch_stem_walk<0, decltype(rg)::value>(p, raw, rflag, s); });
     if (kind == 2) {
         const int n = p.M / (p.pool_h1 * p.pool_w1);
         raw.bytes = (uint32_t)((long long)n * raw.ncam * raw.h * raw.wcam * 3);
-        return launch_stem_walk<2>(p, raw, s);
+        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_stem_walk<2, decltype(rg)::value>(p, raw, rflag, s); });
     }
     if (kind == 1) {
         const int n = p.M / (p.pool_h1 * p.pool_w1);
         raw.bytes = (uint32_t)(((long long)(n - 1) * raw.sn + 2 * raw.sc + (long long)(raw.h - 1) * raw.sh + raw.w) * 4);
-        return launch_stem_walk<1>(p, raw, s);
+        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_stem_walk<1, decltype(rg)::value>(p, raw, rflag, s); });
     }
     return AGP_E_BADARG;
 }

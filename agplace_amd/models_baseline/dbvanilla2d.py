@@ -12,7 +12,7 @@ from typing import List
 import torch
 import torch.nn as nn
 
-from .. import autograd_ops, ops, train_fns
+from .. import autograd_ops, ops, range_guard, train_fns
 from ..network.image_fe import ImageFE
 from ..network.image_pooling import GeM
 from ..network_mm.ffns import _PreparedLinear
@@ -57,6 +57,14 @@ class DBVanilla2D(nn.Module):
         self._frozen_backbone = True
         return self
 
+    def poll_fp16_range(self):
+        """NON-BLOCKING fp16 range check of the guarded inference forwards so far (MM.poll_fp16_range)."""
+        range_guard.poll(self)
+
+    def fp16_range_ok(self):
+        """False if a guarded inference forward since the last report stored a saturated fp16 map value (MM.fp16_range_ok)."""
+        return range_guard.ok(self)
+
     def final_pool_request(self, i):
         """The GeM of map type i's last stage output (dbvanilla2d.py:74) as an ops.PoolReq the trunk's last conv fills."""
         j = 0 if self.opt.share_dbfe is True else i
@@ -77,7 +85,8 @@ class DBVanilla2D(nn.Module):
         train = self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
                                   and any(p.requires_grad for p in self.parameters()))
         if not train:
-            return self._forward_db(data_dict, train, trunk_maps, out_rows, defer_head)
+            with range_guard.guarded(self, opt, opt.mfma_precision, False):
+                return self._forward_db(data_dict, train, trunk_maps, out_rows, defer_head)
         from .. import train_graph
         # the opt-in fast modes (train_graph.py) for THIS model's forward only, as in MM.forward_q
         with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1):

@@ -8,6 +8,7 @@ ConvNeXt / SqueezeNet branches of the reference are not built (never selected by
 """
 import torch.nn as nn
 
+from .. import range_guard
 from ..options import get_options
 from ..resnet import ResNet
 
@@ -17,8 +18,9 @@ class ImageFE(nn.Module):
     _LAST_DIM = {"resnet18": {2: 128, 3: 256, 4: 512}, "resnet34": {2: 128, 3: 256, 4: 512},
                  "resnet50": {2: 512, 3: 1024, 4: 2048}}
 
-    def __init__(self, fe_type, layers):
+    def __init__(self, fe_type, layers, opt=None):
         super().__init__()
+        self.opt = opt              # None: the process-wide options at call time (get_options())
         self.fe_type = fe_type
         layers = [int(x) for x in layers.split('_')]
         self.layers = layers
@@ -44,6 +46,18 @@ class ImageFE(nn.Module):
         return 2 if p == 4 else p
 
     def forward(self, x, prec=None):
-        maps = self.forward_maps(x, prec=self.export_precision() if prec is None else prec)
-        x_list = [m.to_f32() for m in maps]
+        prec = self.export_precision() if prec is None else prec
+        # the fp16 range guard of the op-level drop-in (Options.fp16_range_guard): around its own forward only -- inside MM /
+        # DBVanilla2D the trunk's maps report through the model that runs it
+        with range_guard.guarded(self, self.opt or get_options(), prec, self.training):
+            maps = self.forward_maps(x, prec=prec)
+            x_list = [m.to_f32() for m in maps]
         return x_list[-1], x_list
+
+    def poll_fp16_range(self):
+        """NON-BLOCKING fp16 range check of the guarded forwards so far (MM.poll_fp16_range)."""
+        range_guard.poll(self)
+
+    def fp16_range_ok(self):
+        """False if a guarded forward since the last report stored a saturated fp16 map value (MM.fp16_range_ok)."""
+        return range_guard.ok(self)

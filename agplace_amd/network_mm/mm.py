@@ -25,7 +25,7 @@ Execution modes:
 import torch
 import torch.nn as nn
 
-from .. import autograd_ops, ops, sparse, train_fns
+from .. import autograd_ops, ops, range_guard, sparse, train_fns
 from ..options import get_options
 from .ffns import _PreparedLinear
 from .fuse_block_toshallow import FuseBlockToShallow
@@ -127,6 +127,18 @@ class MM(nn.Module):
         torch.cuda.synchronize()
         return all(int(sl['sticky'].item()) == 0 for sl in slots.values())
 
+    # ---- the fp16 range guard (Options.fp16_range_guard, agplace_amd/range_guard.py): the same contract as the voxel-range flag
+    def poll_fp16_range(self):
+        """NON-BLOCKING: raises ValueError if a guarded inference forward (eager or replayed) whose state has reached the host so
+        far stored a saturated fp16 map value."""
+        range_guard.poll(self)
+
+    def fp16_range_ok(self):
+        """False if ANY guarded inference forward since the last report stored a saturated fp16 map value.  Synchronises.
+        Under agplace_amd.pair.embed_pair this word also covers the database model's image trunks (run in lock-step with this
+        model's)."""
+        return range_guard.ok(self)
+
     def _publish_voxel_flag(self, flag):
         """Behind the build, on the calling stream (which has joined the voxel side stream).  Eager calls also check: the first call
         of a stream its own flag at once, every later call the flag of the call BEFORE it on that stream (an event behind that
@@ -192,7 +204,8 @@ class MM(nn.Module):
         train = self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
                                   and any(p.requires_grad for p in self.parameters()))
         if not train:
-            return self._forward_q(data_dict, train, image_maps, out_rows, rider)
+            with range_guard.guarded(self, opt, opt.mfma_precision, False):
+                return self._forward_q(data_dict, train, image_maps, out_rows, rider)
         from .. import train_graph
         # the opt-in fast modes (train_graph.py): one-product forward convs, one-product data gradients -- for THIS model's
         # forward only, the process-wide switches restored when it returns

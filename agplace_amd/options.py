@@ -79,6 +79,13 @@ class Options:
     # saturated map elements and warns (resnet.SATURATION_CHECK) -- such a checkpoint needs mode 3.  Training (.train()) always
     # runs on split-bf16 maps (3); kNN has its own setting.
     mfma_precision: int = 4
+    # Opt-in fp16 range guard (agplace_amd/range_guard.py): inference forwards in modes 2 / 4 bind a sticky device word that
+    # every kernel storing an inference fp16 map (the table in DESIGN.md section 2) sets when it had to clamp a value to +-65504
+    # -- eager forwards then raise ValueError
+    # (one call late; the last call by fp16_range_ok()), captured replays publish it to pinned memory for poll_fp16_range().
+    # Stored values are the same bits either way.  Mode 3 and training store no fp16 maps and never bind.  Independent of the
+    # first-forward warning above (resnet.SATURATION_CHECK).
+    fp16_range_guard: bool = False
     # TRAINING (.train(), or .eval() with gradients): 32 (default) = the tight mode -- split-bf16 maps, three MFMA products in
     # every forward and data-gradient conv, one fp16 product in the weight gradients; every parameter gradient within 1e-3 of
     # fp64 autograd (tests/test_gpu_train.py).  16 = the opt-in FAST mode: the forward of the 3x3 stride-1 convs as ONE
@@ -116,6 +123,8 @@ class Options:
             raise ValueError(f"train_precision {self.train_precision!r}: 32 (tight) | 16 (one-product forward convs)")
         if self.train_dgrad_products not in (1, 3):
             raise ValueError(f"train_dgrad_products {self.train_dgrad_products!r}: 3 (tight) | 1 (one-product data gradients)")
+        if not isinstance(self.fp16_range_guard, bool):
+            raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
 
     def copy(self, **kw):
         d = {f.name: getattr(self, f.name) for f in fields(self)}

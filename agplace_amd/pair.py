@@ -12,7 +12,7 @@ Outputs are bit-identical to calling the two models separately (tests/test_gpu_m
 import torch
 
 
-from . import resnet
+from . import range_guard, resnet
 
 RIDER = True      # False: the database head as a launch of its own behind the query network's tail
 
@@ -32,9 +32,25 @@ def can_pair(modelq, modeldb, qdata, dbdata):
 
 def embed_pair(modelq, modeldb, qdata, dbdata):
     """(modelq(qdata, 'q'), modeldb(dbdata, 'db')) with the image trunks run in lock-step.  Falls back to the two
-    separate forwards when the models cannot be paired (training, different trunk architectures)."""
+    separate forwards when the models cannot be paired (training, different trunk architectures).
+    fp16 range guard (Options.fp16_range_guard): the lock-step trunks of BOTH models report through the query model's word when
+    its guard is on (else the database model's): a saturated database tile then shows in modelq.fp16_range_ok() /
+    poll_fp16_range(), whose message names the database trunks as a possible source."""
     if not can_pair(modelq, modeldb, qdata, dbdata):
         return modelq(qdata, mode='q'), modeldb(dbdata, mode='db')
+    # the fp16 range guard: the grouped trunk launches below run outside either model's forward and hold BOTH models' image trunks
+    # -- they report through the query model's word when its guard is on, else the database model's (each model's forward then
+    # binds and publishes its own word for the rest of its work); the report names the other model's trunks as a possible source
+    for m, other in ((modelq, modeldb), (modeldb, modelq)):
+        if range_guard.active(m.opt, m.opt.mfma_precision, False):
+            g = range_guard.guard_of(m)
+            g.also.add(f"the {type(other).__name__} image trunks run in lock-step with this model's (agplace_amd.pair.embed_pair)")
+            with g.bind(range_guard.model_device(m)):
+                return _embed_pair_dispatch(modelq, modeldb, qdata, dbdata)
+    return _embed_pair_dispatch(modelq, modeldb, qdata, dbdata)
+
+
+def _embed_pair_dispatch(modelq, modeldb, qdata, dbdata):
     k = modelq.opt.query_substreams
     img = qdata['query_image']
     db_map = dbdata['db_map']
@@ -158,6 +174,8 @@ class CapturedPair:
         self._n += 1
         if self._n % self.poll_every == 0:
             self.modelq.poll_voxel_range()
+            self.modelq.poll_fp16_range()
+            self.modeldb.poll_fp16_range()
         # what the caller's stream has enqueued so far (the refill of the static inputs) comes first
         self.stream.wait_stream(torch.cuda.current_stream(self.stream.device))
         with torch.cuda.stream(self.stream):
@@ -168,4 +186,7 @@ class CapturedPair:
         self.stream.synchronize()
         if not self.modelq.voxel_coords_in_range():
             self.modelq._raise_voxel_range("a replayed")
+        for m in (self.modelq, self.modeldb):
+            if not m.fp16_range_ok():
+                range_guard.guard_of(m).report("a replayed")
         return self.out_q, self.out_db

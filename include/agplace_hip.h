@@ -75,6 +75,24 @@ const char* agp_version(void);
 /* Returns the gfx arch string the device code was built for ("gfx950"). */
 const char* agp_arch(void);
 
+/* ------------------------------------------------------ fp16 range guard */
+
+/* The fp16 feature maps of precision modes 2 and 4 saturate at +-65504 (a value beyond it is stored as +-65504, not as
+ * infinity).  While a 32-bit device word is BOUND, every guarded kernel that stores an fp16 map (the stem, conv and fused-block
+ * kernels: the table in DESIGN.md section 2) ORs 1 into it when a value it stored had to be clamped: |v| > 65504 before the clamp, or v > 65504 where a ReLU is folded into the clamp (lower bound 0); +-inf counts,
+ * NaN does not.  The word is sticky (kernels only OR into it; the caller zeroes it) and the stored values are the same bits
+ * whether a word is bound or not.  Guarded kernels fold the check into their epilogue: a per-lane running maximum and one
+ * wave ballot at the end of a tile, one atomic OR per wave that saw a clamped value.
+ *
+ * The binding belongs to the CALLING HOST THREAD: every launcher reads it when it enqueues its kernel, on whatever stream it
+ * is given, and passes the pointer as a kernel argument.  Under stream capture the pointer becomes part of the captured node,
+ * so every replay ORs into the same word.  Another host thread sees its own binding (NULL until it sets one).
+ *
+ * agp_range_flag_set binds `word` (a device pointer, or NULL to unbind) and returns the previous binding of this thread;
+ * agp_range_flag_get returns the current one.  Neither touches the device. */
+uint32_t* agp_range_flag_set(uint32_t* word);
+uint32_t* agp_range_flag_get(void);
+
 /* ---------------------------------------------------------------- layout */
 
 /* Split an fp32 tensor into 16-bit hi/lo planes (elementwise), n elements:
