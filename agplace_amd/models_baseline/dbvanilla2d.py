@@ -143,11 +143,13 @@ class DBVanilla2D(nn.Module):
                     else:
                         fpool = self.final_pool_request(i)
                         self.dbimage_fes[j].forward_maps(x, prec=prec, final_pool=fpool)
-                    v = fpool.gem
+                    # (a last map stored with an exponent: the stored map's GeM; the fused head multiplies by 2^e where it loads
+                    # the vector, the per-op head with a small launch)
+                    v, vscale = (fpool.gem, fpool.scale) if fused is not None else (fpool.true_gem(), None)
                 if fused is not None:
                     # MLP + F.normalize of this map type; register 2 + i holds its vector
                     mlp = self.dbimage_mlps[j]
-                    fused.linear(0, mlp._p0.get(), v)
+                    fused.linear(0, mlp._p0.get(), v, scale=vscale)
                     fused.layernorm(0, mlp.seq[1], 0, relu=True)
                     fused.linear(2 + i, mlp._p3.get(), 0)
                     if opt.output_l2 is True:

@@ -39,13 +39,20 @@ class _PreparedLinear:
         self.linear, self.with_transpose = linear, with_transpose
         self._key, self._lw = None, None
 
-    def get(self, with_transpose=False):
-        """Split planes of W (and of W^T when a backward pass needs gz W)."""
+    def get(self, with_transpose=False, exp=0):
+        """Split planes of W (and of W^T when a backward pass needs gz W).  exp (inference only): W and b times 2^exp -- the
+        projection of a vector that is added into a map stored with an exponent (agplace_amd/map_exponents.py); exact, the
+        split planes scale with it."""
         w, b = self.linear.weight, self.linear.bias
         wt = self.with_transpose or with_transpose
-        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
+        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version), exp)
         if key != self._key or (wt and self._lw.wt_hi is None):
-            self._lw = ops.LinearWeights(w, b, with_transpose=wt)
+            if exp:
+                e = torch.tensor(exp, device=w.device)
+                self._lw = ops.LinearWeights(torch.ldexp(w.detach().float(), e), None if b is None else torch.ldexp(b.detach().float(), e),
+                                             with_transpose=wt)
+            else:
+                self._lw = ops.LinearWeights(w, b, with_transpose=wt)
             self._key = key
         return self._lw
 

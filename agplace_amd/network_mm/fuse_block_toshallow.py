@@ -22,7 +22,7 @@ from .ffns import _PreparedLinear
 def _avgpool(m):
     """adaptive_avg_pool2d(e, 1).flatten(1) for an ops.SplitMap or an fp32 [b,c,h,w] tensor."""
     if hasattr(m, "vec"):          # pre-pooled level handed over by MM.forward_q
-        return m.vec
+        return m.true()
     if isinstance(m, ops.SplitMap):
         return ops.pool_map(m, None, want_mean=True, want_gem=False)[0]
     return ops.pool_f32(m.float(), None, want_mean=True, want_gem=False)[0]
@@ -80,17 +80,19 @@ class FuseBlockToShallow(nn.Module):
         from ..vecprog import VecProgramUnfit
         if 'cde' in self.opt.diff_type or self.opt.diff_direction not in ('forward', 'backward') or self.dims[-1] != 256:
             raise VecProgramUnfit("diff block options")
-        imageveclist = [_avgpool(e) for e in imagemaplist]
+        # a pre-pooled level of a map stored with an exponent: the stored map's mean, times 2^e on its way into the program
+        imageveclist = [e.vec if hasattr(e, "vec") else _avgpool(e) for e in imagemaplist]
+        scales = [e.scale if hasattr(e, "vec") else None for e in imagemaplist]
         n = len(self.dims)
         first = True
         for it in range(n):
             i = it if self.opt.diff_direction == 'forward' else n - 1 - it
             imagevec, voxvec = imageveclist[i], voxmaplist[i].float()
             if self._prep_img[i] is not None:
-                vp.linear(1, self._prep_img[i].get(), imagevec)
+                vp.linear(1, self._prep_img[i].get(), imagevec, scale=scales[i])
                 vp.linear(2, self._prep_vox[i].get(), voxvec)
             else:
-                vp.load(1, imagevec)
+                vp.load(1, imagevec, scales[i])
                 vp.load(2, voxvec)
             blocks = list(self.blocks[i].blocks)
             src = (1, 2, -1) if first else (0, 1, 2)          # fusevec = 0 + imagevec + voxvec on the first level

@@ -277,8 +277,10 @@ class MM(nn.Module):
                     lvl_means, fpool = [], self.final_pool_request()
                     maps = self.image_fe.forward_maps(image, prec=prec, level_means=lvl_means, final_pool=fpool)
                 imagefeatmap = maps[-1]
+                # (maps stored with an exponent: the pooled vectors are the stored maps', times 2^-e; the fused vector path
+                # restores the factor where its programs load them, the per-op path below with a small launch each)
                 mean3, imagefeatvec = fpool.mean, fpool.gem
-                levels = [_Pooled(m) for m in lvl_means] + [_Pooled(mean3)]
+                levels = [_Pooled(m, mp.exp) for m, mp in zip(lvl_means, maps)] + [_Pooled(mean3, fpool.exp)]
             if vox_side is not None:
                 cur = torch.cuda.current_stream(image.device)
                 with torch.cuda.stream(vox_side):
@@ -297,9 +299,12 @@ class MM(nn.Module):
             # ---- inference: the whole vector path as two launches (vecprog.hip) around the stage-2 conv block
             if not train and not torch.is_grad_enabled() and opt.fused_vector_path:
                 try:
-                    return self._vector_path_fused(data_dict, imagefeatmap, levels, imagefeatvec, voxmap, prec, out_rows or {}, rider)
+                    return self._vector_path_fused(data_dict, imagefeatmap, levels, imagefeatvec, voxmap, prec, out_rows or {}, rider,
+                                                   gem3_exp=fpool.exp)
                 except VecProgramUnfit:
                     pass                      # an option set the program cannot express: the per-op path below
+            if not train:
+                imagefeatvec = fpool.true_gem()
             if opt.output_l2 is True:
                 imagefeatvec = autograd_ops.l2normalize(imagefeatvec)
             imagefeatvec_org = imagefeatvec
@@ -354,7 +359,7 @@ class MM(nn.Module):
             'embedding': x,
         }
 
-    def _vector_path_fused(self, data_dict, imagefeatmap, levels, gem3, voxmap, prec, out_rows, rider=None):
+    def _vector_path_fused(self, data_dict, imagefeatmap, levels, gem3, voxmap, prec, out_rows, rider=None, gem3_exp=0):
         """Everything of forward_q after the backbones (mm.py:91-129) for inference: program 1 = descriptors' F.normalize,
         FuseBlockToShallow, the stage-2 projections of the fusion vector; the stage-2 conv block (and sparse block) on
         their own kernels; program 2 = fusion update, FFNFuse, stg2fusefc, the final weighted sum.  Same arithmetic as
@@ -366,7 +371,7 @@ class MM(nn.Module):
         b, dev = gem3.shape[0], gem3.device
         sparse_vox = voxmap is not None
         vp = VecProgram(b, dev)
-        vp.load(0, gem3)
+        vp.load(0, gem3, ops.pow2_scalar(dev, gem3_exp))
         if opt.output_l2 is True:
             vp.l2norm(0, 0)
         imagevec_org = vp.store(0, out_rows.get('imagevec_org'))
@@ -383,8 +388,14 @@ class MM(nn.Module):
         vp.wsum(1, [r], [self.shallow_weight])
         fusevec = vp.store(1)
         fv_img = fv_vox = fusevec
+        # the vector that bcast_add adds into the layer-3 map takes that map's 2^-e: folded into the projection's weights and bias
+        # (no projection: one op of this program)
+        e3 = imagefeatmap.exp
         if s2._prep_fuseimg[0] is not None:
-            vp.linear(2, s2._prep_fuseimg[0].get(), 1)
+            vp.linear(2, s2._prep_fuseimg[0].get(exp=-e3), 1)
+            fv_img = vp.store(2)
+        elif e3:
+            vp.wsum(2, [1], [ops.pow2_scalar(dev, -e3)])
             fv_img = vp.store(2)
         if sparse_vox and s2._prep_fusevox[0] is not None:
             vp.linear(3, s2._prep_fusevox[0].get(), 1)
@@ -398,7 +409,9 @@ class MM(nn.Module):
         ops.bcast_add(imagefeatmap, fv_img, m)
         s2pool = ops.PoolReq(s2.poolimage.p, eps=s2.poolimage.eps, want_mean=True, want_gem=True, gem_out=out_rows.get('stg2imagevec'))
         imap = s2.ffnsimg[0].forward_map(m, prec, pool=s2pool)       # GeM + mean of the block's output ride in its last conv
-        mean, stg2imagevec = s2pool.mean, s2pool.gem
+        # (stored-map poolings: `mean` enters program 2 through a scaled load; the GeM -- an output -- is loaded scaled and stored
+        # back over itself by that program, below)
+        mean, stg2imagevec, s2scale = s2pool.mean, s2pool.gem, s2pool.scale
         if sparse_vox:
             vm = sparse.modules.seg_affine(voxmap, add=fv_vox)
             vm = s2.ffnsvox[0](vm, prec=prec)
@@ -410,9 +423,9 @@ class MM(nn.Module):
         # ---- program 2
         vt = VecProgram(b, dev)
         if s2._prep_imgfuse[0] is not None:
-            vt.linear(0, s2._prep_imgfuse[0].get(), mean)
+            vt.linear(0, s2._prep_imgfuse[0].get(), mean, scale=s2scale)
         else:
-            vt.load(0, mean)
+            vt.load(0, mean, s2scale)
         vt.load(1, fusevec)
         vt.load(2, voxvec_fuse.float())
         vt.wsum(1, [1, 0, 2])
@@ -428,11 +441,21 @@ class MM(nn.Module):
             if vec is None:
                 regs.append(0)
             else:
-                regs.append(vt.load(nxt, vec.float()))
+                if name == 'stg2image' and s2scale is not None:
+                    regs.append(vt.load(nxt, vec, s2scale))
+                    vt.store(nxt, vec)                      # the true GeM over the stored map's, in place
+                    s2scale = None
+                else:
+                    regs.append(vt.load(nxt, vec.float()))
                 nxt += 1
             weights.append(wt)
         if not regs:
             raise VecProgramUnfit("empty final_type")
+        if s2scale is not None:                             # stg2imagevec is an output even when the final sum leaves it out
+            if nxt >= 6:
+                raise VecProgramUnfit("registers")
+            vt.load(nxt, stg2imagevec, s2scale)
+            vt.store(nxt, stg2imagevec)
         vt.wsum(nxt if nxt < 6 else 0, regs, weights)
         out = nxt if nxt < 6 else 0
         if opt.final_l2 is True:
@@ -510,5 +533,12 @@ class MM(nn.Module):
 class _Pooled:
     """An already average-pooled level (saves re-reading l3, which GeM just streamed)."""
 
-    def __init__(self, vec):
-        self.vec = vec
+    def __init__(self, vec, exp=0):
+        self.vec, self.exp = vec, exp          # exp: the pooled map's exponent -- vec is the true mean times 2^-exp
+
+    @property
+    def scale(self):
+        return ops.pow2_scalar(self.vec.device, self.exp)
+
+    def true(self):
+        return ops.scale_pow2(self.vec, self.exp)

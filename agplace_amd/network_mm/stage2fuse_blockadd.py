@@ -71,26 +71,35 @@ class BasicBlock(nn.Module):
         self._key, self._cw = None, None
         self._ws = ops.Workspace()
         self._units = None
+        # map exponent of the block-internal map (agplace_amd/map_exponents.py; a plain attribute, not a buffer).  The block's
+        # input and output share the exponent of the map that comes in (x.exp): the input is the residual operand.
+        self._map_exp = {}
 
-    def _prepared(self):
-        key = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+    def _prepared(self, e_io=0, e_mid=0):
+        """e_io / e_mid: the exponents of the input = output maps and of conv1's output (0, 0: today's constants)."""
+        key = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers())) + (e_io, e_mid)
         if key != self._key:
             cws = []
-            for conv, bn in ((self.conv1, self.bn1), (self.conv2, self.bn2)):
-                s, t = ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
-                                   conv_bias=conv.bias)
+            for conv, bn, e_in, e_out in ((self.conv1, self.bn1, e_io, e_mid), (self.conv2, self.bn2, e_mid, e_io)):
+                s, t = ops.fold_exp(*ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
+                                                 conv_bias=conv.bias), e_in, e_out)
                 cws.append(ops.ConvWeights(conv.weight, s, t, 1, 1))
             self._cw, self._key = cws, key
         return self._cw
 
     def forward_map(self, x: ops.SplitMap, prec=3, pool=None):
         """pool: optional ops.PoolReq filled with the global pooling of the block's output (in the last conv's launch)."""
-        c1, c2 = self._prepared()
+        e_mid = int(self._map_exp.get("conv1", 0)) if prec != 3 else 0       # (mode 3: fp32 range, no exponents)
+        c1, c2 = self._prepared(x.exp, e_mid)
         dev = x.hi.device
         t = self._ws.map("t", x.n, x.h, x.w, x.c, 1, prec, dev)
         o = self._ws.map("o", x.n, x.h, x.w, x.c, 1, prec, dev)
+        t.exp, o.exp = e_mid, x.exp
+        ops.probe_map(self, "in", x)
         ops.conv2d(x, c1, t, relu=True, prec=prec)
+        ops.probe_map(self, "conv1", t)
         ops.conv2d(t, c2, o, residual=x, relu=True, prec=prec, pool=pool)
+        ops.probe_map(self, "out", o)
         return o
 
     def forward(self, x, prec=3):
@@ -263,10 +272,12 @@ class Stage2FuseBlockAdd(nn.Module):
                 mean, imgoutvec = res if want_fuse else (None, res)
             else:
                 m = self._ws.map(f"add{i}", imgmap.n, imgmap.h, imgmap.w, imgmap.c, 1, prec, imgmap.hi.device)
-                ops.bcast_add(imgmap, fusevec_img, m)
+                # (a map with an exponent takes the vector times 2^-e; the per-op path spends a small launch on it, the fused
+                # vector path folds it into the projection: MM._vector_path_fused)
+                ops.bcast_add(imgmap, ops.scale_pow2(fusevec_img.detach().contiguous().float(), -imgmap.exp) if imgmap.exp else fusevec_img, m)
                 req = ops.PoolReq(self.poolimage.p, eps=self.poolimage.eps, want_mean=want_fuse, want_gem=True)
                 imgmap = self.ffnsimg[i].forward_map(m, prec, pool=req)
-                mean, imgoutvec = req.mean, req.gem
+                mean, imgoutvec = (req.true_mean() if want_fuse else None), req.true_gem()
             if want_fuse:
                 if opt.stg2_useproj is True:
                     imgvec_fuse = autograd_ops.linear(mean, self._prep_imgfuse[i].as_linear, self._prep_imgfuse[i])

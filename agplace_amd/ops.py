@@ -43,11 +43,15 @@ class SplitMap:
       prec 3 (BF16X3): split-bf16 planes, value = float(hi) + float(lo)
       prec 2 / 4 (F16W2 / F16): ONE fp16 plane in `hi`, lo is None
     (`hi` is allocated as a 16-bit torch tensor either way; only the kernels interpret it.)
+    `exp` (agplace_amd/map_exponents.py): the planes hold the true values times 2^-exp; 0 unless a calibrated exponent is installed
+    for this map.  The kernels never see it -- the producer's and the consumers' host-prepared constants carry the factor -- and
+    whatever turns the map into user-visible fp32 (to_f32) restores the true scale.
     """
-    __slots__ = ("hi", "lo", "n", "h", "w", "c", "pad", "h16")
+    __slots__ = ("hi", "lo", "n", "h", "w", "c", "pad", "h16", "exp")
 
-    def __init__(self, hi, lo, n, h, w, c, pad, h16=None):
+    def __init__(self, hi, lo, n, h, w, c, pad, h16=None, exp=0):
         self.hi, self.lo, self.n, self.h, self.w, self.c, self.pad = hi, lo, n, h, w, c, pad
+        self.exp = exp
         # training (split-bf16 maps): the same values once more as ONE fp16 plane (zero halo), written by the pass that
         # produces the map (agp_map_affine / agp_affine_maxpool3x3s2_fwd: o_h16) for the one-pass weight gradient of the conv
         # that consumes it (agp_conv_desc.in_h16); None = not kept
@@ -83,6 +87,8 @@ class SplitMap:
         out = torch.empty((self.n, self.h, self.w, self.c), dtype=torch.float32, device=self.hi.device)
         check(_L().agp_unpack_nhwc_to_f32(ptr(self.hi), ptr(self.lo), self.n, self.h, self.w, self.c,
                                           self.pad, ptr(out), _lib.stream()), "agp_unpack_nhwc_to_f32")
+        if self.exp:
+            out = scale_pow2(out, self.exp)          # the true values (exact: a power of two)
         return out.permute(0, 3, 1, 2)
 
 
@@ -108,7 +114,61 @@ def slice_map(m: SplitMap, lo, hi):
     if lo == 0 and hi == m.n:
         return m
     return SplitMap(m.hi[lo:hi], None if m.lo is None else m.lo[lo:hi], hi - lo, m.h, m.w, m.c, m.pad,
-                    None if m.h16 is None else m.h16[lo:hi])
+                    None if m.h16 is None else m.h16[lo:hi], m.exp)
+
+
+# ---- map exponents (agplace_amd/map_exponents.py): an fp16 map stored as x * 2^-e.  Everything here is host-side preparation
+# of constants the kernels already read; with every exponent 0 nothing below does anything.
+_POW2 = {}
+
+
+def pow2_scalar(device, e):
+    """The 1-element fp32 device tensor 2^e (cached per device: made once, outside any capture, by the first eager forward that
+    needs it), or None for e == 0: the optional factor of a vector-program load (VecProgram.load(scale=...)) and of wsum."""
+    if not e:
+        return None
+    key = (str(device), int(e))
+    t = _POW2.get(key)
+    if t is None:
+        t = _POW2[key] = torch.full((1,), 2.0 ** int(e), dtype=torch.float32, device=device)
+    return t
+
+
+def scale_pow2(x, e):
+    """x * 2^e for a dense fp32 tensor (agp_wsum_fwd; exact), x itself for e == 0."""
+    if not e:
+        return x
+    return wsum([x], [pow2_scalar(x.device, e)])
+
+
+def fold_exp(scale, shift, e_in, e_out):
+    """The folded BatchNorm constants of a conv that READS a map stored as x * 2^-e_in and WRITES one stored as y * 2^-e_out:
+    y * 2^-e_out = (scale * 2^(e_in - e_out)) * conv(x * 2^-e_in) + shift * 2^-e_out.  torch.ldexp: exact; (0, 0) returns the
+    inputs themselves.  A residual operand of the conv must already be stored with e_out."""
+    if not e_in and not e_out:
+        return scale, shift
+    return (torch.ldexp(scale.float(), torch.tensor(e_in - e_out, device=scale.device)),
+            torch.ldexp(shift.float(), torch.tensor(-e_out, device=shift.device)))
+
+
+# Calibration hook: None, or a callable (owner module, map name, SplitMap) that forward_maps_multi and the stage-2 image block
+# call for every map they produce (map_exponents.calibrate installs one for the duration of its mode-3 forwards).
+MAP_PROBE = None
+
+
+def probe_map(owner, name, m):
+    if MAP_PROBE is not None:
+        MAP_PROBE(owner, name, m)
+
+
+def map_absmax(m: SplitMap, word):
+    """word[0] = max(word[0], max |stored value| of m) (agp_map_absmax); word: 1-element fp32 device tensor (a view is fine)."""
+    check(_L().agp_map_absmax(ptr(m.hi), ptr(m.lo), m.n, m.h, m.w, m.c, m.pad, ptr(word), _lib.stream()), "agp_map_absmax")
+
+
+def absmax_reset(words):
+    """Zero a contiguous fp32 device tensor of running maxima with a kernel."""
+    check(_L().agp_map_absmax_reset(ptr(words), words.numel(), _lib.stream()), "agp_map_absmax_reset")
 
 
 def count_saturated(m: SplitMap):
@@ -399,7 +459,7 @@ class PoolReq:
     path reduces the values in its epilogue (agp_conv_desc::pool_partial) and agp_pool_from_conv finishes the sums, so no
     pass re-reads the map; convs that kernel does not run are pooled by agp_pool_fwd after the launch.  After
     ops.conv2d / ops.conv2d_grouped: `.mean` [n,c] and / or `.gem` [n,c]."""
-    __slots__ = ("p", "eps", "want_mean", "want_gem", "mean", "gem", "fused", "_partial", "gem_out")
+    __slots__ = ("p", "eps", "want_mean", "want_gem", "mean", "gem", "fused", "_partial", "gem_out", "exp")
 
     def __init__(self, p=None, eps=GEM_EPS, want_mean=True, want_gem=False, gem_out=None):
         """gem_out: optional preallocated fp32 [n, c] target of the GeM vector (a row slice of a whole-batch buffer)."""
@@ -410,17 +470,35 @@ class PoolReq:
         self.mean = self.gem = self._partial = None
         self.gem_out = gem_out
         self.fused = False
+        # the pooled map's exponent (SplitMap.exp), taken from the map when the request is filled.  `.mean` / `.gem` then hold the
+        # STORED map's pooling, i.e. the true vectors times 2^-exp: GeM ran with eps * 2^-exp, which makes that exact
+        # (clamp(x, eps) = 2^e clamp(x 2^-e, eps 2^-e)).  Consumers multiply by 2^exp where they read the vector anyway: a vector
+        # program's load (`.scale`), or true_mean() / true_gem() on the per-op paths.
+        self.exp = 0
+
+    @property
+    def scale(self):
+        """2^exp as a 1-element device tensor, None for exp == 0."""
+        t = self.mean if self.mean is not None else self.gem
+        return pow2_scalar(t.device, self.exp)
+
+    def true_mean(self):
+        return scale_pow2(self.mean, self.exp)
+
+    def true_gem(self):
+        return scale_pow2(self.gem, self.exp)
 
     def attach(self, d, x, cw, out, prec):
         """Before the launch: point the descriptor at a partial buffer if the kernel can pool."""
         self.fused = False
+        self.exp = out.exp
         if x.lo is None and out.lo is None:
             blocks = int(_L().agp_conv2d_pool_blocks(C.byref(d)))
             if blocks > 0:
                 self._partial = torch.empty(blocks * 2 * cw.cout, dtype=torch.float32, device=out.hi.device)
                 d.pool_partial = ptr(self._partial)
                 d.pool_p = ptr(self.p) if self.want_gem else None
-                d.pool_eps = self.eps
+                d.pool_eps = math.ldexp(self.eps, -self.exp)
                 self.fused = True
 
     def finish(self, out):
@@ -428,8 +506,10 @@ class PoolReq:
         go = self.gem_out
         if go is not None and (tuple(go.shape) != (out.n, out.c) or go.dtype != torch.float32 or not go.is_contiguous()):
             go = None
+        self.exp = out.exp
         if not self.fused:
-            self.mean, self.gem = pool_map(out, self.p, want_mean=self.want_mean, want_gem=self.want_gem, eps=self.eps, gem_out=go)
+            self.mean, self.gem = pool_map(out, self.p, want_mean=self.want_mean, want_gem=self.want_gem, eps=self.eps, gem_out=go,
+                                           raw=True)
             return
         dev = out.hi.device
         self.mean = torch.empty((out.n, out.c), dtype=torch.float32, device=dev) if self.want_mean else None
@@ -610,6 +690,7 @@ def bblock64_grouped(jobs, exact=False):
             pool.fused = True
             pool.mean = torch.empty((out.n, 64), dtype=torch.float32, device=out.hi.device)
             pool.gem = None
+            pool.exp = out.exp
             check(_L().agp_bblock64_pool_finish(ptr(pool._partial), out.n, out.h, out.w, ptr(pool.mean), _lib.stream()),
                   "agp_bblock64_pool_finish")
     return [j[3] for j in jobs]
@@ -706,19 +787,26 @@ def bcast_add(x: SplitMap, vec, out: SplitMap):
     vec = vec.contiguous().float()
     check(_L().agp_bcast_add_fwd(ptr(x.hi), ptr(x.lo), ptr(vec), x.n, x.h, x.w, x.c, x.pad,
                                  ptr(out.hi), ptr(out.lo), out.pad, _lib.stream()), "agp_bcast_add_fwd")
+    out.exp = x.exp          # (the caller hands a vector already multiplied by 2^-x.exp)
     return out
 
 
 # ------------------------------------------------------------------------- pooling
-def pool_map(x: SplitMap, p=None, want_mean=True, want_gem=True, eps=GEM_EPS, gem_out=None):
-    """(mean [n,c] or None, gem [n,c] or None) of a SplitMap in one pass."""
+def pool_map(x: SplitMap, p=None, want_mean=True, want_gem=True, eps=GEM_EPS, gem_out=None, raw=False):
+    """(mean [n,c] or None, gem [n,c] or None) of a SplitMap in one pass.  A map with an exponent (x.exp != 0) is pooled with
+    eps * 2^-exp; raw=True returns the stored values' pooling (true vectors times 2^-exp: ops.PoolReq), else the vectors are
+    multiplied by 2^exp (one more small launch each; `gem_out` then receives the stored values' GeM, not the returned one)."""
     dev = x.hi.device
+    eps = math.ldexp(eps, -x.exp)
     nfl = _L().agp_pool_workspace_floats(x.n, x.c, x.h, x.w)
     partial = torch.empty(nfl, dtype=torch.float32, device=dev)
     mean = torch.empty((x.n, x.c), dtype=torch.float32, device=dev) if want_mean else None
     gem = (gem_out if gem_out is not None else torch.empty((x.n, x.c), dtype=torch.float32, device=dev)) if want_gem else None
     check(_L().agp_pool_fwd(ptr(x.hi), ptr(x.lo), x.n, x.h, x.w, x.c, x.pad, ptr(p) if want_gem else None,
                             eps, ptr(mean), ptr(gem), ptr(partial), _lib.stream()), "agp_pool_fwd")
+    if x.exp and not raw:
+        mean = None if mean is None else scale_pow2(mean, x.exp)
+        gem = None if gem is None else scale_pow2(gem, x.exp)
     return mean, gem
 
 

@@ -76,8 +76,10 @@ class Options:
     #       perturbation, is what the lo product removes; about half the throughput of mode 4
     #   3 = BF16X3: split-bf16 activations and weights, three products, ~1e-5 everywhere, fp32 range
     # Modes 2 and 4 store fp16 maps, which saturate at +-65504: the first inference forward after a weight (re)load counts
-    # saturated map elements and warns (resnet.SATURATION_CHECK) -- such a checkpoint needs mode 3.  Training (.train()) always
-    # runs on split-bf16 maps (3); kNN has its own setting.
+    # saturated map elements and warns (resnet.SATURATION_CHECK).  Such a checkpoint stays in modes 2 / 4 with calibrated map
+    # exponents (agplace_amd/map_exponents.py: the image path's maps stored times 2^-e, folded into host-prepared constants --
+    # same kernels, same speed); mode 3 remains the remedy for what they do not cover (the sparse-voxel branch's maps).  Training
+    # (.train()) always runs on split-bf16 maps (3); kNN has its own setting.
     mfma_precision: int = 4
     # Opt-in fp16 range guard (agplace_amd/range_guard.py): inference forwards in modes 2 / 4 bind a sticky device word that
     # every kernel storing an inference fp16 map (the table in DESIGN.md section 2) sets when it had to clamp a value to +-65504

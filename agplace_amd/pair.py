@@ -154,7 +154,11 @@ class CapturedPair:
     replay() enqueues one replay and -- every `poll_every` replays -- looks at the query model's voxel-range mirror in pinned host
     memory (MM.poll_voxel_range: no stream is synchronised) and raises ValueError when an earlier replay embedded a cloud outside
     the device-side coordinate manager's limits; finish() waits for the stream and checks the replays the polls could not have
-    seen yet.  Without `coords` in qdata the polls are no-ops."""
+    seen yet.  Without `coords` in qdata the polls are no-ops.
+
+    Map exponents (agplace_amd/map_exponents.py) only change host-prepared buffers (folded scale / shift, projection planes, the
+    pools' eps and 2^e factors), all read at capture time: a graph captured AFTER set_exponents / calibrate replays them;
+    changing the exponents afterwards invalidates the capture exactly like a weight reload does -- capture again."""
 
     def __init__(self, modelq, modeldb, qdata, dbdata, stream=None, warmup=2, poll_every=8):
         dev = qdata['query_image'].device

@@ -3,7 +3,9 @@
 Precision modes 2 and 4 store every feature map as fp16 and the conv epilogues clamp each value to +-65504 before the
 conversion (csrc/common.hpp), so a map beyond fp16's range saturates silently.  While a device word is BOUND to the calling
 host thread (agp_range_flag_set, include/agplace_hip.h), every guarded kernel that had to clamp a value ORs 1 into that word.
-The stored values are the same bits with and without a binding.
+The stored values are the same bits with and without a binding.  With map exponents installed
+(agplace_amd/map_exponents.py) a map is stored times 2^-e and the guard keeps watching the stored values: it then reports only
+what the calibration did not cover.
 
 One Guard per model: one sticky int32 word per device, one pinned host mirror and one event per launching stream.  After a
 guarded forward, publish() enqueues a non-blocking copy of the word to the stream's mirror; captured into a hipGraph that copy
@@ -126,7 +128,9 @@ class Guard:
         also = "".join(f"; this report also covers {a}" for a in sorted(self.also))
         raise ValueError(f"{self.owner}: in {which} batch a feature map left fp16's range (|v| > 65504) and was stored saturated in "
                          f"precision mode {prec}: its outputs are wrong{also}. Run this model with Options.mfma_precision = 3 "
-                         "(split-bf16 maps, fp32 range)")
+                         "(split-bf16 maps, fp32 range). For the image path agplace_amd.map_exponents.calibrate chooses per-map "
+                         "power-of-two exponents that keep such a checkpoint in this mode; the guard watches the STORED values, so "
+                         "with exponents installed it reports what the calibration did not cover")
 
 
 def guard_of(model):

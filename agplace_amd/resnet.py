@@ -99,31 +99,69 @@ class ResNet(nn.Module):
         # (never part of a forward: it cannot receive a gradient.  Frozen, so that a data-parallel gradient exchange does not carry
         # 513 k zeros per trunk and optimizers built from .parameters() skip it; the state_dict keys stay)
         self.fc.requires_grad_(False)
-        self._prep = None
+        self._prep = {}
         self._prep_key = None
         self._ws = ops.Workspace()
+        # map exponents (agplace_amd/map_exponents.py): {map name: e}, a plain attribute -- not a parameter or a buffer, so
+        # state_dict() keeps the reference's keys.  Names: "layer{L}" = the residual group of stage L (its incoming identity and
+        # every block output; for layer1 also the pooled stem output), "layer{L}.{b}.conv{k}" = a block-internal map.
+        self._map_exp = {}
 
     # ------------------------------------------------------------------ weights
     def _version_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters()) + \
-            tuple((b.data_ptr(), b._version) for b in self.buffers())
+            tuple((b.data_ptr(), b._version) for b in self.buffers()) + tuple(sorted(self._map_exp.items()))
 
-    def _prepared(self):
-        key = self._version_key()
-        if self._prep is not None and key == self._prep_key:
-            return self._prep
-        prep = {}
-
-        def fold(conv, bn, stem=False):
-            s, t = ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-            return ops.ConvWeights(conv.weight, s, t, conv.stride[0], conv.padding[0], stem=stem)
-
-        prep["stem"] = fold(self.conv1, self.bn1, stem=True)
+    def map_exponent_names(self):
+        """(groups, internal): {group name: [member map names]} and [block-internal map names] of this trunk -- the names
+        forward_maps_multi hands to ops.MAP_PROBE and map_exponents works with."""
+        groups, internal = {}, []
         for li in range(self.nstages):
+            mem = ["stem"] if li == 0 else []
             for bi, blk in enumerate(getattr(self, f"layer{li + 1}")):
                 seq, ds = blk.convs()
-                prep[(li, bi)] = ([fold(c, b) for c, b in seq], fold(*ds) if ds else None)
-        self._prep, self._prep_key = prep, key
+                if ds:
+                    mem.append(f"layer{li + 1}.{bi}.downsample")
+                internal += [f"layer{li + 1}.{bi}.conv{ci + 1}" for ci in range(len(seq) - 1)]
+                mem.append(f"layer{li + 1}.{bi}.out")
+            groups[f"layer{li + 1}"] = mem
+        return groups, internal
+
+    def _prepared(self, scaled=False):
+        """scaled: fold the map exponents into the BatchNorm constants (inference on fp16 maps, modes 2 / 4).  Mode 3 and the
+        training graph use the unscaled constants.  With no non-zero exponent both are ONE set of tensors."""
+        key = self._version_key()
+        if key != self._prep_key:
+            self._prep, self._prep_key = {}, key
+        scaled = bool(scaled) and any(self._map_exp.values())
+        if scaled in self._prep:
+            return self._prep[scaled]
+        prep = {}
+        mexp = prep["exp"] = {}      # exponent of every map the prepared convs write: "stem", (li, bi, ci), ("ds", li, bi)
+
+        def E(name):
+            return int(self._map_exp.get(name, 0)) if scaled else 0
+
+        def fold(conv, bn, e_in, e_out, stem=False):
+            s, t = ops.fold_exp(*ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps), e_in, e_out)
+            return ops.ConvWeights(conv.weight, s, t, conv.stride[0], conv.padding[0], stem=stem)
+
+        mexp["stem"] = E("layer1")
+        prep["stem"] = fold(self.conv1, self.bn1, 0, mexp["stem"], stem=True)     # (conv + BN + ReLU + max-pool: positively homogeneous)
+        for li in range(self.nstages):
+            g_out = E(f"layer{li + 1}")
+            for bi, blk in enumerate(getattr(self, f"layer{li + 1}")):
+                seq, ds = blk.convs()
+                g_in = E(f"layer{li}") if (bi == 0 and li > 0) else g_out
+                cws, e_prev = [], g_in
+                for ci, (c, b) in enumerate(seq):
+                    e_o = g_out if ci == len(seq) - 1 else E(f"layer{li + 1}.{bi}.conv{ci + 1}")
+                    cws.append(fold(c, b, e_prev, e_o))
+                    mexp[(li, bi, ci)] = e_prev = e_o
+                # the downsample folds to the NEW stage's exponent: the residual operand is then stored like the output
+                mexp[("ds", li, bi)] = g_out
+                prep[(li, bi)] = (cws, fold(*ds, g_in, g_out) if ds else None)
+        self._prep[scaled] = prep
         return prep
 
     @staticmethod
@@ -298,7 +336,9 @@ class ResNet(nn.Module):
 STEM_READS_INPUT = "auto"
 # fp16 maps (precision modes 2 / 4) saturate at +-65504.  The first inference forward after a weight (re)load counts the
 # saturated elements of the stage outputs (one small reduction + one host read, never inside a stream capture) and warns:
-# such a checkpoint needs Options.mfma_precision = 3 (split-bf16 maps, fp32 range).  SATURATION_CHECK = False turns it off.
+# such a checkpoint needs calibrated map exponents (agplace_amd/map_exponents.py: the maps stored times 2^-e, same kernels, same
+# speed) or Options.mfma_precision = 3 (split-bf16 maps, fp32 range).  The census counts STORED values, so with exponents
+# installed it reports what the calibration did not cover.  SATURATION_CHECK = False turns it off.
 SATURATION_CHECK = True
 STAGE1_CHUNK = 1 << 30   # images of the first (largest) trunk per pass over stem + stage 1 (off: see forward_maps_multi)
 
@@ -325,7 +365,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
     for b in nets[1:]:
         if (b.fe_type, b.nstages) != (a.fe_type, a.nstages):
             raise ValueError("forward_maps_multi: the trunks must share one architecture")
-    preps = [net._prepared() for net in nets]
+    preps = [net._prepared(scaled=prec != 3) for net in nets]
     geo = [net._input_geometry(x) for net, x in zip(nets, xs)]
     devs = [g[3] for g in geo]
     nchunks = max(1, -(-geo[0][0] // STAGE1_CHUNK))
@@ -347,15 +387,19 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
             cws = {r: preps[r][(li, bi)] for r in act}
             idt = dict(cur)
 
-            def view(r, tag, h_, w_, c_):
-                return ops.slice_map(nets[r]._ws.map(tag, geo[r][0], h_, w_, c_, 1, prec, devs[r]), lo[r], hi[r])
+            def view(r, tag, h_, w_, c_, e_):
+                v = ops.slice_map(nets[r]._ws.map(tag, geo[r][0], h_, w_, c_, 1, prec, devs[r]), lo[r], hi[r])
+                v.exp = e_
+                return v
+            mexp = {r: preps[r]["exp"] for r in act}
+            lname = f"layer{li + 1}.{bi}"
             ds_jobs = []
             if cws[act[0]][1] is not None:
                 for r in act:
                     dsw = cws[r][1]
                     ho = ops.conv_out_size(cur[r].h, 3, blks[r].stride, 1)
                     wo = ops.conv_out_size(cur[r].w, 3, blks[r].stride, 1)
-                    idt[r] = view(r, f"ds{li}.{bi}", ho, wo, dsw.cout)
+                    idt[r] = view(r, f"ds{li}.{bi}", ho, wo, dsw.cout, mexp[r][("ds", li, bi)])
                     ds_jobs.append((cur[r], dsw, idt[r], None, False))
             t = dict(cur)
             nconv = len(cws[act[0]][0])
@@ -369,7 +413,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                 for r in act:
                     pool = stage_pool[r].get(li) if (bi == nblocks - 1 and (li > 0 or nchunks == 1)) else None
                     pools[r] = pool
-                    out_ = view(r, f"c{li}.{bi}.1", cur[r].h, cur[r].w, 64)
+                    out_ = view(r, f"c{li}.{bi}.1", cur[r].h, cur[r].w, 64, mexp[r][(li, bi, 1)])
                     jobs.append((cur[r], cws[r][0][0], cws[r][0][1], out_, pool if (pool is not None and not pool.want_gem) else None))
                 outs_ = ops.bblock64_grouped(jobs)
                 for r, o in zip(act, outs_):
@@ -377,6 +421,9 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                         pools[r].fused = False
                         pools[r].finish(o)
                 cur = {r: o for r, o in zip(act, outs_)}
+                if ops.MAP_PROBE is not None:       # (a calibration runs in mode 3 and never takes the fused block; for completeness)
+                    for r in act:
+                        ops.probe_map(nets[r], f"{lname}.out", cur[r])
                 continue
             for ci in range(nconv):
                 last = ci == nconv - 1
@@ -388,7 +435,8 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                     # the conv that writes a stage output also pools it (whole-batch passes only: a chunk's partial sums
                     # would cover a slice of the images)
                     pool = stage_pool[r].get(li) if (last and bi == nblocks - 1 and (li > 0 or nchunks == 1)) else None
-                    jobs.append((t[r], cw, view(r, f"c{li}.{bi}.{ci}", oh, ow, cw.cout), idt[r] if last else None, True, pool))
+                    jobs.append((t[r], cw, view(r, f"c{li}.{bi}.{ci}", oh, ow, cw.cout, mexp[r][(li, bi, ci)]), idt[r] if last else None,
+                                 True, pool))
                 if ci == 0 and ds_jobs:
                     # the downsample reads the block's input like conv1 and is independent of it: one grouped launch
                     # (agp_conv2d_fwd_grouped: the latency-bound 1x1 hides between the tiles of the stride-2 3x3)
@@ -400,6 +448,11 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                 else:
                     outs_ = ops.conv2d_grouped(jobs, prec)
                 t = {r: o for r, o in zip(act, outs_)}
+                if ops.MAP_PROBE is not None:
+                    for r in act:
+                        ops.probe_map(nets[r], f"{lname}.out" if last else f"{lname}.conv{ci + 1}", t[r])
+                        if ci == 0 and ds_jobs:
+                            ops.probe_map(nets[r], f"{lname}.downsample", idt[r])
             cur = t
         return cur
 
@@ -417,6 +470,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
             h1, w1 = ops.conv_out_size(h, 7, 2, 3), ops.conv_out_size(w, 7, 2, 3)
             h2, w2 = ops.conv_out_size(h1, 3, 2, 1), ops.conv_out_size(w1, 3, 2, 1)
             c = ops.slice_map(ws.map("pool", n, h2, w2, 64, 1, prec, dev), lo[r], hi[r])
+            c.exp = prep["exp"]["stem"]
             if prec == 4 and FUSE_STEM_POOL and STEM_READS_INPUT != "0" and not isinstance(x, ops.SplitMap) and (
                     STEM_READS_INPUT == "1" or ops.stem_walk_reads(x[lo[r]:hi[r]])):
                 # the stem kernel converts the raw input (fp32 image or uint8 tiles) on its way into LDS: no packed copy
@@ -432,6 +486,8 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                 ops.conv2d(xin, prep["stem"], s_, relu=True, prec=prec)
                 ops.maxpool3x3s2(s_, c)
             cur[r] = c
+        for r in cur:
+            ops.probe_map(nets[r], "stem", cur[r])
         last_views = run_stage(0, cur, lo, hi)
         if stage1_tags is None:
             stage1_tags = {r: (v.h, v.w, v.c) for r, v in last_views.items()}
@@ -441,6 +497,8 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
     nb0 = len(a.layer1)
     nc0 = len(preps[0][(0, nb0 - 1)][0])
     cur = {r: nets[r]._ws.map(f"c0.{nb0 - 1}.{nc0 - 1}", geo[r][0], *stage1_tags[r], 1, prec, devs[r]) for r in range(R)}
+    for r in range(R):
+        cur[r].exp = preps[r]["exp"][(0, nb0 - 1, nc0 - 1)]
     outs = [[] for _ in nets]
     zero, full = [0] * R, [g[0] for g in geo]
     for li in range(a.nstages):
@@ -464,6 +522,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                 if nsat:
                     import warnings
                     warnings.warn(f"agplace_amd: {nsat} feature-map elements of a {net.fe_type} trunk sit at the fp16 limit (+-65504): "
-                                  f"these weights / inputs leave fp16's range in precision mode {prec}; run this model with "
-                                  "Options.mfma_precision = 3 (split-bf16 maps)")
+                                  f"these weights / inputs leave fp16's range in precision mode {prec}; calibrate map exponents "
+                                  "(agplace_amd.map_exponents.calibrate) or run this model with Options.mfma_precision = 3 "
+                                  "(split-bf16 maps)")
     return outs

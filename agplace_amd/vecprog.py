@@ -84,15 +84,16 @@ class VecProgram:
         self._op(_lib.VP_STORE, r=(r,), p=(ptr(out),))
         return out
 
-    def linear(self, dst, lw, src, add1=-1, add2=-1, act=None):
-        """src: a register, or a [b, lw.k] tensor read straight from memory."""
+    def linear(self, dst, lw, src, add1=-1, add2=-1, act=None, scale=None):
+        """src: a register, or a [b, lw.k] tensor read straight from memory -- then `scale` (optional 1-element device tensor)
+        multiplies it on the way in: the 2^e of a vector pooled from a map stored with an exponent (ops.PoolReq.scale)."""
         wh, wl, bias = self._weights(lw)
         if torch.is_tensor(src):
             if src.shape[1] != lw.k:
                 raise VecProgramUnfit("operand width")
-            src = self.load(dst, src)                 # through the destination register (the product reads before it writes)
-        elif lw.k != 256:
-            raise VecProgramUnfit("a register operand is 256 wide")
+            src = self.load(dst, src, scale)          # through the destination register (the product reads before it writes)
+        elif lw.k != 256 or scale is not None:
+            raise VecProgramUnfit("a register operand is 256 wide and takes no scale")
         return self._op(_lib.VP_LINEAR, dst, r=(src, add1, add2), k=lw.k, act=_lib.ACT[act], p=(wh, wl, bias))
 
     def fcode(self, dst, mod, src, add1=-1, add2=-1):

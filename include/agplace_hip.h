@@ -141,6 +141,15 @@ int agp_unpack_nhwc_to_f32(const void* hi, const void* lo, int n, int h, int w, 
  * allocated map needs before the kernel that writes its interior (the halo is a convolution's zero padding; no kernel writes it). */
 int agp_map_zero_halo(void* hi, void* lo, int n, int h, int w, int c, int pad, void* stream);
 
+/* *inout_max = max(*inout_max, max |x|) over a halo-padded NHWC map in either storage format (lo == NULL: one fp16 plane, else
+ * the bf16 pair hi + lo); c % 8 == 0.  One HBM pass; the word ACCUMULATES, so the maximum over several maps or batches needs no
+ * host round trip (zero it first with agp_map_absmax_reset).  The halo is read with the interior and must be zero (it is by the
+ * map contract).  A NaN in the map propagates: the word then holds a NaN pattern.  The calibration pass of
+ * agplace_amd/map_exponents.py measures every fp16-stored map of the image path with it. */
+int agp_map_absmax(const void* hi, const void* lo, int n, int h, int w, int c, int pad, float* inout_max, void* stream);
+/* words[0 .. n) = 0 with a kernel (capturable next to replayed graphs, unlike a memset node). */
+int agp_map_absmax_reset(float* words, int n, void* stream);
+
 /* ------------------------------------------------------------ convolution */
 
 /* One fused implicit-GEMM convolution on the MFMA pipes:
