@@ -17,7 +17,11 @@ PREC_BF16X3 = 3
 PREC_F16 = 4
 FMT_BF16, FMT_F16 = 0, 1
 ACT = {None: 0, "id": 0, "relu": 1, "tanh": 2, "sigmoid": 3}
-ODE = {"euler": 0, "midpoint": 1, "rk4": 2}
+ODE = {"euler": 0, "midpoint": 1, "rk4": 2}      # fixed-grid methods (agp_fcode_fwd, the vector programs)
+ODE_ADAPTIVE = {"dopri5": 3}                     # adaptive methods (agp_fcode_adaptive_fwd)
+ODE_STATUS = {0: "ok", 1: "odeint_max_steps attempted steps did not reach t = 1", 2: "step size underflow (t + dt == t)",
+              3: "the error ratio is NaN"}
+ODE_MAX_STEPS_LIMIT = 4096
 E_UNSUPPORTED = 3
 GP_FLOATS = 1 + 16384 + 1     # AGP_GP_FLOATS (include/agplace_hip.h): the dL/dp buffer of the GeM backward entries
 _ERR = {1: "AGP_E_BADARG (unsupported shape / enum / null pointer)",
@@ -107,6 +111,11 @@ SIGNATURES = {
     "agp_fcode_traj_floats": (_L, [_I, _I, _I]),
     "agp_fcode_bwd_workspace_bytes": (_L, [_I, _I, _I]),
     "agp_fcode_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, _P, _P, _P, _P, _L, _P]),
+    "agp_fcode_adaptive_ctrl_bytes": (_L, [_I]),
+    "agp_fcode_adaptive_ring_floats": (_L, [_I, _I, _I]),
+    "agp_fcode_adaptive_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P]),
+    "agp_fcode_adaptive_bwd_workspace_bytes": (_L, [_I, _I]),
+    "agp_fcode_adaptive_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
     "agp_linear_bwd_workspace_bytes": (_L, [_I, _I, _I]),
     "agp_linear_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
     "agp_layernorm_bwd": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P]),

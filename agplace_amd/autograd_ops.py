@@ -43,12 +43,22 @@ def linear(x, module, prep, act=None, add1=None, add2=None):
 
 
 class FCODEFn(torch.autograd.Function):
-    """Fixed-grid Neural-ODE block; backward is discretise-then-optimise (agp_fcode_bwd)."""
+    """Neural-ODE block; backward is discretise-then-optimise (agp_fcode_bwd; agp_fcode_adaptive_bwd for an adaptive method,
+    through the accepted steps, with the step control a constant)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, add1, add2):
         need = any(ctx.needs_input_grad)
         lw = mod._prep.get(with_transpose=need)
+        if mod.adaptive:
+            out = ops.fcode_adaptive(x, lw, mod.act_name, mod.method, mod.tol, mod.max_steps, add1=add1, add2=add2,
+                                     want_traj=need)
+            mod._ctrl = out[1]
+            if need:
+                ctx.save_for_backward(out[2], out[1])
+                ctx.mod = mod
+                ctx.has = (add1 is not None, add2 is not None)
+            return out[0]
         out = ops.fcode(x, lw, mod.act_name, mod.method, mod.dts, add1=add1, add2=add2, want_traj=need)
         if not need:
             return out
@@ -60,10 +70,14 @@ class FCODEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        (traj,) = ctx.saved_tensors
         mod = ctx.mod
         lw = mod._prep.get(with_transpose=True)
-        gx, gw, gb = ops.fcode_bwd(traj, gy, lw, mod.act_name, mod.method, mod.dts)
+        if mod.adaptive:
+            traj, ctrl = ctx.saved_tensors
+            gx, gw, gb = ops.fcode_adaptive_bwd(traj, ctrl, gy, lw, mod.act_name, mod.method, mod.max_steps)
+        else:
+            (traj,) = ctx.saved_tensors
+            gx, gw, gb = ops.fcode_bwd(traj, gy, lw, mod.act_name, mod.method, mod.dts)
         return (gx if ctx.needs_input_grad[0] else None, gw if ctx.needs_input_grad[1] else None,
                 gb if ctx.needs_input_grad[2] else None, None,
                 gx if ctx.has[0] and ctx.needs_input_grad[4] else None,

@@ -7,6 +7,8 @@ used: the whole fixed-grid solve (all steps, all stages) is ONE persistent HIP k
 torchdiffeq's constructor exactly (niters = ceil(1/step + 1), arange * step, last point forced
 to 1) and is kept in fp32 (the reference builds t with .float().type_as(x)).
 'rk4' is torchdiffeq's 3/8-rule variant.  rtol/atol (opt.tol) are ignored by fixed-grid solvers.
+odeint_method = 'dopri5' (torchdiffeq's default, adaptive) reads them: rtol = atol = opt.tol, one launch per solve as well
+(agp_fcode_adaptive_fwd), at most opt.odeint_max_steps attempted steps; odeint_size is ignored.
 state_dict keys: func.func.fc.{weight,bias} (via ODEFunc -> FC -> nn.Linear).
 """
 import torch
@@ -88,9 +90,15 @@ class FCODE(nn.Module):
         self.act_name = act
         self.method = opt.odeint_method
         self.step_size = opt.odeint_size
-        if self.method not in ('euler', 'midpoint', 'rk4'):
+        if self.method not in ('euler', 'midpoint', 'rk4', 'dopri5'):
             raise NotImplementedError(self.method)
-        self.dts = ops.ode_grid_dts(self.step_size)
+        self.adaptive = self.method == 'dopri5'
+        self.tol = float(opt.tol)
+        self.max_steps = int(opt.odeint_max_steps)
+        if self.adaptive and not self.tol > 0.0:
+            raise ValueError(f"tol {opt.tol!r}: dopri5 needs rtol = atol > 0")
+        self.dts = None if self.adaptive else ops.ode_grid_dts(self.step_size)
+        self._ctrl = None                 # device control block of the last adaptive solve (solver_stats)
         self._prep = _PreparedLinear(self.func.func.fc)
 
     def forward(self, x, add1=None, add2=None):
@@ -98,6 +106,18 @@ class FCODE(nn.Module):
         if fc.in_features == 256:
             return autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, self, add1, add2)
         return self._forward_any_width(x, add1, add2)
+
+    def solver_stats(self):
+        """The record of this block's last adaptive solve (synchronises): status, accepted, rejected, attempted, f_evals,
+        t0, t1, dts.  Raises RuntimeError when that solve failed (its output is NaN)."""
+        if self._ctrl is None:
+            raise RuntimeError("solver_stats: no adaptive solve has run on this block")
+        st = ops.ode_stats(self._ctrl)
+        if st["status"] != 0:
+            from .. import _lib
+            raise RuntimeError(f"FCODE {self.method}: {_lib.ODE_STATUS.get(st['status'], st['status'])} after "
+                               f"{st['attempted']} attempted steps (t = {st['t0']:.6g}); the output is NaN")
+        return st
 
     def _forward_any_width(self, x, add1, add2):
         """FCODE(dim) for dim != 256 (the reference's class takes any width, ffns.py:78-87; `--mm_stg2fuse_dim`,
@@ -107,6 +127,8 @@ class FCODE(nn.Module):
         time grid of torchdiffeq's constructor.  Latency-bound like the fused kernel, ~3 launches per stage instead of one
         per solve."""
         fc, dev = self.func.func.fc, x.device
+        if self.adaptive:
+            raise NotImplementedError(f"FCODE {self.method}: the adaptive solver is built for dim=256, got {fc.in_features}")
         if fc.in_features % 32:
             raise NotImplementedError("FCODE: dim must be a multiple of 32")
         key = str(dev)

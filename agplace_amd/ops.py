@@ -956,6 +956,68 @@ def fcode_bwd(traj, gy, lw: LinearWeights, act, method, dts):
     return gx, gw, gb
 
 
+def _adaptive_args(x, lw, act, method, tol, max_steps):
+    if x.shape[1] != 256 or lw.k != 256 or lw.n != 256:
+        raise NotImplementedError(f"FCODE {method}: the adaptive solver is built for dim=256")
+    if method not in _lib.ODE_ADAPTIVE:
+        raise NotImplementedError(method)
+    if act not in _lib.ACT:
+        raise NotImplementedError(act)
+    if not (isinstance(max_steps, int) and 1 <= max_steps <= _lib.ODE_MAX_STEPS_LIMIT):
+        raise ValueError(f"odeint_max_steps {max_steps!r}: an integer in 1 .. {_lib.ODE_MAX_STEPS_LIMIT}")
+    if not float(tol) > 0.0:
+        raise ValueError(f"tol {tol!r}: the adaptive solver needs rtol = atol > 0")
+
+
+def fcode_adaptive(x, lw: LinearWeights, act, method, tol, max_steps=64, add1=None, add2=None, want_traj=False):
+    """y(1) of y' = act(y W^T + b), y(0) = x + add1 + add2, by the adaptive solver `method` ('dopri5') with rtol = atol = tol:
+    ONE launch (agp_fcode_adaptive_fwd), no host synchronisation, capturable.  Returns (y, ctrl) or, with want_traj,
+    (y, ctrl, traj): ctrl is the device control block (ode_stats(ctrl) reads it), traj the record fcode_adaptive_bwd needs.
+    A solve that fails (step cap, step-size underflow, NaN) returns NaN and says why in ctrl."""
+    _need_cuda(x, "fcode_adaptive")
+    x = x.contiguous().float()
+    b = x.shape[0]
+    add1, add2 = _vec_operand(add1, x, "fcode add1"), _vec_operand(add2, x, "fcode add2")
+    _adaptive_args(x, lw, act, method, tol, max_steps)
+    y = torch.empty_like(x)
+    ctrl = torch.empty(_L().agp_fcode_adaptive_ctrl_bytes(max_steps), dtype=torch.uint8, device=x.device)
+    ring = torch.empty(_L().agp_fcode_adaptive_ring_floats(b, max_steps, int(want_traj)), dtype=torch.float32, device=x.device)
+    check(_L().agp_fcode_adaptive_fwd(ptr(x), ptr(add1), ptr(add2), ptr(lw.w_hi), ptr(lw.w_lo), ptr(lw.bias), b, _lib.ACT[act],
+                                      _lib.ODE_ADAPTIVE[method], float(tol), float(tol), max_steps, ptr(y), ptr(ring),
+                                      int(want_traj), ptr(ctrl), _lib.stream()), "agp_fcode_adaptive_fwd")
+    return (y, ctrl, ring) if want_traj else (y, ctrl)
+
+
+def fcode_adaptive_bwd(traj, ctrl, gy, lw: LinearWeights, act, method, max_steps=64):
+    """(gx, gw, gb) of fcode_adaptive(..., want_traj=True); the step count and the step sizes stay on the device."""
+    gy = gy.contiguous().float()
+    b, d = gy.shape
+    gx = torch.empty_like(gy)
+    gw = torch.empty((d, d), dtype=torch.float32, device=gy.device)
+    gb = torch.empty(d, dtype=torch.float32, device=gy.device)
+    nbytes = _L().agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
+    check(_L().agp_fcode_adaptive_bwd(ptr(traj), ptr(ctrl), ptr(gy), ptr(lw.wt_hi), ptr(lw.wt_lo), b, _lib.ACT[act],
+                                      _lib.ODE_ADAPTIVE[method], max_steps, ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes,
+                                      _lib.stream()), "agp_fcode_adaptive_bwd")
+    return gx, gw, gb
+
+
+def ode_stats(ctrl):
+    """The record an adaptive solve left in its control block, as a dict (synchronises): status, accepted, rejected,
+    attempted, f_evals, t0, t1 (the span of the last accepted step), dts (the accepted step sizes) and attempts
+    ((dt, ratio, accepted) of every attempted step)."""
+    raw = ctrl.cpu()
+    i = raw[:16].view(torch.int32).tolist()
+    t = raw[16:32].view(torch.float64).tolist()
+    cap = (raw.numel() - 32) // 24
+    n, m = max(0, min(i[1], cap)), max(0, min(i[1] + i[2], cap))
+    att = raw[32 + 8 * cap:32 + 8 * cap + 16 * m].view(torch.float64).view(-1, 2).tolist()
+    return {"status": i[0], "accepted": i[1], "rejected": i[2], "attempted": i[1] + i[2], "f_evals": i[3],
+            "t0": t[0], "t1": t[1], "dts": raw[32:32 + 8 * n].view(torch.float64).tolist(),
+            "attempts": [(d, r, r <= 1) for d, r in att]}
+
+
 def linear_bwd(x, y, gy, lw: LinearWeights, act=None, need_gx=True, need_gw=True, need_gb=True):
     """Backward of y = act(x W^T + b): (gx [b,k], gw [n,k], gb [n]); lw must hold W^T planes."""
     gy = gy.contiguous().float()

@@ -53,7 +53,8 @@ class Options:
     diff_direction: str = "backward"
     odeint_method: str = "euler"
     odeint_size: float = 0.1
-    tol: float = 1e-3
+    tol: float = 1e-3                 # rtol = atol of the adaptive solver (odeint_method = "dopri5"); fixed grids ignore it
+    odeint_max_steps: int = 64        # attempted steps after which an adaptive solve gives up and returns NaN (torchdiffeq: 2^31 - 1)
     imagevoxorg_weight: float = 0.0
     imagevoxorg_learnweight: bool = False
     shalloworg_weight: float = 1.0
@@ -125,6 +126,8 @@ class Options:
             raise ValueError(f"train_precision {self.train_precision!r}: 32 (tight) | 16 (one-product forward convs)")
         if self.train_dgrad_products not in (1, 3):
             raise ValueError(f"train_dgrad_products {self.train_dgrad_products!r}: 3 (tight) | 1 (one-product data gradients)")
+        if not (isinstance(self.odeint_max_steps, int) and 1 <= self.odeint_max_steps <= 4096):
+            raise ValueError(f"odeint_max_steps {self.odeint_max_steps!r}: an integer in 1 .. 4096")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
 

@@ -98,6 +98,8 @@ class VecProgram:
 
     def fcode(self, dst, mod, src, add1=-1, add2=-1):
         """mod: network_mm.ffns.FCODE."""
+        if mod.adaptive:
+            raise VecProgramUnfit("adaptive solver")
         lw = mod._prep.get()
         if lw.k != 256:
             raise VecProgramUnfit("FCODE width")

@@ -70,6 +70,14 @@ extern "C" {
 #define AGP_ODE_EULER 0
 #define AGP_ODE_MIDPOINT 1
 #define AGP_ODE_RK4 2 /* torchdiffeq 'rk4' = 3/8 rule */
+/* adaptive solver (agp_fcode_adaptive_fwd / _bwd only): Dormand-Prince 5(4), torchdiffeq's default method */
+#define AGP_ODE_DOPRI5 3
+/* agp_ode_stats.status of an adaptive solve; non-zero = the output is NaN */
+#define AGP_ODE_OK 0
+#define AGP_ODE_E_MAXSTEPS 1  /* max_steps attempted steps did not reach t = 1 */
+#define AGP_ODE_E_UNDERFLOW 2 /* t + dt == t */
+#define AGP_ODE_E_NAN 3       /* the error ratio is NaN */
+#define AGP_ODE_MAX_STEPS_LIMIT 4096
 
 const char* agp_version(void);
 /* Returns the gfx arch string the device code was built for ("gfx950"). */
@@ -388,6 +396,41 @@ int64_t agp_fcode_bwd_workspace_bytes(int b, int method, int nsteps);
 int agp_fcode_bwd(const float* traj, const float* gy, const void* wt_hi, const void* wt_lo, int b,
                   int act, int method, const float* dt, int nsteps, float* gx, float* gw, float* gb,
                   void* workspace, int64_t workspace_bytes, void* stream);
+
+/* FCODE by the ADAPTIVE solver dopri5 (method = AGP_ODE_DOPRI5; D = 256 only): y(1) of dy/dt = act(y W^T + b),
+ * y(0) = x (+ add1 + add2), with torchdiffeq's step control -- one RMS error norm over all b * 256 elements, steps not
+ * clipped to the end time, the result read off the last step's quartic interpolant.  ONE launch of
+ * one persistent workgroup per solve, no host round trip: capturable.  f runs on W's two split-bf16 planes and THREE bf16 planes
+ * of the state (five MFMA products): the error estimate is a cancelling sum of the k_i and needs fp32-class stages.  It always ends: after max_steps attempted steps
+ * (1 .. AGP_ODE_MAX_STEPS_LIMIT), when t + dt == t, or on a NaN error ratio it writes a non-zero status and fills y with NaN.
+ *   ctrl: agp_fcode_adaptive_ctrl_bytes(max_steps) bytes of DEVICE memory, written by the launch: an agp_ode_stats record,
+ *         double dt[max_steps], the step size of every ACCEPTED step, and double attempt[max_steps][2], the step size and
+ *         the error ratio of every ATTEMPTED step (accepted iff ratio <= 1).
+ *   ring: agp_fcode_adaptive_ring_floats(b, max_steps, want_traj) floats of DEVICE scratch.  want_traj != 0: on return
+ *         ring[n][0][b][256] = y before accepted step n, ring[n][1 + j][b][256] = its k_{j+1} (j < 7) -- the trajectory
+ *         agp_fcode_adaptive_bwd reads. */
+typedef struct agp_ode_stats {
+    int32_t status;   /* AGP_ODE_OK or AGP_ODE_E_* */
+    int32_t accepted; /* accepted steps */
+    int32_t rejected; /* rejected steps */
+    int32_t f_evals;  /* evaluations of f, the two of the first-step choice included */
+    double t0, t1;    /* the last accepted step spans [t0, t1], t1 >= 1 on success */
+} agp_ode_stats;
+int64_t agp_fcode_adaptive_ctrl_bytes(int max_steps);
+int64_t agp_fcode_adaptive_ring_floats(int b, int max_steps, int want_traj);
+int agp_fcode_adaptive_fwd(const float* x, const float* add1, const float* add2, const void* w_hi, const void* w_lo,
+                           const float* bias, int b, int act, int method, double rtol, double atol, int max_steps,
+                           float* y, float* ring, int want_traj, void* ctrl, void* stream);
+
+/* Backward of agp_fcode_adaptive_fwd: discretise-then-optimise through the ACCEPTED steps with their recorded step sizes
+ * (step control is a constant, as in torchdiffeq), the last step through its interpolation weights; the adjoint of a step's
+ * first stage flows into the step before (FSAL).  The step count and the step sizes are read from `ctrl` on the device.
+ * traj = the forward's ring (want_traj != 0, same max_steps).  Outputs as agp_fcode_bwd; after a failed forward they are
+ * NaN.  workspace: agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps) bytes. */
+int64_t agp_fcode_adaptive_bwd_workspace_bytes(int b, int max_steps);
+int agp_fcode_adaptive_bwd(const float* traj, const void* ctrl, const float* gy, const void* wt_hi, const void* wt_lo,
+                           int b, int act, int method, int max_steps, float* gx, float* gw, float* gb, void* workspace,
+                           int64_t workspace_bytes, void* stream);
 
 /* Linear backward for y = act(x W^T + b): gz = gy * act'(y) (y = forward output, NULL for act id);
  * gx[b][k] = gz W (wt planes = split W^T, k % 256 == 0 after padding by the caller), and
