@@ -94,6 +94,7 @@ SIGNATURES = {
     "agp_bblock64_pool_floats": (_L, [C.POINTER(BBlock64Desc)]),
     "agp_bblock64_pool_finish": (_I, [_P, _I, _I, _I, _P, _P]),
     "agp_conv_w_q8_prepare": (_I, [_P, _I, _I, _P, C.POINTER(C.c_int32), _P]),
+    "agp_conv2d_tile_plan": (_I, [C.POINTER(ConvDesc), _I, C.POINTER(C.c_int32)]),
     "agp_conv2d_stat_tiles": (_I, [C.POINTER(ConvDesc)]),
     "agp_conv2d_pool_blocks": (_I, [C.POINTER(ConvDesc)]),
     "agp_pool_from_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),

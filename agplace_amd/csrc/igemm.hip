@@ -579,7 +579,7 @@ int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s);
 int agp_internal_conv_d16_pool(agp_igemm::IgemmParams& p, int prec, hipStream_t s);
 int agp_internal_stem_raw(agp_igemm::IgemmParams& p, int kind, const void* x, long long sn, long long sc, long long sh, long long sw,
                           int h, int w, int ncam, const float* mean3, const float* std3, hipStream_t s);
-int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hipStream_t s);
+int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hipStream_t s, agp_igemm::TilePlan* plan);
 
 // Row tiles of the kernel that would run `d`, if that kernel can emit per-tile channel statistics
 // (agp_conv_desc::stat_partial): the 3x3 stride-1 kernel on bf16-pair maps.  Must mirror agp_internal_conv_kxr.
@@ -626,12 +626,15 @@ static bool conv_kxr_ok(const agp_conv_desc* d) {
 static int conv_fill_params(const agp_conv_desc* d, IgemmParams& p);
 void agp_internal_conv_kxr_geometry(agp_igemm::IgemmParams& p, const agp_conv_desc* d);
 bool agp_internal_use_kxr2(const agp_conv_desc* d);
-int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s);
+int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
 int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s);
 
 // Several convolutions of ONE channel shape (cin, cout, 3x3 stride 1) and precision as ONE launch: the tiles of
 // every problem form one grid (igemm_kxr2.hip).  Groups the kernel cannot take run as `n` launches, in order.
-extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* stream) {
+static int conv2d_fwd_one(const agp_conv_desc* d, void* stream, TilePlan* plan);
+
+// `plan` != NULL (agp_conv2d_tile_plan): the same decisions, reported instead of launched.
+static int conv2d_fwd_group(const agp_conv_desc* descs, int n, void* stream, TilePlan* plan) {
     if (!descs || n <= 0) return AGP_E_BADARG;
     bool group = n >= 2 && n <= 4;
     for (int i = 0; i < n && group; ++i) {
@@ -669,6 +672,7 @@ extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* s
                 const agp_conv_desc* d = descs + h + i;
                 ps[i].w2_hi = d->w_hi; ps[i].w2_cm = d->w_cm; ps[i].scale2 = d->scale; ps[i].shift2 = d->shift; ps[i].o2_hi = d->out_hi;
             }
+            if (plan) { *plan = TilePlan{AGP_CONV_KERNEL_S2, 0, 0, 0, 0, 0, 0, 0}; return AGP_OK; }
             return agp_internal_conv_s2(ps, descs, h, (hipStream_t)stream);
         }
     }
@@ -689,10 +693,12 @@ extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* s
                 const int rc = conv_fill_params(descs + i, ps[i]);
                 if (rc != AGP_OK) return rc;
             }
+            if (plan) { *plan = TilePlan{AGP_CONV_KERNEL_GENERIC, 0, 0, 0, 0, 0, 0, 0}; return AGP_OK; }
             return launch_group_f16(ps, n, (hipStream_t)stream);
         }
+        if (plan && n > 1) return AGP_E_UNSUPPORTED;      // `n` launches: ask for each descriptor's plan
         for (int i = 0; i < n; ++i) {
-            const int rc = agp_conv2d_fwd(descs + i, stream);
+            const int rc = conv2d_fwd_one(descs + i, stream, plan);
             if (rc != AGP_OK) return rc;
         }
         return AGP_OK;
@@ -704,10 +710,28 @@ extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* s
         if (rc != AGP_OK) return rc;
         agp_internal_conv_kxr_geometry(ps[i], descs + i);
     }
-    return agp_internal_conv_kxr2(ps, n, (hipStream_t)stream);
+    return agp_internal_conv_kxr2(ps, n, (hipStream_t)stream, plan);
 }
 
-extern "C" int agp_conv2d_fwd(const agp_conv_desc* d, void* stream) {
+extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* stream) {
+    return conv2d_fwd_group(descs, n, stream, nullptr);
+}
+
+extern "C" int agp_conv2d_fwd(const agp_conv_desc* d, void* stream) { return conv2d_fwd_one(d, stream, nullptr); }
+
+// The tile plan of the launch that agp_conv2d_fwd (n == 1) / agp_conv2d_fwd_grouped (n > 1) would make for these descriptors:
+// the launch path itself, stopped in the launcher before anything touches the device.
+extern "C" int agp_conv2d_tile_plan(const agp_conv_desc* descs, int n, int32_t plan[8]) {
+    if (!descs || !plan || n <= 0) return AGP_E_BADARG;
+    TilePlan tp = {};
+    const int rc = n == 1 ? conv2d_fwd_one(descs, nullptr, &tp) : conv2d_fwd_group(descs, n, nullptr, &tp);
+    if (rc != AGP_OK) return rc;
+    const int32_t v[8] = {tp.kernel, tp.BM, tp.BN, tp.MT, tp.NT, tp.MT_full, tp.half_tiles, tp.grid};
+    for (int i = 0; i < 8; ++i) plan[i] = v[i];
+    return AGP_OK;
+}
+
+static int conv2d_fwd_one(const agp_conv_desc* d, void* stream, TilePlan* plan) {
     if (!d || !d->in_hi || !d->w_hi || !d->out_hi) return AGP_E_BADARG;
     // storage format follows the precision: BF16X3 = bf16 plane pairs everywhere; F16W2 / F16 = one
     // fp16 activation plane (lo pointers NULL) and an fp16 weight pair / single plane
@@ -746,7 +770,9 @@ extern "C" int agp_conv2d_fwd(const agp_conv_desc* d, void* stream) {
     // w_cm == w_hi: the caller holds chunk-major planes ONLY (training planes written that way): every kernel but the 3x3 stride-1
     // one would read them as row-major -- refuse instead
     if (d->w_cm && d->w_cm == d->w_hi && (which != 3 || !p.w_cm)) return AGP_E_BADARG;
-    if (which == 3) return agp_internal_conv_kxr(p, d, (hipStream_t)stream);
+    if (which == 3) return agp_internal_conv_kxr(p, d, (hipStream_t)stream, plan);
+    // (the tile fields are reported for the 3x3 stride-1 family; the other kernels answer with their id alone)
+    if (plan) { *plan = TilePlan{which == 2 ? AGP_CONV_KERNEL_DIRECT_X : AGP_CONV_KERNEL_GENERIC, 0, 0, 0, 0, 0, 0, 0}; return AGP_OK; }
     if (which == 2) return agp_internal_conv_d16(p, d->prec, (hipStream_t)stream);
     return launch_igemm<EPI_CONV>(p, d->prec, (hipStream_t)stream);
 }

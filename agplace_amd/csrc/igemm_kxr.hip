@@ -889,34 +889,36 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
 }
 
 template <int BM, int BN, int WM, int WN, int NPREC, int RING, int MF = 32, bool LDS_EPI = false, bool Q8 = false>
-int launch_kxr(IgemmParams& p, hipStream_t s) {
+int launch_kxr(IgemmParams& p, hipStream_t s, TilePlan* plan) {
     constexpr int lds = kxr_lds_bytes<BM, BN, WM, WN, NPREC, RING>();
     static_assert(lds <= (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 3 ? 53 : (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 2 ? 80 : 160)) * 1024,
                   "LDS budget of the intended workgroups per CU");
     static std::atomic<uint64_t> attr_done{0}, attr_done_rg{0};
-    p.MT = (p.M + BM - 1) / BM;
-    p.NT = (p.N + BN - 1) / BN;
-    p.mt_chunk = (p.MT + 7) / 8;
+    const XcdGrid xg = xcd_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
+    if (plan) return plan_xcd(plan, AGP_CONV_KERNEL_KXR, BM, BN, xg);
+    p.MT = xg.MT;
+    p.NT = xg.NT;
+    p.mt_chunk = xg.mt_chunk;
     // fp16 maps (modes 2 / 4): the guarded twin while a range-guard word is bound (common.hpp RangeTrack)
     if constexpr (PrecT<NPREC>::F16) {
         if (uint32_t* const rflag = agp_range_flag_get()) {
             if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>, lds, attr_done_rg))
                 return AGP_E_LAUNCH;
-            AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>), dim3(p.mt_chunk * 8 * p.NT),
+            AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>), dim3(xg.blocks),
                        dim3(WM * WN * 64), lds, s, p, rflag);
             AGP_CHECK_LAUNCH();
             return AGP_OK;
         }
     }
     if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
-    AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>), dim3(p.mt_chunk * 8 * p.NT), dim3(WM * WN * 64), lds, s, p);
+    AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>), dim3(xg.blocks), dim3(WM * WN * 64), lds, s, p);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
 
 }  // namespace agp_igemm
 
-int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s);
+int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
 
 // Rewrites the generic geometry of `p` for the padded-width raster of the 3x3 stride-1 kernels.
 void agp_internal_conv_kxr_geometry(agp_igemm::IgemmParams& p, const agp_conv_desc* d) {
@@ -943,10 +945,10 @@ bool agp_internal_use_kxr2(const agp_conv_desc* d) {
 }
 
 // 3x3 / stride 1 / pad 1 convs on 1-pixel-halo planes.  `p` arrives with the generic geometry.
-int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hipStream_t s) {
+int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
     agp_internal_conv_kxr_geometry(p, d);
-    if (agp_internal_use_kxr2(d)) return agp_internal_conv_kxr2(&p, 1, s);
+    if (agp_internal_use_kxr2(d)) return agp_internal_conv_kxr2(&p, 1, s, plan);
     const bool wide = (p.N % 128 == 0);
     const int var = AGP_TUNE("KXR_VARIANT", 0);
     (void)var;
@@ -955,42 +957,42 @@ int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hip
         // form; 256-row tiles at every width (agp_conv2d_stat_tiles mirrors it)
         // wide: a wave owns 64 rows x 128 columns -- 16 MFMAs per phase and barrier, the inference kernel's shape (8 on 128 x 128
         // tiles of four waves: 0.20 MFMA-busy at 2.2 TB/s, bound by neither)
-        return wide ? launch_kxr<256, 128, 4, 1, 1, 3, 32, true>(p, s) : launch_kxr<256, 64, 4, 1, 1, 3, 32, true>(p, s);
+        return wide ? launch_kxr<256, 128, 4, 1, 1, 3, 32, true>(p, s, plan) : launch_kxr<256, 64, 4, 1, 1, 3, 32, true>(p, s, plan);
     }
     if (d->prec == AGP_PREC_BF16X3) {
 #if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 3, 0>(p, s) : launch_kxr<256, 64, 4, 1, 3, 0>(p, s);
-        if (var == 7 && wide) return launch_kxr<256, 128, 4, 1, 3, 4>(p, s);
-        if (var == 2 && wide) return launch_kxr<128, 128, 2, 2, 3, 2>(p, s);
-        if (var == 3 && wide) return launch_kxr<128, 128, 2, 2, 3, 3>(p, s);
-        if (var == 2 && !wide) return launch_kxr<128, 64, 2, 1, 3, 2>(p, s);
-        if (var == 3 && !wide) return launch_kxr<128, 64, 2, 1, 3, 3>(p, s);
+        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 3, 0>(p, s, plan) : launch_kxr<256, 64, 4, 1, 3, 0>(p, s, plan);
+        if (var == 7 && wide) return launch_kxr<256, 128, 4, 1, 3, 4>(p, s, plan);
+        if (var == 2 && wide) return launch_kxr<128, 128, 2, 2, 3, 2>(p, s, plan);
+        if (var == 3 && wide) return launch_kxr<128, 128, 2, 2, 3, 3>(p, s, plan);
+        if (var == 2 && !wide) return launch_kxr<128, 64, 2, 1, 3, 2>(p, s, plan);
+        if (var == 3 && !wide) return launch_kxr<128, 64, 2, 1, 3, 3>(p, s, plan);
 #endif
         // 256-channel layers (K = 2304: 24 macro-steps per tile, few tiles): the phase-pipelined loop (X double-buffered, every load
         // a phase ahead; two workgroups per CU) -- 94 -> 82 us on the panorama maps, 181 -> 175 on the tile maps of the training
         // step; the 128-channel layers are even (74 / 76, 160 / 155) and the 64-channel ones lose (82 -> 93), tools/conv_bench.py
-        if (wide && p.N % 256 == 0) return launch_kxr<128, 128, 2, 2, 3, 3>(p, s);
-        return wide ? launch_kxr<128, 128, 2, 2, 3, 1>(p, s) : launch_kxr<256, 64, 4, 1, 3, 1>(p, s);
+        if (wide && p.N % 256 == 0) return launch_kxr<128, 128, 2, 2, 3, 3>(p, s, plan);
+        return wide ? launch_kxr<128, 128, 2, 2, 3, 1>(p, s, plan) : launch_kxr<256, 64, 4, 1, 3, 1>(p, s, plan);
     }
     if (d->prec == AGP_PREC_F16W2) {
 #if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 2, 0>(p, s) : launch_kxr<256, 64, 4, 1, 2, 0>(p, s);
-        if (var == 6) return wide ? launch_kxr<128, 128, 2, 2, 2, 1>(p, s) : launch_kxr<256, 64, 4, 1, 2, 1>(p, s);
-        if (var == 12) return wide ? launch_kxr<128, 128, 2, 2, 2, 2>(p, s) : launch_kxr<256, 64, 4, 1, 2, 2>(p, s);
-        if (var == 13) return launch_kxr<256, 64, 4, 1, 2, 3, 16>(p, s);
-        if (var == 15) return launch_kxr<256, 64, 4, 1, 2, 3, 32, true>(p, s);
-        if (var == 12) return launch_kxr<256, 64, 4, 1, 2, 3>(p, s);
+        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 2, 0>(p, s, plan) : launch_kxr<256, 64, 4, 1, 2, 0>(p, s, plan);
+        if (var == 6) return wide ? launch_kxr<128, 128, 2, 2, 2, 1>(p, s, plan) : launch_kxr<256, 64, 4, 1, 2, 1>(p, s, plan);
+        if (var == 12) return wide ? launch_kxr<128, 128, 2, 2, 2, 2>(p, s, plan) : launch_kxr<256, 64, 4, 1, 2, 2>(p, s, plan);
+        if (var == 13) return launch_kxr<256, 64, 4, 1, 2, 3, 16>(p, s, plan);
+        if (var == 15) return launch_kxr<256, 64, 4, 1, 2, 3, 32, true>(p, s, plan);
+        if (var == 12) return launch_kxr<256, 64, 4, 1, 2, 3>(p, s, plan);
 #endif
-        if (p.w_q8 && p.CK % 64 == 0) return launch_kxr<256, 64, 4, 1, 2, 3, 32, false, true>(p, s);
-        return launch_kxr<256, 64, 4, 1, 2, 3>(p, s);
+        if (p.w_q8 && p.CK % 64 == 0) return launch_kxr<256, 64, 4, 1, 2, 3, 32, false, true>(p, s, plan);
+        return launch_kxr<256, 64, 4, 1, 2, 3>(p, s, plan);
     }
     if (d->prec == AGP_PREC_F16) {
         // (reached only where igemm_kxr2 does not take the conv: output planes past its 32-bit element offsets, stat_partial)
 #if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 4, 0>(p, s) : launch_kxr<256, 64, 4, 1, 4, 0>(p, s);
-        if (var == 12) return wide ? launch_kxr<128, 128, 2, 2, 4, 2>(p, s) : launch_kxr<256, 64, 4, 1, 4, 2>(p, s);
+        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 4, 0>(p, s, plan) : launch_kxr<256, 64, 4, 1, 4, 0>(p, s, plan);
+        if (var == 12) return wide ? launch_kxr<128, 128, 2, 2, 4, 2>(p, s, plan) : launch_kxr<256, 64, 4, 1, 4, 2>(p, s, plan);
 #endif
-        return launch_kxr<256, 64, 4, 1, 4, 3>(p, s);
+        return launch_kxr<256, 64, 4, 1, 4, 3>(p, s, plan);
     }
     return AGP_E_BADARG;
 }

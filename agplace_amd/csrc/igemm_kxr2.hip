@@ -787,25 +787,27 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
 }
 
 template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW = 4, bool SCH = false, bool RG = false>
-int launch_kxr2(Kxr2Group& g, hipStream_t s) {
+int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
     constexpr int lds = kxr2_lds_bytes<BM, PF>();
     static_assert(lds * (MINB * 4 / NW) <= 160 * 1024, "LDS budget of the intended workgroups per CU");
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr(RG ? (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>
-                         : (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>, lds, attr_done)) return AGP_E_LAUNCH;
     int mt = 0;
     for (int i = 0; i < g.nprob; ++i) {
         mt += (g.p[i].M + BM - 1) / BM;
         g.mt_end[i] = mt;
     }
-    g.MT = mt;
-    g.NT = (g.p[0].N + 63) / 64;
-    g.mt_chunk = (g.MT + 7) / 8;
+    const XcdGrid xg = xcd_grid(mt, (g.p[0].N + 63) / 64);
+    if (plan) return plan_xcd(plan, AGP_CONV_KERNEL_KXR2, BM, 64, xg);
+    g.MT = xg.MT;
+    g.NT = xg.NT;
+    g.mt_chunk = xg.mt_chunk;
+    if (!agp_lds_attr(RG ? (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>
+                         : (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>, lds, attr_done)) return AGP_E_LAUNCH;
     if constexpr (RG) {
-        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>), dim3(g.mt_chunk * 8 * g.NT), dim3(NW * 64), lds, s, g,
+        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>), dim3(xg.blocks), dim3(NW * 64), lds, s, g,
                    agp_range_flag_get());
     } else {
-        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>), dim3(g.mt_chunk * 8 * g.NT), dim3(NW * 64), lds, s, g);
+        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>), dim3(xg.blocks), dim3(NW * 64), lds, s, g);
     }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
@@ -813,14 +815,14 @@ int launch_kxr2(Kxr2Group& g, hipStream_t s) {
 
 }  // namespace agp_igemm
 
-int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s);
+int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
 
 // `ps[i]` arrive with the padded-width raster geometry of agp_internal_conv_kxr_geometry; all share N, CK, prec F16.
-int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s) {
+int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
     if (n < 1 || n > KXR2_MAXP) return AGP_E_BADARG;
     // layers with cout % 128 == 0 run on the wide form (256 x 128 tiles, igemm_kxrw.hip)
-    if (AGP_TUNE("KXR_WIDE", 1) && ps[0].N % 128 == 0 && !AGP_TUNE("KXR2_VARIANT", 0)) return agp_internal_conv_kxrw(ps, n, s);
+    if (AGP_TUNE("KXR_WIDE", 1) && ps[0].N % 128 == 0 && !AGP_TUNE("KXR2_VARIANT", 0)) return agp_internal_conv_kxrw(ps, n, s, plan);
     Kxr2Group g = {};
     g.nprob = n;
     for (int i = 0; i < n; ++i) {
@@ -830,21 +832,21 @@ int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s) {
     bool pool = false;
     for (int i = 0; i < n; ++i) pool = pool || ps[i].pool_partial != nullptr;
 #if defined(AGP_TUNING)
-    if (AGP_TUNE("KXR_TALL", 0) && !pool && ps[0].N == 64 && !AGP_TUNE("KXR2_VARIANT", 0)) return agp_internal_conv_kxrw(ps, n, s);
+    if (AGP_TUNE("KXR_TALL", 0) && !pool && ps[0].N == 64 && !AGP_TUNE("KXR2_VARIANT", 0)) return agp_internal_conv_kxrw(ps, n, s, plan);
     // experiments that were measured and NOT adopted (profiles/README.md), development build only: 512-row tiles, 8-wave
     // workgroups, the 16x16x32 form, two-slot rings, LDS-DMA pieces at the head of a phase (KXR2_SCHED = 0)
     const int var = AGP_TUNE("KXR2_VARIANT", 0);
-    if (var == 8) return pool ? launch_kxr2<512, 4, false, true, false, 8>(g, s) : launch_kxr2<512, 4, false, false, false, 8>(g, s);
-    if (var == 16) return pool ? launch_kxr2<256, 3, false, true, true>(g, s) : launch_kxr2<256, 3, false, false, true>(g, s);
-    if (!AGP_TUNE("KXR2_SCHED", 1)) return pool ? launch_kxr2<256, 3, false, true>(g, s) : launch_kxr2<256, 3>(g, s);
-    if (!pool && var == 1) return launch_kxr2<512, 2>(g, s);
-    if (!pool && var == 2) return launch_kxr2<256, 2>(g, s);
-    if (!pool && var == 3) return launch_kxr2<256, 2, true>(g, s);
+    if (var == 8) return pool ? launch_kxr2<512, 4, false, true, false, 8>(g, s, plan) : launch_kxr2<512, 4, false, false, false, 8>(g, s, plan);
+    if (var == 16) return pool ? launch_kxr2<256, 3, false, true, true>(g, s, plan) : launch_kxr2<256, 3, false, false, true>(g, s, plan);
+    if (!AGP_TUNE("KXR2_SCHED", 1)) return pool ? launch_kxr2<256, 3, false, true>(g, s, plan) : launch_kxr2<256, 3>(g, s, plan);
+    if (!pool && var == 1) return launch_kxr2<512, 2>(g, s, plan);
+    if (!pool && var == 2) return launch_kxr2<256, 2>(g, s, plan);
+    if (!pool && var == 3) return launch_kxr2<256, 2, true>(g, s, plan);
 #endif
     return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) {
         constexpr bool RG = decltype(rg)::value;
         if (pool)                       // (agp_conv2d_pool_blocks promises this tile shape)
-            return launch_kxr2<256, 3, false, true, false, 4, true, RG>(g, s);
-        return launch_kxr2<256, 3, false, false, false, 4, true, RG>(g, s);
+            return launch_kxr2<256, 3, false, true, false, 4, true, RG>(g, s, plan);
+        return launch_kxr2<256, 3, false, false, false, 4, true, RG>(g, s, plan);
     });
 }

@@ -373,12 +373,24 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     const float relu_lo = p.relu ? 0.f : -65504.f;
     RangeTrack<RG> rg;
     float psum[2][2] = {{0.f, 0.f}, {0.f, 0.f}};       // [channel half][stat]
+    float psum0[2][2] = {{0.f, 0.f}, {0.f, 0.f}};      // a full tile: the sums of its tile row 0 (32 rows) while tile row 1 is swept
     const float* const ppp = POOL ? p.pool_p : nullptr;
     const float pool_pw = ppp ? ppp[0] : 1.f, pool_eps = POOL ? p.pool_eps : 0.f;
     const bool pool_cube = pool_pw == 3.f;
     const bool pool_sq = POOL && p.pool_sq;           // stat 1 = sum of squares (BatchNorm statistics), no exponent tensor
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
+        if constexpr (POOL && TM == 2) {
+            // a 64-row block is summed as (rows 0..31) + (rows 32..63) in EVERY schedule: a half tile holds the two halves in two
+            // waves (even + odd below), so a full tile keeps them apart as well -- an image's pooled values must not depend on
+            // whether its rows fall into the launch's full or half tiles
+            if (tm == 1) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) { psum0[a][b] = psum[a][b]; psum[a][b] = 0.f; }
+            }
+        }
         u32x4 rres[TN * 2];
         if (rhi) {
             // line layout -> strip -> accumulator layout; then the next tile row's residual loads go out BEFORE this row's stores
@@ -456,6 +468,12 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     }
     if constexpr (POOL) {
         if (ppart) {
+            if constexpr (TM == 2) {
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) psum[a][b] = psum0[a][b] + psum[a][b];
+            }
             // [64-row block][stat][N]: a wave of a full tile IS a block; in a half tile (32 rows per wave) the odd wave hands its sums
             // to the even wave of its pair through LDS (fixed order: even + odd)
             if constexpr (TM == 1) {
@@ -529,15 +547,45 @@ __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
 #endif
 }
 
+// The tile schedule of a launch of MT x NT tiles (`mix_ok`: the wide form's half-tile schedule may be used): the XCD-chunked
+// part [0, MT_full) and the half tiles that follow it.  The launch and agp_conv2d_tile_plan both take their numbers from here.
+struct KxrwPlan {
+    int MT_full, mt_chunk, half_bid0, half_tiles, blocks;
+    bool mix;
+};
+inline KxrwPlan kxrw_plan(int MT, int NT, bool mix_ok) {
+    KxrwPlan k = {};
+    k.MT_full = MT;
+    // ---- the last round of workgroups as half tiles.  512 workgroups are resident (two per CU); a launch of T tiles runs
+    // ceil(T / 512) rounds and its last round holds `tail` tiles.  When that round would leave more than half of the CUs without
+    // a workgroup (tail <= 128), its tiles run as twice as many 128-row tiles, each still alone on a CU: the round takes about half
+    // as long (stage 2: 602 tiles = 512 + 90 -> 180 half tiles, 89.7 -> 80.1 us; a launch of <= 128 tiles -- the C1 / C2 shapes --
+    // covers twice the CUs).  Measured and NOT done: a larger tail (layer 3: 714 = 512 + 202 -> 404 half tiles, two per CU) loses
+    // 3-4 us per launch -- a lone 256-row workgroup already runs 1.65 x as fast as one of a pair, two half tiles per CU do not.
+    if (mix_ok) {
+        const int slots = 512, T = MT * NT;
+        const int tail = T - (T - 1) / slots * slots;         // 1 .. slots
+        if (tail <= slots / 4 && tail % NT == 0) {
+            k.MT_full = MT - tail / NT;
+            k.mix = true;
+        }
+    }
+    const XcdGrid xg = xcd_grid(k.MT_full, NT);
+    k.mt_chunk = xg.mt_chunk;
+    k.half_bid0 = xg.blocks;
+    k.half_tiles = k.mix ? 2 * (MT - k.MT_full) * NT : 0;
+    k.blocks = k.half_bid0 + k.half_tiles;
+    return k;
+}
+
 template <bool POOL, bool SCHED, int TM_ = 2, int TN_ = 4, bool MIX = false, bool RG = false>
-int launch_kxrw(KxrwGroup& g, hipStream_t s) {
+int launch_kxrw(KxrwGroup& g, const KxrwPlan& k, hipStream_t s) {
     constexpr int lds = KwShape<TM_, TN_>::LDS;
     static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
     static_assert(!MIX || (TM_ == 2 && KwShape<1, TN_>::LDS + 3072 <= lds), "half tiles: their stage + the pooling scratch fit the full tile's LDS");
     static std::atomic<uint64_t> attr_done{0};
     if (!agp_lds_attr((const void*)igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>, lds, attr_done)) return AGP_E_LAUNCH;
-    const int nblocks = g.mt_chunk * 8 * g.NT + (MIX ? 2 * (g.MT - g.MT_full) * g.NT : 0);
-    AGP_LAUNCH((igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>), dim3(nblocks), dim3(256), lds, s, g);
+    AGP_LAUNCH((igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>), dim3(MIX ? k.blocks : k.half_bid0), dim3(256), lds, s, g);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -548,7 +596,7 @@ int launch_kxrw(KxrwGroup& g, hipStream_t s) {
 // N % 128 == 0: the wide form (256 x 128 tiles).  (The tall form, 512 x 64 tiles for N == 64 -- a round-3 experiment that measured
 // the same alone and 4 % slower in the grouped launch -- exists in the development build only: KXR_TALL.)
 static constexpr bool KXRW_MIX = true;     // false: every tile 256 rows (rounds 3-5)
-int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s) {
+int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
 #if defined(AGP_TUNING)
     const bool tall = ps[0].N == 64;
@@ -570,36 +618,27 @@ int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s) {
     }
     g.MT = mt;
     g.NT = ps[0].N / bn;
-    g.MT_full = g.MT;
-    // ---- the last round of workgroups as half tiles.  512 workgroups are resident (two per CU); a launch of T tiles runs
-    // ceil(T / 512) rounds and its last round holds `tail` tiles.  When that round would leave more than half of the CUs without
-    // a workgroup (tail <= 128), its tiles run as twice as many 128-row tiles, each still alone on a CU: the round takes about half
-    // as long (stage 2: 602 tiles = 512 + 90 -> 180 half tiles, 89.7 -> 80.1 us; a launch of <= 128 tiles -- the C1 / C2 shapes --
-    // covers twice the CUs).  Measured and NOT done: a larger tail (layer 3: 714 = 512 + 202 -> 404 half tiles, two per CU) loses
-    // 3-4 us per launch -- a lone 256-row workgroup already runs 1.65 x as fast as one of a pair, two half tiles per CU do not.
-    bool mix = false;
-    if (!tall && KXRW_MIX) {
-        const int slots = 512, T = g.MT * g.NT;
-        const int tail = T - (T - 1) / slots * slots;         // 1 .. slots
-        if (tail <= slots / 4 && tail % g.NT == 0) {
-            g.MT_full = g.MT - tail / g.NT;
-            mix = true;
-        }
+    const KxrwPlan k = kxrw_plan(g.MT, g.NT, !tall && KXRW_MIX);
+    if (plan) {
+        *plan = TilePlan{AGP_CONV_KERNEL_KXRW, bm, bn, g.MT, g.NT, k.MT_full, k.half_tiles, k.blocks};
+        return AGP_OK;
     }
-    g.mt_chunk = (g.MT_full + 7) / 8;
-    g.half_bid0 = g.mt_chunk * 8 * g.NT;
+    const bool mix = k.mix;
+    g.MT_full = k.MT_full;
+    g.mt_chunk = k.mt_chunk;
+    g.half_bid0 = k.half_bid0;
 #if defined(AGP_TUNING)
     const int sched = AGP_TUNE("KXRW_SCHED", 1);    // 0: LDS-DMA pieces at the head of a phase (the round-3 order) instead of among the MFMAs
     if (tall) {
         if (pool) return AGP_E_BADARG;
-        return sched ? launch_kxrw<false, true, 4, 2>(g, s) : launch_kxrw<false, false, 4, 2>(g, s);
+        return sched ? launch_kxrw<false, true, 4, 2>(g, k, s) : launch_kxrw<false, false, 4, 2>(g, k, s);
     }
-    if (!sched) return pool ? launch_kxrw<true, false>(g, s) : launch_kxrw<false, false>(g, s);
+    if (!sched) return pool ? launch_kxrw<true, false>(g, k, s) : launch_kxrw<false, false>(g, k, s);
 #endif
     g.rflag = agp_range_flag_get();
     return agp_rg_dispatch(g.rflag, [&](auto rg) {
         constexpr bool RG = decltype(rg)::value;
-        if (mix) return pool ? launch_kxrw<true, true, 2, 4, true, RG>(g, s) : launch_kxrw<false, true, 2, 4, true, RG>(g, s);
-        return pool ? launch_kxrw<true, true, 2, 4, false, RG>(g, s) : launch_kxrw<false, true, 2, 4, false, RG>(g, s);
+        if (mix) return pool ? launch_kxrw<true, true, 2, 4, true, RG>(g, k, s) : launch_kxrw<false, true, 2, 4, true, RG>(g, k, s);
+        return pool ? launch_kxrw<true, true, 2, 4, false, RG>(g, k, s) : launch_kxrw<false, true, 2, 4, false, RG>(g, k, s);
     });
 }

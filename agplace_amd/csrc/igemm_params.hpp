@@ -102,4 +102,24 @@ __device__ __forceinline__ void mfma16(f32x4& acc, const bf16x8& wh, const bf16x
 
 constexpr int EPI_ROWB = 64 * 4 + 16;  // 64 fp32 channels + 16 B pad per pixel row
 
+// What a conv launcher decided on the host, in the order of agp_conv2d_tile_plan's plan[8].  The launchers take an optional
+// `TilePlan*`: non-NULL = fill it from the SAME arithmetic that sizes the grid and return before anything touches the device.
+struct TilePlan {
+    int32_t kernel, BM, BN, MT, NT, MT_full, half_tiles, grid;
+};
+
+// The XCD-chunked grid of MT x NT tiles (block -> xcd = bid & 7, mt = xcd * mt_chunk + (bid >> 3) / NT): every kernel of the
+// 3x3 stride-1 family sizes its grid here.
+struct XcdGrid {
+    int MT, NT, mt_chunk, blocks;
+};
+inline XcdGrid xcd_grid(int MT, int NT) {
+    const int mt_chunk = (MT + 7) / 8;
+    return XcdGrid{MT, NT, mt_chunk, mt_chunk * 8 * NT};
+}
+inline int plan_xcd(TilePlan* plan, int kernel, int BM, int BN, const XcdGrid& x) {
+    *plan = TilePlan{kernel, BM, BN, x.MT, x.NT, x.MT, 0, x.blocks};
+    return AGP_OK;
+}
+
 }  // namespace agp_igemm

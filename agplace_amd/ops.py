@@ -453,6 +453,41 @@ def conv_stat_tiles(x: SplitMap, cw: ConvWeights, out: SplitMap, prec, hi_only=F
     return int(_L().agp_conv2d_stat_tiles(C.byref(d)))
 
 
+CONV_KERNELS = {1: "generic", 2: "direct-x", 3: "kxr", 4: "kxr2", 5: "kxrw", 6: "s2"}      # AGP_CONV_KERNEL_*
+TILE_PLAN_FIELDS = ("kernel", "BM", "BN", "MT", "NT", "MT_full", "half_tiles", "grid")
+
+
+def tile_plan(descs):
+    """agp_conv2d_tile_plan of a ConvDesc (agp_conv2d_fwd) or a ctypes array of them (agp_conv2d_fwd_grouped) as a dict of
+    TILE_PLAN_FIELDS, `kernel` by name.  Host-only: nothing is launched."""
+    n = 1 if isinstance(descs, _lib.ConvDesc) else len(descs)
+    plan = (C.c_int32 * 8)()
+    check(_L().agp_conv2d_tile_plan(C.byref(descs) if n == 1 and isinstance(descs, _lib.ConvDesc) else descs, n, plan),
+          "agp_conv2d_tile_plan")
+    out = dict(zip(TILE_PLAN_FIELDS, (int(v) for v in plan)))
+    out["kernel"] = CONV_KERNELS[out["kernel"]]
+    return out
+
+
+def conv_tile_plan(jobs, prec, stat_partial=False, hi_only=False):
+    """The tile plan (tile_plan) of the launch ops.conv2d_grouped(jobs, prec) would make -- ops.conv2d for one job, then with its
+    `stat_partial` / `hi_only` forms.  jobs: [(x, cw, out, residual, relu[, pool]), ...]; a pool request counts where the kernel
+    would take it (its raster gives every image a multiple of 64 rows)."""
+    jobs = [tuple(j) + (None,) * (6 - len(j)) for j in jobs]
+    arr = (_lib.ConvDesc * len(jobs))()
+    for d, (x, cw, out, residual, relu, pool) in zip(arr, jobs):
+        _fill_conv_desc(d, x, cw, out, residual, relu, prec)
+        if pool is not None and x.lo is None and out.lo is None and int(_L().agp_conv2d_pool_blocks(C.byref(d))) > 0:
+            d.pool_partial = 1            # (looked at as non-NULL only)
+    if len(jobs) == 1:
+        if stat_partial:
+            arr[0].stat_partial = 1
+        if hi_only:
+            arr[0].hi_only = 1
+        return tile_plan(arr[0])
+    return tile_plan(arr)
+
+
 class PoolReq:
     """Global pooling of a conv's output map requested WITH the conv (reference: GeM / adaptive_avg_pool2d of a stage output,
     network_mm/image_pooling.py:16, fuse_block_toshallow.py:82, stage2fuse_blockadd.py:201-206): the 3x3 kernel of the fp16

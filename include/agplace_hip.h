@@ -259,6 +259,21 @@ int agp_conv2d_fwd(const agp_conv_desc* d, void* stream);
  * agp_conv2d_fwd in order.  Results are bit-identical to separate launches. */
 int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* stream);
 
+/* The tile plan of the launch that agp_conv2d_fwd (n == 1) or agp_conv2d_fwd_grouped (n > 1) would make for `descs`, computed
+ * on the host by the launch path itself (nothing is launched, no device is needed; pointers are looked at as NULL / non-NULL
+ * only).  plan = { kernel (AGP_CONV_KERNEL_*), BM, BN (rows x channels of a tile), MT, NT (row x column tiles of all problems),
+ * MT_full (row tiles in the XCD-chunked part of the grid), half tiles launched behind it (igemm_kxrw: the row tiles
+ * [MT_full, MT) as 2 * NT tiles of BM / 2 rows each), grid size in workgroups }.  The tile fields are reported for the 3x3
+ * stride-1 kernels (KXR, KXR2, KXRW) and are 0 for the others.  Returns what the launch would return for invalid descriptors,
+ * and AGP_E_UNSUPPORTED for a group that runs as `n` separate launches. */
+#define AGP_CONV_KERNEL_GENERIC 1
+#define AGP_CONV_KERNEL_DIRECT_X 2
+#define AGP_CONV_KERNEL_KXR 3
+#define AGP_CONV_KERNEL_KXR2 4
+#define AGP_CONV_KERNEL_KXRW 5
+#define AGP_CONV_KERNEL_S2 6
+int agp_conv2d_tile_plan(const agp_conv_desc* descs, int n, int32_t plan[8]);
+
 /* Row tiles of agp_conv_desc::stat_partial for `d`, or 0 when the kernel that runs `d` cannot produce it. */
 int agp_conv2d_stat_tiles(const agp_conv_desc* d);
 
