@@ -449,16 +449,15 @@ __global__ void __launch_bounds__(WM* WN * 64) igemm_group_kernel(IgemmGroup g) 
 
 // Grouped launch of the fp16 single-product configuration (the only one the product groups): every problem must
 // satisfy CK % 32 == 0 and N % 128 == 0.
+// plan: MT = the row tiles of all problems, NT = the column tiles of a problem (0 when the problems differ in it).
 template <int BK, int NST, bool RG = false>
-int launch_group_f16_cfg(IgemmParams* ps, int n, hipStream_t s) {
+int launch_group_f16_cfg(IgemmParams* ps, int n, hipStream_t s, TilePlan* plan = nullptr) {
     constexpr int WM = 2, WN = 2, NPREC = 4;
     constexpr int lds = igemm_lds_bytes<WM, WN, BK, NPREC, NST>();
-    static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     IgemmGroup g = {};
-    g.rflag = RG ? agp_range_flag_get() : nullptr;
     g.n = n;
-    int grid = 0;
+    int grid = 0, mt = 0;
+    bool one_nt = true;
     for (int i = 0; i < n; ++i) {
         IgemmParams& p = ps[i];
         p.MT = (p.M + WM * 64 - 1) / (WM * 64);
@@ -467,36 +466,49 @@ int launch_group_f16_cfg(IgemmParams* ps, int n, hipStream_t s) {
         g.p[i] = p;
         g.start[i] = grid;
         grid += p.mt_chunk * 8 * p.NT;
+        mt += p.MT;
+        one_nt = one_nt && p.NT == ps[0].NT;
     }
     for (int i = n; i < 5; ++i) g.start[i] = grid;
+    if (plan) {
+        *plan = TilePlan{AGP_CONV_KERNEL_GENERIC, WM * 64, WN * 64, mt, one_nt ? ps[0].NT : 0, mt, 0, grid};
+        return AGP_OK;
+    }
+    static std::atomic<uint64_t> attr_done{0};
+    if (!agp_lds_attr((const void*)igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST, RG>, lds, attr_done)) return AGP_E_LAUNCH;
+    g.rflag = RG ? agp_range_flag_get() : nullptr;
     AGP_LAUNCH((igemm_group_kernel<WM, WN, BK, NPREC, EPI_CONV, NST, RG>), dim3(grid), dim3(WM * WN * 64), lds, s, g);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
 
-int launch_group_f16(IgemmParams* ps, int n, hipStream_t s) {
+int launch_group_f16(IgemmParams* ps, int n, hipStream_t s, TilePlan* plan = nullptr) {
     // measured on the bench workload (serial conv-family fraction of peak / ms per step): BK 64 x 2 stages 0.275 / 2.215,
     // BK 32 x 3 stages with counted vmcnt 0.319 / 2.215 (default), BK 32 x 4 0.311 / 2.215, BK 64 x 3 0.304 / 2.30,
     // BK 32 x 2 0.316 / 2.207
 #if defined(AGP_TUNING)
     const int var = AGP_TUNE("GROUP_VARIANT", 0);
-    if (var == 1) return launch_group_f16_cfg<64, 2>(ps, n, s);
-    if (var == 2) return launch_group_f16_cfg<32, 2>(ps, n, s);
+    if (var == 1) return launch_group_f16_cfg<64, 2>(ps, n, s, plan);
+    if (var == 2) return launch_group_f16_cfg<32, 2>(ps, n, s, plan);
 #endif
-    return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) { return launch_group_f16_cfg<32, 3, decltype(rg)::value>(ps, n, s); });
+    return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) { return launch_group_f16_cfg<32, 3, decltype(rg)::value>(ps, n, s, plan); });
 }
 
 template <int WM, int WN, int BK, int NPREC, int EPI, int NST, bool RG = false>
-int launch_cfg_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s) {
+int launch_cfg_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s, TilePlan* plan = nullptr) {
     constexpr int lds = igemm_lds_bytes<WM, WN, BK, NPREC, NST>();
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_kernel<WM, WN, BK, NPREC, EPI, NST, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     constexpr int BM = WM * 64, BN = WN * 64;
     p.MT = (p.M + BM - 1) / BM;
     p.NT = (p.N + BN - 1) / BN;
     p.mt_chunk = (p.MT + 7) / 8;
     const int grid = p.mt_chunk * 8 * p.NT;
+    if (plan) {
+        *plan = TilePlan{AGP_CONV_KERNEL_GENERIC, BM, BN, p.MT, p.NT, p.MT, 0, grid};
+        return AGP_OK;
+    }
+    static std::atomic<uint64_t> attr_done{0};
+    if (!agp_lds_attr((const void*)igemm_kernel<WM, WN, BK, NPREC, EPI, NST, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     const int splits = 1;
     AGP_LAUNCH((igemm_kernel<WM, WN, BK, NPREC, EPI, NST, RG>), dim3(grid, splits), dim3(WM * WN * 64), lds, s, p, rflag);
     AGP_CHECK_LAUNCH();
@@ -504,58 +516,58 @@ int launch_cfg_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s) {
 }
 // the fp16 conv configurations have a guarded twin (fp16 maps); the bf16-pair and kNN ones store no fp16 map
 template <int WM, int WN, int BK, int NPREC, int EPI, int NST>
-int launch_cfg(IgemmParams& p, hipStream_t s) {
+int launch_cfg(IgemmParams& p, hipStream_t s, TilePlan* plan = nullptr) {
     if constexpr (EPI == EPI_CONV && PrecT<NPREC>::F16) {
         uint32_t* const rflag = agp_range_flag_get();
-        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_cfg_rg<WM, WN, BK, NPREC, EPI, NST, decltype(rg)::value>(p, rflag, s); });
+        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_cfg_rg<WM, WN, BK, NPREC, EPI, NST, decltype(rg)::value>(p, rflag, s, plan); });
     }
-    return launch_cfg_rg<WM, WN, BK, NPREC, EPI, NST>(p, nullptr, s);
+    return launch_cfg_rg<WM, WN, BK, NPREC, EPI, NST>(p, nullptr, s, plan);
 }
 
 // Tuning hook (development build only): IGEMM_VARIANT selects an alternative tile / pipeline configuration.
 inline int igemm_variant() { return AGP_TUNE("IGEMM_VARIANT", 0); }
 
 template <int EPI>
-int launch_igemm(IgemmParams& p, int prec, hipStream_t s) {
+int launch_igemm(IgemmParams& p, int prec, hipStream_t s, TilePlan* plan = nullptr) {
     const bool wide = (p.N % 128 == 0) || (EPI == EPI_GMIN);
     const int var = igemm_variant();
     p.dbg = AGP_TUNE("IGEMM_DBG", 0);
     if (EPI == EPI_GMIN && var == 0) {
         // kNN coarse pass: 256 queries x 128 database rows per 8-wave workgroup (measured best)
-        if (prec == AGP_PREC_BF16X3) return launch_cfg<4, 2, 32, 3, EPI, 2>(p, s);
+        if (prec == AGP_PREC_BF16X3) return launch_cfg<4, 2, 32, 3, EPI, 2>(p, s, plan);
         if (prec == AGP_PREC_BF16)
-            return p.CK % 64 == 0 ? launch_cfg<4, 2, 64, 1, EPI, 2>(p, s) : launch_cfg<4, 2, 32, 1, EPI, 2>(p, s);
+            return p.CK % 64 == 0 ? launch_cfg<4, 2, 64, 1, EPI, 2>(p, s, plan) : launch_cfg<4, 2, 32, 1, EPI, 2>(p, s, plan);
         if (prec == AGP_PREC_F16)
-            return p.CK % 64 == 0 ? launch_cfg<4, 2, 64, 4, EPI, 2>(p, s) : launch_cfg<4, 2, 32, 4, EPI, 2>(p, s);
+            return p.CK % 64 == 0 ? launch_cfg<4, 2, 64, 4, EPI, 2>(p, s, plan) : launch_cfg<4, 2, 32, 4, EPI, 2>(p, s, plan);
         return AGP_E_BADARG;
     }
     if (prec == AGP_PREC_BF16X3) {
 #if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_cfg<2, 2, 32, 3, EPI, 3>(p, s) : launch_cfg<4, 1, 32, 3, EPI, 3>(p, s);
-        if (var == 2) return wide ? launch_cfg<4, 2, 32, 3, EPI, 2>(p, s) : launch_cfg<4, 1, 32, 3, EPI, 2>(p, s);
-        if (var == 3) return wide ? launch_cfg<4, 2, 32, 3, EPI, 3>(p, s) : launch_cfg<4, 1, 32, 3, EPI, 3>(p, s);
-        if (var == 4) return wide ? launch_cfg<2, 2, 32, 3, EPI, 4>(p, s) : launch_cfg<4, 1, 32, 3, EPI, 4>(p, s);
+        if (var == 1) return wide ? launch_cfg<2, 2, 32, 3, EPI, 3>(p, s, plan) : launch_cfg<4, 1, 32, 3, EPI, 3>(p, s, plan);
+        if (var == 2) return wide ? launch_cfg<4, 2, 32, 3, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 32, 3, EPI, 2>(p, s, plan);
+        if (var == 3) return wide ? launch_cfg<4, 2, 32, 3, EPI, 3>(p, s, plan) : launch_cfg<4, 1, 32, 3, EPI, 3>(p, s, plan);
+        if (var == 4) return wide ? launch_cfg<2, 2, 32, 3, EPI, 4>(p, s, plan) : launch_cfg<4, 1, 32, 3, EPI, 4>(p, s, plan);
 #endif
-        return wide ? launch_cfg<2, 2, 32, 3, EPI, 2>(p, s) : launch_cfg<4, 1, 32, 3, EPI, 2>(p, s);
+        return wide ? launch_cfg<2, 2, 32, 3, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 32, 3, EPI, 2>(p, s, plan);
     } else if (prec == AGP_PREC_BF16) {
         if (p.CK % 64 == 0) {
 #if defined(AGP_TUNING)
-            if (var == 1) return wide ? launch_cfg<2, 2, 64, 1, EPI, 3>(p, s) : launch_cfg<4, 1, 64, 1, EPI, 3>(p, s);
+            if (var == 1) return wide ? launch_cfg<2, 2, 64, 1, EPI, 3>(p, s, plan) : launch_cfg<4, 1, 64, 1, EPI, 3>(p, s, plan);
 #endif
-            return wide ? launch_cfg<2, 2, 64, 1, EPI, 2>(p, s) : launch_cfg<4, 1, 64, 1, EPI, 2>(p, s);
+            return wide ? launch_cfg<2, 2, 64, 1, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 64, 1, EPI, 2>(p, s, plan);
         }
-        return wide ? launch_cfg<2, 2, 32, 1, EPI, 2>(p, s) : launch_cfg<4, 1, 32, 1, EPI, 2>(p, s);
+        return wide ? launch_cfg<2, 2, 32, 1, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 32, 1, EPI, 2>(p, s, plan);
     }
     if constexpr (EPI == EPI_CONV) {       // fp16 modes exist for the convolutions only
         if (prec == AGP_PREC_F16W2)
-            return wide ? launch_cfg<2, 2, 32, 2, EPI, 2>(p, s) : launch_cfg<4, 1, 32, 2, EPI, 2>(p, s);
+            return wide ? launch_cfg<2, 2, 32, 2, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 32, 2, EPI, 2>(p, s, plan);
         if (prec == AGP_PREC_F16) {
             // 32-deep K-steps through a 3-slot ring with counted vmcnt (see launch_group_f16: 0.319 against 0.275 of peak
             // for the conv family with 64-deep steps and one stage of prefetch)
 #if defined(AGP_TUNING)
             if (var == 5) {          // the old choice
-                if (p.CK % 64 == 0) return wide ? launch_cfg<2, 2, 64, 4, EPI, 2>(p, s) : launch_cfg<4, 1, 64, 4, EPI, 2>(p, s);
-                return wide ? launch_cfg<2, 2, 32, 4, EPI, 2>(p, s) : launch_cfg<4, 1, 32, 4, EPI, 2>(p, s);
+                if (p.CK % 64 == 0) return wide ? launch_cfg<2, 2, 64, 4, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 64, 4, EPI, 2>(p, s, plan);
+                return wide ? launch_cfg<2, 2, 32, 4, EPI, 2>(p, s, plan) : launch_cfg<4, 1, 32, 4, EPI, 2>(p, s, plan);
             }
 #endif
             if (p.tap_stride && var == 0) {
@@ -563,10 +575,10 @@ int launch_igemm(IgemmParams& p, int prec, hipStream_t s) {
                 // ONE stage of prefetch behind __syncthreads than through the 3-slot ring (a tap's gather table is read at the head
                 // of a stage: the ring's counted waits drain behind it anyway); 128+ channels on 256 x 128 tiles (8 waves) when
                 // that still fills the chip twice over
-                if (!wide) return launch_cfg<4, 1, 32, 4, EPI, 2>(p, s);
-                if ((int64_t)((p.M + 255) / 256) * (p.N / 128) >= 512) return launch_cfg<4, 2, 32, 4, EPI, 3>(p, s);
+                if (!wide) return launch_cfg<4, 1, 32, 4, EPI, 2>(p, s, plan);
+                if ((int64_t)((p.M + 255) / 256) * (p.N / 128) >= 512) return launch_cfg<4, 2, 32, 4, EPI, 3>(p, s, plan);
             }
-            return wide ? launch_cfg<2, 2, 32, 4, EPI, 3>(p, s) : launch_cfg<4, 1, 32, 4, EPI, 3>(p, s);
+            return wide ? launch_cfg<2, 2, 32, 4, EPI, 3>(p, s, plan) : launch_cfg<4, 1, 32, 4, EPI, 3>(p, s, plan);
         }
     }
     return AGP_E_BADARG;
@@ -575,7 +587,7 @@ int launch_igemm(IgemmParams& p, int prec, hipStream_t s) {
 }  // namespace agp_igemm
 using namespace agp_igemm;
 
-int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s);
+int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s, agp_igemm::TilePlan* plan);
 int agp_internal_conv_d16_pool(agp_igemm::IgemmParams& p, int prec, hipStream_t s);
 int agp_internal_stem_raw(agp_igemm::IgemmParams& p, int kind, const void* x, long long sn, long long sc, long long sh, long long sw,
                           int h, int w, int ncam, const float* mean3, const float* std3, hipStream_t s);
@@ -627,7 +639,7 @@ static int conv_fill_params(const agp_conv_desc* d, IgemmParams& p);
 void agp_internal_conv_kxr_geometry(agp_igemm::IgemmParams& p, const agp_conv_desc* d);
 bool agp_internal_use_kxr2(const agp_conv_desc* d);
 int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
-int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s);
+int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan);
 
 // Several convolutions of ONE channel shape (cin, cout, 3x3 stride 1) and precision as ONE launch: the tiles of
 // every problem form one grid (igemm_kxr2.hip).  Groups the kernel cannot take run as `n` launches, in order.
@@ -672,8 +684,7 @@ static int conv2d_fwd_group(const agp_conv_desc* descs, int n, void* stream, Til
                 const agp_conv_desc* d = descs + h + i;
                 ps[i].w2_hi = d->w_hi; ps[i].w2_cm = d->w_cm; ps[i].scale2 = d->scale; ps[i].shift2 = d->shift; ps[i].o2_hi = d->out_hi;
             }
-            if (plan) { *plan = TilePlan{AGP_CONV_KERNEL_S2, 0, 0, 0, 0, 0, 0, 0}; return AGP_OK; }
-            return agp_internal_conv_s2(ps, descs, h, (hipStream_t)stream);
+            return agp_internal_conv_s2(ps, descs, h, (hipStream_t)stream, plan);
         }
     }
     if (!group) {
@@ -693,8 +704,7 @@ static int conv2d_fwd_group(const agp_conv_desc* descs, int n, void* stream, Til
                 const int rc = conv_fill_params(descs + i, ps[i]);
                 if (rc != AGP_OK) return rc;
             }
-            if (plan) { *plan = TilePlan{AGP_CONV_KERNEL_GENERIC, 0, 0, 0, 0, 0, 0, 0}; return AGP_OK; }
-            return launch_group_f16(ps, n, (hipStream_t)stream);
+            return launch_group_f16(ps, n, (hipStream_t)stream, plan);
         }
         if (plan && n > 1) return AGP_E_UNSUPPORTED;      // `n` launches: ask for each descriptor's plan
         for (int i = 0; i < n; ++i) {
@@ -771,10 +781,8 @@ static int conv2d_fwd_one(const agp_conv_desc* d, void* stream, TilePlan* plan) 
     // one would read them as row-major -- refuse instead
     if (d->w_cm && d->w_cm == d->w_hi && (which != 3 || !p.w_cm)) return AGP_E_BADARG;
     if (which == 3) return agp_internal_conv_kxr(p, d, (hipStream_t)stream, plan);
-    // (the tile fields are reported for the 3x3 stride-1 family; the other kernels answer with their id alone)
-    if (plan) { *plan = TilePlan{which == 2 ? AGP_CONV_KERNEL_DIRECT_X : AGP_CONV_KERNEL_GENERIC, 0, 0, 0, 0, 0, 0, 0}; return AGP_OK; }
-    if (which == 2) return agp_internal_conv_d16(p, d->prec, (hipStream_t)stream);
-    return launch_igemm<EPI_CONV>(p, d->prec, (hipStream_t)stream);
+    if (which == 2) return agp_internal_conv_d16(p, d->prec, (hipStream_t)stream, plan);
+    return launch_igemm<EPI_CONV>(p, d->prec, (hipStream_t)stream, plan);
 }
 
 // The generic geometry of `d` (every conv kernel starts from it).

@@ -509,24 +509,28 @@ int launch_stem_pool_lds(IgemmParams& p, const StemRaw& raw, hipStream_t s) {
 }
 
 template <int NTW, int NPREC, bool RG>
-int launch_d16_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s) {
+int launch_d16_rg(IgemmParams& p, uint32_t* rflag, hipStream_t s, TilePlan* plan) {
     constexpr int lds = d16_lds_bytes<NTW, NPREC>();
-    static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_d16_kernel<NTW, NPREC, 0, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     p.MT = (p.M + 255) / 256;
     p.NT = (p.N + NTW * 16 - 1) / (NTW * 16);
     p.mt_chunk = (p.MT + 7) / 8;
+    if (plan) {
+        *plan = TilePlan{AGP_CONV_KERNEL_DIRECT_X, 256, NTW * 16, p.MT, p.NT, p.MT, 0, p.mt_chunk * 8 * p.NT};
+        return AGP_OK;
+    }
+    static std::atomic<uint64_t> attr_done{0};
+    if (!agp_lds_attr((const void*)igemm_d16_kernel<NTW, NPREC, 0, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     AGP_LAUNCH((igemm_d16_kernel<NTW, NPREC, 0, RG>), dim3(p.mt_chunk * 8 * p.NT), dim3(256), lds, s, p, rflag);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
 template <int NTW, int NPREC>
-int launch_d16(IgemmParams& p, hipStream_t s) {
+int launch_d16(IgemmParams& p, hipStream_t s, TilePlan* plan) {
     if constexpr (PrecT<NPREC>::F16) {
         uint32_t* const rflag = agp_range_flag_get();
-        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_d16_rg<NTW, NPREC, decltype(rg)::value>(p, rflag, s); });
+        return agp_rg_dispatch(rflag, [&](auto rg) { return launch_d16_rg<NTW, NPREC, decltype(rg)::value>(p, rflag, s, plan); });
     }
-    return launch_d16_rg<NTW, NPREC, false>(p, nullptr, s);
+    return launch_d16_rg<NTW, NPREC, false>(p, nullptr, s, plan);
 }
 
 // fused stem + max-pool launch (fp16 maps, 64 output channels)
@@ -571,12 +575,12 @@ int agp_internal_conv_d16_pool(agp_igemm::IgemmParams& p, int prec, hipStream_t 
 }
 
 // Conv dispatch for the direct-X kernel (called from igemm.hip's agp_conv2d_fwd).
-int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s) {
+int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
     const bool wide = (p.N % 128 == 0);
-    if (prec == AGP_PREC_BF16X3) return wide ? launch_d16<8, 3>(p, s) : launch_d16<4, 3>(p, s);
-    if (prec == AGP_PREC_F16W2) return wide ? launch_d16<8, 2>(p, s) : launch_d16<4, 2>(p, s);
-    if (prec == AGP_PREC_F16) return wide ? launch_d16<8, 4>(p, s) : launch_d16<4, 4>(p, s);
+    if (prec == AGP_PREC_BF16X3) return wide ? launch_d16<8, 3>(p, s, plan) : launch_d16<4, 3>(p, s, plan);
+    if (prec == AGP_PREC_F16W2) return wide ? launch_d16<8, 2>(p, s, plan) : launch_d16<4, 2>(p, s, plan);
+    if (prec == AGP_PREC_F16) return wide ? launch_d16<8, 4>(p, s, plan) : launch_d16<4, 4>(p, s, plan);
     return AGP_E_BADARG;
 }
 

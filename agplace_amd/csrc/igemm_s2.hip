@@ -429,8 +429,9 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
 }  // namespace agp_igemm
 
 // ps[i]: the 3x3 / stride-2 conv of problem i in the generic geometry (conv_fill_params), with w2_hi / scale2 / shift2 / o2_hi
-// = its 1x1 / stride-2 downsample (or NULL); all problems share N and CK.
-int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s) {
+// = its 1x1 / stride-2 downsample (or NULL); all problems share N and CK.  plan != NULL: the tile plan instead of the launch (MT = the
+// row tiles of all problems).
+int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
     if (n < 1 || n > S2_MAXP) return AGP_E_BADARG;
     S2Group g = {};
@@ -467,7 +468,7 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
     int rc;
 #if defined(AGP_TUNING)
     static std::atomic<uint64_t> a4{0}, a2{0};
-    if (!sch) {
+    if (!sch && !plan) {
         if (wide && ps[0].N % 128 == 0) { g.NT = ps[0].N / 128; rc = launch(igemm_s2_kernel<4, false>, s2_lds<4>(), a4); }
         else { g.NT = (ps[0].N + 63) / 64; rc = launch(igemm_s2_kernel<2, false>, s2_lds<2>(), a2); }
     } else
@@ -477,6 +478,10 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
         uint32_t* const rflag = agp_range_flag_get();
         const bool w4 = wide && ps[0].N % 128 == 0;
         g.NT = w4 ? ps[0].N / 128 : (ps[0].N + 63) / 64;
+        if (plan) {
+            *plan = TilePlan{AGP_CONV_KERNEL_S2, S2_BM, w4 ? 128 : 64, g.MT, g.NT, g.MT, 0, g.mt_chunk * 8 * g.NT};
+            return AGP_OK;
+        }
         if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, true, uint32_t*>, s2_lds<4>(), a4g, rflag)
                            : launch(igemm_s2_kernel<2, true, uint32_t*>, s2_lds<2>(), a2g, rflag);
         else rc = w4 ? launch(igemm_s2_kernel<4, true>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2, true>, s2_lds<2>(), a2s);

@@ -263,9 +263,10 @@ int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* stream);
  * on the host by the launch path itself (nothing is launched, no device is needed; pointers are looked at as NULL / non-NULL
  * only).  plan = { kernel (AGP_CONV_KERNEL_*), BM, BN (rows x channels of a tile), MT, NT (row x column tiles of all problems),
  * MT_full (row tiles in the XCD-chunked part of the grid), half tiles launched behind it (igemm_kxrw: the row tiles
- * [MT_full, MT) as 2 * NT tiles of BM / 2 rows each), grid size in workgroups }.  The tile fields are reported for the 3x3
- * stride-1 kernels (KXR, KXR2, KXRW) and are 0 for the others.  Returns what the launch would return for invalid descriptors,
- * and AGP_E_UNSUPPORTED for a group that runs as `n` separate launches. */
+ * [MT_full, MT) as 2 * NT tiles of BM / 2 rows each), grid size in workgroups }.  Every kernel reports its tile fields; the
+ * kernels other than KXRW have MT_full = MT and no half tiles.  A grouped launch of the generic kernel whose problems differ in
+ * their column tiles reports NT = 0.  Returns what the launch would return for invalid descriptors, and AGP_E_UNSUPPORTED for a
+ * group that runs as `n` separate launches. */
 #define AGP_CONV_KERNEL_GENERIC 1
 #define AGP_CONV_KERNEL_DIRECT_X 2
 #define AGP_CONV_KERNEL_KXR 3
