@@ -16,9 +16,11 @@ typedef unsigned short bf16_t;
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 // ---- tuning switches.  The release library reads NO process environment and keeps no switch state (stateless,
-// re-entrant): AGP_TUNE(key, default) IS its default -- a compile-time constant -- and the experiment variants, guarded by
-// `#if defined(AGP_TUNING)`, are not compiled.  The development build (`make tuning` -> lib/libagplace_hip_tuning.so, loaded by
-// the A/B harnesses under tools/ through AGP_HIP_LIB) keeps them and exports agp_debug_set(key, value) (csrc/api.hip).
+// re-entrant): AGP_TUNE(key, default) IS its default -- a compile-time constant -- and what is guarded by
+// `#if defined(AGP_TUNING)` is not compiled.  In the development build (`make tuning` -> lib/libagplace_hip_tuning.so, loaded by
+// the A/B harnesses under tools/ through AGP_HIP_LIB) the switches select between kernels that ship or turn on instruments, set
+// through the exported agp_debug_set(key, value) (csrc/api.hip).  The measured-and-rejected variants of the 3x3 stride-1 and
+// stage-entry kernels (igemm_kxr*, igemm_s2) are not kept behind switches: profiles/README.md and the history are their record.
 #if defined(AGP_TUNING)
 int agp_tune_lookup(const char* key, int def);
 #define AGP_TUNE(key, def) agp_tune_lookup(key, def)

@@ -10,8 +10,7 @@
 // One macro-step = (ky, 32-channel chunk): stage BM+16 X rows once and the three W taps, then run
 // 3 x (BK/16) x tiles x passes MFMAs from it: X LDS-DMA traffic / 3, 72 MFMAs per wave (split-bf16)
 // between barriers.  Outputs at the two halo columns (x' = 0, W+1) are computed and discarded
-// (2/(W+2) waste).  No double buffering: the stage is 58-66 KB, so TWO workgroups fit per CU and
-// alternate -- one stages while the other computes.
+// (2/(W+2) waste).  The two forms of the loop that exist (RING = 1, RING = 3) are described above the kernel.
 
 // -DAGP_CENSUS=1 compiles in the per-workgroup census / phase stamps read by tools/census.py
 #ifndef AGP_CENSUS
@@ -19,68 +18,51 @@
 #endif
 
 #include <type_traits>
-#include <utility>
 
 #include "igemm_params.hpp"
 
 namespace agp_igemm {
 
-template <class F, int... I>
-__device__ __forceinline__ void kxr_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    kxr_static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
-
-__device__ __forceinline__ int swz32(int row) { return (row >> 2) & 3; }
-// 16x16x32 fragments (lane = row l&15, 16-byte K chunk l>>4): conflict-free ds_read_b128 for every kx row shift
-__device__ __forceinline__ int swz16(int row) { return (row >> 1) & 2; }
-template <int MF> __device__ __forceinline__ int swz(int row) { return MF == 16 ? swz16(row) : swz32(row); }
-
 // Tile BM x BN per workgroup, WM x WN waves, each wave TM x TN MFMA tiles of 32x32.
 template <int BM, int BN, int WM, int WN, int NPREC, int RING>
 constexpr int kxr_lds_bytes() {
-    constexpr int stage = ((RING >= 2 ? 2 : 1) * (BM + 16) * PrecT<NPREC>::XPL + (RING == 4 ? 4 : (RING ? 2 : 3)) * BN * PrecT<NPREC>::WPL) * 64;
+    static_assert(RING == 1 || RING == 3, "the two-slot W ring or the phase pipeline");
+    // X block (double buffered in the phase pipeline) + two W slots
+    constexpr int stage = ((RING == 3 ? 2 : 1) * (BM + 16) * PrecT<NPREC>::XPL + 2 * BN * PrecT<NPREC>::WPL) * 64;
     // the waves' staging rows + the statistics epilogue's [wave][columns][2] sums behind them
     constexpr int epi = WM * WN * 32 * ((BN / WN) * 4 + 16) + WM * WN * (BN / WN) * 8;
     return (stage > epi ? stage : epi) + 2 * BN * 4;     // + the scale/shift table of the direct epilogue
 }
 
-// RING = 2: phase pipeline.  A phase = one (macro-step, kx) tap: 2 x TM x TN x products MFMAs per wave.
-// The X block is double buffered and EVERY load (the next tap's W; the next macro-step's X together
-// with its tap 0) is issued at the start of the phase before the one that consumes it, so no phase
-// waits for a full memory round trip: one barrier per phase, nothing staged up front per macro-step.
-// RING = 3: as 2, with the DMA issue placed behind the phase's first fragment reads (off the path to the first
-// MFMA).  Tiles: 256 x 64 for every width since the measurements of profiles/README.md ("kxr sensitivity"):
-// the W tap a workgroup re-stages per phase is what the loop is most sensitive to (8 KB instead of 16 KB
-// at equal MFMAs per phase), +8 % on the 128/256-channel layers against 128 x 128 tiles although
-// the X block is then staged once per 64-channel column tile (from L2).
-// RING = 1: the three W taps of a macro-step go through a 2-slot ring (tap kx=2 is fetched while
-// kx=1 computes): 51 KB instead of 59-66 KB per workgroup -> THREE workgroups per CU.
-// workgroups per CU the register budget is sized for: 8-tile waves (TM*TN = 8) hold 128 accumulator
-// registers -> 2 waves per SIMD; 4-tile waves fit 3 (W ring) or 2 workgroups of 4 waves.
+// RING = 1: two-slot W ring.  Per (ky, 32-channel chunk) macro-step the X block and the W taps kx = 0, 1 are staged up front
+// (one barrier), tap kx = 2 is fetched into slot 0 while kx = 1 computes: 51 KB per workgroup -> THREE workgroups per CU hide
+// each other's stage (no double buffering).
+// RING = 3: phase pipeline.  A phase = one (macro-step, kx) tap: 2 x TM x TN x products MFMAs per wave.  The X block is double
+// buffered and EVERY load (the next tap's W; the next macro-step's X together with its tap 0) is issued in the phase before
+// the one that consumes it, behind that phase's first fragment reads (off the path to the first MFMA), so no phase waits for
+// a full memory round trip: one barrier per phase, nothing staged up front per macro-step.  Tiles: 256 x 64 for every width
+// since the measurements of profiles/README.md ("kxr sensitivity"): the W tap a workgroup re-stages per phase is what the loop
+// is most sensitive to (8 KB instead of 16 KB at equal MFMAs per phase), +8 % on the 128/256-channel layers against 128 x 128
+// tiles although the X block is then staged once per 64-channel column tile (from L2).
+// (Retired, in the history before the commit that removed them: all three taps staged up front (RING = 0), the DMA issue at the
+// head of a phase (RING = 2), one wave per SIMD (RING = 4: profiles/README.md, round 5, "The three-product training convs") and
+// the 16x16x32 MFMA form (profiles/README.md, "kxr sensitivity").)
+// workgroups per CU the register budget is sized for: 8-tile waves (TM*TN = 8) hold 128 accumulator registers -> 2 waves per
+// SIMD; 4-tile waves fit 3 workgroups of 4 waves.
 template <int BM, int BN, int WM, int WN, int RING, int NPREC = 0>
 constexpr int kxr_min_blocks() {
     constexpr int tiles = (BM / (WM * 32)) * (BN / (WN * 32));
-    if (RING == 4) return 1;                             // one wave per SIMD, the whole register file (RING = 4 below)
-    if (NPREC == 3 && RING >= 2) return 2;               // two-plane operands, double-buffered X: 70 KB of LDS
-    return (WM * WN == 8) ? 2 : (tiles >= 8 ? 2 : (RING ? 3 : 2));
+    if (NPREC == 3 && RING == 3) return 2;               // two-plane operands, double-buffered X: 70 KB of LDS
+    return tiles >= 8 ? 2 : 3;
 }
 
-// MF = MFMA shape: 32 = 32x32x16 (two K-steps per tap phase), 16 = 16x16x32 (one): same operand bytes and MFMA
-// cycles per phase, but the chip holds a higher clock under load with the 16x16x32 form (MI355X_MICROARCH.md,
-// DVFS item 7), and these kernels are clock-limited: the same launch runs 1.37x faster on all-zero operands.
 // rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
-template <int BM, int BN, int WM, int WN, int NPREC, int RING, int MF = 32, bool LDS_EPI = false, bool Q8 = false, class... RF>
+template <int BM, int BN, int WM, int WN, int NPREC, int RING, bool LDS_EPI = false, bool Q8 = false, class... RF>
 __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>())) igemm_kxr_kernel(IgemmParams p, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool RG = sizeof...(RF) != 0;
     RangeTrack<RG> rg;
-    static_assert(MF == 32 || (MF == 16 && RING >= 2), "the 16x16x32 form exists for the phase-pipelined loop only");
-    static_assert(!Q8 || (NPREC == 2 && RING >= 2 && MF == 32), "Q8: the fp8 lo product of the F16W2 mode, phase-pipelined 32x32 loop only");
+    static_assert(!Q8 || (NPREC == 2 && RING == 3), "Q8: the fp8 lo product of the F16W2 mode, phase-pipelined loop only");
     constexpr int NW = WM * WN;
     constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);     // MFMA tiles per wave
     constexpr int EROWB = TN * 32 * 4 + 16;                     // epilogue row of one wave
@@ -88,22 +70,22 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
     constexpr int BMX = BM + 16;                 // staged X rows (the extra block feeds kx = 1, 2)
     constexpr int ROWB = 64;                     // 32 bf16 per row
     constexpr int XPL = PrecT<NPREC>::XPL, WPL = PrecT<NPREC>::WPL;
-    constexpr int X_PLANE = BMX * ROWB, W_TAP = BN * ROWB, W_PLANE = 3 * W_TAP;
+    constexpr int X_PLANE = BMX * ROWB, W_TAP = BN * ROWB;
     constexpr int XINS = BMX / 16;               // X LDS-DMA instructions per plane (16 rows each)
     constexpr int XI = (XINS + NW - 1) / NW;
-    constexpr int WINS = (RING ? 1 : 3) * BN / 16;  // W instructions per plane per issue group
+    constexpr int WINS = BN / 16;                // W instructions per plane per tap
     constexpr int WI = (WINS + NW - 1) / NW;
 
-    // DIRECT epilogue (fp16 maps, 32x32 MFMA): the W rows a wave feeds to the MFMA are permuted (bits 2 and 3 of
+    // DIRECT epilogue (fp16 maps): the W rows a wave feeds to the MFMA are permuted (bits 2 and 3 of
     // the row index swapped) so that accumulator registers 8h..8h+7 of a lane are 8 CONSECUTIVE channels
     // (16h + 8*(lane>>5) + e) of its pixel (lane & 31): 16-byte stores straight from registers, no LDS transpose,
     // no barrier before the epilogue, one output offset per 32-pixel tile instead of one per read-back iteration.
-    constexpr bool DIRECT = (PrecT<NPREC>::XPL == 1) && MF == 32 && !LDS_EPI;
+    constexpr bool DIRECT = (PrecT<NPREC>::XPL == 1) && !LDS_EPI;
     constexpr int BN_TAB = kxr_lds_bytes<BM, BN, WM, WN, NPREC, RING>() - 2 * BN * 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const xs_hi = smem;
     char* const xs_lo = smem + X_PLANE;                  // only when XPL == 2
-    char* const ws_hi = smem + X_PLANE * XPL * (RING >= 2 ? 2 : 1);
+    char* const ws_hi = smem + X_PLANE * XPL * (RING == 3 ? 2 : 1);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -151,18 +133,16 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
         const uint32_t y = fdiv(rem, p.d_wo);
         const uint32_t xq = rem - y * p.d_wo.d;
         const int el = (int)img * p.x_sn + (int)y * p.x_sh + (int)xq * p.x_sw + p.x_base;
-        xoff[q] = el * 2 + ((lpos ^ swz<MF>(row)) << 4);
+        xoff[q] = el * 2 + ((lpos ^ swz32(row)) << 4);
     }
 #pragma unroll
     for (int q = 0; q < WI; ++q) {
-        const int ins = wave + NW * q;               // instruction index over (3 taps x) BN/16
-        const int tap = RING ? 0 : ins / (BN / 16), row = (ins % (BN / 16)) * 16 + lrow;
+        const int row = ((wave + NW * q) % (BN / 16)) * 16 + lrow;
         int n = n0 + row;
         n = n < p.N ? n : p.N - 1;
-        // tap kx adds kx*CK elements along K
         // (chunk-major planes [Ktot/32][N][32], agp_conv_desc::w_cm: a 64-byte K chunk is N * 64 bytes on)
-        woff[q] = (p.w_cm ? n * 64 + tap * p.CK * 2 * p.N : (n * p.Ktot + tap * p.CK) * 2) + ((lpos ^ swz<MF>(row)) << 4);
-        if (Q8) woffq[q] = n * p.Ktot + ((lpos ^ swz<MF>(row)) << 4);
+        woff[q] = (p.w_cm ? n * 64 : n * p.Ktot * 2) + ((lpos ^ swz32(row)) << 4);
+        if (Q8) woffq[q] = n * p.Ktot + ((lpos ^ swz32(row)) << 4);
     }
     const int wmul = __builtin_amdgcn_readfirstlane(p.w_cm ? p.N : 1);
     const __amdgpu_buffer_rsrc_t rx_hi = __builtin_amdgcn_make_buffer_rsrc((void*)p.x_hi, 0, p.x_bytes, 0x00020000);
@@ -173,37 +153,30 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
 
     // ---- fragment read offsets: X rows shifted by kx, W rows per tap
     const int l31 = lane & 31, lh = lane >> 5;
-    const int l15 = lane & 15, lq = lane >> 4;
-    constexpr int FT = 32 / MF;                  // MFMA tiles per 32 rows
-    int xro[3][TM * FT], xsw[3][TM * FT], wro[TN * FT], wsw[TN * FT];
+    int xro[3][TM], xsw[3][TM], wro[TN], wsw[TN];
 #pragma unroll
-    for (int t = 0; t < TM * FT; ++t)
+    for (int t = 0; t < TM; ++t)
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
-            const int r = wm * (TM * 32) + t * MF + (MF == 16 ? l15 : l31) + kx;
+            const int r = wm * (TM * 32) + t * 32 + l31 + kx;
             xro[kx][t] = r * ROWB;
-            xsw[kx][t] = swz<MF>(r);
+            xsw[kx][t] = swz32(r);
         }
 #pragma unroll
-    for (int t = 0; t < TN * FT; ++t) {
-        const int wrow = DIRECT ? ((l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1)) : (MF == 16 ? l15 : l31);
-        const int wr = wn * (TN * 32) + t * MF + wrow;
+    for (int t = 0; t < TN; ++t) {
+        const int wrow = DIRECT ? ((l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1)) : l31;
+        const int wr = wn * (TN * 32) + t * 32 + wrow;
         wro[t] = wr * ROWB;
-        wsw[t] = swz<MF>(wr);
+        wsw[t] = swz32(wr);
     }
 
-    f32x16 acc[MF == 32 ? TN : 1][MF == 32 ? TM : 1];
-    f32x4 acc4[MF == 16 ? TN * 2 : 1][MF == 16 ? TM * 2 : 1];    // 16x16 tiles: [channel tile][pixel tile]
+    f32x16 acc[TN][TM];
 #pragma unroll
-    for (int a = 0; a < (MF == 32 ? TN : 1); ++a)
+    for (int a = 0; a < TN; ++a)
 #pragma unroll
-        for (int b = 0; b < (MF == 32 ? TM : 1); ++b)
+        for (int b = 0; b < TM; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-#pragma unroll
-    for (int a = 0; a < (MF == 16 ? TN * 2 : 1); ++a)
-#pragma unroll
-        for (int b = 0; b < (MF == 16 ? TM * 2 : 1); ++b) acc4[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // Residual prefetch (single-plane fp16 maps): the epilogue's residual reads are issued before the
     // LAST macro-step's MFMAs, so that their HBM latency (1-2k cycles each, 8 of them in sequence
@@ -271,146 +244,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
     const int cchunks = p.CK / 32;
     const int nsteps = 3 * cchunks;                  // (ky, cc) macro-steps
     int ky = 0, cc = 0;
-    if constexpr (RING == 4) {
-        // ---- one wave per SIMD (round 5): the three-product loop of the TRAINING convs with everything a step ahead.
-        // The other forms lean on two or three workgroups per CU to hide their stage behind each other and read 0.67 LDS
-        // fragments per MFMA at two planes per operand (LDS cycles ~ MFMA cycles: profiles/README.md, round 5).  Here a
-        // workgroup is 256 x 128 (a wave = 64 pixels x 128 channels: 0.5 fragment reads per MFMA, half the W staging per
-        // MFMA), alone on its CU with the whole register file, and the pipeline is spelled out:
-        //   * a phase = one tap kx of a (ky, 32-channel chunk) macro-step = two K-steps of 24 MFMAs; the fragments of the
-        //     NEXT K-step (across phase and macro-step borders) are read while this one's MFMAs run, the interleave is
-        //     fixed with sched_group_barrier (one LDS read behind each of the first twelve MFMAs);
-        //   * the barrier that publishes phase q + 1's operands sits in the MIDDLE of phase q; behind it a wave issues the
-        //     W tap of phase q + 3 (ring of four slots) and, over three half-phases, its ten pieces of the next macro-step's
-        //     X block (double buffered); counted vmcnt: 4 / 11 / 0 by tap;
-        //   * dependent MFMAs (the three products of one accumulator) are eight MFMAs apart: product-major order, the same
-        //     order per accumulator as mfma32<3> -- results are bit-identical to the other forms.
-        // Loads past the last macro-step run out of the planes' ranges and return zeros nobody reads.
-        static_assert(NPREC == 3 && MF == 32 && NW == 4 && !Q8 && !DIRECT, "RING = 4: split-bf16 operands, four waves");
-        constexpr int WSLOT = WPL * W_TAP, XBUF = X_PLANE * XPL;
-        const int tapb = __builtin_amdgcn_readfirstlane(p.CK * 2);
-        int xo4[XI], xd4[XI];                            // this wave's X pieces, clamped to the block (a repeat lands on itself)
-#pragma unroll
-        for (int q = 0; q < XI; ++q) {
-            int ins = wave + NW * q;
-            ins = ins < XINS ? ins : XINS - 1;
-            const int row = ins * 16 + lrow;
-            const int m = m0 + row;
-            const uint32_t img = fdiv((uint32_t)m, p.d_howo);
-            const uint32_t rem = (uint32_t)m - img * p.d_howo.d;
-            const uint32_t y = fdiv(rem, p.d_wo);
-            const uint32_t xq = rem - y * p.d_wo.d;
-            const int el = (int)img * p.x_sn + (int)y * p.x_sh + (int)xq * p.x_sw + p.x_base;
-            xo4[q] = el * 2 + ((lpos ^ swz32(row)) << 4);
-            xd4[q] = __builtin_amdgcn_readfirstlane(ins * 1024);
-        }
-        auto dma_x = [&](auto jc, int buf, int xs) {     // piece j = 2 q + plane of this wave's ten
-            constexpr int j = decltype(jc)::value, q = j >> 1, pl = j & 1;
-            char* dst = smem + buf * XBUF + pl * X_PLANE + xd4[q];
-            if (pl) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_lo, LDS_PTR(dst), 16, xo4[q], xs, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_hi, LDS_PTR(dst), 16, xo4[q], xs, 0, 0);
-        };
-        auto dma_w = [&](int slot, int wbytes) {         // one tap: WI row blocks x two planes per wave
-            const int so = __builtin_amdgcn_readfirstlane(wbytes * wmul);
-#pragma unroll
-            for (int q = 0; q < WI; ++q) {
-                char* dst = ws_hi + slot * WSLOT + (wave + NW * q) * 1024;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_hi, LDS_PTR(dst), 16, woff[q], so, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_lo, LDS_PTR(dst + W_TAP), 16, woff[q], so, 0, 0);
-            }
-        };
-        static_assert(XI * XPL == 10 && WI * WPL == 4, "the vmcnt counts below are written for ten X and four W pieces per wave");
-        bf16x8 fxh[2][TM], fxl[2][TM], fwh[2][TN], fwl[2][TN];
-        auto load_frags = [&](auto setc, const char* xb, const char* wb, auto kxc, auto ksc) {
-            constexpr int S = decltype(setc)::value, kx = decltype(kxc)::value, ks = decltype(ksc)::value;
-#pragma unroll
-            for (int t = 0; t < TM; ++t) {
-                const int xo = xro[kx][t] + (((2 * ks + lh) ^ xsw[kx][t]) << 4);
-                fxh[S][t] = *(const bf16x8*)(xb + xo);
-                fxl[S][t] = *(const bf16x8*)(xb + X_PLANE + xo);
-            }
-#pragma unroll
-            for (int t = 0; t < TN; ++t) {
-                const int wo = wro[t] + (((2 * ks + lh) ^ wsw[t]) << 4);
-                fwh[S][t] = *(const bf16x8*)(wb + wo);
-                fwl[S][t] = *(const bf16x8*)(wb + W_TAP + wo);
-            }
-        };
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        // prologue: X(0), taps 0 .. 2 of macro-step 0
-        static_for<10>([&](auto jc) { dma_x(jc, 0, 0); });
-        dma_w(0, 0); dma_w(1, tapb); dma_w(2, 2 * tapb);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        load_frags(I0{}, smem, ws_hi, I0{}, I0{});
-        int wslot = 0;                                   // ring slot of the current phase's tap (q & 3)
-        for (int st = 0; st < nsteps; ++st) {
-            int nky = ky, ncc = cc + 1;
-            if (ncc == cchunks) { ncc = 0; ++nky; }
-            const int wnext = (nky * 3 * p.CK + ncc * 32) * 2;
-            const int xsn = __builtin_amdgcn_readfirstlane((nky * p.x_sh + ncc * 32) * 2);
-            const char* xb = smem + (st & 1) * XBUF;
-            const char* xbn = smem + ((st + 1) & 1) * XBUF;
-            static_for<3>([&](auto kxc) {
-                constexpr int kx = decltype(kxc)::value;
-                const char* wb = ws_hi + wslot * WSLOT;
-                const int ns = (wslot + 1) & 3;
-                const char* wbn = ws_hi + ns * WSLOT;
-                static_for<2>([&](auto ksc) {
-                    constexpr int ks = decltype(ksc)::value;
-                    constexpr int cur = ks;              // fragment set of this K-step (two K-steps per phase: the sets alternate)
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (ks == 1) {
-                        // phase q + 1's operands are published here
-                        if constexpr (kx == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                        else if constexpr (kx == 1) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        dma_w((wslot + 3) & 3, wnext + kx * tapb);        // tap kx of the next macro-step = phase q + 3
-                        if constexpr (kx == 0) { dma_x(I0{}, (st + 1) & 1, xsn); dma_x(I1{}, (st + 1) & 1, xsn); dma_x(I2{}, (st + 1) & 1, xsn);
-                                                 dma_x(std::integral_constant<int, 3>{}, (st + 1) & 1, xsn); }
-                        if constexpr (kx == 1) { dma_x(std::integral_constant<int, 7>{}, (st + 1) & 1, xsn); dma_x(std::integral_constant<int, 8>{}, (st + 1) & 1, xsn);
-                                                 dma_x(std::integral_constant<int, 9>{}, (st + 1) & 1, xsn); }
-                    } else {
-                        if constexpr (kx == 1) { dma_x(std::integral_constant<int, 4>{}, (st + 1) & 1, xsn); dma_x(std::integral_constant<int, 5>{}, (st + 1) & 1, xsn);
-                                                 dma_x(std::integral_constant<int, 6>{}, (st + 1) & 1, xsn); }
-                    }
-                    // the next K-step's fragments: this phase's second K-step, or the first of the next phase (next tap of this
-                    // macro-step, or tap 0 of the next one from the other X buffer)
-                    if constexpr (ks == 0) load_frags(I1{}, xb, wb, kxc, I1{});
-                    else if constexpr (kx < 2) load_frags(I0{}, xb, wbn, std::integral_constant<int, kx + 1>{}, I0{});
-                    else load_frags(I0{}, xbn, wbn, I0{}, I0{});
-                    // 24 MFMAs, product-major
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fwl[cur][tn], fxh[cur][tm], acc[tn][tm], 0, 0, 0);
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fwh[cur][tn], fxl[cur][tm], acc[tn][tm], 0, 0, 0);
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fwh[cur][tn], fxh[cur][tm], acc[tn][tm], 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < 3 * TM * TN; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (i < 2 * (TM + TN)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        if (i >= 12 && i < 20) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-                    }
-                });
-                wslot = ns;
-            });
-            ky = nky; cc = ncc;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the loads issued past the last macro-step have landed (zeros)
-        __syncthreads();                                     // before the epilogue reuses the stage
-    } else
-    if constexpr (RING >= 2) {
+    if constexpr (RING == 3) {
         const int tapb = __builtin_amdgcn_readfirstlane(p.CK * 2);   // bytes between consecutive kx taps
         auto load_x = [&](int buf, int ky_, int cc_) {
             const int xs = __builtin_amdgcn_readfirstlane((ky_ * p.x_sh + cc_ * 32) * 2);
@@ -477,35 +311,9 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                         if (!(p.dbg & 1024)) load_w((st + 3) & 1, wnext);
                     }
                 };
-                if (RING == 2) issue_loads();
                 if (RPF && rhi && st == nsteps - 1 && kx == 0) prefetch_residual();
                 const char* wbase_hi = ws_hi + ((st + kx) & 1) * WSLOT;
                 const char* wbase_lo = wbase_hi + W_TAP;
-                if constexpr (MF == 16) {
-                    // offsets: the swizzle term (row >> 1) & 2 does not depend on the 16-row tile index
-                    bf16x8 xh[TM * 2], xl[TM * 2];
-                    const int xq = xro[kx][0] + ((lq ^ xsw[kx][0]) << 4), wq = wro[0] + ((lq ^ wsw[0]) << 4);
-#pragma unroll
-                    for (int t = 0; t < TM * 2; ++t) {
-                        xh[t] = *(const bf16x8*)(xb_hi + xq + t * 16 * ROWB);
-                        if (XPL == 2) xl[t] = *(const bf16x8*)(xb_lo + xq + t * 16 * ROWB);
-                    }
-#pragma unroll
-                    for (int half = 0; half < 2; ++half) {
-                        bf16x8 wh[TN], wl[TN];
-#pragma unroll
-                        for (int t = 0; t < TN; ++t) {
-                            wh[t] = *(const bf16x8*)(wbase_hi + wq + (half * TN + t) * 16 * ROWB);
-                            if (WPL == 2) wl[t] = *(const bf16x8*)(wbase_lo + wq + (half * TN + t) * 16 * ROWB);
-                        }
-                        if (RING == 3 && half == 0) issue_loads();
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                            for (int tm = 0; tm < TM * 2; ++tm)
-                                mfma16<NPREC>(acc4[half * TN + tn][tm], wh[tn], wl[tn], xh[tm], xl[tm]);
-                    }
-                } else {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     bf16x8 xh[TM], xl[TM], wh[TN], wl[TN];
@@ -521,8 +329,8 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                         wh[t] = *(const bf16x8*)(wbase_hi + wo);
                         if (WPL == 2 && !Q8) wl[t] = *(const bf16x8*)(wbase_lo + wo);
                     }
-                    // RING = 3: the DMA issue sits behind the first fragment reads, off the path to the first MFMA
-                    if (RING == 3 && ks == 0) issue_loads();
+                    // the DMA issue sits behind the first fragment reads, off the path to the first MFMA
+                    if (ks == 0) issue_loads();
                     if constexpr (Q8) {
                         // the lane's 8 fp16 activations of this K-step -> 8 e4m3 bytes (2 dwords) of its K subset of the pair
 #pragma unroll
@@ -569,7 +377,6 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                         }
                     }
                 }
-                }
             }
             ky = nky; cc = ncc;
         }
@@ -589,7 +396,7 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rx_lo, LDS_PTR(xs_lo + ins * 1024), 16, xoff[q], xs, 0, 0);
                 }
             }
-            // W: all three taps at once (RING = 0), or taps 0 and 1 into ring slots 0 and 1
+            // W: taps 0 and 1 into ring slots 0 and 1
             auto load_w = [&](int slot, int tapoff) {
     #pragma unroll
                 for (int q = 0; q < WI; ++q) {
@@ -598,13 +405,13 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                         char* dst = ws_hi + slot * (WPL * W_TAP) + ins * 1024;
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_hi, LDS_PTR(dst), 16, woff[q], ws + tapoff * wmul, 0, 0);
                         if (WPL == 2)
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_lo, LDS_PTR(dst + (RING ? W_TAP : W_PLANE)), 16, woff[q], ws + tapoff * wmul, 0, 0);
+                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_lo, LDS_PTR(dst + W_TAP), 16, woff[q], ws + tapoff * wmul, 0, 0);
                     }
                 }
             };
             const int tapb = __builtin_amdgcn_readfirstlane(p.CK * 2);   // bytes between consecutive kx taps
             load_w(0, 0);
-            if (RING) load_w(1, tapb);
+            load_w(1, tapb);
             // macro-step order: the three row blocks (ky) of ONE 32-channel chunk back to back, then the next chunk (round 6; before:
             // ky outermost).  A tile's three ky blocks overlap in 3/4 of their rows, and 96 tiles in flight per XCD hold more than
             // its 4 MB L2: with the re-read one macro-step away instead of `cchunks` the training step runs 16.06 / 16.30 ->
@@ -616,13 +423,13 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
             if (RPF && rhi && st == nsteps - 1) prefetch_residual();
     #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
-                if (RING && kx == 1) {
+                if (kx == 1) {
                     __syncthreads();                     // every wave is done with ring slot 0 (tap 0)
                     load_w(0, 2 * tapb);                 // tap 2 streams in while tap 1 computes
                 }
-                if (RING && kx == 2) __syncthreads();    // tap 2 has landed
-                const char* wbase_hi = RING ? ws_hi + (kx & 1) * (WPL * W_TAP) : ws_hi + kx * W_TAP;
-                const char* wbase_lo = wbase_hi + (RING ? W_TAP : W_PLANE);
+                if (kx == 2) __syncthreads();            // tap 2 has landed
+                const char* wbase_hi = ws_hi + (kx & 1) * (WPL * W_TAP);
+                const char* wbase_lo = wbase_hi + W_TAP;
     #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     bf16x8 xh[TM], xl[TM], wh[TN], wl[TN];
@@ -652,17 +459,11 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
     if (p.dbg & 128) {                               // timing experiment: no epilogue at all
         float t = 0.f;
 #pragma unroll
-        for (int a = 0; a < (MF == 32 ? TN : 1); ++a)
+        for (int a = 0; a < TN; ++a)
 #pragma unroll
-            for (int b = 0; b < (MF == 32 ? TM : 1); ++b)
+            for (int b = 0; b < TM; ++b)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) t += acc[a][b][r];
-#pragma unroll
-        for (int a = 0; a < (MF == 16 ? TN * 2 : 1); ++a)
-#pragma unroll
-            for (int b = 0; b < (MF == 16 ? TM * 2 : 1); ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) t += acc4[a][b][r];
         if (t == 1.2345e30f) ((float*)p.o_hi)[0] = t;
         return;
     }
@@ -744,14 +545,6 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
         // (the staging rows are private to the wave: LDS ops of one wave execute in order, no barrier)
-        if constexpr (MF == 16) {
-            // D tile (channel tile a, pixel tile b): lane holds pixel l15, channels 4*lq .. 4*lq+3
-#pragma unroll
-            for (int a = 0; a < TN * 2; ++a)
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    *(f32x4*)(er + (h * 16 + l15) * EROWB + (a * 16 + 4 * lq) * 4) = acc4[a][tm * 2 + h];
-        } else {
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
@@ -759,7 +552,6 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
                 f32x4 v = {acc[tn][tm][4 * q], acc[tn][tm][4 * q + 1], acc[tn][tm][4 * q + 2], acc[tn][tm][4 * q + 3]};
                 *(f32x4*)(er + l31 * EROWB + (tn * 32 + 8 * q + 4 * lh) * 4) = v;
             }
-        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         if (bstats) {
             // data-gradient conv feeding a BatchNorm backward: no scale / shift / ReLU (agp_conv_desc::bstat_*)
@@ -888,11 +680,10 @@ __global__ void __launch_bounds__(WM* WN * 64, (kxr_min_blocks<BM, BN, WM, WN, R
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int BM, int BN, int WM, int WN, int NPREC, int RING, int MF = 32, bool LDS_EPI = false, bool Q8 = false>
+template <int BM, int BN, int WM, int WN, int NPREC, int RING, bool LDS_EPI = false, bool Q8 = false>
 int launch_kxr(IgemmParams& p, hipStream_t s, TilePlan* plan) {
     constexpr int lds = kxr_lds_bytes<BM, BN, WM, WN, NPREC, RING>();
-    static_assert(lds <= (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 3 ? 53 : (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 2 ? 80 : 160)) * 1024,
-                  "LDS budget of the intended workgroups per CU");
+    static_assert(lds <= (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 3 ? 53 : 80) * 1024, "LDS budget of the intended workgroups per CU");
     static std::atomic<uint64_t> attr_done{0}, attr_done_rg{0};
     const XcdGrid xg = xcd_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
     if (plan) return plan_xcd(plan, AGP_CONV_KERNEL_KXR, BM, BN, xg);
@@ -902,16 +693,16 @@ int launch_kxr(IgemmParams& p, hipStream_t s, TilePlan* plan) {
     // fp16 maps (modes 2 / 4): the guarded twin while a range-guard word is bound (common.hpp RangeTrack)
     if constexpr (PrecT<NPREC>::F16) {
         if (uint32_t* const rflag = agp_range_flag_get()) {
-            if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>, lds, attr_done_rg))
+            if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8, uint32_t*>, lds, attr_done_rg))
                 return AGP_E_LAUNCH;
-            AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8, uint32_t*>), dim3(xg.blocks),
+            AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8, uint32_t*>), dim3(xg.blocks),
                        dim3(WM * WN * 64), lds, s, p, rflag);
             AGP_CHECK_LAUNCH();
             return AGP_OK;
         }
     }
-    if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
-    AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, MF, LDS_EPI, Q8>), dim3(xg.blocks), dim3(WM * WN * 64), lds, s, p);
+    if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
+    AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8>), dim3(xg.blocks), dim3(WM * WN * 64), lds, s, p);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -950,24 +741,14 @@ int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hip
     agp_internal_conv_kxr_geometry(p, d);
     if (agp_internal_use_kxr2(d)) return agp_internal_conv_kxr2(&p, 1, s, plan);
     const bool wide = (p.N % 128 == 0);
-    const int var = AGP_TUNE("KXR_VARIANT", 0);
-    (void)var;
     if (d->prec == AGP_PREC_BF16X3 && d->hi_only) {
         // one bf16 product on the hi planes, the split-pair epilogue (residual, statistics, out_hi / out_lo) of the three-product
         // form; 256-row tiles at every width (agp_conv2d_stat_tiles mirrors it)
         // wide: a wave owns 64 rows x 128 columns -- 16 MFMAs per phase and barrier, the inference kernel's shape (8 on 128 x 128
         // tiles of four waves: 0.20 MFMA-busy at 2.2 TB/s, bound by neither)
-        return wide ? launch_kxr<256, 128, 4, 1, 1, 3, 32, true>(p, s, plan) : launch_kxr<256, 64, 4, 1, 1, 3, 32, true>(p, s, plan);
+        return wide ? launch_kxr<256, 128, 4, 1, 1, 3, true>(p, s, plan) : launch_kxr<256, 64, 4, 1, 1, 3, true>(p, s, plan);
     }
     if (d->prec == AGP_PREC_BF16X3) {
-#if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 3, 0>(p, s, plan) : launch_kxr<256, 64, 4, 1, 3, 0>(p, s, plan);
-        if (var == 7 && wide) return launch_kxr<256, 128, 4, 1, 3, 4>(p, s, plan);
-        if (var == 2 && wide) return launch_kxr<128, 128, 2, 2, 3, 2>(p, s, plan);
-        if (var == 3 && wide) return launch_kxr<128, 128, 2, 2, 3, 3>(p, s, plan);
-        if (var == 2 && !wide) return launch_kxr<128, 64, 2, 1, 3, 2>(p, s, plan);
-        if (var == 3 && !wide) return launch_kxr<128, 64, 2, 1, 3, 3>(p, s, plan);
-#endif
         // 256-channel layers (K = 2304: 24 macro-steps per tile, few tiles): the phase-pipelined loop (X double-buffered, every load
         // a phase ahead; two workgroups per CU) -- 94 -> 82 us on the panorama maps, 181 -> 175 on the tile maps of the training
         // step; the 128-channel layers are even (74 / 76, 160 / 155) and the 64-channel ones lose (82 -> 93), tools/conv_bench.py
@@ -975,23 +756,11 @@ int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hip
         return wide ? launch_kxr<128, 128, 2, 2, 3, 1>(p, s, plan) : launch_kxr<256, 64, 4, 1, 3, 1>(p, s, plan);
     }
     if (d->prec == AGP_PREC_F16W2) {
-#if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 2, 0>(p, s, plan) : launch_kxr<256, 64, 4, 1, 2, 0>(p, s, plan);
-        if (var == 6) return wide ? launch_kxr<128, 128, 2, 2, 2, 1>(p, s, plan) : launch_kxr<256, 64, 4, 1, 2, 1>(p, s, plan);
-        if (var == 12) return wide ? launch_kxr<128, 128, 2, 2, 2, 2>(p, s, plan) : launch_kxr<256, 64, 4, 1, 2, 2>(p, s, plan);
-        if (var == 13) return launch_kxr<256, 64, 4, 1, 2, 3, 16>(p, s, plan);
-        if (var == 15) return launch_kxr<256, 64, 4, 1, 2, 3, 32, true>(p, s, plan);
-        if (var == 12) return launch_kxr<256, 64, 4, 1, 2, 3>(p, s, plan);
-#endif
-        if (p.w_q8 && p.CK % 64 == 0) return launch_kxr<256, 64, 4, 1, 2, 3, 32, false, true>(p, s, plan);
+        if (p.w_q8 && p.CK % 64 == 0) return launch_kxr<256, 64, 4, 1, 2, 3, false, true>(p, s, plan);
         return launch_kxr<256, 64, 4, 1, 2, 3>(p, s, plan);
     }
     if (d->prec == AGP_PREC_F16) {
         // (reached only where igemm_kxr2 does not take the conv: output planes past its 32-bit element offsets, stat_partial)
-#if defined(AGP_TUNING)
-        if (var == 1) return wide ? launch_kxr<128, 128, 2, 2, 4, 0>(p, s, plan) : launch_kxr<256, 64, 4, 1, 4, 0>(p, s, plan);
-        if (var == 12) return wide ? launch_kxr<128, 128, 2, 2, 4, 2>(p, s, plan) : launch_kxr<256, 64, 4, 1, 4, 2>(p, s, plan);
-#endif
         return launch_kxr<256, 64, 4, 1, 4, 3>(p, s, plan);
     }
     return AGP_E_BADARG;

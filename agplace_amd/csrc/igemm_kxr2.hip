@@ -12,23 +12,45 @@
 //     use, the barriers are raw `s_barrier`s and each is preceded by a COUNTED `s_waitcnt vmcnt(N)` that retires
 //     exactly the loads the next phase reads (the count per phase is derived below; every wave issues the same
 //     number of LDS-DMA instructions per phase, surplus X pieces re-issue the block's last piece);
+//   * a phase's LDS-DMA pieces are issued AMONG its MFMAs -- one behind each -- instead of in front of them (an LDS-DMA
+//     instruction costs ~60 cycles of issue between bare MFMAs against 100-185 at the head of a phase, and in front of
+//     the MFMAs that time sits on the wave's chain); all fragment reads of the phase come first (an LDS-DMA write may
+//     not pass an LDS read in program order), the last macro-step is peeled so that the loop body has no branch (one
+//     scheduling region per phase);
 //   * one launch serves up to four PROBLEMS of the same channel shape (`Kxr2Group`): the query network's and the
 //     database network's conv of one layer run as one grid -- the 64-tile database launches of a step were one-wave
 //     launches at a third of the big launches' rate -- and a conv on a small map no longer pays a launch of its own;
 //   * residual reads are unconditional (clamped address) so that the in-flight count does not depend on the data.
 //
-// vmcnt bookkeeping (per wave, in issue order; NX = X pieces per wave, W = one piece per wave and tap):
+// vmcnt bookkeeping (per wave, in issue order; NX = 5 X pieces per wave, W = one piece per wave and tap, NR = 8 residual
+// reads per lane; L = the last macro-step):
 //     prologue          : X(0)[NX]  W(0,0)  W(0,1)
 //     phase (st,0)      : W(st,2)   X(st+1)[NX]
 //     phase (st,1)      : W(st+1,0)
 //     phase (st,2)      : W(st+1,1)
-//   before the barrier that opens (st,1): W(st,1) must have landed; younger: W(st,2), X(st+1)        -> vmcnt(NX+1)
-//   before the barrier that opens (st,2): W(st,2);                 younger: X(st+1), W(st+1,0)       -> vmcnt(NX+1)
+//     phase (L,0)       : W(L,2)
+//     phase (L,1)       : R[NR]                          (only with a residual; issued in front of the phase)
+//     phase (L,2)       : nothing
+//   before the barrier that opens (0,0):    X(0) and W(0,0) must have landed; younger: W(0,1)        -> vmcnt(1)
+//   before the barrier that opens (st,1):   W(st,1);               younger: W(st,2), X(st+1)         -> vmcnt(NX+1)
+//   before the barrier that opens (st,2):   W(st,2);               younger: X(st+1), W(st+1,0)       -> vmcnt(NX+1)
 //   before the barrier that opens (st+1,0): W(st+1,0) and X(st+1); younger: W(st+1,1)                -> vmcnt(1)
-//   last macro-step L (no X(L+1), no W beyond it; the residual reads R[NR] are issued in (L,1)):
-//     opens (L,1): W(L,1); younger: W(L,2) -> vmcnt(1);   opens (L,2): W(L,2); younger: R -> vmcnt(NR or 0).
+//   before the barrier that opens (L,1):    W(L,1);                younger: W(L,2)                   -> vmcnt(1)
+//   before the barrier that opens (L,2):    W(L,2);                younger: R                        -> vmcnt(NR), or vmcnt(0)
+//                                                                                                       without a residual
 // W(st,kx) lives in ring slot kx (a phase index is 3 st + kx and the ring has 3 slots); the slot written in phase p
 // was last read in phase p-1, whose reads every wave has retired (lgkmcnt(0)) before the barrier that opens p.
+//
+// Retired forms (measured and rejected; the code is in the history before the commit that removed it):
+//   * the fragment-prefetch pipeline (a phase's fragments read a phase ahead into a second register set; three X buffers and
+//     a four-slot W ring, 69 KB -> two workgroups per CU): profiles/README.md, round 2, "What was measured and rejected
+//     this round";
+//   * the products on v_mfma_f32_16x16x32_f16 (4 x 4 tiles of 16 x 16 per wave): profiles/README.md, round 3, "What was
+//     measured this round";
+//   * 512-row tiles on eight waves (two workgroups per CU = four waves per SIMD): profiles/README.md, round 3, "What was
+//     measured this round";
+//   * the LDS-DMA pieces at the head of a phase, in front of its MFMAs (the loop before round 3): profiles/README.md,
+//     round 3, "What was measured this round".
 
 #include <type_traits>
 
@@ -46,11 +68,6 @@
 
 namespace agp_igemm {
 
-__device__ __forceinline__ int swz32(int row) { return (row >> 2) & 3; }   // XOR-swizzle of a row's four 16-byte chunks
-// the 16x16x32 fragment shape (16 consecutive rows x one chunk per 16 lanes): X rows / permuted W rows
-__device__ __forceinline__ int swz16x(int row) { return (row >> 1) & 2; }
-__device__ __forceinline__ int swz16w(int row) { return (row >> 3) & 2; }
-
 constexpr int KXR2_MAXP = 4;
 struct Kxr2Group {
     IgemmParams p[KXR2_MAXP];
@@ -58,80 +75,31 @@ struct Kxr2Group {
     int nprob, MT, NT, mt_chunk;
 };
 
-template <int N> __device__ __forceinline__ void wait_vm_lgkm() {
-    // retire all but the N youngest vector-memory operations of this wave, and all of its LDS reads
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-    else static_assert(N < 0, "add the count");
-}
+constexpr int KXR2_BM = 256, KXR2_MINB = 3;      // rows of a tile; workgroups per CU the register and LDS budgets are sized for
+// X double buffer, 3-slot W ring, scale / shift table
+constexpr int kxr2_lds_bytes() { return 2 * (KXR2_BM + 16) * 64 + 3 * 64 * 64 + 2 * 64 * 4; }
 
-template <int BM, bool PF = false>
-constexpr int kxr2_lds_bytes() { return (PF ? 3 : 2) * (BM + 16) * 64 + (PF ? 4 : 3) * 64 * 64 + 2 * 64 * 4; }
-
-// BM x 64 tile, four waves (wave w: rows 32 TM w .. ), TM x 2 MFMA tiles of 32 x 32 per wave.
-// PF (fragment prefetch): the MFMA fragments of phase p+1 are read from LDS DURING phase p into a second register set,
-// so a phase opens with its MFMAs instead of an LDS round trip.  The census (tools/census2.py) shows what bounds these
-// kernels: a workgroup needs ~1000 cycles per phase for 256 cycles of MFMA work per SIMD -- barrier, fragment-read latency,
-// MFMAs, second read latency, MFMAs, in series -- and a CU's throughput is (resident workgroups) / (that latency).
-// Reading a phase ahead needs the data a phase earlier: three X buffers and a four-slot W ring (69 KB, two workgroups
-// per CU), every load issued three phases (W) or five to six (X) ahead.  Bookkeeping (per wave, issue order):
-//     prologue     : X(0)[NX] W(0,0) W(0,1) X(1)[NX] W(0,2);      wait vmcnt(NX+1), barrier, read fragments of (0,0)
-//     phase (st,0) : reads of (st,1);   issues W(st+1,0) X(st+2)[NX]
-//     phase (st,1) : reads of (st,2);   issues W(st+1,1)
-//     phase (st,2) : reads of (st+1,0); issues W(st+1,2)
-//   the wait that closes phase p retires what phase p+1 READS, i.e. the operands of phase p+2:
-//     closes (st,0): W(st,2);           younger: W(st+1,0) X(st+2)      -> vmcnt(NX+1)   [st = L-1: 1;  st = L: 0]
-//     closes (st,1): W(st+1,0) X(st+1); younger: X(st+2) W(st+1,1)      -> vmcnt(NX+1)   [st = L-1: 1;  st = L: none]
-//     closes (st,2): W(st+1,1);         younger: W(st+1,2)              -> vmcnt(1)      [st = L: none]
-//   W(p) lives in ring slot p & 3 (p = 3 st + kx), X(st) in buffer st % 3; the slot / buffer a phase writes was last
-//   READ two phases earlier (its reads retired by lgkmcnt(0) before the barrier in between).
+// 256 x 64 tile, four waves (wave w: rows 64 w .. ), 2 x 2 MFMA tiles of 32 x 32 per wave.
 // POOL: problems with IgemmParams::pool_partial also reduce the map they store for the global pooling behind it (GeM /
 // average pool of a stage output): per 64-row wave block and channel, the sum of the stored values and of max(x, eps)^p
 // over the block's pixels.  Such a problem's raster gives every image a multiple of 64 rows (img_rows real ones, the rest
 // dead: computed, never stored), so a wave block lies inside ONE image at an image-relative position: the sums do not
 // depend on where in the batch an image sits (bit-identical under batch permutation / splitting).  The values are read
 // back from the epilogue's LDS strip (the fp16 bits that go to memory), one channel per lane, in pixel order.
-// M16: the products run on v_mfma_f32_16x16x32_f16 (16 per wave and phase on 4 x 4 tiles of 16 pixels x 16 channels) instead
-// of v_mfma_f32_32x32x16_f16 (8 on 2 x 2 tiles of 32 x 32): the same cycles, LDS fragment reads and registers, but the chip
-// holds a higher clock on this shape under load (MI355X_MICROARCH.md, DVFS give-back item 7).  A lane's accumulators are 16
-// consecutive channels of its pixel (W rows permuted accordingly); the LDS images are XOR-swizzled for this fragment shape
-// (X: chunk ^ 2 * bit 2 of the row, W: chunk ^ 2 * bit 4 of the row: conflict-free ds_read_b128 for rows 16 apart in a tile).
-// NW_ = 8 (round 3 experiment, AGP_KXR2_VARIANT=8): 512-row tiles on EIGHT waves (512 threads), two workgroups per CU = four waves
-// per SIMD instead of three: the X block and the W ring of a workgroup then serve twice the MFMAs (10 KB of LDS per wave instead
-// of 12), which is what buys the fourth wave.  Needs <= 128 VGPRs: the residual is loaded in the epilogue, not prefetched.  Every
-// wave issues the W piece of its (wave & 3) row block -- waves 4..7 duplicate waves 0..3's 4 KB -- so that all waves count the same
-// number of LDS-DMA instructions per phase.
-// SCH (round 3, the default of the production instantiation; AGP_KXR2_SCHED=0 turns it off): a phase's LDS-DMA pieces are issued
-// AMONG its MFMAs -- one behind each -- instead of in front of them (an LDS-DMA instruction costs ~60 cycles of issue between
-// bare MFMAs against 100-185 at the head of a phase, and in front of the MFMAs that time sits on the wave's chain); all fragment
-// reads of the phase come first (an LDS-DMA write may not pass an LDS read in program order), the last macro-step is peeled so
-// that the loop body has no branch (one scheduling region per phase).
 // rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
-template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW_ = 4, bool SCH = false, class... RF>
-__global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g, RF... rf) {
+template <bool POOL, class... RF>
+__global__ void __launch_bounds__(256, KXR2_MINB) igemm_kxr2_kernel(Kxr2Group g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool RG = sizeof...(RF) != 0;
-    static_assert(!SCH || (!PF && !M16 && NW_ == 4), "scheduled variant: the plain loop of the four-wave 32x32x16 kernel");
-    static_assert(!(M16 && PF), "the 16x16x32 variant is built without the fragment-prefetch pipeline");
-    static_assert(!M16 || BM == 256, "16x16x32 variant: 256-row tiles");
-    static_assert(NW_ == 4 || (NW_ == 8 && !PF && !M16), "eight-wave variant: plain loop only");
-    constexpr int BN = 64, NW = NW_, TM = BM / (NW * 32), TN = 2;
-    constexpr bool RPF = NW == 4;                  // residual prefetched during the last macro-step (costs 32 VGPRs in the loop)
+    constexpr int BM = KXR2_BM, BN = 64, NW = 4, TM = BM / (NW * 32), TN = 2;
     constexpr int BMX = BM + 16, ROWB = 64;
     constexpr int X_BUF = BMX * ROWB, W_TAP = BN * ROWB;
     constexpr int XINS = BMX / 16;                 // LDS-DMA pieces (16 rows x 64 B) per X block
     constexpr int NX = (XINS + NW - 1) / NW;       // per wave; pieces beyond XINS re-issue the last one
-    constexpr int TMP = RPF ? (TM < 2 ? TM : 2) : 1;   // tile rows whose residual is loaded per round (prefetched during the last macro-step when RPF)
-    constexpr int NR = RPF ? TMP * TN * 2 : 0;     // prefetched residual reads per lane (16 bytes each)
+    constexpr int NR = TM * 4;                     // residual reads per lane (16 bytes each), prefetched during the last macro-step (32 VGPRs in the loop)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* const ws = smem + (PF ? 3 : 2) * X_BUF;
-    float* const tab = (float*)(ws + (PF ? 4 : 3) * W_TAP);
+    char* const ws = smem + 2 * X_BUF;
+    float* const tab = (float*)(ws + 3 * W_TAP);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -147,11 +115,7 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
     const int nt = j % gNT;
     int mt = xcd * gchunk + j / gNT;
     if (mt >= gMT) return;
-    int pid = 0, base = 0;
-    if (gnprob > 1 && mt >= e0) { pid = 1; base = e0; }
-    if (gnprob > 2 && mt >= e1) { pid = 2; base = e1; }
-    if (gnprob > 3 && mt >= e2) { pid = 3; base = e2; }
-    mt -= base;
+    const int pid = group_problem(mt, gnprob, e0, e1, e2);
     const IgemmParams& p = g.p[pid];
     const int m0 = mt * BM, n0 = nt * BN;
 #if AGP_CENSUS
@@ -190,13 +154,13 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
         const uint32_t y = fdiv(rem, d_wo);
         const uint32_t xq = rem - y * d_wo.d;
         const int el = (int)img * x_sn + (int)y * x_sh_ + (int)xq * x_sw + x_base;
-        xoff[q] = el * 2 + ((lpos ^ (M16 ? swz16x(row) : swz32(row))) << 4);
+        xoff[q] = el * 2 + ((lpos ^ swz32(row)) << 4);
     }
     {
         const int row = (wave & 3) * 16 + lrow;
         int n = n0 + row;
         n = n < pN ? n : pN - 1;
-        woff = (p.w_cm ? n * 64 : n * pKtot * 2) + ((lpos ^ (M16 ? swz16w(row) : swz32(row))) << 4);   // chunk-major W: [Ktot/32][N][32]
+        woff = (p.w_cm ? n * 64 : n * pKtot * 2) + ((lpos ^ swz32(row)) << 4);   // chunk-major W: [Ktot/32][N][32]
     }
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x_hi, 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w_cm ? p.w_cm : p.w_hi), 0, p.w_bytes, 0x00020000);
@@ -232,59 +196,31 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
     load_x(0, 0, 0);
     load_w(0, 0);
     load_w(1, tapb);
-    if constexpr (PF) {
-        __builtin_amdgcn_sched_barrier(0);          // the counts rely on this order
-        load_x(1, cchunks == 1 ? 1 : 0, cchunks == 1 ? 0 : 1);
-        load_w(2, 2 * tapb);
-    }
 
     // ---- fragment read offsets.  The swizzle term of a row depends on (row mod 16) only.
     const int l31 = lane & 31, lh = lane >> 5;
     int xrd[3][2];                                  // [kx][ks]: byte offset of tile row 0, K-step ks
     int wrd[2];                                     // [ks]: byte offset of column tile 0 inside a ring slot
-    int xrd16[3], wrd16[4];                         // M16: [kx] byte offset of pixel tile 0; [ct] byte offset of channel tile ct
-    if constexpr (!M16) {
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
+    for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const int r = wave * (TM * 32) + l31 + kx;
-                xrd[kx][ks] = r * ROWB + (((2 * ks + lh) ^ swz32(r)) << 4);
-            }
-        // DIRECT epilogue: W rows permuted (bits 2 and 3 swapped) so that accumulator registers 8h .. 8h+7 of a lane
-        // are 8 consecutive channels of its pixel
-        const int wrow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ swz32(wrow)) << 4);
-    } else {
-        const int a = lane & 15, q = lane >> 4;     // fragment row, 16-byte K chunk
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            // pixel tiles are 16 rows apart: the swizzle term (bit 2 of the row) is the same for all four
-            const int r = wave * 64 + a + kx;
-            xrd16[kx] = r * ROWB + ((q ^ swz16x(r)) << 4);
+        for (int ks = 0; ks < 2; ++ks) {
+            const int r = wave * (TM * 32) + l31 + kx;
+            xrd[kx][ks] = r * ROWB + (((2 * ks + lh) ^ swz32(r)) << 4);
         }
-        // channel tile ct, fragment row a holds channel 16 (a >> 2) + 4 ct + (a & 3) of the tile's 64: accumulator registers
-        // j = 0..3 of the four channel tiles of a lane (quad q = lane >> 4) are then channels 16 q .. 16 q + 15 of its pixel
+    // DIRECT epilogue: W rows permuted (bits 2 and 3 swapped) so that accumulator registers 8h .. 8h+7 of a lane
+    // are 8 consecutive channels of its pixel
+    const int wrow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            const int wrow = 16 * (a >> 2) + 4 * ct + (a & 3);
-            wrd16[ct] = wrow * ROWB + ((q ^ swz16w(wrow)) << 4);
-        }
-    }
+    for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ swz32(wrow)) << 4);
 
     f32x16 acc[TN][TM];
-    f32x4 acc16[4][4];                              // M16: [channel tile][pixel tile]
 #pragma unroll
     for (int a = 0; a < TN; ++a)
 #pragma unroll
         for (int b = 0; b < TM; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc16[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // ---- epilogue addressing, LINE layout: in store / residual-load instruction i (0..3) of tile row tm a lane handles
     // pixel 8 i + (lane >> 3) of the 32 and 16-byte chunk (lane & 7) of the tile's 128-byte channel segment, so that one
@@ -330,285 +266,99 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
         }
     }
 
-    u32x4 rpf[TMP * TN * 2];
-    auto load_residual = [&](int tm0) {             // tile rows tm0 .. tm0 + TMP - 1, line layout
+    u32x4 rpf[NR];
+    auto prefetch_residual = [&]() {                // every tile row, line layout
 #pragma unroll
-        for (int t = 0; t < TMP; ++t)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {           // every lane loads (element 0 when its pixel is not stored): fixed vmcnt
-                const int off = eoff[(tm0 + t) * 4 + i];
-                rpf[t * 4 + i] = *(const u32x4*)(rhi + (off >= 0 ? off : 0));
-            }
+        for (int q = 0; q < TM * 4; ++q) {          // every lane loads (element 0 when its pixel is not stored): fixed vmcnt
+            const int off = eoff[q];
+            rpf[q] = *(const u32x4*)(rhi + (off >= 0 ? off : 0));
+        }
     };
-    auto prefetch_residual = [&]() { load_residual(0); };
 
     int ky = 0, cc = 0;
     KXR2_STAMP(0);                                  // prologue arithmetic done, first stage in flight
-    if constexpr (PF) {
-        wait_vm_lgkm<NX + 1>();
-        __builtin_amdgcn_s_barrier();
-        KXR2_STAMP(1);
-        const int L = nsteps - 1;
-        bf16x8 fx[2][2][TM], fw[2][2][TN];          // [register set][K-step][tile]
-        auto read_frags = [&](auto setc, auto kxc, int st_) {
-            constexpr int S = decltype(setc)::value, KX = decltype(kxc)::value;
-            const char* xb = smem + (st_ % 3) * X_BUF;
-            const char* wb = ws + ((3 * st_ + KX) & 3) * W_TAP;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                for (int t = 0; t < TM; ++t) fx[S][ks][t] = *(const bf16x8*)(xb + xrd[KX][ks] + t * (32 * ROWB));
-#pragma unroll
-                for (int t = 0; t < TN; ++t) fw[S][ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
-            }
-        };
-        read_frags(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, 0);
-        // one macro-step = three phases; P0 = register set of its first phase (macro-steps alternate 0, 1)
-        auto macro_step = [&](auto p0c, int st, int ky_, int cc_) {
-            constexpr int P0 = decltype(p0c)::value;
-            int nky = ky_, ncc = cc_ + 1;
-            if (ncc == cchunks) { ncc = 0; ++nky; }
-            int n2ky = nky, n2cc = ncc + 1;
-            if (n2cc == cchunks) { n2cc = 0; ++n2ky; }
-            const int wnext = (nky * 3 * CK + ncc * 32) * 2;
-            const bool has1 = st < L, has2 = st + 2 <= L;
-            // ---- phase (st,0)
-            if (true) {
-                read_frags(std::integral_constant<int, P0 ^ 1>{}, std::integral_constant<int, 1>{}, st);
-                if (has1) load_w((3 * st + 3) & 3, wnext);
-                __builtin_amdgcn_sched_barrier(0);
-                if (has2) load_x((st + 2) % 3, n2ky, n2cc);
-                if (st == 0 && tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
-                __builtin_amdgcn_sched_barrier(0);      // reads and loads first, then the MFMAs (whose operands were read a phase ago)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fw[P0][ks][tn]),
-                                                                                 __builtin_bit_cast(f16x8, fx[P0][ks][tm]), acc[tn][tm], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);      // the MFMAs stay in their phase (hipcc moves register-only MFMAs across waits and barriers)
-                if (has2) wait_vm_lgkm<NX + 1>();
-                else if (has1) wait_vm_lgkm<1>();
-                else wait_vm_lgkm<0>();
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // ---- phase (st,1)
-            if (true) {
-                read_frags(std::integral_constant<int, P0>{}, std::integral_constant<int, 2>{}, st);
-                if (has1) load_w((3 * st + 4) & 3, wnext + tapb);
-                else if (rhi) prefetch_residual();
-                __builtin_amdgcn_sched_barrier(0);      // reads and loads first, then the MFMAs (whose operands were read a phase ago)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fw[P0 ^ 1][ks][tn]),
-                                                                                 __builtin_bit_cast(f16x8, fx[P0 ^ 1][ks][tm]), acc[tn][tm], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (has2) wait_vm_lgkm<NX + 1>();
-                else if (has1) wait_vm_lgkm<1>();
-                else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // last macro-step: nothing left to land
-                if (has1) __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // ---- phase (st,2)
-            if (true) {
-                if (has1) {
-                    read_frags(std::integral_constant<int, P0 ^ 1>{}, std::integral_constant<int, 0>{}, st + 1);
-                    load_w((3 * st + 5) & 3, wnext + 2 * tapb);
-                }
-                __builtin_amdgcn_sched_barrier(0);      // reads and loads first, then the MFMAs (whose operands were read a phase ago)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fw[P0][ks][tn]),
-                                                                                 __builtin_bit_cast(f16x8, fx[P0][ks][tm]), acc[tn][tm], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (has1) {
-                    wait_vm_lgkm<1>();
-                    __builtin_amdgcn_s_barrier();
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        int st = 0;
-        for (; st + 1 < nsteps; st += 2) {
-            macro_step(std::integral_constant<int, 0>{}, st, ky, cc);
-            if (++cc == cchunks) { cc = 0; ++ky; }
-            macro_step(std::integral_constant<int, 1>{}, st + 1, ky, cc);
-            if (++cc == cchunks) { cc = 0; ++ky; }
-        }
-        if (st < nsteps) macro_step(std::integral_constant<int, 0>{}, st, ky, cc);
-    } else if constexpr (SCH) {
-        if (tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
-        wait_vm_lgkm<1>();
-        __builtin_amdgcn_s_barrier();
-        auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int nky_, int ncc_, int wcur_, int wnext_) {
-            constexpr int kx = decltype(KX)::value;
-            constexpr bool last = decltype(LAST)::value;
-            const char* wb = ws + kx * W_TAP;
-            bf16x8 xf[2][TM], wf[2][TN];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                for (int t = 0; t < TM; ++t) xf[ks][t] = *(const bf16x8*)(xb + xrd[kx][ks] + t * (32 * ROWB));
-#pragma unroll
-                for (int t = 0; t < TN; ++t) wf[ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
-            }
-            constexpr int ndma = kx == 0 ? (last ? 1 : 1 + NX) : (last ? 0 : 1);
-            // piece i of this phase's LDS-DMA list in the order the vmcnt counts assume: the W piece, then X(st + 1)
-            auto piece = [&](int i) {
-                if (kx == 0) {
-                    if (i == 0) {
-                        load_w(2, wcur_ + 2 * tapb);
-                    } else {
-                        const int q = i - 1;
-                        const int xs = __builtin_amdgcn_readfirstlane((nky_ * x_sh + ncc_ * 32) * 2);
-                        int ins = wave + NW * q;
-                        ins = ins < XINS ? ins : XINS - 1;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(smem + ((st_ + 1) & 1) * X_BUF + ins * 1024), 16, xoff[q], xs, 0, 0);
-                    }
-                } else {
-                    load_w(kx - 1, wnext_ + (kx - 1) * tapb);
-                }
-            };
-            int ip = 0;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) {
-                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
-                                                                             __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
-                        if (ip < ndma) { piece(ip); ++ip; }
-                    }
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM + TN), 0);
-#pragma unroll
-            for (int i = 0; i < 2 * TM * TN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        for (int st = 0; st < nsteps - 1; ++st) {
-            int nky = ky, ncc = cc + 1;
-            if (ncc == cchunks) { ncc = 0; ++nky; }
-            const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
-            const char* xb = smem + (st & 1) * X_BUF;
-            phase(I0{}, std::false_type{}, xb, st, nky, ncc, wcur, wnext);
-            wait_vm_lgkm<NX + 1>();
-            __builtin_amdgcn_s_barrier();
-            phase(I1{}, std::false_type{}, xb, st, nky, ncc, wcur, wnext);
-            wait_vm_lgkm<NX + 1>();
-            __builtin_amdgcn_s_barrier();
-            phase(I2{}, std::false_type{}, xb, st, nky, ncc, wcur, wnext);
-            wait_vm_lgkm<1>();
-            __builtin_amdgcn_s_barrier();
-            ky = nky; cc = ncc;
-        }
-        {
-            const int st = nsteps - 1;
-            const int wcur = (ky * 3 * CK + cc * 32) * 2;
-            const char* xb = smem + (st & 1) * X_BUF;
-            phase(I0{}, std::true_type{}, xb, st, 0, 0, wcur, 0);
-            wait_vm_lgkm<1>();
-            __builtin_amdgcn_s_barrier();
-            if (rhi && RPF) prefetch_residual();
-            phase(I1{}, std::true_type{}, xb, st, 0, 0, wcur, 0);
-            if (rhi && RPF) wait_vm_lgkm<NR>();     // (L,1): W(L,2) must have landed; younger: the residual reads
-            else wait_vm_lgkm<0>();
-            __builtin_amdgcn_s_barrier();
-            phase(I2{}, std::true_type{}, xb, st, 0, 0, wcur, 0);
-        }
-    } else {
+    if (tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
     wait_vm_lgkm<1>();
     __builtin_amdgcn_s_barrier();
-    KXR2_STAMP(1);                                  // first stage landed
-    for (int st = 0; st < nsteps; ++st) {
+    auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int nky_, int ncc_, int wcur_, int wnext_) {
+        constexpr int kx = decltype(KX)::value;
+        constexpr bool last = decltype(LAST)::value;
+        const char* wb = ws + kx * W_TAP;
+        bf16x8 xf[2][TM], wf[2][TN];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int t = 0; t < TM; ++t) xf[ks][t] = *(const bf16x8*)(xb + xrd[kx][ks] + t * (32 * ROWB));
+#pragma unroll
+            for (int t = 0; t < TN; ++t) wf[ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
+        }
+        constexpr int ndma = kx == 0 ? (last ? 1 : 1 + NX) : (last ? 0 : 1);
+        // piece i of this phase's LDS-DMA list in the order the vmcnt counts assume: the W piece, then X(st + 1)
+        auto piece = [&](int i) {
+            if (kx == 0) {
+                if (i == 0) {
+                    load_w(2, wcur_ + 2 * tapb);
+                } else {
+                    const int q = i - 1;
+                    const int xs = __builtin_amdgcn_readfirstlane((nky_ * x_sh + ncc_ * 32) * 2);
+                    int ins = wave + NW * q;
+                    ins = ins < XINS ? ins : XINS - 1;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(smem + ((st_ + 1) & 1) * X_BUF + ins * 1024), 16, xoff[q], xs, 0, 0);
+                }
+            } else {
+                load_w(kx - 1, wnext_ + (kx - 1) * tapb);
+            }
+        };
+        int ip = 0;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm) {
+                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
+                                                                         __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
+                    if (ip < ndma) { piece(ip); ++ip; }
+                }
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM + TN), 0);
+#pragma unroll
+        for (int i = 0; i < 2 * TM * TN; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    for (int st = 0; st < nsteps - 1; ++st) {
         int nky = ky, ncc = cc + 1;
         if (ncc == cchunks) { ncc = 0; ++nky; }
         const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
-        const bool last = st == nsteps - 1;
         const char* xb = smem + (st & 1) * X_BUF;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const char* wb = ws + kx * W_TAP;
-            bf16x8 xf[2][TM], wf[2][TN];
-            bf16x8 xg[4], wg[4];                    // M16: one K = 32 fragment per pixel / channel tile
-            if constexpr (!M16) {
-#pragma unroll
-                for (int t = 0; t < TM; ++t) xf[0][t] = *(const bf16x8*)(xb + xrd[kx][0] + t * (32 * ROWB));
-#pragma unroll
-                for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) wg[t] = *(const bf16x8*)(wb + wrd16[t]);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) xg[t] = *(const bf16x8*)(xb + xrd16[kx] + t * (16 * ROWB));
-            }
-            // ---- this phase's loads (behind the first fragment reads, off the path to the first MFMA)
-            if (kx == 0) {
-                load_w(2, wcur + 2 * tapb);
-                if (!last) load_x((st + 1) & 1, nky, ncc);
-                if (st == 0 && tid < BN) {          // scale / shift table: its loads were issued first thing and have landed by
-                    tab[tid] = tab_s;               // now (census: writing it in the prologue cost 1-2 us of load latency per tile);
-                    tab[BN + tid] = tab_t;          // read only in the epilogue, many barriers later
-                }
-            } else if (!last) {
-                load_w(kx - 1, wnext + (kx - 1) * tapb);
-            } else if (kx == 1 && rhi && RPF) {
-                prefetch_residual();
-            }
-            if constexpr (!M16) {
-#pragma unroll
-                for (int t = 0; t < TM; ++t) xf[1][t] = *(const bf16x8*)(xb + xrd[kx][1] + t * (32 * ROWB));
-#pragma unroll
-                for (int t = 0; t < TN; ++t) wf[1][t] = *(const bf16x8*)(wb + wrd[1] + t * (32 * ROWB));
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                        for (int tm = 0; tm < TM; ++tm)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
-                                                                                 __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int t = 2; t < 4; ++t) xg[t] = *(const bf16x8*)(xb + xrd16[kx] + t * (16 * ROWB));
-#pragma unroll
-                for (int pt = 0; pt < 4; ++pt)
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct)
-                        acc16[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wg[ct]),
-                                                                               __builtin_bit_cast(f16x8, xg[pt]), acc16[ct][pt], 0, 0, 0);
-            }
-            // ---- retire what the next phase reads, then open it
-            if (kx == 2) {
-                if (last) break;                    // the epilogue reads no staged data
-                wait_vm_lgkm<1>();
-            } else if (!last) {
-                wait_vm_lgkm<NX + 1>();
-            } else if (kx == 0) {
-                wait_vm_lgkm<1>();
-            } else {                                // (L,1): W(L,2) must have landed; younger: the residual reads
-                if (rhi && RPF) wait_vm_lgkm<NR>();
-                else wait_vm_lgkm<0>();
-            }
-            __builtin_amdgcn_s_barrier();
-        }
+        phase(I0{}, std::false_type{}, xb, st, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NX + 1>();
+        __builtin_amdgcn_s_barrier();
+        phase(I1{}, std::false_type{}, xb, st, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NX + 1>();
+        __builtin_amdgcn_s_barrier();
+        phase(I2{}, std::false_type{}, xb, st, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<1>();
+        __builtin_amdgcn_s_barrier();
         ky = nky; cc = ncc;
     }
-    }   // !PF
+    {
+        const int st = nsteps - 1;
+        const int wcur = (ky * 3 * CK + cc * 32) * 2;
+        const char* xb = smem + (st & 1) * X_BUF;
+        phase(I0{}, std::true_type{}, xb, st, 0, 0, wcur, 0);
+        wait_vm_lgkm<1>();
+        __builtin_amdgcn_s_barrier();
+        if (rhi) prefetch_residual();
+        phase(I1{}, std::true_type{}, xb, st, 0, 0, wcur, 0);
+        if (rhi) wait_vm_lgkm<NR>();            // (L,1): W(L,2) must have landed; younger: the residual reads
+        else wait_vm_lgkm<0>();
+        __builtin_amdgcn_s_barrier();
+        phase(I2{}, std::true_type{}, xb, st, 0, 0, wcur, 0);
+    }
 
     KXR2_STAMP(2);                                  // main loop done
     if (p.dbg & 128) {                              // timing experiment: no epilogue at all
@@ -619,12 +369,6 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
             for (int b = 0; b < TM; ++b)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) t += acc[a][b][r];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) t += acc16[a][b][r];
         if (t == 1.2345e30f) ((float*)p.o_hi)[0] = t;
         return;
     }
@@ -637,7 +381,6 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
     constexpr int ERS = 144;
     char* const strip = smem + wave * (32 * ERS);
     const int a_off = l31 * ERS + lh * 16;                      // accumulator layout: chunk 2 jj + lh of the lane's pixel
-    const int a_off16 = (lane & 15) * ERS + (lane >> 4) * 32;   // M16 accumulator layout: 32 bytes (16 channels) at 32 q of pixel lane & 15 (+ 16 rows for odd pixel tiles)
     const int l_off = (lane >> 3) * ERS + (lane & 7) * 16;      // line layout: + 8 i rows
     const float* tb = tab + 8 * lh;
     bf16_t* const ohi = (bf16_t*)p.o_hi;
@@ -649,22 +392,15 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
     // Residual FIRST, for every tile row, before any store is issued: loads and stores retire through ONE in-order
     // counter (vmcnt), so a wait for a residual load placed behind a tile row's stores waits for those stores' full round
     // trip (census: ~2 us per tile row).  Line layout -> strip -> accumulator layout, the prefetch registers are reused.
-    static_assert(TM <= TMP || TM == 2 * TMP, "residual staging below handles one or two prefetch rounds");
-    u32x4 rres[TM][TN * 2];                                     // M16: [tm][2 ph + u] = pixel tile 2 tm + ph, channels 16 q + 8 u ..
+    u32x4 rres[TM][TN * 2];
     if (rhi) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
-            if (!RPF || (TM > TMP && tm == TMP)) load_residual(tm);         // not prefetched / second round (512-row tiles)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) *(u32x4*)(strip + l_off + i * (8 * ERS)) = rpf[(tm % TMP) * 4 + i];
+            for (int i = 0; i < 4; ++i) *(u32x4*)(strip + l_off + i * (8 * ERS)) = rpf[tm * 4 + i];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            if constexpr (!M16) {
 #pragma unroll
-                for (int jj = 0; jj < TN * 2; ++jj) rres[tm][jj] = *(const u32x4*)(strip + a_off + jj * 32);
-            } else {
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) rres[tm][jj] = *(const u32x4*)(strip + a_off16 + (jj >> 1) * (16 * ERS) + (jj & 1) * 16);
-            }
+            for (int jj = 0; jj < TN * 2; ++jj) rres[tm][jj] = *(const u32x4*)(strip + a_off + jj * 32);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         }
     }
@@ -676,7 +412,6 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
         u32x4 outv[TN * 2];
-        if constexpr (!M16) {
 #pragma unroll
         for (int jp = 0; jp < TN; ++jp) {
             f32x4 sc4[2][2], sh4[2][2];
@@ -706,32 +441,6 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
         }
 #pragma unroll
         for (int jj = 0; jj < TN * 2; ++jj) *(u32x4*)(strip + a_off + jj * 32) = outv[jj];
-        } else {
-            // a lane holds channels 16 q .. 16 q + 15 of pixel (lane & 15) of each pixel tile: channel 16 q + 4 ct + j = acc16[ct][pt][j]
-            const float* tb16 = tab + 16 * (lane >> 4);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {               // channels 16 q + 8 u .. + 7 (scale / shift re-read per half: registers)
-                f32x4 sc4[2], sh4[2];
-#pragma unroll
-                for (int c4 = 0; c4 < 2; ++c4) { sc4[c4] = *(const f32x4*)(tb16 + 8 * u + 4 * c4); sh4[c4] = *(const f32x4*)(tb16 + BN + 8 * u + 4 * c4); }
-#pragma unroll
-                for (int ph = 0; ph < 2; ++ph) {
-                    float v[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = acc16[2 * u + (e >> 2)][2 * tm + ph][e & 3] * sc4[e >> 2][e & 3] + sh4[e >> 2][e & 3];
-                    if (rhi) {
-                        float r[8];
-                        unpack8_h(rres[tm][2 * ph + u], r);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += r[e];
-                    }
-                    rg.any8(v);
-                    outv[2 * ph + u] = pack8_h_lo(v, relu_lo);
-                }
-            }
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) *(u32x4*)(strip + a_off16 + (jj >> 1) * (16 * ERS) + (jj & 1) * 16) = outv[jj];
-        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         u32x4 lines[4];
 #pragma unroll
@@ -786,10 +495,10 @@ __global__ void __launch_bounds__(NW_ * 64, MINB) igemm_kxr2_kernel(Kxr2Group g,
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int BM, int MINB, bool PF = false, bool POOL = false, bool M16 = false, int NW = 4, bool SCH = false, bool RG = false>
+template <bool POOL, bool RG>
 int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
-    constexpr int lds = kxr2_lds_bytes<BM, PF>();
-    static_assert(lds * (MINB * 4 / NW) <= 160 * 1024, "LDS budget of the intended workgroups per CU");
+    constexpr int BM = KXR2_BM, lds = kxr2_lds_bytes();
+    static_assert(lds * KXR2_MINB <= 160 * 1024, "LDS budget of the intended workgroups per CU");
     static std::atomic<uint64_t> attr_done{0};
     int mt = 0;
     for (int i = 0; i < g.nprob; ++i) {
@@ -801,13 +510,11 @@ int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
     g.MT = xg.MT;
     g.NT = xg.NT;
     g.mt_chunk = xg.mt_chunk;
-    if (!agp_lds_attr(RG ? (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>
-                         : (const void*)igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>, lds, attr_done)) return AGP_E_LAUNCH;
+    if (!agp_lds_attr(RG ? (const void*)igemm_kxr2_kernel<POOL, uint32_t*> : (const void*)igemm_kxr2_kernel<POOL>, lds, attr_done)) return AGP_E_LAUNCH;
     if constexpr (RG) {
-        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH, uint32_t*>), dim3(xg.blocks), dim3(NW * 64), lds, s, g,
-                   agp_range_flag_get());
+        AGP_LAUNCH((igemm_kxr2_kernel<POOL, uint32_t*>), dim3(xg.blocks), dim3(256), lds, s, g, agp_range_flag_get());
     } else {
-        AGP_LAUNCH((igemm_kxr2_kernel<BM, MINB, PF, POOL, M16, NW, SCH>), dim3(xg.blocks), dim3(NW * 64), lds, s, g);
+        AGP_LAUNCH((igemm_kxr2_kernel<POOL>), dim3(xg.blocks), dim3(256), lds, s, g);
     }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
@@ -822,7 +529,7 @@ int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
     using namespace agp_igemm;
     if (n < 1 || n > KXR2_MAXP) return AGP_E_BADARG;
     // layers with cout % 128 == 0 run on the wide form (256 x 128 tiles, igemm_kxrw.hip)
-    if (AGP_TUNE("KXR_WIDE", 1) && ps[0].N % 128 == 0 && !AGP_TUNE("KXR2_VARIANT", 0)) return agp_internal_conv_kxrw(ps, n, s, plan);
+    if (AGP_TUNE("KXR_WIDE", 1) && ps[0].N % 128 == 0) return agp_internal_conv_kxrw(ps, n, s, plan);
     Kxr2Group g = {};
     g.nprob = n;
     for (int i = 0; i < n; ++i) {
@@ -831,22 +538,9 @@ int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
     }
     bool pool = false;
     for (int i = 0; i < n; ++i) pool = pool || ps[i].pool_partial != nullptr;
-#if defined(AGP_TUNING)
-    if (AGP_TUNE("KXR_TALL", 0) && !pool && ps[0].N == 64 && !AGP_TUNE("KXR2_VARIANT", 0)) return agp_internal_conv_kxrw(ps, n, s, plan);
-    // experiments that were measured and NOT adopted (profiles/README.md), development build only: 512-row tiles, 8-wave
-    // workgroups, the 16x16x32 form, two-slot rings, LDS-DMA pieces at the head of a phase (KXR2_SCHED = 0)
-    const int var = AGP_TUNE("KXR2_VARIANT", 0);
-    if (var == 8) return pool ? launch_kxr2<512, 4, false, true, false, 8>(g, s, plan) : launch_kxr2<512, 4, false, false, false, 8>(g, s, plan);
-    if (var == 16) return pool ? launch_kxr2<256, 3, false, true, true>(g, s, plan) : launch_kxr2<256, 3, false, false, true>(g, s, plan);
-    if (!AGP_TUNE("KXR2_SCHED", 1)) return pool ? launch_kxr2<256, 3, false, true>(g, s, plan) : launch_kxr2<256, 3>(g, s, plan);
-    if (!pool && var == 1) return launch_kxr2<512, 2>(g, s, plan);
-    if (!pool && var == 2) return launch_kxr2<256, 2>(g, s, plan);
-    if (!pool && var == 3) return launch_kxr2<256, 2, true>(g, s, plan);
-#endif
     return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) {
         constexpr bool RG = decltype(rg)::value;
-        if (pool)                       // (agp_conv2d_pool_blocks promises this tile shape)
-            return launch_kxr2<256, 3, false, true, false, 4, true, RG>(g, s, plan);
-        return launch_kxr2<256, 3, false, false, false, 4, true, RG>(g, s, plan);
+        if (pool) return launch_kxr2<true, RG>(g, s, plan);     // (agp_conv2d_pool_blocks promises this tile shape)
+        return launch_kxr2<false, RG>(g, s, plan);
     });
 }

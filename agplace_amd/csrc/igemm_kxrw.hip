@@ -28,8 +28,6 @@
 
 namespace agp_igemm {
 
-__device__ __forceinline__ int kw_swz(int row) { return (row >> 2) & 3; }   // XOR-swizzle of a row's four 16-byte chunks
-
 constexpr int KXRW_MAXP = 4;
 struct KxrwGroup {
     IgemmParams p[KXRW_MAXP];
@@ -41,22 +39,11 @@ struct KxrwGroup {
     uint32_t* rflag;           // the fp16 range guard's word (agp_range_flag_get), read by the RG = true instantiations only
 };
 
-template <int N> __device__ __forceinline__ void kw_wait() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
-    else static_assert(N < 0, "add the count");
-}
-
 // Tile shapes (a wave = TM_ x TN_ MFMA tiles of 32 x 32, four waves stacked along the rows):
-//   TM_ = 2, TN_ = 4: 256 rows x 128 channels -- the WIDE form, cout % 128 == 0;
-//   TM_ = 4, TN_ = 2: 512 rows x  64 channels -- the TALL form for cout = 64 (ResNet layer 1): the same 16 MFMAs per phase on 12
-//     fragment reads, and HALF as many tiles: layer 1's K is 576 = 18 phases, so the fixed cost of a tile (first stage in
-//     flight, epilogue round trips) is a third of a 256 x 64 tile's time (timed: K 576 -> 1152 on the same map raises the kernel
-//     from 650 to 800 TFLOP/s).
+//   TM_ = 2, TN_ = 4: 256 rows x 128 channels -- the full tile of the WIDE form, cout % 128 == 0;
+//   TM_ = 1, TN_ = 4: 128 rows x 128 channels -- its HALF tile, the launch's last round of workgroups (kxrw_plan).
+// (The tall form, 512 x 64 tiles on 4 x 2 MFMA tiles per wave for cout = 64, was measured and retired: profiles/README.md,
+// round 3, "What was measured this round"; the code is in the history before the commit that removed it.)
 constexpr int KW_ROWB = 64;
 template <int TM_, int TN_> struct KwShape {
     static constexpr int BM = 128 * TM_, BN = 32 * TN_, BMX = BM + 16;
@@ -65,18 +52,17 @@ template <int TM_, int TN_> struct KwShape {
 };
 
 // One tile: rows [m0, m0 + 128 TM_) x columns [n0, n0 + 32 TN_) of problem g.p[pid].
-template <bool POOL, bool SCHED, int TM_, int TN_, bool RG = false>
+template <bool POOL, int TM_, int TN_, bool RG = false>
 __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, const int m0, const int n0) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using SH = KwShape<TM_, TN_>;
-    constexpr int BM = SH::BM, BN = SH::BN, NW = 4, TM = TM_, TN = TN_, ROWB = KW_ROWB;
+    constexpr int BN = SH::BN, NW = 4, TM = TM_, TN = TN_, ROWB = KW_ROWB;
     constexpr int X_BUF = SH::XBUF, W_TAP = SH::WTAP;
-    constexpr int XINS = SH::BMX / 16;                 // LDS-DMA pieces (16 rows x 64 B) per X block: 17 / 33
-    constexpr int NX = (XINS + NW - 1) / NW;           // 5 / 9 per wave; pieces beyond XINS re-issue the last one
-    constexpr int NWP = BN / (NW * 16);                // 2 / 1 instructions per wave and W piece
-    static_assert((NX == 5 && NWP == 2) || (NX == 9 && NWP == 1) || (NX == 3 && NWP == 2), "the vmcnt counts exist for these");
-    static_assert(!POOL || ((TM == 2 || TM == 1) && TN == 4), "conv-epilogue pooling: the wide form (and its half tiles) only");
-    static_assert(TM * TN == 8 || (TM == 1 && TN == 4), "16 MFMAs per phase and wave (8 in a half tile)");
+    constexpr int XINS = SH::BMX / 16;                 // LDS-DMA pieces (16 rows x 64 B) per X block: 17 / 9
+    constexpr int NX = (XINS + NW - 1) / NW;           // 5 / 3 per wave; pieces beyond XINS re-issue the last one
+    constexpr int NWP = BN / (NW * 16);                // 2 instructions per wave and W piece
+    static_assert(TN == 4 && (TM == 2 || TM == 1), "the full tile (256 x 128) and its half tile (128 x 128)");
+    static_assert(NWP == 2 && (NX == 5 || NX == 3), "the vmcnt counts exist for these");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ws = smem + 2 * X_BUF;
     float* const tab = (float*)(ws + 3 * W_TAP);       // [scale 128][shift 128]
@@ -109,14 +95,14 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         const uint32_t y = fdiv(rem, d_wo);
         const uint32_t xq = rem - y * d_wo.d;
         const int el = (int)img * x_sn + (int)y * x_sh_ + (int)xq * x_sw + x_base;
-        xoff[q] = el * 2 + ((lpos ^ kw_swz(row)) << 4);
+        xoff[q] = el * 2 + ((lpos ^ swz32(row)) << 4);
     }
 #pragma unroll
     for (int i = 0; i < NWP; ++i) {
         const int row = (wave + NW * i) * 16 + lrow;
         int n = n0 + row;
         n = n < pN ? n : pN - 1;
-        woff[i] = (p.w_cm ? n * 64 : n * pKtot * 2) + ((lpos ^ kw_swz(row)) << 4);     // chunk-major W: [Ktot/32][N][32]
+        woff[i] = (p.w_cm ? n * 64 : n * pKtot * 2) + ((lpos ^ swz32(row)) << 4);     // chunk-major W: [Ktot/32][N][32]
     }
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x_hi, 0, p.x_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)(p.w_cm ? p.w_cm : p.w_hi), 0, p.w_bytes, 0x00020000);
@@ -160,13 +146,13 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int r = wave * (TM * 32) + l31 + kx;
-            xrd[kx][ks] = r * ROWB + (((2 * ks + lh) ^ kw_swz(r)) << 4);
+            xrd[kx][ks] = r * ROWB + (((2 * ks + lh) ^ swz32(r)) << 4);
         }
     {
         // W rows permuted (bits 2 and 3 swapped): accumulator registers 8h .. 8h+7 of a lane are 8 consecutive channels of its pixel
         const int wrow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ kw_swz(wrow)) << 4);
+        for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ swz32(wrow)) << 4);
     }
 
     f32x16 acc[TN][TM];
@@ -200,155 +186,95 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     float* const ppart = POOL ? p.pool_partial : nullptr;
 
     int ky = 0, cc = 0;
-    kw_wait<NWP>();
+    wait_vm_lgkm<NWP>();
     __builtin_amdgcn_s_barrier();
-    if constexpr (SCHED) {
-        // ---- the same phases with their LDS-DMA pieces spread AMONG the MFMAs (igroup pipeline: sched_group_barrier) instead
-        // of in front of them: an LDS-DMA instruction costs ~60 cycles of issue between bare MFMAs against 100-185 at the head of
-        // a phase beside the fragment reads (MI355X_MICROARCH.md), and in front of the MFMAs that time is on the wave's chain.
-        // The loop body has no branch (one scheduling region per phase): the last macro-step is peeled.
-        if (tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
-        auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int nky_, int ncc_, int wcur_, int wnext_) {
-            constexpr int kx = decltype(KX)::value;
-            constexpr bool last = decltype(LAST)::value;
-            const char* wb = ws + kx * W_TAP;
-            bf16x8 xf[2][TM], wf[2][TN];
+    // ---- main loop: a phase's LDS-DMA pieces are spread AMONG its MFMAs (igroup pipeline: sched_group_barrier) instead
+    // of in front of them: an LDS-DMA instruction costs ~60 cycles of issue between bare MFMAs against 100-185 at the head of
+    // a phase beside the fragment reads (MI355X_MICROARCH.md), and in front of the MFMAs that time is on the wave's chain.
+    // The loop body has no branch (one scheduling region per phase): the last macro-step is peeled.
+    if (tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
+    auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int nky_, int ncc_, int wcur_, int wnext_) {
+        constexpr int kx = decltype(KX)::value;
+        constexpr bool last = decltype(LAST)::value;
+        const char* wb = ws + kx * W_TAP;
+        bf16x8 xf[2][TM], wf[2][TN];
 #pragma unroll
-            for (int t = 0; t < TM; ++t) xf[0][t] = *(const bf16x8*)(xb + xrd[kx][0] + t * (32 * ROWB));
+        for (int t = 0; t < TM; ++t) xf[0][t] = *(const bf16x8*)(xb + xrd[kx][0] + t * (32 * ROWB));
 #pragma unroll
-            for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
-            constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : NWP);
+        for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
+        constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : NWP);
 #pragma unroll
-            for (int t = 0; t < TM; ++t) xf[1][t] = *(const bf16x8*)(xb + xrd[kx][1] + t * (32 * ROWB));
+        for (int t = 0; t < TM; ++t) xf[1][t] = *(const bf16x8*)(xb + xrd[kx][1] + t * (32 * ROWB));
 #pragma unroll
-            for (int t = 0; t < TN; ++t) wf[1][t] = *(const bf16x8*)(wb + wrd[1] + t * (32 * ROWB));
-            // piece i of this phase's LDS-DMA list, in the order the vmcnt counts assume: W pieces first, then X(st + 1)
-            auto piece = [&](int i) {
-                if (kx == 0) {
-                    if (i < NWP) {
-                        const int so = __builtin_amdgcn_readfirstlane((wcur_ + 2 * tapb) * wmul);
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + 2 * W_TAP + (wave + NW * i) * 1024), 16, woff[i], so, 0, 0);
-                    } else {
-                        const int q = i - NWP;
-                        const int xs = __builtin_amdgcn_readfirstlane((nky_ * x_sh + ncc_ * 32) * 2);
-                        int ins = wave + NW * q;
-                        ins = ins < XINS ? ins : XINS - 1;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(smem + ((st_ + 1) & 1) * X_BUF + ins * 1024), 16, xoff[q], xs, 0, 0);
-                    }
+        for (int t = 0; t < TN; ++t) wf[1][t] = *(const bf16x8*)(wb + wrd[1] + t * (32 * ROWB));
+        // piece i of this phase's LDS-DMA list, in the order the vmcnt counts assume: W pieces first, then X(st + 1)
+        auto piece = [&](int i) {
+            if (kx == 0) {
+                if (i < NWP) {
+                    const int so = __builtin_amdgcn_readfirstlane((wcur_ + 2 * tapb) * wmul);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + 2 * W_TAP + (wave + NW * i) * 1024), 16, woff[i], so, 0, 0);
                 } else {
-                    const int so = __builtin_amdgcn_readfirstlane((wnext_ + (kx - 1) * tapb) * wmul);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + (kx - 1) * W_TAP + (wave + NW * i) * 1024), 16, woff[i], so, 0, 0);
-                }
-            };
-            // all 12 fragment reads first (an LDS-DMA write may not pass an LDS read in program order), then MFMA pairs with one
-            // piece behind each until the pieces are out
-            int ip = 0;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm) {
-                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
-                                                                             __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
-                        if ((ndma > 8 || TM == 1 || (tm & 1)) && ip < ndma) { piece(ip); ++ip; }     // behind every second MFMA; every one if > 8 pieces (or 8 MFMAs)
-                    }
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM + TN), 0);
-            if constexpr (ndma > 8) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+                    const int q = i - NWP;
+                    const int xs = __builtin_amdgcn_readfirstlane((nky_ * x_sh + ncc_ * 32) * 2);
+                    int ins = wave + NW * q;
+                    ins = ins < XINS ? ins : XINS - 1;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(smem + ((st_ + 1) & 1) * X_BUF + ins * 1024), 16, xoff[q], xs, 0, 0);
                 }
             } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, TM == 1 ? 1 : 2, 0);
-                    if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-                }
+                const int so = __builtin_amdgcn_readfirstlane((wnext_ + (kx - 1) * tapb) * wmul);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + (kx - 1) * W_TAP + (wave + NW * i) * 1024), 16, woff[i], so, 0, 0);
             }
-            __builtin_amdgcn_sched_barrier(0);
         };
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        using BF = std::false_type; using BT = std::true_type;
-        for (int st = 0; st < nsteps - 1; ++st) {
-            int nky = ky, ncc = cc + 1;
-            if (ncc == cchunks) { ncc = 0; ++nky; }
-            const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
-            const char* xb = smem + (st & 1) * X_BUF;
-            phase(I0{}, BF{}, xb, st, nky, ncc, wcur, wnext);
-            kw_wait<NX + NWP>();
-            __builtin_amdgcn_s_barrier();
-            phase(I1{}, BF{}, xb, st, nky, ncc, wcur, wnext);
-            kw_wait<NX + NWP>();
-            __builtin_amdgcn_s_barrier();
-            phase(I2{}, BF{}, xb, st, nky, ncc, wcur, wnext);
-            kw_wait<NWP>();
-            __builtin_amdgcn_s_barrier();
-            ky = nky; cc = ncc;
+        // all 12 fragment reads first (an LDS-DMA write may not pass an LDS read in program order), then MFMA pairs with one
+        // piece behind each until the pieces are out
+        int ip = 0;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm) {
+                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
+                                                                         __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
+                    if ((TM == 1 || (tm & 1)) && ip < ndma) { piece(ip); ++ip; }     // behind every second MFMA (every one of a half tile's 8)
+                }
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM + TN), 0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, TM == 1 ? 1 : 2, 0);
+            if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
         }
-        {
-            const int st = nsteps - 1;
-            const int wcur = (ky * 3 * CK + cc * 32) * 2;
-            const char* xb = smem + (st & 1) * X_BUF;
-            phase(I0{}, BT{}, xb, st, 0, 0, wcur, 0);
-            kw_wait<NWP>();
-            __builtin_amdgcn_s_barrier();
-            phase(I1{}, BT{}, xb, st, 0, 0, wcur, 0);
-            kw_wait<0>();
-            __builtin_amdgcn_s_barrier();
-            phase(I2{}, BT{}, xb, st, 0, 0, wcur, 0);
-        }
-    } else {
-    for (int st = 0; st < nsteps; ++st) {
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    using BF = std::false_type; using BT = std::true_type;
+    for (int st = 0; st < nsteps - 1; ++st) {
         int nky = ky, ncc = cc + 1;
         if (ncc == cchunks) { ncc = 0; ++nky; }
         const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
-        const bool last = st == nsteps - 1;
         const char* xb = smem + (st & 1) * X_BUF;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const char* wb = ws + kx * W_TAP;
-            bf16x8 xf[2][TM], wf[2][TN];
-#pragma unroll
-            for (int t = 0; t < TM; ++t) xf[0][t] = *(const bf16x8*)(xb + xrd[kx][0] + t * (32 * ROWB));
-#pragma unroll
-            for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
-            // ---- this phase's loads (behind the first fragment reads)
-            if (kx == 0) {
-                load_w(2, wcur + 2 * tapb);
-                if (!last) load_x((st + 1) & 1, nky, ncc);
-                if (st == 0 && tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
-            } else if (!last) {
-                load_w(kx - 1, wnext + (kx - 1) * tapb);
-            }
-#pragma unroll
-            for (int t = 0; t < TM; ++t) xf[1][t] = *(const bf16x8*)(xb + xrd[kx][1] + t * (32 * ROWB));
-#pragma unroll
-            for (int t = 0; t < TN; ++t) wf[1][t] = *(const bf16x8*)(wb + wrd[1] + t * (32 * ROWB));
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                    for (int tm = 0; tm < TM; ++tm)
-                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
-                                                                             __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
-            // ---- retire what the next phase reads, then open it
-            if (kx == 2) {
-                if (last) break;
-                kw_wait<NWP>();
-            } else if (!last) {
-                kw_wait<NX + NWP>();
-            } else if (kx == 0) {
-                kw_wait<NWP>();
-            } else {
-                kw_wait<0>();
-            }
-            __builtin_amdgcn_s_barrier();
-        }
+        phase(I0{}, BF{}, xb, st, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NX + NWP>();
+        __builtin_amdgcn_s_barrier();
+        phase(I1{}, BF{}, xb, st, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NX + NWP>();
+        __builtin_amdgcn_s_barrier();
+        phase(I2{}, BF{}, xb, st, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NWP>();
+        __builtin_amdgcn_s_barrier();
         ky = nky; cc = ncc;
     }
+    {
+        const int st = nsteps - 1;
+        const int wcur = (ky * 3 * CK + cc * 32) * 2;
+        const char* xb = smem + (st & 1) * X_BUF;
+        phase(I0{}, BT{}, xb, st, 0, 0, wcur, 0);
+        wait_vm_lgkm<NWP>();
+        __builtin_amdgcn_s_barrier();
+        phase(I1{}, BT{}, xb, st, 0, 0, wcur, 0);
+        wait_vm_lgkm<0>();
+        __builtin_amdgcn_s_barrier();
+        phase(I2{}, BT{}, xb, st, 0, 0, wcur, 0);
     }
 
     // ---- epilogue: accumulator layout (a lane = one pixel, 8 x 8 consecutive channels) <-> line layout through a wave-private
@@ -506,9 +432,10 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
 // block -> (problem, row tile, column tile).  XCD x owns a contiguous chunk of the global row tiles [0, MT_full); MIX: the blocks
 // from half_bid0 on are the HALF tiles (128 rows) of the row tiles [MT_full, MT) -- the launch's last, partial round of workgroups.
 // They carry the highest block ids, so they are dispatched last: the long tiles first, the short ones fill the end.
-template <bool POOL, bool SCHED = false, int TM_ = 2, int TN_ = 4, bool MIX = false, bool RG = false>
+template <bool POOL, bool MIX, bool RG>
 __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int TM_ = 2, TN_ = 4;
     constexpr int BM = KwShape<TM_, TN_>::BM, BN = KwShape<TM_, TN_>::BN;
     const int bid = blockIdx.x;
     const int gNT = g.NT, gnprob = g.nprob;
@@ -529,31 +456,27 @@ __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
         mt = xcd * g.mt_chunk + j / gNT;
         if (mt >= g.MT_full) return;
     }
-    int pid = 0, base = 0;
-    if (gnprob > 1 && mt >= e0) { pid = 1; base = e0; }
-    if (gnprob > 2 && mt >= e1) { pid = 2; base = e1; }
-    if (gnprob > 3 && mt >= e2) { pid = 3; base = e2; }
-    mt -= base;
+    const int pid = group_problem(mt, gnprob, e0, e1, e2);
     const int n0 = nt * BN;
     if constexpr (MIX) {
         if (half) {
             const int m0 = mt * BM + sub * (BM / 2);
             if (m0 >= g.p[pid].M) return;                  // the second half of a problem's last, partial row tile
-            kxrw_tile<POOL, SCHED, 1, TN_, RG>(g, pid, m0, n0);
+            kxrw_tile<POOL, 1, TN_, RG>(g, pid, m0, n0);
             return;
         }
     }
-    kxrw_tile<POOL, SCHED, TM_, TN_, RG>(g, pid, mt * BM, n0);
+    kxrw_tile<POOL, TM_, TN_, RG>(g, pid, mt * BM, n0);
 #endif
 }
 
-// The tile schedule of a launch of MT x NT tiles (`mix_ok`: the wide form's half-tile schedule may be used): the XCD-chunked
-// part [0, MT_full) and the half tiles that follow it.  The launch and agp_conv2d_tile_plan both take their numbers from here.
+// The tile schedule of a launch of MT x NT tiles: the XCD-chunked part [0, MT_full) and the half tiles that follow it.  The launch
+// and agp_conv2d_tile_plan both take their numbers from here.
 struct KxrwPlan {
     int MT_full, mt_chunk, half_bid0, half_tiles, blocks;
     bool mix;
 };
-inline KxrwPlan kxrw_plan(int MT, int NT, bool mix_ok) {
+inline KxrwPlan kxrw_plan(int MT, int NT) {
     KxrwPlan k = {};
     k.MT_full = MT;
     // ---- the last round of workgroups as half tiles.  512 workgroups are resident (two per CU); a launch of T tiles runs
@@ -562,13 +485,11 @@ inline KxrwPlan kxrw_plan(int MT, int NT, bool mix_ok) {
     // as long (stage 2: 602 tiles = 512 + 90 -> 180 half tiles, 89.7 -> 80.1 us; a launch of <= 128 tiles -- the C1 / C2 shapes --
     // covers twice the CUs).  Measured and NOT done: a larger tail (layer 3: 714 = 512 + 202 -> 404 half tiles, two per CU) loses
     // 3-4 us per launch -- a lone 256-row workgroup already runs 1.65 x as fast as one of a pair, two half tiles per CU do not.
-    if (mix_ok) {
-        const int slots = 512, T = MT * NT;
-        const int tail = T - (T - 1) / slots * slots;         // 1 .. slots
-        if (tail <= slots / 4 && tail % NT == 0) {
-            k.MT_full = MT - tail / NT;
-            k.mix = true;
-        }
+    const int slots = 512, T = MT * NT;
+    const int tail = T - (T - 1) / slots * slots;         // 1 .. slots
+    if (tail <= slots / 4 && tail % NT == 0) {
+        k.MT_full = MT - tail / NT;
+        k.mix = true;
     }
     const XcdGrid xg = xcd_grid(k.MT_full, NT);
     k.mt_chunk = xg.mt_chunk;
@@ -578,33 +499,26 @@ inline KxrwPlan kxrw_plan(int MT, int NT, bool mix_ok) {
     return k;
 }
 
-template <bool POOL, bool SCHED, int TM_ = 2, int TN_ = 4, bool MIX = false, bool RG = false>
+template <bool POOL, bool MIX, bool RG>
 int launch_kxrw(KxrwGroup& g, const KxrwPlan& k, hipStream_t s) {
-    constexpr int lds = KwShape<TM_, TN_>::LDS;
+    constexpr int lds = KwShape<2, 4>::LDS;
     static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-    static_assert(!MIX || (TM_ == 2 && KwShape<1, TN_>::LDS + 3072 <= lds), "half tiles: their stage + the pooling scratch fit the full tile's LDS");
+    static_assert(KwShape<1, 4>::LDS + 3072 <= lds, "half tiles: their stage + the pooling scratch fit the full tile's LDS");
     static std::atomic<uint64_t> attr_done{0};
-    if (!agp_lds_attr((const void*)igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>, lds, attr_done)) return AGP_E_LAUNCH;
-    AGP_LAUNCH((igemm_kxrw_kernel<POOL, SCHED, TM_, TN_, MIX, RG>), dim3(MIX ? k.blocks : k.half_bid0), dim3(256), lds, s, g);
+    if (!agp_lds_attr((const void*)igemm_kxrw_kernel<POOL, MIX, RG>, lds, attr_done)) return AGP_E_LAUNCH;
+    AGP_LAUNCH((igemm_kxrw_kernel<POOL, MIX, RG>), dim3(MIX ? k.blocks : k.half_bid0), dim3(256), lds, s, g);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
 
 }  // namespace agp_igemm
 
-// `ps[i]` arrive with the padded-width raster geometry of agp_internal_conv_kxr_geometry; all share N, CK, prec F16.
-// N % 128 == 0: the wide form (256 x 128 tiles).  (The tall form, 512 x 64 tiles for N == 64 -- a round-3 experiment that measured
-// the same alone and 4 % slower in the grouped launch -- exists in the development build only: KXR_TALL.)
-static constexpr bool KXRW_MIX = true;     // false: every tile 256 rows (rounds 3-5)
+// `ps[i]` arrive with the padded-width raster geometry of agp_internal_conv_kxr_geometry; all share N, CK, prec F16 and
+// N % 128 == 0 (256 x 128 tiles).
 int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
-#if defined(AGP_TUNING)
-    const bool tall = ps[0].N == 64;
-#else
-    constexpr bool tall = false;
-#endif
-    if (n < 1 || n > KXRW_MAXP || (!tall && ps[0].N % 128)) return AGP_E_BADARG;
-    const int bm = tall ? KwShape<4, 2>::BM : KwShape<2, 4>::BM, bn = tall ? 64 : 128;
+    if (n < 1 || n > KXRW_MAXP || ps[0].N % 128) return AGP_E_BADARG;
+    constexpr int bm = KwShape<2, 4>::BM, bn = KwShape<2, 4>::BN;
     KxrwGroup g = {};
     g.nprob = n;
     int mt = 0;
@@ -618,7 +532,7 @@ int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
     }
     g.MT = mt;
     g.NT = ps[0].N / bn;
-    const KxrwPlan k = kxrw_plan(g.MT, g.NT, !tall && KXRW_MIX);
+    const KxrwPlan k = kxrw_plan(g.MT, g.NT);
     if (plan) {
         *plan = TilePlan{AGP_CONV_KERNEL_KXRW, bm, bn, g.MT, g.NT, k.MT_full, k.half_tiles, k.blocks};
         return AGP_OK;
@@ -627,18 +541,10 @@ int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
     g.MT_full = k.MT_full;
     g.mt_chunk = k.mt_chunk;
     g.half_bid0 = k.half_bid0;
-#if defined(AGP_TUNING)
-    const int sched = AGP_TUNE("KXRW_SCHED", 1);    // 0: LDS-DMA pieces at the head of a phase (the round-3 order) instead of among the MFMAs
-    if (tall) {
-        if (pool) return AGP_E_BADARG;
-        return sched ? launch_kxrw<false, true, 4, 2>(g, k, s) : launch_kxrw<false, false, 4, 2>(g, k, s);
-    }
-    if (!sched) return pool ? launch_kxrw<true, false>(g, k, s) : launch_kxrw<false, false>(g, k, s);
-#endif
     g.rflag = agp_range_flag_get();
     return agp_rg_dispatch(g.rflag, [&](auto rg) {
         constexpr bool RG = decltype(rg)::value;
-        if (mix) return pool ? launch_kxrw<true, true, 2, 4, true, RG>(g, k, s) : launch_kxrw<false, true, 2, 4, true, RG>(g, k, s);
-        return pool ? launch_kxrw<true, true, 2, 4, false, RG>(g, k, s) : launch_kxrw<false, true, 2, 4, false, RG>(g, k, s);
+        if (mix) return pool ? launch_kxrw<true, true, RG>(g, k, s) : launch_kxrw<false, true, RG>(g, k, s);
+        return pool ? launch_kxrw<true, false, RG>(g, k, s) : launch_kxrw<false, false, RG>(g, k, s);
     });
 }

@@ -100,6 +100,36 @@ __device__ __forceinline__ void mfma16(f32x4& acc, const bf16x8& wh, const bf16x
     }
 }
 
+// ---- shared by the 3x3 stride-1 family and the stage entry (igemm_kxr, igemm_kxr2, igemm_kxrw, igemm_s2)
+// XOR-swizzle of a staged 64-byte row's four 16-byte chunks: conflict-free ds_read_b128 of 32x32x16 fragments
+__device__ __forceinline__ int swz32(int row) { return (row >> 2) & 3; }
+
+// retire all but the N youngest vector-memory operations of this wave, and all of its LDS reads
+template <int N> __device__ __forceinline__ void wait_vm_lgkm() {
+    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+    else static_assert(N < 0, "add the count");
+}
+
+// Grouped launches (Kxr2Group, KxrwGroup): global row tile `mt` -> problem index; `mt` becomes the row tile inside that
+// problem.  nprob and e0..e2 = the group's mt_end[0..2] are passed by value: the kernel reads them unconditionally, first
+// thing (the compiler then fetches the header with one wide scalar load instead of a chain of dependent single-dword round
+// trips).
+__device__ __forceinline__ int group_problem(int& mt, int nprob, int e0, int e1, int e2) {
+    int pid = 0, base = 0;
+    if (nprob > 1 && mt >= e0) { pid = 1; base = e0; }
+    if (nprob > 2 && mt >= e1) { pid = 2; base = e1; }
+    if (nprob > 3 && mt >= e2) { pid = 3; base = e2; }
+    mt -= base;
+    return pid;
+}
+
 constexpr int EPI_ROWB = 64 * 4 + 16;  // 64 fp32 channels + 16 B pad per pixel row
 
 // What a conv launcher decided on the host, in the order of agp_conv2d_tile_plan's plan[8].  The launchers take an optional

@@ -24,6 +24,9 @@
 //   opens (st,2): W(st,2);          younger: X(st+1) W(st+1,0)          -> vmcnt(NX+1)
 //   opens (st+1,0): W(st+1,0) X(st+1); younger: W(st+1,1) D(st+1)       -> vmcnt(2)
 //   last macro-step L: (L,0) issues W(L,2) only -> opens (L,1): vmcnt(1); (L,1) issues nothing -> opens (L,2): vmcnt(0).
+// A phase's LDS-DMA pieces are issued among its MFMAs instead of in front of them, all of the phase's fragment reads first, the
+// last macro-step peeled (see igemm_kxrw.hip).  (The loop with the pieces at the head of a phase was retired: profiles/README.md,
+// round 3, "What was measured this round"; the code is in the history before the commit that removed it.)
 
 #include <type_traits>
 
@@ -31,24 +34,12 @@
 
 namespace agp_igemm {
 
-__device__ __forceinline__ int s2_swz(int row) { return (row >> 2) & 3; }   // XOR-swizzle of a row's four 16-byte chunks
-
 constexpr int S2_MAXP = 2;
 struct S2Group {
     IgemmParams p[S2_MAXP];
     int mt_end[S2_MAXP];
     int nprob, MT, NT, mt_chunk;
 };
-
-template <int N> __device__ __forceinline__ void s2_wait() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");
-    else static_assert(N < 0, "add the count");
-}
 
 constexpr int S2_BM = 128, S2_ROWB = 64;
 constexpr int S2_BMX = S2_BM + 16;                      // rows of a staged block (offsets 0 and 1 are read)
@@ -60,10 +51,8 @@ template <int TN> constexpr int s2_lds() {              // X double buffer, W ri
 
 // TN = column tiles of 32 channels per wave: 2 = 128 x 64 tiles (54 KB LDS: three workgroups per CU, 4 MFMAs per phase and wave);
 // 4 = 128 x 128 tiles (71 KB: two per CU, 8 MFMAs per phase, the X blocks staged once per 128 channels).
-// SCH (the default; AGP_S2_SCHED=0 turns it off): a phase's LDS-DMA pieces are issued among its MFMAs instead of in front of them,
-// all of the phase's fragment reads first, the last macro-step peeled (see igemm_kxrw.hip).
 // rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
-template <int TN, bool SCH = false, class... RF>
+template <int TN, class... RF>
 __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool RG = sizeof...(RF) != 0;
@@ -117,14 +106,14 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
         const uint32_t xq = rem - y * d_wo.d;
         // element offset of padded input pixel (2 y + ky, 2 x' - 2) for ky = 0 (x_sh = two input rows, x_sw = two input pixels)
         const int el = (int)img * x_sn + (int)y * x_sh_ + (int)xq * x_sw + x_base;
-        xoff[q] = el * 2 + blk * cpix + ((lpos ^ s2_swz(row)) << 4);
+        xoff[q] = el * 2 + blk * cpix + ((lpos ^ swz32(row)) << 4);
     }
     int woff_c[NWP], woff_d[NWP];                      // W piece i of a wave: rows (wave + 4 i) * 16 .. of the BN-row slot
 #pragma unroll
     for (int i = 0; i < NWP; ++i) {
         const int row = (wave + NW * i) * 16 + lrow;
         const int n = (n0 + row) < pN ? (n0 + row) : pN - 1;
-        const int wsw = (lpos ^ s2_swz(row)) << 4;
+        const int wsw = (lpos ^ swz32(row)) << 4;
         woff_c[i] = (p.w_cm ? n * 64 : n * pKtot * 2) + wsw;     // 3x3 weights [N][3][3][CK], or chunk-major [9 CK / 32][N][32]
         woff_d[i] = (p.w2_cm ? n * 64 : n * p.CK * 2) + wsw;     // 1x1 weights [N][CK], or chunk-major [CK / 32][N][32]
     }
@@ -164,13 +153,6 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
         for (int i = 0; i < NWP; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + slot * S2_WTAP + (wave + NW * i) * 1024), 16, woff_c[i], so, 0, 0);
     };
-    auto load_d = [&](int cc_) {                        // the 1x1 weights' 32-channel chunk -> slot 3
-        const int so = __builtin_amdgcn_readfirstlane(cc_ * 64 * dmul);
-#pragma unroll
-        for (int i = 0; i < NWP; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, LDS_PTR(ws + 3 * S2_WTAP + (wave + NW * i) * 1024), 16,
-                                                     has_ds ? woff_d[i] : woff_c[i], has_ds ? so : 0, 0, 0);
-    };
     load_x(0, 0, 0);
     load_w(0, 0);
     load_w(1, tapb);
@@ -183,14 +165,14 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int r = wave * 32 + l31 + (kx == 2 ? 1 : 0);
-            xrd[kx][ks] = (kx == 1 ? S2_XBLK : 0) + r * ROWB + (((2 * ks + lh) ^ s2_swz(r)) << 4);
+            xrd[kx][ks] = (kx == 1 ? S2_XBLK : 0) + r * ROWB + (((2 * ks + lh) ^ swz32(r)) << 4);
         }
     int wrd[2];
     {
         // W rows permuted (bits 2 and 3 swapped): accumulator registers 8h .. 8h+7 of a lane are 8 consecutive channels of its pixel
         const int wrow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ s2_swz(wrow)) << 4);
+        for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ swz32(wrow)) << 4);
     }
 
     f32x16 acc[TN], acc2[TN];
@@ -220,171 +202,106 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
     }
 
     int ky = 0, cc = 0;
-    s2_wait<NWP>();
+    wait_vm_lgkm<NWP>();
     __builtin_amdgcn_s_barrier();
-    if constexpr (SCH) {
-        if (tid < BN) { tab[tid] = tab_v[0]; tab[BN + tid] = tab_v[1]; tab[2 * BN + tid] = tab_v[2]; tab[3 * BN + tid] = tab_v[3]; }
-        auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int ky_, int nky_, int ncc_, int wcur_, int wnext_) {
-            constexpr int kx = decltype(KX)::value;
-            constexpr bool last = decltype(LAST)::value;
-            const char* wb = ws + kx * S2_WTAP;
-            bf16x8 xf[2], wf[2][TN];
+    if (tid < BN) { tab[tid] = tab_v[0]; tab[BN + tid] = tab_v[1]; tab[2 * BN + tid] = tab_v[2]; tab[3 * BN + tid] = tab_v[3]; }
+    auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int ky_, int nky_, int ncc_, int wcur_, int wnext_) {
+        constexpr int kx = decltype(KX)::value;
+        constexpr bool last = decltype(LAST)::value;
+        const char* wb = ws + kx * S2_WTAP;
+        bf16x8 xf[2], wf[2][TN];
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                xf[ks] = *(const bf16x8*)(xb + xrd[kx][ks]);
+        for (int ks = 0; ks < 2; ++ks) {
+            xf[ks] = *(const bf16x8*)(xb + xrd[kx][ks]);
 #pragma unroll
-                for (int t = 0; t < TN; ++t) wf[ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
-            }
-            // the phase's LDS-DMA list in the order the vmcnt counts assume
-            constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : (kx == 2 ? 2 * NWP : NWP));
-            auto piece = [&](int i) {
-                if (kx == 0) {
-                    if (i < NWP) {
-                        const int so = __builtin_amdgcn_readfirstlane((wcur_ + 2 * tapb) * wmul);
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + 2 * S2_WTAP + (wave + NW * i) * 1024), 16, woff_c[i], so, 0, 0);
-                    } else {
-                        const int q = i - NWP;
-                        const int xs = __builtin_amdgcn_readfirstlane((nky_ * in_row + ncc_ * 32) * 2);
-                        int ins = wave + NW * q;
-                        ins = ins < XINS ? ins : XINS - 1;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(smem + ((st_ + 1) & 1) * S2_XBUF + ins * 1024), 16, xoff[q], xs, 0, 0);
-                    }
-                } else if (i < NWP) {
-                    const int so = __builtin_amdgcn_readfirstlane((wnext_ + (kx - 1) * tapb) * wmul);
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + (kx - 1) * S2_WTAP + (wave + NW * i) * 1024), 16, woff_c[i], so, 0, 0);
+            for (int t = 0; t < TN; ++t) wf[ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
+        }
+        // the phase's LDS-DMA list in the order the vmcnt counts assume
+        constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : (kx == 2 ? 2 * NWP : NWP));
+        auto piece = [&](int i) {
+            if (kx == 0) {
+                if (i < NWP) {
+                    const int so = __builtin_amdgcn_readfirstlane((wcur_ + 2 * tapb) * wmul);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + 2 * S2_WTAP + (wave + NW * i) * 1024), 16, woff_c[i], so, 0, 0);
                 } else {
-                    const int so = __builtin_amdgcn_readfirstlane((nky_ == 1 ? ncc_ : 0) * 64 * dmul);
-                    const int k = i - NWP;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, LDS_PTR(ws + 3 * S2_WTAP + (wave + NW * k) * 1024), 16,
-                                                             has_ds ? woff_d[k] : woff_c[k], has_ds ? so : 0, 0, 0);
+                    const int q = i - NWP;
+                    const int xs = __builtin_amdgcn_readfirstlane((nky_ * in_row + ncc_ * 32) * 2);
+                    int ins = wave + NW * q;
+                    ins = ins < XINS ? ins : XINS - 1;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(smem + ((st_ + 1) & 1) * S2_XBUF + ins * 1024), 16, xoff[q], xs, 0, 0);
                 }
-            };
-            int ip = 0;
+            } else if (i < NWP) {
+                const int so = __builtin_amdgcn_readfirstlane((wnext_ + (kx - 1) * tapb) * wmul);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + (kx - 1) * S2_WTAP + (wave + NW * i) * 1024), 16, woff_c[i], so, 0, 0);
+            } else {
+                const int so = __builtin_amdgcn_readfirstlane((nky_ == 1 ? ncc_ : 0) * 64 * dmul);
+                const int k = i - NWP;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, LDS_PTR(ws + 3 * S2_WTAP + (wave + NW * k) * 1024), 16,
+                                                         has_ds ? woff_d[k] : woff_c[k], has_ds ? so : 0, 0, 0);
+            }
+        };
+        int ip = 0;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {
+                acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]), __builtin_bit_cast(f16x8, xf[ks]),
+                                                                 acc[tn], 0, 0, 0);
+                if (ip < ndma) { piece(ip); ++ip; }
+            }
+#pragma unroll
+        for (int i = 2 * TN; i < ndma; ++i) piece(i);       // (64-channel tiles: more pieces than MFMAs in the kx = 0 phase)
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (1 + TN), 0);
+#pragma unroll
+        for (int i = 0; i < 2 * TN; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (kx == 1 && ky_ == 1 && has_ds) {
+            // the downsample: centre tap of the staged E block on the 1x1 weights (slot 3)
+            const char* db = ws + 3 * S2_WTAP;
+            bf16x8 df[2][TN];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                for (int tn = 0; tn < TN; ++tn) {
-                    acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]), __builtin_bit_cast(f16x8, xf[ks]),
-                                                                     acc[tn], 0, 0, 0);
-                    if (ip < ndma) { piece(ip); ++ip; }
-                }
-#pragma unroll
-            for (int i = 2 * TN; i < ndma; ++i) piece(i);       // (64-channel tiles: more pieces than MFMAs in the kx = 0 phase)
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (1 + TN), 0);
-#pragma unroll
-            for (int i = 0; i < 2 * TN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (kx == 1 && ky_ == 1 && has_ds) {
-                // the downsample: centre tap of the staged E block on the 1x1 weights (slot 3)
-                const char* db = ws + 3 * S2_WTAP;
-                bf16x8 df[2][TN];
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) df[ks][t] = *(const bf16x8*)(db + wrd[ks] + t * (32 * ROWB));
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-                        acc2[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, df[ks][tn]),
-                                                                          __builtin_bit_cast(f16x8, xf[ks]), acc2[tn], 0, 0, 0);
-            }
-        };
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        for (int st = 0; st < nsteps - 1; ++st) {
-            int nky = ky, ncc = cc + 1;
-            if (ncc == cchunks) { ncc = 0; ++nky; }
-            const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
-            const char* xb = smem + (st & 1) * S2_XBUF;
-            phase(I0{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
-            s2_wait<NX + NWP>();
-            __builtin_amdgcn_s_barrier();
-            phase(I1{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
-            s2_wait<NX + NWP>();
-            __builtin_amdgcn_s_barrier();
-            phase(I2{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
-            s2_wait<2 * NWP>();
-            __builtin_amdgcn_s_barrier();
-            ky = nky; cc = ncc;
-        }
-        {
-            const int st = nsteps - 1;
-            const int wcur = (ky * 3 * CK + cc * 32) * 2;
-            const char* xb = smem + (st & 1) * S2_XBUF;
-            phase(I0{}, std::true_type{}, xb, st, ky, 0, 0, wcur, 0);
-            s2_wait<NWP>();
-            __builtin_amdgcn_s_barrier();
-            phase(I1{}, std::true_type{}, xb, st, ky, 0, 0, wcur, 0);
-            s2_wait<0>();
-            __builtin_amdgcn_s_barrier();
-            phase(I2{}, std::true_type{}, xb, st, ky, 0, 0, wcur, 0);
-        }
-    } else
-    for (int st = 0; st < nsteps; ++st) {
-        int nky = ky, ncc = cc + 1;
-        if (ncc == cchunks) { ncc = 0; ++nky; }
-        const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
-        const bool last = st == nsteps - 1;
-        const char* xb = smem + (st & 1) * S2_XBUF;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const char* wb = ws + kx * S2_WTAP;
-            bf16x8 xf[2], wf[2][TN];
-            xf[0] = *(const bf16x8*)(xb + xrd[kx][0]);
-#pragma unroll
-            for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
-            // ---- this phase's loads (behind the first fragment reads)
-            if (kx == 0) {
-                load_w(2, wcur + 2 * tapb);
-                if (!last) load_x((st + 1) & 1, nky, ncc);
-                if (st == 0 && tid < BN) {
-                    tab[tid] = tab_v[0]; tab[BN + tid] = tab_v[1]; tab[2 * BN + tid] = tab_v[2]; tab[3 * BN + tid] = tab_v[3];
-                }
-            } else if (!last) {
-                load_w(kx - 1, wnext + (kx - 1) * tapb);
-                if (kx == 2) load_d(nky == 1 ? ncc : 0);
-            }
-            xf[1] = *(const bf16x8*)(xb + xrd[kx][1]);
-#pragma unroll
-            for (int t = 0; t < TN; ++t) wf[1][t] = *(const bf16x8*)(wb + wrd[1] + t * (32 * ROWB));
+                for (int t = 0; t < TN; ++t) df[ks][t] = *(const bf16x8*)(db + wrd[ks] + t * (32 * ROWB));
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn)
-                    acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]), __builtin_bit_cast(f16x8, xf[ks]),
-                                                                     acc[tn], 0, 0, 0);
-            if (kx == 1 && ky == 1 && has_ds) {
-                // the downsample: centre tap of the staged E block on the 1x1 weights (slot 3)
-                const char* db = ws + 3 * S2_WTAP;
-                bf16x8 df[2][TN];
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) df[ks][t] = *(const bf16x8*)(db + wrd[ks] + t * (32 * ROWB));
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int tn = 0; tn < TN; ++tn)
-                        acc2[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, df[ks][tn]),
-                                                                          __builtin_bit_cast(f16x8, xf[ks]), acc2[tn], 0, 0, 0);
-            }
-            // ---- retire what the next phase reads, then open it
-            if (kx == 2) {
-                if (last) break;
-                s2_wait<2 * NWP>();
-            } else if (!last) {
-                s2_wait<NX + NWP>();
-            } else if (kx == 0) {
-                s2_wait<NWP>();
-            } else {
-                s2_wait<0>();
-            }
-            __builtin_amdgcn_s_barrier();
+                    acc2[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, df[ks][tn]),
+                                                                      __builtin_bit_cast(f16x8, xf[ks]), acc2[tn], 0, 0, 0);
         }
+    };
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    for (int st = 0; st < nsteps - 1; ++st) {
+        int nky = ky, ncc = cc + 1;
+        if (ncc == cchunks) { ncc = 0; ++nky; }
+        const int wcur = (ky * 3 * CK + cc * 32) * 2, wnext = (nky * 3 * CK + ncc * 32) * 2;
+        const char* xb = smem + (st & 1) * S2_XBUF;
+        phase(I0{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NX + NWP>();
+        __builtin_amdgcn_s_barrier();
+        phase(I1{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<NX + NWP>();
+        __builtin_amdgcn_s_barrier();
+        phase(I2{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
+        wait_vm_lgkm<2 * NWP>();
+        __builtin_amdgcn_s_barrier();
         ky = nky; cc = ncc;
+    }
+    {
+        const int st = nsteps - 1;
+        const int wcur = (ky * 3 * CK + cc * 32) * 2;
+        const char* xb = smem + (st & 1) * S2_XBUF;
+        phase(I0{}, std::true_type{}, xb, st, ky, 0, 0, wcur, 0);
+        wait_vm_lgkm<NWP>();
+        __builtin_amdgcn_s_barrier();
+        phase(I1{}, std::true_type{}, xb, st, ky, 0, 0, wcur, 0);
+        wait_vm_lgkm<0>();
+        __builtin_amdgcn_s_barrier();
+        phase(I2{}, std::true_type{}, xb, st, ky, 0, 0, wcur, 0);
     }
 
     // ---- epilogues: accumulator layout (a lane = one pixel, 4 x 8 consecutive channels) -> wave-private LDS strip -> line layout
@@ -458,35 +375,23 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
     g.MT = mt;
     g.mt_chunk = (g.MT + 7) / 8;
     const int wide = AGP_TUNE("S2_WIDE", 1);            // development build, 0: 64-channel tiles for every width
-    const int sch = AGP_TUNE("S2_SCHED", 1);            // development build, 0: LDS-DMA pieces at the head of a phase
     auto launch = [&](auto kern, int lds, std::atomic<uint64_t>& attr, auto... rf) -> int {
         if (!agp_lds_attr((const void*)kern, lds, attr)) return AGP_E_LAUNCH;
         AGP_LAUNCH(kern, dim3(g.mt_chunk * 8 * g.NT), dim3(256), lds, s, g, rf...);
         return AGP_OK;
     };
-    static std::atomic<uint64_t> a4s{0}, a2s{0};
-    int rc;
-#if defined(AGP_TUNING)
-    static std::atomic<uint64_t> a4{0}, a2{0};
-    if (!sch && !plan) {
-        if (wide && ps[0].N % 128 == 0) { g.NT = ps[0].N / 128; rc = launch(igemm_s2_kernel<4, false>, s2_lds<4>(), a4); }
-        else { g.NT = (ps[0].N + 63) / 64; rc = launch(igemm_s2_kernel<2, false>, s2_lds<2>(), a2); }
-    } else
-#endif
-    {
-        static std::atomic<uint64_t> a4g{0}, a2g{0};
-        uint32_t* const rflag = agp_range_flag_get();
-        const bool w4 = wide && ps[0].N % 128 == 0;
-        g.NT = w4 ? ps[0].N / 128 : (ps[0].N + 63) / 64;
-        if (plan) {
-            *plan = TilePlan{AGP_CONV_KERNEL_S2, S2_BM, w4 ? 128 : 64, g.MT, g.NT, g.MT, 0, g.mt_chunk * 8 * g.NT};
-            return AGP_OK;
-        }
-        if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, true, uint32_t*>, s2_lds<4>(), a4g, rflag)
-                           : launch(igemm_s2_kernel<2, true, uint32_t*>, s2_lds<2>(), a2g, rflag);
-        else rc = w4 ? launch(igemm_s2_kernel<4, true>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2, true>, s2_lds<2>(), a2s);
+    static std::atomic<uint64_t> a4s{0}, a2s{0}, a4g{0}, a2g{0};
+    uint32_t* const rflag = agp_range_flag_get();
+    const bool w4 = wide && ps[0].N % 128 == 0;
+    g.NT = w4 ? ps[0].N / 128 : (ps[0].N + 63) / 64;
+    if (plan) {
+        *plan = TilePlan{AGP_CONV_KERNEL_S2, S2_BM, w4 ? 128 : 64, g.MT, g.NT, g.MT, 0, g.mt_chunk * 8 * g.NT};
+        return AGP_OK;
     }
-    (void)sch;
+    int rc;
+    if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, uint32_t*>, s2_lds<4>(), a4g, rflag)
+                       : launch(igemm_s2_kernel<2, uint32_t*>, s2_lds<2>(), a2g, rflag);
+    else rc = w4 ? launch(igemm_s2_kernel<4>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2>, s2_lds<2>(), a2s);
     if (rc != AGP_OK) return rc;
     AGP_CHECK_LAUNCH();
     return AGP_OK;

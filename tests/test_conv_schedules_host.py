@@ -57,6 +57,20 @@ def test_tile_plan_of_the_other_3x3_kernels(name):
         assert p["MT"] * p["NT"] > 768           # more than one residency round of three workgroups per CU
 
 
+def test_f16_conv_past_the_32_bit_output_offsets_plans_on_igemm_kxr():
+    """igemm_kxr2 / igemm_kxrw address the output plane with 32-bit element offsets: with 2^31 or more elements in the padded output
+    map an AGP_PREC_F16 conv leaves them for igemm_kxr's one-product fp16 form (<256, 64, 4, 1, 4, 3>, 256 x 64 tiles) -- the only
+    way to that instantiation; one image fewer and it stays.  (32 -> 128 channels, 993 images of 128 x 128: 1.07e9 input bytes,
+    under the kernels' 2^31.)"""
+    pad = 130 * 130
+    assert 993 * pad * 32 * 2 < 2 ** 31 <= 993 * pad * 128 and 992 * pad * 128 < 2 ** 31
+    p = plan3x3(32, 128, 128, 128, 993, prec=4)
+    assert (p["kernel"], p["BM"], p["BN"], p["NT"]) == ("kxr", 256, 64, 2) and p["MT"] == (993 * 128 * 130 + 255) // 256
+    _consistent(p)
+    assert plan3x3(32, 128, 128, 128, 992, prec=4)["kernel"] == "kxrw"
+    assert plan3x3(32, 64, 128, 128, 993, prec=4)["kernel"] == "kxr2"          # (cout 64: the output is half as large)
+
+
 @pytest.mark.parametrize("name", list(GROUPS))
 def test_tile_plan_of_the_grouped_launches_is_mixed(name):
     p = plan_group(GROUPS[name], 128, 128)
