@@ -173,6 +173,10 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
     const float* const tb1 = tab + role * 128 + 32 * cA + 8 * ch1;
     // conv1: intermediate column x0 - 1 + px must lie inside the image, else it is conv2's zero padding
     const bool cin0 = (x0 - 1 + px0 >= 0) && (x0 - 1 + px0 < W), cin1 = (x0 - 1 + px1 >= 0) && (x0 - 1 + px1 < W);
+    // ... and the range guard counts it only where a STORED output reads it (px <= TW + 1).  Pixels 30, 31 take XR slots 32, 33 =
+    // slots 0, 1 of the NEXT ring row, which at the head of a walk may not have been fetched yet: whatever an earlier kernel left in
+    // LDS.  They feed dead output columns only, and the next strip counts the same image columns as its pixels 2, 3.
+    const bool ctk0 = cin0 && px0 < TW + 2, ctk1 = cin1 && px1 < TW + 2;
     // conv2: output column x0 + px is stored if it belongs to the strip and to the image
     const bool sok0 = px0 < TW && x0 + px0 < W, sok1 = px1 < TW && x0 + px1 < W;
     // conv2 output through the wave's strip: the lane's two chunks go in, and come back as line layout -- store instruction i covers
@@ -320,7 +324,7 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         char* const dst = IR + __builtin_amdgcn_readfirstlane((R & (RING - 1)) * ROWB);
         float v[16];
         bn(acc, v);
-        if constexpr (RG) track16(v, real && cin0, real && cin1);
+        if constexpr (RG) track16(v, real && ctk0, real && ctk1);
         u32x4 o0 = pack8_h_lo(v, 0.f), o1 = pack8_h_lo(v + 8, 0.f);
         if (!(real && cin0)) o0 = u32x4{0u, 0u, 0u, 0u};
         if (!(real && cin1)) o1 = u32x4{0u, 0u, 0u, 0u};

@@ -7,10 +7,20 @@
 // what changes is the arithmetic per staged byte and per barrier:
 //   * the X row block of a (ky, channel chunk) macro-step is staged ONCE for 128 output channels (kxr2: once per 64);
 //   * a phase is 16 MFMAs per wave (kxr2: 8) on 12 LDS fragment reads (kxr2: 8): 0.75 instead of 1.0 ds_read_b128 per MFMA;
-//   * 60 KB of LDS and ~200 VGPRs: two workgroups per CU = two waves per SIMD, each with 512 MFMA cycles per phase.
-// (The stride-2 entry kernel gained 18 % from the same change, igemm_s2.hip; round 3.)  The residual is not prefetched during the
-// last macro-step (the accumulators take 128 VGPRs): tile row 0's residual loads are issued before the epilogue barrier, tile
-// row 1's before tile row 0's stores.  POOL as in igemm_kxr2 (conv-epilogue pooling over image-aligned 64-row blocks).
+//   * 59 KB of stage + 16 KB of epilogue strips = 75 KB of LDS and ~220 VGPRs: two workgroups per CU = two waves per SIMD, each
+//     with 512 MFMA cycles per phase.
+// (The stride-2 entry kernel gained 18 % from the same change, igemm_s2.hip; round 3.)  POOL as in igemm_kxr2 (conv-epilogue pooling
+// over image-aligned 64-row blocks).
+//
+// The residual comes in by LDS-DMA and takes no VGPR (the accumulators hold 128): a wave's tile row (32 pixels x 256 bytes = 8 KB =
+// 8 pieces of 4 pixel lines) lands in the wave's own epilogue STRIP, from which the wave reads it in the accumulator layout, and into
+// which it then writes the packed result.  Tile row 0's strips lie where nothing else lives during the last macro-step -- the X
+// buffer that step does not read and the spare LDS behind the stage (KwShape::EPI_LDS) -- so its pieces are issued behind the MFMAs
+// of the last macro-step's first two phases; tile row 1's strips are the other X buffer and the W ring, dead after the K loop: its
+// pieces go out right after the final barrier and are waited for behind tile row 0's arithmetic.  A strip has no row pad (a DMA
+// instruction lays its 64 lanes down contiguously): the 16-byte chunk index is XOR-swizzled with the pixel's low 4 bits on the
+// GLOBAL side (eoff[], shared by the DMA and the output stores) and in the accumulator-layout accesses, so those stay conflict-free
+// (a ds_read_b128 lane group holds 16 different pixels mod 16).  Pixels that are not stored read out of the buffer's range: zeros.
 //
 // vmcnt bookkeeping (per wave, issue order; NX = 5 X pieces, a W piece = 128 rows = NWP = 2 instructions per wave):
 //     prologue          : X(0)[NX]  W(0,0)[2]  W(0,1)[2]
@@ -21,6 +31,12 @@
 //   opens (st,2): W(st,2);            younger: X(st+1) W(st+1,0)      -> vmcnt(NX+2)
 //   opens (st+1,0): W(st+1,0) X(st+1); younger: W(st+1,1)             -> vmcnt(2)
 //   last macro-step L: opens (L,1): younger W(L,2) -> vmcnt(2); opens (L,2): nothing younger -> vmcnt(0).
+//   last macro-step L of a tile WITH a residual (R0 = tile row 0's 8 pieces, R1 = tile row 1's, full tile only):
+//     phase (L,0)       : W(L,2)[2]  R0[0..3]          phase (L,1) : R0[4..7]          after the final barrier: R1[8]
+//   opens (L,1): W(L,1);  younger: W(L,2) R0[0..3]     -> vmcnt(6)
+//   opens (L,2): W(L,2);  younger: R0[0..7]            -> vmcnt(8)
+//   tile row 0 reads its strip: R0; younger: R1        -> vmcnt(8)   (half tile: vmcnt(0))
+//   tile row 1 reads its strip: R1                     -> vmcnt(0), placed BEFORE tile row 0's stores (a store counts too)
 
 #include <type_traits>
 
@@ -37,7 +53,9 @@ struct KxrwGroup {
     // not in the XCD-ordered part of the grid but follow it as 2 (MT - MT_full) NT blocks from block `half_bid0` on
     int MT_full, half_bid0;
     uint32_t* rflag;           // the fp16 range guard's word (agp_range_flag_get), read by the RG = true instantiations only
+    uint32_t r_bytes[KXRW_MAXP];   // bytes of each problem's residual plane (the buffer range of its LDS-DMA)
 };
+constexpr uint32_t KXRW_ROOB = 0xffffff00u;      // a residual offset past every plane: the piece's lane reads zeros
 
 // Tile shapes (a wave = TM_ x TN_ MFMA tiles of 32 x 32, four waves stacked along the rows):
 //   TM_ = 2, TN_ = 4: 256 rows x 128 channels -- the full tile of the WIDE form, cout % 128 == 0;
@@ -49,10 +67,15 @@ template <int TM_, int TN_> struct KwShape {
     static constexpr int BM = 128 * TM_, BN = 32 * TN_, BMX = BM + 16;
     static constexpr int XBUF = BMX * KW_ROWB, WTAP = BN * KW_ROWB;
     static constexpr int LDS = 2 * XBUF + 3 * WTAP + 2 * BN * 4;
+    // the epilogue strips (a wave's tile row, 32 pixels x 2 BN bytes): as many waves as fit use the idle X buffer, the others the
+    // spare region behind the stage (a half tile: behind its 2 KB of pooling scratch)
+    static constexpr int STRIP = 32 * 2 * BN, XWAVES = XBUF / STRIP, SPARE = LDS + (TM_ == 1 ? 2048 : 0);
+    static constexpr int EPI_LDS = SPARE + (4 - XWAVES) * STRIP;
 };
 
-// One tile: rows [m0, m0 + 128 TM_) x columns [n0, n0 + 32 TN_) of problem g.p[pid].
-template <bool POOL, int TM_, int TN_, bool RG = false>
+// One tile: rows [m0, m0 + 128 TM_) x columns [n0, n0 + 32 TN_) of problem g.p[pid]; RES: the problem has a residual (chosen per
+// tile, outside the tile's code: a branch around the last macro-step's MFMAs would cost the accumulators a trip through scratch).
+template <bool POOL, int TM_, int TN_, bool RG, bool RES>
 __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, const int m0, const int n0) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using SH = KwShape<TM_, TN_>;
@@ -117,6 +140,10 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         if (pscale) tab_s = pscale[n];
         if (pshift) tab_t = pshift[n];
     }
+    // the GeM exponent is fetched here, with the table, and lives in an SGPR: its first use in the pooled sweep would otherwise be
+    // a vmcnt(0) that also waits for the tile row's output stores
+    float pool_pw_v = 1.f;
+    if (POOL && p.pool_p) pool_pw_v = p.pool_p[0];
     auto load_x = [&](int buf, int ky_, int cc_) {
         const int xs = __builtin_amdgcn_readfirstlane((ky_ * x_sh + cc_ * 32) * 2);
         char* base_ = smem + buf * X_BUF;
@@ -167,7 +194,6 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     // covers 4 pixels; 8 instructions per tile row of 32 pixels
     constexpr int LPP = BN / 8, PPI = 64 / LPP, NEI = 32 / PPI;
     int eoff[TM * NEI];
-    const bf16_t* const rhi = (const bf16_t*)p.r_hi;
     {
         const uint32_t wlast = d_wo.d - 1;
         const int img_extra = o_sn - (int)d_howo.d * o_sw;
@@ -180,10 +206,23 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
             const uint32_t y = fdiv(rem, d_wo);
             const uint32_t xq = rem - y * d_wo.d;
             const bool ok = (m < pM) && rem < pR && xq != 0 && xq != wlast;
-            eoff[q] = ok ? (int)mm * o_sw + (int)img * img_extra + o_base + n0 + 8 * (lane % LPP) : -1;
+            // the lane's 16-byte chunk of the pixel line, swizzled with the pixel's row in the strip (file header)
+            const int chunk = (lane % LPP) ^ (((q % NEI) * PPI + lane / LPP) & 15);
+            eoff[q] = ok ? (int)mm * o_sw + (int)img * img_extra + o_base + n0 + 8 * chunk : -1;
         }
     }
     float* const ppart = POOL ? p.pool_partial : nullptr;
+    // ---- epilogue strips (wave-private, file header) and the residual's LDS-DMA
+    static_assert(LPP == 16 && PPI == 4 && NEI == 8 && SH::STRIP == NEI * 1024, "a tile row = 8 pieces of 4 pixel lines of 256 bytes");
+    const int xidle = nsteps & 1;                      // the X buffer the last macro-step does not read
+    char* const strip0 = wave < SH::XWAVES ? smem + xidle * X_BUF + wave * SH::STRIP : smem + SH::SPARE + (wave - SH::XWAVES) * SH::STRIP;
+    char* const strip1 = wave < 2 ? smem + (xidle ^ 1) * X_BUF + wave * SH::STRIP : ws + (wave - 2) * SH::STRIP;      // full tile only
+    static_assert(TM == 1 || (SH::XWAVES == 2 && 2 * SH::STRIP <= 3 * W_TAP), "tile row 1: two waves per X buffer, two in the W ring");
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void*)p.r_hi, 0, g.r_bytes[pid], 0x00020000);
+    auto load_residual = [&](char* strip, int tm, int i) {
+        const int off = eoff[tm * NEI + i];
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rr, LDS_PTR(strip + i * 1024), 16, off >= 0 ? off * 2 : (int)KXRW_ROOB, 0, 0, 0);
+    };
 
     int ky = 0, cc = 0;
     wait_vm_lgkm<NWP>();
@@ -193,23 +232,28 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     // a phase beside the fragment reads (MI355X_MICROARCH.md), and in front of the MFMAs that time is on the wave's chain.
     // The loop body has no branch (one scheduling region per phase): the last macro-step is peeled.
     if (tid < BN) { tab[tid] = tab_s; tab[BN + tid] = tab_t; }
+    const float pool_pw = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pool_pw_v)));
     auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int nky_, int ncc_, int wcur_, int wnext_) {
         constexpr int kx = decltype(KX)::value;
         constexpr bool last = decltype(LAST)::value;
+        constexpr int nres = last && RES && kx < 2 ? NEI / 2 : 0;     // tile row 0's residual pieces of this phase
         const char* wb = ws + kx * W_TAP;
         bf16x8 xf[2][TM], wf[2][TN];
 #pragma unroll
         for (int t = 0; t < TM; ++t) xf[0][t] = *(const bf16x8*)(xb + xrd[kx][0] + t * (32 * ROWB));
 #pragma unroll
         for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
-        constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : NWP);
+        constexpr int ndma = (kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : NWP)) + nres;
+        static_assert(ndma <= 8, "one piece per MFMA pair");
 #pragma unroll
         for (int t = 0; t < TM; ++t) xf[1][t] = *(const bf16x8*)(xb + xrd[kx][1] + t * (32 * ROWB));
 #pragma unroll
         for (int t = 0; t < TN; ++t) wf[1][t] = *(const bf16x8*)(wb + wrd[1] + t * (32 * ROWB));
         // piece i of this phase's LDS-DMA list, in the order the vmcnt counts assume: W pieces first, then X(st + 1)
         auto piece = [&](int i) {
-            if (kx == 0) {
+            if (nres && i >= ndma - nres) {
+                load_residual(strip0, 0, kx * (NEI / 2) + i - (ndma - nres));
+            } else if (kx == 0) {
                 if (i < NWP) {
                     const int so = __builtin_amdgcn_readfirstlane((wcur_ + 2 * tapb) * wmul);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + 2 * W_TAP + (wave + NW * i) * 1024), 16, woff[i], so, 0, 0);
@@ -269,31 +313,30 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         const int wcur = (ky * 3 * CK + cc * 32) * 2;
         const char* xb = smem + (st & 1) * X_BUF;
         phase(I0{}, BT{}, xb, st, 0, 0, wcur, 0);
-        wait_vm_lgkm<NWP>();
+        wait_vm_lgkm<NWP + (RES ? NEI / 2 : 0)>();
         __builtin_amdgcn_s_barrier();
         phase(I1{}, BT{}, xb, st, 0, 0, wcur, 0);
-        wait_vm_lgkm<0>();
+        wait_vm_lgkm<(RES ? NEI : 0)>();
         __builtin_amdgcn_s_barrier();
         phase(I2{}, BT{}, xb, st, 0, 0, wcur, 0);
     }
 
-    // ---- epilogue: accumulator layout (a lane = one pixel, 8 x 8 consecutive channels) <-> line layout through a wave-private
-    // LDS strip of 32 rows x (256 + 16) bytes.  Residual of tile row 0 in flight before the barrier.
-    constexpr int ERS = 2 * BN + 16;
-    u32x4 rpf[NEI];
-    auto load_residual = [&](int tm) {
-#pragma unroll
-        for (int i = 0; i < NEI; ++i) {
-            const int off = eoff[tm * NEI + i];
-            rpf[i] = *(const u32x4*)(rhi + (off >= 0 ? off : 0));
-        }
-    };
-    if (rhi) load_residual(0);
+    // ---- epilogue: accumulator layout (a lane = one pixel, 8 x 8 consecutive channels) <-> line layout through the wave's strip of
+    // 32 rows x 256 bytes (file header): row = pixel, 16-byte slot s of row r = chunk s ^ (r & 15) of the pixel's line.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    char* const strip = smem + wave * (32 * ERS);
-    const int a_off = l31 * ERS + lh * 16;
-    const int l_off = (lane / LPP) * ERS + (lane % LPP) * 16;
+    if constexpr (RES) {
+        if constexpr (TM == 2) {
+#pragma unroll
+            for (int i = 0; i < NEI; ++i) load_residual(strip1, 1, i);
+            wait_vm_lgkm<NEI>();
+        } else {
+            wait_vm_lgkm<0>();
+        }
+    }
+    // accumulator layout: pixel l31, chunks 2 jj + lh; line layout: piece i = rows 4 i .. 4 i + 3, lane = (row, slot)
+    const int a_off = l31 * (2 * BN) + ((lh ^ (l31 & 1)) << 4), a_swz = (l31 >> 1) & 7;
+    const int l_off = lane * 16;
     const float* tb = tab + 8 * lh;
     bf16_t* const ohi = (bf16_t*)p.o_hi;
     const float relu_lo = p.relu ? 0.f : -65504.f;
@@ -301,11 +344,12 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     float psum[2][2] = {{0.f, 0.f}, {0.f, 0.f}};       // [channel half][stat]
     float psum0[2][2] = {{0.f, 0.f}, {0.f, 0.f}};      // a full tile: the sums of its tile row 0 (32 rows) while tile row 1 is swept
     const float* const ppp = POOL ? p.pool_p : nullptr;
-    const float pool_pw = ppp ? ppp[0] : 1.f, pool_eps = POOL ? p.pool_eps : 0.f;
+    const float pool_eps = POOL ? p.pool_eps : 0.f;
     const bool pool_cube = pool_pw == 3.f;
     const bool pool_sq = POOL && p.pool_sq;           // stat 1 = sum of squares (BatchNorm statistics), no exponent tensor
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
+        char* const strip = tm == 0 ? strip0 : strip1;
         if constexpr (POOL && TM == 2) {
             // a 64-row block is summed as (rows 0..31) + (rows 32..63) in EVERY schedule: a half tile holds the two halves in two
             // waves (even + odd below), so a full tile keeps them apart as well -- an image's pooled values must not depend on
@@ -318,15 +362,9 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
             }
         }
         u32x4 rres[TN * 2];
-        if (rhi) {
-            // line layout -> strip -> accumulator layout; then the next tile row's residual loads go out BEFORE this row's stores
+        if constexpr (RES) {
 #pragma unroll
-            for (int i = 0; i < NEI; ++i) *(u32x4*)(strip + l_off + i * (PPI * ERS)) = rpf[i];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#pragma unroll
-            for (int jj = 0; jj < TN * 2; ++jj) rres[jj] = *(const u32x4*)(strip + a_off + jj * 32);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            if (tm + 1 < TM) load_residual(tm + 1);
+            for (int jj = 0; jj < TN * 2; ++jj) rres[jj] = *(const u32x4*)(strip + a_off + ((jj ^ a_swz) << 5));
         }
         u32x4 outv[TN * 2];
 #pragma unroll
@@ -337,7 +375,7 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 v[e] = acc[jj >> 1][tm][8 * (jj & 1) + e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? h0[e & 3] : h1[e & 3]);
-            if (rhi) {
+            if constexpr (RES) {
                 float r[8];
                 unpack8_h(rres[jj], r);
 #pragma unroll
@@ -347,11 +385,16 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
             outv[jj] = pack8_h_lo(v, relu_lo);
         }
 #pragma unroll
-        for (int jj = 0; jj < TN * 2; ++jj) *(u32x4*)(strip + a_off + jj * 32) = outv[jj];
+        for (int jj = 0; jj < TN * 2; ++jj) *(u32x4*)(strip + a_off + ((jj ^ a_swz) << 5)) = outv[jj];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         u32x4 lines[NEI];
 #pragma unroll
-        for (int i = 0; i < NEI; ++i) lines[i] = *(const u32x4*)(strip + l_off + i * (PPI * ERS));
+        for (int i = 0; i < NEI; ++i) lines[i] = *(const u32x4*)(strip + l_off + i * 1024);
+        if constexpr (TM == 2) {
+            // tile row 1's residual has had this tile row's arithmetic to land; the wait stands before the stores because a store
+            // counts in vmcnt as well
+            if (tm == 0 && RES) wait_vm_lgkm<0>();
+        }
 #pragma unroll
         for (int i = 0; i < NEI; ++i) {
             const int off = eoff[tm * NEI + i];
@@ -359,35 +402,46 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         }
         if constexpr (POOL) {
             if (ppart) {
-                // the strip holds the tile row as stored: 32 pixels x 128 channels fp16.  Pixels that are not stored (halo columns,
-                // raster rows past the image) are ZEROED in the strip first (the lanes that hold their lines, exec-masked 16-byte
-                // writes), so the sweep below needs no per-element mask: a zero adds nothing to the mean and eps^p ~ 1e-18 to the
-                // GeM sum.  lane = a PAIR of channels (2 lane, 2 lane + 1): one ds_read_b32 per pixel covers the 128 channels.
+                // the strip holds the tile row as stored: 32 pixels x 128 channels fp16; the sweep runs while the stores above drain.
+                // Pixels that are not stored (halo columns, raster rows past the image) are ZEROED in the strip first (the lanes that
+                // hold their lines, exec-masked 16-byte writes), so the sweep needs no per-element mask: a zero adds nothing to the
+                // mean and eps^p ~ 1e-18 to the GeM sum.  lane = a PAIR of channels (2 lane, 2 lane + 1): one ds_read_b32 per pixel
+                // covers the 128 channels.  The statistic is chosen ONCE per tile row (four straight-line bodies); every sum is a
+                // separately rounded multiply / add chain over the pixels in ascending order (no contraction: the pooled values
+                // are the same bits in every schedule and statistic body).
 #pragma unroll
                 for (int i = 0; i < NEI; ++i)
-                    if (eoff[tm * NEI + i] < 0) *(u32x4*)(strip + l_off + i * (PPI * ERS)) = u32x4{0u, 0u, 0u, 0u};
+                    if (eoff[tm * NEI + i] < 0) *(u32x4*)(strip + l_off + i * 1024) = u32x4{0u, 0u, 0u, 0u};
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                const uint32_t* const col = (const uint32_t*)strip + lane;
+                auto sweep = [&](auto STAT) {
+#pragma clang fp contract(off)
+                    constexpr int stat = decltype(STAT)::value;     // 0 mean only, 1 squares, 2 GeM p = 3, 3 GeM any p
 #pragma unroll
-                for (int p8 = 0; p8 < 32; p8 += 8) {
-                    uint32_t w[8];
+                    for (int p8 = 0; p8 < 32; p8 += 8) {
+                        uint32_t w[8];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) w[u] = col[(p8 + u) * (ERS / 4)];
+                        for (int u = 0; u < 8; ++u) w[u] = *(const uint32_t*)(strip + (p8 + u) * (2 * BN) + ((lane * 4) ^ (((p8 + u) & 15) << 4)));
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const float v0 = h2f((bf16_t)(w[u] & 0xffffu)), v1 = h2f((bf16_t)(w[u] >> 16));
-                        psum[0][0] += v0;
-                        psum[1][0] += v1;
-                        if (pool_sq) {
-                            psum[0][1] += v0 * v0;
-                            psum[1][1] += v1 * v1;
-                        } else if (ppp) {
-                            const float c0 = fmaxf(v0, pool_eps), c1 = fmaxf(v1, pool_eps);
-                            psum[0][1] += pool_cube ? c0 * c0 * c0 : __builtin_exp2f(pool_pw * __builtin_log2f(c0));
-                            psum[1][1] += pool_cube ? c1 * c1 * c1 : __builtin_exp2f(pool_pw * __builtin_log2f(c1));
+                        for (int u = 0; u < 8; ++u) {
+                            const float v0 = h2f((bf16_t)(w[u] & 0xffffu)), v1 = h2f((bf16_t)(w[u] >> 16));
+                            psum[0][0] += v0;
+                            psum[1][0] += v1;
+                            if constexpr (stat == 1) {
+                                psum[0][1] += v0 * v0;
+                                psum[1][1] += v1 * v1;
+                            } else if constexpr (stat >= 2) {
+                                const float c0 = fmaxf(v0, pool_eps), c1 = fmaxf(v1, pool_eps);
+                                psum[0][1] += stat == 2 ? c0 * c0 * c0 : __builtin_exp2f(pool_pw * __builtin_log2f(c0));
+                                psum[1][1] += stat == 2 ? c1 * c1 * c1 : __builtin_exp2f(pool_pw * __builtin_log2f(c1));
+                            }
                         }
                     }
-                }
+                };
+                using I3 = std::integral_constant<int, 3>;
+                if (pool_sq) sweep(I1{});
+                else if (!ppp) sweep(I0{});
+                else if (pool_cube) sweep(I2{});
+                else sweep(I3{});
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -462,11 +516,13 @@ __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
         if (half) {
             const int m0 = mt * BM + sub * (BM / 2);
             if (m0 >= g.p[pid].M) return;                  // the second half of a problem's last, partial row tile
-            kxrw_tile<POOL, 1, TN_, RG>(g, pid, m0, n0);
+            if (g.p[pid].r_hi) kxrw_tile<POOL, 1, TN_, RG, true>(g, pid, m0, n0);
+            else kxrw_tile<POOL, 1, TN_, RG, false>(g, pid, m0, n0);
             return;
         }
     }
-    kxrw_tile<POOL, TM_, TN_, RG>(g, pid, mt * BM, n0);
+    if (g.p[pid].r_hi) kxrw_tile<POOL, TM_, TN_, RG, true>(g, pid, mt * BM, n0);
+    else kxrw_tile<POOL, TM_, TN_, RG, false>(g, pid, mt * BM, n0);
 #endif
 }
 
@@ -501,9 +557,9 @@ inline KxrwPlan kxrw_plan(int MT, int NT) {
 
 template <bool POOL, bool MIX, bool RG>
 int launch_kxrw(KxrwGroup& g, const KxrwPlan& k, hipStream_t s) {
-    constexpr int lds = KwShape<2, 4>::LDS;
+    constexpr int lds = KwShape<2, 4>::EPI_LDS;
     static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-    static_assert(KwShape<1, 4>::LDS + 3072 <= lds, "half tiles: their stage + the pooling scratch fit the full tile's LDS");
+    static_assert(KwShape<1, 4>::EPI_LDS <= lds, "half tiles: their stage, the pooling scratch and their strips fit the full tile's LDS");
     static std::atomic<uint64_t> attr_done{0};
     if (!agp_lds_attr((const void*)igemm_kxrw_kernel<POOL, MIX, RG>, lds, attr_done)) return AGP_E_LAUNCH;
     AGP_LAUNCH((igemm_kxrw_kernel<POOL, MIX, RG>), dim3(MIX ? k.blocks : k.half_bid0), dim3(256), lds, s, g);
@@ -529,6 +585,10 @@ int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
         mt += (ps[i].M + bm - 1) / bm;
         g.mt_end[i] = mt;
         pool = pool || ps[i].pool_partial != nullptr;
+        // the residual plane has the output's geometry: M / (raster rows per image) images of o_sn elements
+        const int64_t rb = (int64_t)(ps[i].M / (int)ps[i].d_howo.d) * ps[i].o_sn * 2;
+        if (ps[i].r_hi && (rb <= 0 || rb > (int64_t)KXRW_ROOB)) return AGP_E_BADARG;
+        g.r_bytes[i] = (uint32_t)rb;
     }
     g.MT = mt;
     g.NT = ps[0].N / bn;
