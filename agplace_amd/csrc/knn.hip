@@ -13,6 +13,19 @@
 //      smallest true distance; and a true top-k row has coarse <= d*_k + eps <= T;
 //   c. fp64 direct evaluation sum((q-d)^2) of all rows of the candidate groups from the
 //      ORIGINAL fp32 vectors, rank by (distance, index) -> sorted top-k, faiss layout.
+//
+// 128 < k <= 1024 (select_rerank_kernel<.., BIGK = true>; searches with k <= 128 launch the BIGK = false instantiations, whose
+// code the flag does not touch).  Step (a) only needs SOME T' >= T_k.  Up to 128 neighbours it is the k-th smallest of the 256
+// per-thread minima; beyond that every thread keeps the S = 4 smallest minima of ITS groups (groups are dealt round-robin,
+// thread = g % 256) and T' is the min(k, G)-th smallest of those 256 S = 1024 keys:
+//   * every kept key is the minimum of one group and no group is kept twice, so the j-th smallest kept key has at least j
+//     groups at or below it: j-th smallest kept key >= T_j (the j-th smallest of ALL group minima);
+//   * with G >= k groups at least k keys are real: a thread owns floor or ceil of G / 256 groups, so either G <= 1024 and
+//     every thread keeps all it owns (G >= k keys), or G > 1024 and every thread keeps S (1024 >= k keys);
+//   * with G < k there is no k-th group minimum and T = INF as before (every row is a candidate).
+// The bound is as far above T_k as the deal is uneven (a thread's 5th-smallest group may lie below another thread's smallest),
+// and it costs a 1024-key sort in LDS, so only the BIGK path takes it.  (b) and (c) are unchanged; the entry buffer of (c)
+// holds k running-best entries + one chunk.
 
 #include <type_traits>
 #include <utility>
@@ -37,6 +50,16 @@ constexpr int MAX_ENT_CHUNK = 1024;
 static_assert((MAX_ENT & (MAX_ENT - 1)) == 0, "the bitonic sort pads a round to the next power of two inside the entry buffer");
 static_assert(MAX_ENT >= MAX_ENT_CHUNK + 128, "a round of the exact phase must be able to take one chunk");
 constexpr int MAX_K = 128;
+// 128 < k <= 1024: the same kernel with a buffer that takes 1024 running-best entries + a 2048-row chunk (48 KB; with the 4 KB
+// of threshold keys three workgroups fit a CU's 160 KB), and S group minima per thread behind the threshold (file header).
+constexpr int MAX_K_BIG = AGP_KNN_MAX_K;
+constexpr int MAX_ENT_BIG = 4096;
+constexpr int MAX_ENT_CHUNK_BIG = 2048;
+constexpr int BIGK_S = 4;
+static_assert((MAX_ENT_BIG & (MAX_ENT_BIG - 1)) == 0, "the bitonic sort pads a round to the next power of two inside the entry buffer");
+static_assert(MAX_ENT_BIG >= MAX_ENT_CHUNK_BIG + MAX_K_BIG, "a round of the exact phase must be able to take one chunk");
+static_assert(256 * BIGK_S >= MAX_K_BIG, "the threshold is the min(k, G)-th smallest of 256 * S kept group minima");
+static_assert(MAX_ENT_CHUNK_BIG / 16 <= 256 && MAX_ENT_CHUNK / 16 <= 256, "a chunk's groups are gathered one per thread");
 
 // Database planes + squared norms + the largest norm (the selection's error bound reads it at norm[nb_pad]).  A streaming pass:
 // a wave takes rows in a grid-stride loop, a lane four consecutive columns (one 16-byte load, one 8-byte store per plane), and the
@@ -681,12 +704,16 @@ __global__ void transpose_kernel(const float* __restrict__ in, int rows, int col
 // !PACKED: one float per group (generic coarse pass): every row of a candidate group is examined.
 // VPT_: group minima a thread holds per window (256 * VPT_ groups): 8 when the database has <= 2048 groups (131 072 rows: the
 // bench's 100k), else 32 -- 24 VGPRs less.
-template <bool PACKED, int VPT_ = 32>
-__global__ __launch_bounds__(256, 6) void select_rerank_kernel(
+// BIGK: 128 < k <= 1024 (file header): the threshold of step (a) from BIGK_S minima per thread, the big entry buffer, three
+// workgroups per CU.  Every difference sits behind `if constexpr (BIGK)` or in the two constants below.
+template <bool PACKED, int VPT_ = 32, bool BIGK = false>
+__global__ __launch_bounds__(256, BIGK ? 3 : 6) void select_rerank_kernel(
     const float* __restrict__ xq, const float* __restrict__ xb, const uint32_t* __restrict__ gminT,
     int G, int g_stride, const float* __restrict__ db_norm, int64_t nb, int64_t nb_pad, int d, int k,
     float cerr, float* __restrict__ dist, int64_t* __restrict__ idx, int dbg, const bf16_t* __restrict__ db_f16) {
-    __shared__ uint32_t smin[256];
+    constexpr int MAX_ENT = BIGK ? MAX_ENT_BIG : agp_knn::MAX_ENT;                     // (shadow the small path's constants)
+    constexpr int MAX_ENT_CHUNK = BIGK ? MAX_ENT_CHUNK_BIG : agp_knn::MAX_ENT_CHUNK;
+    __shared__ uint32_t smin[BIGK ? 256 * BIGK_S : 256];
     __shared__ uint32_t s_T;
     __shared__ unsigned int s_count, s_ncand;
     __shared__ double e_d[MAX_ENT];
@@ -730,17 +757,35 @@ __global__ __launch_bounds__(256, 6) void select_rerank_kernel(
     };
     const int nwin = (G + VPT * 256 - 1) / (VPT * 256);
     uint32_t mn = KMAX;
+    [[maybe_unused]] uint32_t ms[BIGK_S];               // BIGK: the thread's BIGK_S smallest group minima, ascending
+    if constexpr (BIGK) {
+#pragma unroll
+        for (int j = 0; j < BIGK_S; ++j) ms[j] = KMAX;
+    }
     for (int w = 0; w < nwin; ++w) {
         load_window(w);
+        if constexpr (BIGK) {
 #pragma unroll
-        for (int i = 0; i < VPT; ++i) mn = v[i] < mn ? v[i] : mn;
+            for (int i = 0; i < VPT; ++i) {
+                uint32_t x = v[i];                      // insertion: x sinks to its place, the largest of the five drops out
+#pragma unroll
+                for (int j = 0; j < BIGK_S; ++j) {
+                    const uint32_t lo_ = ms[j] < x ? ms[j] : x;
+                    x = ms[j] < x ? x : ms[j];
+                    ms[j] = lo_;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VPT; ++i) mn = v[i] < mn ? v[i] : mn;
+        }
     }
     // the kk-th smallest of the 256 minima: every wave sorts its 64 values with a shuffle-only bitonic network (21
     // compare-exchange steps), the four sorted runs go to LDS, and the candidates (the first kk of each run) find their
     // rank in the union by binary search in the other three runs -- ties ordered by (value, wave, position).  (Counting,
     // for every thread, how many of the 256 values are smaller was 1536 VALU instructions per thread: 40 us of the
     // selection's 120 us at 4096 queries.)
-    {
+    if constexpr (!BIGK) {
         uint32_t sv = mn;
 #pragma unroll
         for (int size = 2; size <= 64; size <<= 1)
@@ -774,6 +819,28 @@ __global__ __launch_bounds__(256, 6) void select_rerank_kernel(
             }
             if (r == kk - 1) s_T = sv;
         }
+    } else {
+        // BIGK: the min(k, G)-th smallest of the 256 * BIGK_S kept minima (file header: it is a real group's minimum whenever
+        // G >= k, and at least that many groups lie at or below it) -- a bitonic sort of the 1024 keys in LDS, two
+        // compare-exchanges per thread and step
+        constexpr int NK = 256 * BIGK_S;
+#pragma unroll
+        for (int j = 0; j < BIGK_S; ++j) smin[j * 256 + tid] = ms[j];
+        if (tid == 0) { s_nbest = 0; s_ncand = 0; }
+        for (int size = 2; size <= NK; size <<= 1)
+            for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                __syncthreads();
+#pragma unroll
+                for (int t = tid; t < NK / 2; t += 256) {
+                    const int lo_ = 2 * t - (t & (stride - 1)), hi_ = lo_ + stride;
+                    const uint32_t a = smin[lo_], b = smin[hi_];
+                    const bool up = (lo_ & size) == 0;
+                    if ((a > b) == up) { smin[lo_] = b; smin[hi_] = a; }
+                }
+            }
+        __syncthreads();
+        const int kk = k < G ? k : G;        // 1 <= kk <= 1024 = NK
+        if (tid == 0) s_T = smin[kk - 1];    // (KMAX, were it ever to get there, reads as "no bound": T = INF below)
     }
     // ---- b. candidate threshold
     qn = sqrtf(wave_sum(qn));
@@ -1053,7 +1120,7 @@ extern "C" int agp_knn_prepare_db(const float* xb, int64_t nb, int d, int prec, 
 }
 
 extern "C" int64_t agp_knn_workspace_bytes(int64_t nq, int64_t nb, int d, int k) {
-    (void)k;
+    (void)k;                            // nothing in the workspace grows with k, up to AGP_KNN_MAX_K: the running best lives in LDS
     if (nq < 1) nq = 1;
     return knn_ws(nq, nb, d).total;
 }
@@ -1064,7 +1131,7 @@ static int knn_search_impl(const float* xq, int64_t nq, const float* xb, const v
                            void* stream, bool coarse_only) {
     if (nq == 0) return AGP_OK;
     if (!xq || !db_hi || !db_norm || (!coarse_only && (!dist || !idx)) || !workspace || nq < 0 || nb < 0) return AGP_E_BADARG;
-    if (k < 1 || k > MAX_K || d % 32 || d <= 0) return AGP_E_BADARG;
+    if (k < 1 || k > MAX_K_BIG || d % 32 || d <= 0) return AGP_E_BADARG;
     if (prec == AGP_PREC_BF16X3 && !db_lo) return AGP_E_BADARG;
     if (nb > 0 && !xb && !coarse_only) return AGP_E_BADARG;
     const KnnWs w = knn_ws(nq, nb, d);
@@ -1110,6 +1177,23 @@ static int knn_search_impl(const float* xq, int64_t nq, const float* xb, const v
     const int dbg = AGP_TUNE("KNN_DBG", 0);
     const bf16_t* f16rows = (prec == AGP_PREC_F16 && d % 128 == 0 && !AGP_TUNE("KNN_NOPRUNE", 0)) ? (const bf16_t*)db_hi : nullptr;
     const float ce = prec == AGP_PREC_F16 ? -cerr : cerr;
+    if (k > MAX_K) {
+        // 128 < k <= 1024: the BIGK instantiations, same split on the coarse form and on the number of groups
+        const int Gs = packed ? w.G / 4 : w.G, gs = packed ? w.g_stride64 : w.g_stride;
+        auto big = [&](auto kernel) {
+            AGP_LAUNCH(kernel, dim3((unsigned)nq), dim3(256), 0, s, xq, xb, (const uint32_t*)(ws + w.gminT), Gs, gs, db_norm, nb, nb_pad,
+                       d, k, ce, dist, idx, dbg, f16rows);
+        };
+        if (packed) {
+            if (Gs <= 8 * 256) big(select_rerank_kernel<true, 8, true>);
+            else big(select_rerank_kernel<true, 32, true>);
+        } else {
+            if (Gs <= 8 * 256) big(select_rerank_kernel<false, 8, true>);
+            else big(select_rerank_kernel<false, 32, true>);
+        }
+        AGP_CHECK_LAUNCH();
+        return AGP_OK;
+    }
     if (packed) {
         const int G64 = w.G / 4;
         if (G64 <= 8 * 256) {

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
-from .retrieval import IndexFlatL2
+from .retrieval import IndexFlatL2, MAX_K      # MAX_K: agp_knn_search's limit on k
 
 
 def _dev(x, device, dtype):
@@ -48,9 +48,6 @@ def best_positive_indexes(query_features, database_features, hard_positives_per_
     return out
 
 
-MAX_K = 128      # agp_knn_search's limit on k (csrc/knn.hip)
-
-
 def hardest_negatives_indexes(query_features, database_features, sampled_database_indexes, soft_positives_per_query,
                               negs_num_per_query=10, device="cuda"):
     """[Q, negs] int64 database rows: per query the `negs` nearest rows of
@@ -58,8 +55,8 @@ def hardest_negatives_indexes(query_features, database_features, sampled_databas
     Candidates keep the order of `sampled_database_indexes` (setdiff1d with assume_unique=True does not sort), so
     equal distances resolve to the earlier SAMPLED row, as an index built over that array would.
     One batched search with k = negs + (most in-sample soft positives of any query) serves every query whose soft
-    positives leave k <= 128; the few queries with more in-sample soft positives than that (small or dense
-    databases) are searched one by one over their own candidate set, like the reference does for every query."""
+    positives leave k <= MAX_K (1024); a query with more in-sample soft positives than that is searched on its own
+    over its own candidate set, like the reference does for every query."""
     dev = torch.device(device)
     xq = _dev(query_features, dev, torch.float32)
     xb = _dev(database_features, dev, torch.float32)

@@ -5,7 +5,8 @@ test.py:27-32 and datasets/datasets_ws_nuscenes.py:1241-1258, and `compute_recal
 (test.py:24-84, test_method='hard_resize').  Distances are SQUARED L2 (float32), ascending,
 labels int64, (FLT_MAX, -1) beyond ntotal -- faiss's conventions.  The search is the gfx950
 MFMA kernel pipeline of agp_knn_search; results are exact (fp64 re-evaluation of a provably
-complete candidate set), ties ordered by ascending database index.
+complete candidate set), ties ordered by ascending database index.  k goes up to MAX_K = 1024
+(faiss takes any k; beyond 128 the selection kernel runs with a larger entry buffer, csrc/knn.hip).
 """
 import numpy as np
 import torch
@@ -13,6 +14,15 @@ import torch
 from . import _lib
 from ._lib import ptr, check
 from .options import get_options
+
+MAX_K = 1024     # agp_knn_search's limit on k (AGP_KNN_MAX_K, include/agplace_hip.h)
+
+
+def _check_k(k):
+    """The search's range of k, checked before anything is allocated or launched."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= MAX_K:
+        raise ValueError(f"IndexFlatL2.search: k must be an integer in [1, {MAX_K}] (MAX_K = {MAX_K}), got {k!r}")
+    return int(k)
 
 
 class IndexFlatL2:
@@ -66,6 +76,7 @@ class IndexFlatL2:
 
     def search(self, xq, k):
         """(D float32 [nq,k], I int64 [nq,k]); numpy in -> numpy out, torch in -> torch out."""
+        k = _check_k(k)
         as_numpy = isinstance(xq, np.ndarray)
         D, I = self.search_device(self._to_dev(xq), k)
         if as_numpy:
@@ -97,7 +108,8 @@ class IndexFlatL2:
         return self._prepared
 
     def search_device(self, xq, k):
-        """xq: a device tensor [nq, d] (or already padded [nq, dpad])."""
+        """xq: a device tensor [nq, d] (or already padded [nq, dpad]); 1 <= k <= MAX_K, anything else is a ValueError."""
+        k = _check_k(k)
         L = _lib.load()
         if xq.shape[1] != self.dpad:
             xq = self._to_dev(xq)

@@ -698,8 +698,12 @@ int agp_netvlad_bwd(const float* x, const float* conv_w, const float* centroids,
  *                                     coarse minimum is within the proven error
  *                                     bound of the k-th best, then a sorted top-k.
  * Outputs follow faiss: dist fp32 [nq][k] ascending squared L2, idx int64 [nq][k],
- * (FLT_MAX, -1) beyond nb; ties ordered by ascending index.  d % 32 == 0, k <= 128.
- * Workspace sizes are queried with agp_knn_workspace_bytes. */
+ * (FLT_MAX, -1) beyond nb; ties ordered by ascending index.  d % 32 == 0,
+ * 1 <= k <= AGP_KNN_MAX_K (anything else: AGP_E_BADARG).  k <= 128 runs the selection kernel
+ * with six workgroups per CU; 128 < k <= 1024 a variant of it with a larger entry buffer (three
+ * per CU) and a threshold taken from four group minima per thread -- same exact result.
+ * Workspace sizes are queried with agp_knn_workspace_bytes (independent of k). */
+#define AGP_KNN_MAX_K 1024
 int64_t agp_knn_pad_rows(int64_t nb);
 int agp_knn_prepare_db(const float* xb, int64_t nb, int d, int prec, void* db_hi, void* db_lo,
                        float* db_norm, void* stream);
