@@ -568,3 +568,241 @@ extern "C" int agp_sparse_zplane_perm(const int64_t* keys, const int64_t* seg_of
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Level 0 from RAW lidar points (the reference's host chain: ME.utils.sparse_quantize per scan in __getitem__,
+// batched_coordinates + PCRandomRotation in the collate function, then ME.SparseTensor's floor + merge; specification in
+// DESIGN.md section 1c).  A raw scan has 35 k - 120 k points that fall into a few thousand voxels, so the points are deduplicated
+// BEFORE anything is sorted: one pass quantises every row and inserts (sample, qx, qy, qz) into an open-addressing table of the
+// workspace (64-bit keys, 64-bit atomicCAS, linear probing, >= 2 slots per input row); only the thread whose insert succeeded
+// goes on -- it rotates its voxel, forms the final key and appends it to its sample's bucket.  A sample's bucket is the row range
+// its points occupy in the input ([off[b], off[b+1]): never too small), so no histogram and no scan precede the append: 4 launches
+// (clear, voxelise, per-sample sort, placement; the last two are the bodies of the coarser-level build above on whole keys).
+// The features of the level are all ones (reference: feats = torch.ones([n, 1])), the mean of merged ones is 1: nothing is
+// gathered.  The table is cleared by a kernel, never by a memset node (see agp_sparse_build).
+namespace agp_coords {
+
+constexpr uint64_t HEMPTY = ~0ull;                       // an empty table slot: no key (sample < 0x7fff) equals it
+constexpr int CUR_STRIDE = 32;                           // int32 words between two samples' bucket cursors: one 128-byte line each
+
+__device__ __forceinline__ uint64_t hash_mix64(uint64_t k) {          // the 64-bit finaliser of MurmurHash3
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+    return k ^ (k >> 33);
+}
+
+// slots of the table for `nvalid` rows inside the offsets: a power of two >= 2 nvalid (>= 64), never more than the workspace holds
+__device__ __forceinline__ uint64_t table_slots(int64_t nvalid, uint64_t tsize_max) {
+    uint64_t t = 64;
+    while (t < 2 * (uint64_t)nvalid && t < tsize_max) t <<= 1;
+    return t;
+}
+
+// table (the slots in use) <- empty, cursors <- 0, flag <- 0, features of the rows inside the offsets <- 1, poff <- the caller's
+// offsets clamped into [0, cap]
+__global__ void __launch_bounds__(256) points_init_kernel(const int64_t* __restrict__ off, int nbatch, int64_t cap, uint64_t tsize,
+                                                          uint64_t* __restrict__ table, int64_t* __restrict__ poff,
+                                                          int32_t* __restrict__ cursor, int32_t* __restrict__ flag,
+                                                          float* __restrict__ feats_out) {
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x, gsz = (uint64_t)gridDim.x * 256;
+    typedef __attribute__((ext_vector_type(2))) unsigned long long u64x2;
+    const u64x2 e2 = {HEMPTY, HEMPTY};
+    const int64_t o_end = off[nbatch];
+    const int64_t nvalid = o_end < 0 ? 0 : (o_end > cap ? cap : o_end);        // = poff[nbatch]; valid rows of the level <= nvalid
+    const uint64_t tuse = table_slots(nvalid, tsize);
+    for (uint64_t i = gid; i < tuse / 2; i += gsz) ((u64x2*)table)[i] = e2;
+    for (uint64_t i = gid; i < (uint64_t)nvalid; i += gsz) feats_out[i] = 1.f;
+    for (uint64_t i = gid; i <= (uint64_t)nbatch; i += gsz) {
+        const int64_t o = off[i];
+        poff[i] = o < 0 ? 0 : (o > cap ? cap : o);
+        if (i < (uint64_t)nbatch) cursor[i * CUR_STRIDE] = 0;
+    }
+    if (gid == 0) *flag = 0;
+}
+
+// One thread per input row.  Row i belongs to the sample b with poff[b] <= i < poff[b+1]; rows outside [poff[0], poff[nbatch]) are
+// not looked at (the tail of a fixed-capacity buffer).  Dropped and flagged (bit 0): a row with a non-finite component, with
+// |q| >= 32512 on an axis, or whose ROTATED voxel leaves that range.  The quotient is the correctly rounded fp32 one: the library
+// is compiled without -ffast-math and hipcc's default keeps fp32 division correctly rounded (v_div_scale / v_div_fmas /
+// v_div_fixup), __fdiv_rn says so and stays right if OCML's rounded operations are ever switched on.  The rotation is row vector
+// x matrix in fp64, (qx R0j + qy R1j) + qz R2j: |q| < 2^15 times an fp32 value is exact in fp64, so the floored result is
+// defined bit for bit.  The hash table in use has table_slots(poff[nbatch]) slots: a short scan in a large buffer clears and
+// probes a table of its own size.
+__global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __restrict__ pts, const int64_t* __restrict__ poff, int nbatch,
+                                                             float quant, const float* __restrict__ rot, int rot_per_sample,
+                                                             uint64_t* __restrict__ table, uint64_t tsize, int32_t* __restrict__ cursor,
+                                                             int64_t* __restrict__ bkeys, int32_t* __restrict__ flag) {
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t base = (int64_t)blockIdx.x * ST, i = base + tid;
+    const int64_t n_end = poff[nbatch];
+    if (base >= n_end) return;                              // (uniform) a block of tail rows
+    const uint64_t tmask = table_slots(n_end, tsize) - 1;
+    auto sample_of = [&](int64_t r) {                       // the last b in [0, nbatch) with poff[b] <= r (0 if there is none)
+        int lo = 0, hi = nbatch;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (poff[mid] <= r) lo = mid; else hi = mid;
+        }
+        return lo;
+    };
+    const int b_first = sample_of(base);
+    int b = -1;
+    bool win = false, bad = false;
+    uint64_t key = 0;
+    if (i < n_end) {
+        const int bb = i < poff[b_first + 1] ? b_first : sample_of(i);
+        if (poff[bb] <= i && i < poff[bb + 1]) b = bb;      // (offsets that do not ascend own no rows: nothing is written for them)
+    }
+    if (b >= 0) {
+        float qf[3];
+        bool ok = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float p = pts[i * 3 + a];
+            qf[a] = floorf(__fdiv_rn(p, quant));
+            ok = ok && __builtin_isfinite(p) && fabsf(qf[a]) < (float)(OFF - 256);
+        }
+        if (!ok) {
+            bad = true;
+        } else {
+            const int q0 = (int)qf[0], q1 = (int)qf[1], q2 = (int)qf[2];
+            const uint64_t hk = ((uint64_t)b << (3 * BITS)) | ((uint64_t)(q0 + OFF) << (2 * BITS)) | ((uint64_t)(q1 + OFF) << BITS) |
+                                (uint64_t)(q2 + OFF);
+            uint64_t h = hash_mix64(hk) & tmask;
+            // a voxel already in the table costs a load, not an atomic: 70 000 points of one voxel do one CAS per wave that sees
+            // the slot empty, then read.  The table holds at most tsize / 2 keys, so a probe sequence always meets an empty slot.
+            for (uint64_t step = 0; step <= tmask; ++step) {
+                const uint64_t cur = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (cur == hk) break;
+                if (cur == HEMPTY) {
+                    const uint64_t prev = atomicCAS((unsigned long long*)&table[h], (unsigned long long)HEMPTY, (unsigned long long)hk);
+                    if (prev == HEMPTY) { win = true; break; }
+                    if (prev == hk) break;
+                }
+                h = (h + 1) & tmask;
+            }
+            key = hk;
+            if (win && rot) {
+                const float* R = rot + (rot_per_sample ? (size_t)b * 9 : 0);
+                uint64_t k = (uint64_t)b;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const double c = floor(__dadd_rn(__dadd_rn(__dmul_rn((double)q0, (double)R[j]), __dmul_rn((double)q1, (double)R[3 + j])),
+                                                     __dmul_rn((double)q2, (double)R[6 + j])));
+                    if (!(fabs(c) < (double)(OFF - 256))) { bad = true; win = false; }
+                    k = (k << BITS) | (uint64_t)((bad ? 0 : (int)c) + OFF);
+                }
+                key = k;
+            }
+        }
+    }
+    {
+        const uint64_t anybad = __builtin_amdgcn_ballot_w64(bad);
+        if (anybad && lane == __builtin_ctzll(anybad)) atomicOr(flag, 1);
+    }
+    // append to the sample's bucket bkeys[poff[b] + slot]: a block inside ONE sample claims its slots with one atomic
+    const bool uniform = !win || b == b_first;
+    if (__syncthreads_and(uniform ? 1 : 0)) {
+        int tot;
+        const int pos = block_excl_scan(win ? 1 : 0, &tot);
+        if (tid == 0) s_base = tot ? atomicAdd(&cursor[(size_t)b_first * CUR_STRIDE], tot) : 0;
+        __syncthreads();
+        if (win) bkeys[poff[b_first] + s_base + pos] = (int64_t)key;
+    } else {
+        const int bw = win ? b : -1;
+        uint64_t todo = __builtin_amdgcn_ballot_w64(bw >= 0);
+        while (todo) {
+            const int leader = __ffsll((unsigned long long)todo) - 1;
+            const int b0 = __shfl(bw, leader, 64);
+            const uint64_t same = __builtin_amdgcn_ballot_w64(bw == b0);
+            int pb = 0;
+            if (lane == leader) pb = atomicAdd(&cursor[(size_t)b0 * CUR_STRIDE], __popcll(same));
+            pb = __shfl(pb, leader, 64);
+            if (bw == b0) bkeys[poff[b0] + pb + __popcll(same & ((1ull << lane) - 1ull))] = (int64_t)key;
+            todo &= ~same;
+        }
+    }
+}
+
+// seg_sort_kernel<false> for buckets given as (first row, count): sample b's keys are bkeys[poff[b] .. + cursor[b]), sorted whole
+// (mask = all ones).  More than 65536 VOXELS in one sample: empty sample, flagged (bit 1) like the input-point limit of
+// agp_sparse_build -- the rows a sample may own downstream are the same.
+__global__ void __launch_bounds__(ST) seg_sort_points_kernel(const int64_t* __restrict__ bkeys, const int64_t* __restrict__ poff,
+                                                             const int32_t* __restrict__ cursor, int64_t* __restrict__ uniq_tmp,
+                                                             int32_t* __restrict__ cnt, uint64_t* __restrict__ gscr,
+                                                             int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
+    const int b = blockIdx.x;
+    const int64_t r0 = poff[b];
+    const int n = cursor[(size_t)b * CUR_STRIDE];
+    if (n <= 0) { if (threadIdx.x == 0) cnt[b] = 0; return; }
+    if (n > MAX_SLOT) {
+        if (threadIdx.x == 0) { cnt[b] = 0; atomicOr(flag, 2); }
+        return;
+    }
+    int P = 2;
+    while (P < n) P <<= 1;
+    if (n <= LDS_KEYS) seg_sort_body<false>(KeyArr<true>{sk}, bkeys, r0, n, P, (int64_t)-1, b, nullptr, nullptr, 0, uniq_tmp, nullptr, cnt);
+    else seg_sort_body<false>(KeyArr<false>{gscr + 2 * r0}, bkeys, r0, n, P, (int64_t)-1, b, nullptr, nullptr, 0, uniq_tmp, nullptr, cnt);
+}
+
+struct PWs { int64_t table, bkeys, uniq, gscr, poff, cursor, cnt, total; uint64_t tsize; };
+inline PWs points_layout(int64_t cap, int nbatch) {
+    PWs w;
+    w.tsize = 64;
+    while (w.tsize < 2 * (uint64_t)cap) w.tsize <<= 1;
+    w.table = 0;
+    w.bkeys = al(w.table + (int64_t)w.tsize * 8);
+    w.uniq = al(w.bkeys + cap * 8);
+    w.gscr = al(w.uniq + cap * 8);
+    w.poff = al(w.gscr + 2 * cap * 8);
+    w.cursor = al(w.poff + (int64_t)(nbatch + 1) * 8);
+    w.cnt = al(w.cursor + (int64_t)nbatch * CUR_STRIDE * 4);
+    w.total = al(w.cnt + (int64_t)nbatch * 4);
+    return w;
+}
+
+}  // namespace agp_coords
+
+extern "C" int64_t agp_sparse_points_workspace_bytes(int64_t cap, int nbatch) {
+    if (cap < 1) cap = 1;
+    if (cap >= (1ll << 30)) cap = (1ll << 30) - 1;
+    if (nbatch < 1) nbatch = 1;
+    return points_layout(cap, nbatch).total;
+}
+
+extern "C" int agp_sparse_build_points(const float* points, const int64_t* point_offsets, int64_t cap, int nbatch, float quant_size,
+                                       const float* rotation, int rot_per_sample, int64_t* keys, float* feats_out, int64_t* seg_off,
+                                       int32_t* bidx, int32_t* range_flag, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!points || !point_offsets || !keys || !feats_out || !seg_off || !bidx || !range_flag || !workspace || cap <= 0 ||
+        cap >= (1ll << 30) || nbatch <= 0 || nbatch >= 0x7fff || !(quant_size > 0.f) || !(quant_size <= 3.4e38f) ||
+        rot_per_sample < 0 || rot_per_sample > 1)
+        return AGP_E_BADARG;
+    const PWs w = points_layout(cap, nbatch);
+    if (workspace_bytes < w.total) return AGP_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    uint64_t* table = (uint64_t*)(ws + w.table);
+    int64_t* poff = (int64_t*)(ws + w.poff);
+    int32_t* cursor = (int32_t*)(ws + w.cursor);
+    const uint64_t init_blocks = (w.tsize / 2 + 256 * 8 - 1) / (256 * 8);
+    AGP_LAUNCH(points_init_kernel, dim3((unsigned)(init_blocks < 1 ? 1 : (init_blocks > 65536 ? 65536 : init_blocks))), dim3(256), 0, s,
+               point_offsets, nbatch, cap, w.tsize, table, poff, cursor, range_flag, feats_out);
+    AGP_CHECK_LAUNCH();
+    AGP_LAUNCH(points_voxelize_kernel, dim3((unsigned)((cap + ST - 1) / ST)), dim3(ST), 0, s, points, (const int64_t*)poff, nbatch,
+               quant_size, rotation, rot_per_sample, table, w.tsize, cursor, (int64_t*)(ws + w.bkeys), range_flag);
+    AGP_CHECK_LAUNCH();
+    {
+        constexpr int lds = (LDS_KEYS + LDS_KEYS / 32) * 8;
+        static std::atomic<uint64_t> attr_done{0};
+        if (!agp_lds_attr((const void*)seg_sort_points_kernel, lds, attr_done)) return AGP_E_LAUNCH;
+        AGP_LAUNCH(seg_sort_points_kernel, dim3(nbatch), dim3(ST), lds, s, (const int64_t*)(ws + w.bkeys), (const int64_t*)poff,
+                   (const int32_t*)cursor, (int64_t*)(ws + w.uniq), (int32_t*)(ws + w.cnt), (uint64_t*)(ws + w.gscr), range_flag);
+        AGP_CHECK_LAUNCH();
+    }
+    AGP_LAUNCH(place_kernel, dim3(nbatch), dim3(256), 0, s, (const int64_t*)(ws + w.uniq), (const float*)nullptr, 0, (const int64_t*)poff,
+               (const int32_t*)(ws + w.cnt), nbatch, cap, keys, (float*)nullptr, seg_off, bidx);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}

@@ -23,8 +23,30 @@ packing straight from the pinned arena (zero-copy: 3.9 ms -- PCIe-stalled waves 
 
 Loader workers write straight into `ring.host(slot)[name]` (pinned, page-locked: `torch.from_numpy` views of it can be
 handed to worker processes through shared memory); nothing here touches pixel values.
+
+The lidar half of a query ships as raw scans (`points` [N,3] + `point_offsets` [B+1]; quantisation, deduplication and the
+augmentation rotation run on the device: SparseTensor.from_points_capacity); `random_z_rotation` draws the
+rotation the reference's collate function applies on the CPU.
 """
+import math
+
 import torch
+
+
+def z_rotation(theta):
+    """fp32 [3,3]: the reference's PCRandomRotation._M((0, 0, 1), theta) = expm(np.cross(np.eye(3), (0, 0, theta))) in closed
+    form, [[cos t, -sin t, 0], [sin t, cos t, 0], [0, 0, 1]] (evaluated in double precision, rounded once); applied to ROW
+    vectors, `coords @ R`."""
+    c, s = math.cos(theta), math.sin(theta)
+    return torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float64).to(torch.float32)
+
+
+def random_z_rotation(max_theta_deg=5.0, generator=None):
+    """The matrix of the reference's collate-time augmentation PCRandomRotation(max_theta=max_theta_deg, max_theta2=0, axis=z)
+    (datasets_ws_nuscenes.py:141): an angle drawn uniformly from +-max_theta_deg about z (max_theta2 = 0 makes the second
+    factor the identity).  Host arithmetic; pass the result as data_dict['pc_rotation'] (MM.forward_q) or `rotation=`."""
+    u = float(torch.rand(1, generator=generator, dtype=torch.float64))
+    return z_rotation((math.pi * max_theta_deg / 180.0) * 2.0 * (u - 0.5))
 
 
 class PinnedRing:

@@ -7,8 +7,10 @@ names match what train.py:175-190 reads for its optimizer groups.
 Scope: the image backbone, GeM, stage-1 Neural-ODE fusion, stage-2 fusion
 and the scalar-weight glue run on hand-written gfx950 kernels.  The sparse-voxel branch
 (MinkFPN / MinkGeM / ECABasicBlock, agplace_amd/sparse) runs from `coords` [N,4] / `features` [N,1]
-exactly like mm.py:86-89, in inference and in .train() mode (agplace_amd/sparse/train.py); when
-`coords` is absent data_dict carries the voxel branch's dense outputs instead:
+exactly like mm.py:86-89, in inference and in .train() mode (agplace_amd/sparse/train.py), or -- without
+`coords` -- from raw scans: `points` fp32 [N,3] in metres, `point_offsets` int64 [b+1] and the optional
+`pc_rotation` ([3,3] or [b,3,3]), voxelised on the device with Options.quant_size; when
+neither is present data_dict carries the voxel branch's dense outputs instead:
     vox_levels  [ [b,64], [b,128], [b,256] ]   globally pooled v1..v3  (fuse_block_toshallow.py:83)
     voxfeatvec  [b,256]                          MinkGeM(voxfeatmap)      (mm.py:89)
     stg2voxvec  [b,256], voxvec_fuse [b,256]     stage-2 voxel outputs    (stage2fuse_blockadd.py:201,207)
@@ -88,7 +90,9 @@ class MM(nn.Module):
 
     # ---- the voxel-range flag.  agp_sparse_build zeroes a device word at the start of every build and sets it when it had to clamp
     # a voxel coordinate into the +-32511 range of the 16-bit key fields, met a batch index outside [0, batch size) or a sample of
-    # more than 65536 points: the voxel branch's outputs of that batch are then wrong.  Every inference forward from `coords` ORs
+    # more than 65536 points (from raw `points`, agp_sparse_build_points: when it had to DROP a point -- non-finite, or its voxel outside that
+    # range -- or a sample holds more than 65536 voxels): the voxel branch's outputs of that batch are then wrong.  Every inference
+    # forward from `coords` or `points` ORs
     # that word into a STICKY device word and copies the sticky word to pinned host memory, both enqueued behind the build on the
     # calling stream -- captured into a hipGraph they are nodes of the graph, so every REPLAY publishes its own flag and the host
     # can look at it without touching the stream (poll_voxel_range).
@@ -106,11 +110,12 @@ class MM(nn.Module):
             sl['host'].zero_()
             sl['event'] = None
         raise ValueError(f"MM.forward_q: in {which} batch a voxel coordinate lies outside the supported range (|c| <= 32511 after "
-                         "flooring), a batch index outside [0, batch size), or one sample holds more than 65536 points: the voxel "
-                         "branch's outputs of that batch are wrong")
+                         "flooring; from `coords` the point was clamped into the origin voxel, from raw `points` it was dropped, as "
+                         "was a point with a non-finite component), a batch index outside [0, batch size), or one sample holds more "
+                         "than 65536 points (`coords`) / voxels (`points`): the voxel branch's outputs of that batch are wrong")
 
     def poll_voxel_range(self):
-        """NON-BLOCKING: raises ValueError if any inference forward from `coords` whose flag has reached the host so far -- eager
+        """NON-BLOCKING: raises ValueError if any inference forward from `coords` or raw `points` whose flag has reached the host so far -- eager
         or REPLAYED from a hipGraph -- saw an out-of-range cloud (reads words of pinned host memory; no stream is synchronised,
         so the most recent forwards may not be covered yet: finish a loop with voxel_coords_in_range()).  Call it every few
         replays of a captured forward (agplace_amd.pair.CapturedPair.replay does)."""
@@ -119,8 +124,8 @@ class MM(nn.Module):
                 self._raise_voxel_range("an earlier")
 
     def voxel_coords_in_range(self):
-        """False if ANY inference forward from `coords` since the last report (eager or replayed) had to clamp a voxel coordinate,
-        met a bad batch index or an oversized sample.  Synchronises the device: call it after the loop, not inside it."""
+        """False if ANY inference forward from `coords` or raw `points` since the last report (eager or replayed) had to clamp a voxel
+        coordinate (`coords`) or drop a point (`points`), met a bad batch index or an oversized sample.  Synchronises the device: call it after the loop, not inside it."""
         slots = self.__dict__.get('_vox_flag_slots', {})
         if not slots:
             return True
@@ -223,12 +228,17 @@ class MM(nn.Module):
             prec = 2
         image = self.query_image(data_dict)
         if self.drop == 'pc':
-            if 'coords' not in data_dict:
-                raise NotImplementedError("drop='pc' acts on the sparse voxel branch: pass coords / features")
-            data_dict = dict(data_dict)
-            c = data_dict['coords'].clone()
-            c[:, 1:] = c[:, 1:] * 0
-            data_dict['coords'] = c
+            if 'coords' in data_dict:
+                data_dict = dict(data_dict)
+                c = data_dict['coords'].clone()
+                c[:, 1:] = c[:, 1:] * 0
+                data_dict['coords'] = c
+            elif 'points' in data_dict and 'point_offsets' in data_dict:
+                # the same cloud from raw scans: every FINITE point at the sensor, one origin voxel per sample (a rotation keeps it there)
+                data_dict = dict(data_dict)
+                data_dict['points'] = data_dict['points'] * 0
+            else:
+                raise NotImplementedError("drop='pc' acts on the sparse voxel branch: pass coords / features, or points / point_offsets")
         if not ('image' in opt.output_type and 'vox' in opt.output_type and 'shallow' in opt.output_type):
             raise NotImplementedError   # other output_type values crash in the reference (mm.py:115-118)
         if True:
@@ -239,10 +249,17 @@ class MM(nn.Module):
             # are needed.
             voxmap, vox_train_ctx = None, None
             vox_side = None
-            if 'coords' in data_dict:
+            # raw scans (`points` [N,3] + `point_offsets` [b+1], optional `pc_rotation`) instead of `coords`: the lidar front end
+            # on the device (agp_sparse_build_points: quantise, deduplicate, rotate) feeds the same branch
+            from_points = 'coords' not in data_dict and 'points' in data_dict and 'point_offsets' in data_dict
+            if 'coords' in data_dict or from_points:
                 data_dict = dict(data_dict)
                 if train:
-                    sp = sparse.SparseTensor.from_coords_levels(data_dict['features'], data_dict['coords'], image.shape[0], len(self.vox_fe.convs))
+                    if from_points:
+                        sp = sparse.SparseTensor.from_points_levels(data_dict['points'], data_dict['point_offsets'], image.shape[0],
+                                                                    len(self.vox_fe.convs), opt.quant_size, data_dict.get('pc_rotation'))
+                    else:
+                        sp = sparse.SparseTensor.from_coords_levels(data_dict['features'], data_dict['coords'], image.shape[0], len(self.vox_fe.convs))
                     vsink = train_fns.VoxSink()
                     *vmeans, vgem = train_fns.VoxTrunkFn.apply(train_fns.anchor_of(self.vox_fe, self.vox_pool.p), sp, self.vox_fe, self.vox_pool, vsink)
                     voxmap = vsink.top
@@ -286,7 +303,11 @@ class MM(nn.Module):
                 with torch.cuda.stream(vox_side):
                     # capacity-mode levels: sort / unique / segment offsets on the device, no host synchronisation, every buffer
                     # from the module's workspace -- the branch is hipGraph-capturable (agplace_amd/sparse/coords.py)
-                    sp = sparse.SparseTensor.from_coords_capacity(data_dict['features'], data_dict['coords'], image.shape[0], vox_ws)
+                    if from_points:
+                        sp = sparse.SparseTensor.from_points_capacity(data_dict['points'], data_dict['point_offsets'], image.shape[0],
+                                                                      opt.quant_size, vox_ws, data_dict.get('pc_rotation'))
+                    else:
+                        sp = sparse.SparseTensor.from_coords_capacity(data_dict['features'], data_dict['coords'], image.shape[0], vox_ws)
                     vox_flag = sp.range_flag
                     voxmap, voxmaplist = self.vox_fe(sp, prec=prec)
                     data_dict['voxfeatvec'] = self.vox_pool(voxmap)
@@ -476,7 +497,7 @@ class MM(nn.Module):
         if mode == 'q':
             k = self.opt.query_substreams
             img = data_dict.get('query_image')
-            if (k > 1 and not self.training and not torch.is_grad_enabled() and 'coords' not in data_dict
+            if (k > 1 and not self.training and not torch.is_grad_enabled() and 'coords' not in data_dict and 'points' not in data_dict
                     and torch.is_tensor(img) and img.shape[0] % k == 0 and img.shape[0] >= 2 * k):
                 return self._forward_q_substreams(data_dict, k)
             return self.forward_q(data_dict)

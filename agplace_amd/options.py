@@ -21,6 +21,8 @@ class Options:
     negs_num_per_query: int = 10
     neg_samples_num: int = 1000
     recall_values: List[int] = field(default_factory=lambda: [1, 5, 10, 20])
+    # voxel size in metres of the lidar front end (reference tools/options.py:61); read when MM.forward_q gets raw `points`
+    quant_size: float = 2.0
     # database model
     dbimage_fe: str = "resnet18"
     dbimage_fe_layers: str = "2_2_2"

@@ -55,7 +55,7 @@ def _embed_pair_dispatch(modelq, modeldb, qdata, dbdata):
     img = qdata['query_image']
     db_map = dbdata['db_map']
     b = img.shape[0]
-    if k > 1 and 'coords' not in qdata and b % k == 0 and b >= 2 * k and db_map.shape[0] % k == 0:
+    if k > 1 and 'coords' not in qdata and 'points' not in qdata and b % k == 0 and b >= 2 * k and db_map.shape[0] % k == 0:
         return _embed_pair_substreams(modelq, modeldb, qdata, dbdata, k)
     return _embed_pair_one(modelq, modeldb, qdata, dbdata)
 

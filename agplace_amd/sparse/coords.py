@@ -15,13 +15,15 @@ PARITY UNPINNED):
 Coordinates are linearised into sorted int64 keys; every kernel map is ONE launch of agp_sparse_kernel_map (binary
 search of key + offset).  The arithmetic of the layers runs in csrc/igemm.hip (agp_sparse_conv_fwd) and csrc/sparse.hip.
 
-Three ways to build the levels:
+Ways to build the levels:
   * `SparseTensor.from_coords_capacity` (inference): every level has `cap` = number-of-input-points rows of which the first
     n are valid, n stays on the DEVICE (seg_off[nbatch]); sort / unique / compaction / segment offsets are kernels of
     csrc/coords.hip (agp_sparse_build, agp_sparse_coarsen: one workgroup sorts one batch sample's keys in LDS) -- no host
     synchronisation, no data-dependent allocation: the whole voxel branch is hipGraph-capturable;
   * `SparseTensor.from_coords_levels` (training, what MM uses): the same device-side kernels for ALL levels back to back, then ONE
     read-back of the row counts -> exact-size tensors (the counts size the activation tapes of the backward pass);
+  * `SparseTensor.from_points_capacity` / `from_points_levels`: the same two from RAW lidar points -- quantisation, per-sample
+    deduplication and the optional rotation run on the device too (agp_sparse_build_points; specification: DESIGN.md 1c);
   * `SparseTensor.from_coords` (+ `strided()` on its result): exact-size levels from torch.unique on the keys, one host
     synchronisation per level -- the plain restatement the other two are tested against.
 """
@@ -135,6 +137,96 @@ class SparseTensor:
         if counts[-1]:
             raise ValueError("voxel coordinates out of the +-32511 range (16-bit key fields, kernel offsets need headroom), a batch "
                              "index outside [0, nbatch) or more than 65536 points in one sample")
+        tensors = []
+        for l, (k_, s_, b_) in enumerate(levels):
+            nl = int(counts[l])
+            t = SparseTensor(None, k_[:nl], nbatch, 1 << l, f32=f_out[:nl] if l == 0 else None)
+            t._seg = (s_, b_[:nl])
+            tensors.append(t)
+        for a, b in zip(tensors[:-1], tensors[1:]):
+            a._maps[("coarser",)] = b
+        return tensors[0]
+
+    # ------------------------------------------------------------------ raw lidar points (device-side quantise / deduplicate / rotate)
+    @staticmethod
+    def _points_args(points, point_offsets, nbatch, quant_size, rotation):
+        dev = points.device
+        if dev.type != "cuda":
+            raise RuntimeError("SparseTensor.from_points_*: `points` must be a GPU tensor (agplace_amd has no CPU path)")
+        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise ValueError("points: fp32 [N, 3] with N >= 1")
+        if not float(quant_size) > 0.0:
+            raise ValueError("quant_size must be > 0")
+        p = points.float().contiguous()
+        off = point_offsets.to(dev, torch.int64).contiguous()
+        if off.dim() != 1 or off.shape[0] != nbatch + 1:
+            raise ValueError("point_offsets: int64 [nbatch + 1]")
+        r, per = None, 0
+        if rotation is not None:
+            r = rotation.to(dev, torch.float32).contiguous()
+            if tuple(r.shape) == (nbatch, 3, 3) and r.dim() == 3:
+                per = 1
+            elif tuple(r.shape) != (3, 3):
+                raise ValueError("rotation: fp32 [3, 3] or [nbatch, 3, 3]")
+        return p, off, r, per
+
+    @staticmethod
+    def from_points_capacity(points, point_offsets, nbatch, quant_size, ws, rotation=None):
+        """Level 0 from RAW scans (inference; the counterpart of `from_coords_capacity`): points fp32 [N, 3] in metres, sample b owns
+        rows [point_offsets[b], point_offsets[b+1]) (int64 [nbatch + 1] on the device; rows from point_offsets[nbatch] on are
+        ignored, so one buffer of N rows serves scans of any length under a captured graph), quantised with `quant_size`,
+        deduplicated per sample and -- with `rotation`, fp32 [3, 3] or [nbatch, 3, 3] -- rotated as `coords @ R`.
+        The capacity of every level is N.  Features are the reference's all-ones column.  One call of agp_sparse_build_points: no
+        host synchronisation; pass device tensors (a host `rotation` or `point_offsets` is copied on the calling stream)."""
+        p, off, r, per = SparseTensor._points_args(points, point_offsets, nbatch, quant_size, rotation)
+        dev, n = p.device, p.shape[0]
+        L = _lib.load()
+        keys = ws.tensor("sp.keys0", (n,), torch.int64, dev)
+        f_out = ws.tensor("sp.f0", (n, 1), torch.float32, dev)
+        seg_off = ws.tensor("sp.seg0", (nbatch + 1,), torch.int64, dev)
+        bidx = ws.tensor("sp.bidx0", (n,), torch.int32, dev)
+        flag = ws.tensor("sp.flag", (1,), torch.int32, dev, zero=True)
+        nbytes = L.agp_sparse_points_workspace_bytes(n, nbatch)
+        tmp = ws.tensor("sp.ptmp0", (nbytes,), torch.uint8, dev)
+        check(L.agp_sparse_build_points(ptr(p), ptr(off), n, nbatch, float(quant_size), ptr(r), per, ptr(keys), ptr(f_out), ptr(seg_off),
+                                        ptr(bidx), ptr(flag), ptr(tmp), nbytes, _lib.stream()), "agp_sparse_build_points")
+        t = SparseTensor(None, keys, nbatch, 1, f32=f_out, n_dev=seg_off[nbatch:], ws=ws)
+        t._seg = (seg_off, bidx)
+        t.range_flag = flag
+        return t
+
+    @staticmethod
+    def from_points_levels(points, point_offsets, nbatch, nlevels, quant_size, rotation=None):
+        """The exact-size levels of the training path from RAW scans (the counterpart of `from_coords_levels`, same inputs as
+        `from_points_capacity`): agp_sparse_build_points + `nlevels` x agp_sparse_coarsen back to back, then ONE read-back of the
+        row counts and the flag.  Raises ValueError on a flagged build (a non-finite or out-of-range point, more than 65536
+        voxels in one sample)."""
+        p, off, r, per = SparseTensor._points_args(points, point_offsets, nbatch, quant_size, rotation)
+        dev, n = p.device, p.shape[0]
+        L = _lib.load()
+        nbytes = L.agp_sparse_points_workspace_bytes(n, nbatch)
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        cbytes = L.agp_sparse_coords_workspace_bytes(n, nbatch, 0)
+        ctmp = torch.empty((cbytes,), dtype=torch.uint8, device=dev)
+        flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+        def level_buffers():
+            return (torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((nbatch + 1,), dtype=torch.int64, device=dev),
+                    torch.empty((n,), dtype=torch.int32, device=dev))
+        keys, seg, bidx = level_buffers()
+        f_out = torch.empty((n, 1), dtype=torch.float32, device=dev)
+        check(L.agp_sparse_build_points(ptr(p), ptr(off), n, nbatch, float(quant_size), ptr(r), per, ptr(keys), ptr(f_out), ptr(seg),
+                                        ptr(bidx), ptr(flag), ptr(tmp), nbytes, _lib.stream()), "agp_sparse_build_points")
+        levels = [(keys, seg, bidx)]
+        for l in range(nlevels):
+            k2, s2, b2 = level_buffers()
+            check(L.agp_sparse_coarsen(ptr(levels[-1][0]), ptr(levels[-1][1]), n, 1 << l, nbatch, ptr(k2), ptr(s2), ptr(b2), ptr(ctmp),
+                                       cbytes, _lib.stream()), "agp_sparse_coarsen")
+            levels.append((k2, s2, b2))
+        counts = torch.cat([s_[nbatch:] for _, s_, _ in levels] + [flag.to(torch.int64)]).tolist()      # the one synchronisation
+        if counts[-1]:
+            raise ValueError("a lidar point with a non-finite component or a voxel coordinate out of the +-32511 range (16-bit key "
+                             "fields, kernel offsets need headroom), or more than 65536 voxels in one sample")
         tensors = []
         for l, (k_, s_, b_) in enumerate(levels):
             nl = int(counts[l])

@@ -837,6 +837,29 @@ int agp_sparse_build(const void* coords, int kind, int64_t n, const float* feats
  * (two launches: per-sample sort + placement). */
 int agp_sparse_coarsen(const int64_t* keys, const int64_t* seg_off_in, int64_t cap, int stride, int nbatch, int64_t* keys_out,
                        int64_t* seg_off, int32_t* bidx, void* workspace, int64_t workspace_bytes, void* stream);
+/* Level 0 of a sparse tensor from RAW lidar points -- the reference's host chain ME.utils.sparse_quantize (per scan),
+ * ME.utils.batched_coordinates + PCRandomRotation (collate function) and ME.SparseTensor's floor + merge in one capturable call
+ * (DESIGN.md section 1c is the specification).
+ *   points         fp32 [cap][3] metres (4-byte aligned); sample b owns rows [point_offsets[b], point_offsets[b+1])
+ *   point_offsets  int64 [nbatch + 1] on the DEVICE (8-byte aligned), ascending, clamped into [0, cap]; rows outside
+ *                  [off[0], off[nbatch]) are never read as points: one buffer of `cap` rows serves scans of any length
+ *   quant_size     > 0 and finite: q = floor(fl32(p / quant_size)) per axis, a true floor of the correctly rounded fp32 quotient
+ *   rotation       NULL, or fp32 [3][3] (rot_per_sample = 0) / [nbatch][3][3] (rot_per_sample = 1), row-major:
+ *                  c_j = floor((qx R[0][j] + qy R[1][j]) + qz R[2][j]) in fp64 without contraction (coords @ R)
+ * One row per (b, q) is kept (open-addressing table in the workspace), rotated, and the level is built from (b, c): voxels that
+ * collide after the rotation merge.  Outputs, all of capacity cap: keys int64 [cap] sorted unique (rows >= n padded with
+ * INT64_MAX), feats_out fp32 [cap] = 1 (the reference's all-ones feature of width 1), seg_off int64 [nbatch + 1]
+ * (seg_off[nbatch] = n, the number of valid rows), bidx int32 [cap] (0 in the padding).  *range_flag (int32, 4-byte aligned) is
+ * zeroed first, then |= 1 if a row had a non-finite component, |q| >= 32512 on an axis or a rotated |c| >= 32512 (the row is
+ * DROPPED: it does not join the origin voxel as in agp_sparse_build), |= 2 if one sample holds more than 65536 voxels after
+ * deduplication (that sample comes out empty); the number of raw points per sample is not limited.  workspace: 256-byte
+ * aligned, agp_sparse_points_workspace_bytes(cap, nbatch) bytes.  4 kernel launches on `stream`, no memset node, no host
+ * read-back.  AGP_E_BADARG: a null pointer (rotation excepted), quant_size <= 0 / NaN / inf, cap outside [1, 2^30),
+ * nbatch outside [1, 32767), rot_per_sample outside {0, 1}, a workspace that is too small. */
+int64_t agp_sparse_points_workspace_bytes(int64_t cap, int nbatch);
+int agp_sparse_build_points(const float* points, const int64_t* point_offsets, int64_t cap, int nbatch, float quant_size,
+                            const float* rotation, int rot_per_sample, int64_t* keys, float* feats_out, int64_t* seg_off,
+                            int32_t* bidx, int32_t* range_flag, void* workspace, int64_t workspace_bytes, void* stream);
 /* Per-sample mean (ME.MinkowskiGlobalPooling / GlobalAvgPooling) and GeM (layers/pooling.py:70-87)
  * of a feature matrix: mean_out / gem_out fp32 [nseg][c] (either may be NULL). */
 int agp_seg_pool_fwd(const void* hi, const void* lo, const int64_t* seg_off, int nseg, int c, const float* p,
