@@ -9,19 +9,25 @@
 // leaves the CU and the residual comes from the input rows that are already in LDS: a block reads its input once and writes
 // its output once (~376 MB algorithmic + the strips' halo columns).
 //
-// How.  A workgroup owns a column STRIP of 28 pixels and walks down it over a range of the map's rows -- all images of the
-// batch are one column of "virtual rows" (image i owns rows i (H+2) .. incl. its two halo rows, which is how the planes lie
-// in memory), so a walk crosses image boundaries without a pipeline drain.  LDS holds two rings of 16 rows x 32 pixel slots
-// x 128 B (64 channels fp16), XOR-swizzled per slot pair: XR = input rows (strip columns -2 .. +29, fetched by LDS-DMA one
-// step = 4 rows ahead), IR = intermediate rows (columns -1 .. +30).  Eight waves = two roles (two waves per SIMD, one of
+// How.  A workgroup owns a column STRIP of 28 pixels and walks down it over a range of the map's rows -- the IMAGE rows of
+// all images of the batch are one column of "compact rows" (image i owns rows i H .. i H + H - 1; in memory, with its two halo
+// rows, virtual rows i (H+2) + 1 ..), cut into PAIRS (rows 2 P, 2 P + 1: an image has H / 2 of them, H is even), so a walk
+// crosses image boundaries without a pipeline drain and without a step spent on halo rows.  LDS holds two rings of 16 rows x
+// 32 pixel slots x 128 B (64 channels fp16), indexed by the compact row and XOR-swizzled per slot pair: XR = input rows (strip
+// columns -2 .. +29, fetched by LDS-DMA one step = 4 rows ahead), IR = intermediate rows (columns -1 .. +30).  The row above an
+// image's first and below its last row -- zeros for both convs: the map's halo rows (every kernel stores interior pixels only,
+// SplitMap.alloc zeroes the rest) and conv2's padding -- is never fetched, computed or written: a pair at an image border reads
+// ONE zero row in LDS (ZROW) in its place.  Eight waves = two roles (two waves per SIMD, one of
 // each role -- profiles/README.md, round 4: the "weights in registers, activations from LDS" loop runs at 1330 TFLOP/s
 // with two waves per SIMD and at 1040-1130 with one):
 //   waves 0..3 (conv1): wave (cA, pA) holds the 3x3x64 weights of 32 output channels of conv1 in REGISTERS for the whole
 //     launch (36 MFMA A-fragments = 144 VGPRs) and computes, per step, two intermediate rows (one 32 x 32 MFMA tile each:
 //     36 x {ds_read_b128 of an X fragment at (row + ky, slot + kx), v_mfma_f32_32x32x16_f16}); BN + ReLU + fp16 into IR
-//     (zeros outside the image: that is conv2's padding);
-//   waves 4..7 (conv2): the same with conv2's weights on IR rows, one step behind; epilogue BN + residual (from XR) +
-//     ReLU -> global.
+//     (zeros in the columns outside the image: that is conv2's padding);
+//   waves 4..7 (conv2): the same with conv2's weights on IR rows, three pairs behind (a pair reads the first row of the
+//     next one); epilogue BN + residual (from XR) + ReLU -> global.
+// Every pair either role runs is a pair of image rows: a step is two pairs per role, and a segment of N pairs takes
+// ceil(N / 2) + 2 rounds (the fill: conv1's seam pair and first pair, then its next two) wherever it starts.
 // One s_barrier per step (~70 MFMAs per wave) and no load on any wave's critical path.  A 32-slot tile carries 30 (conv1) /
 // 28 (conv2) useful pixels: 1.14 x the algorithmic flops are issued.
 // The MFMA sequence of an output element (ky, 32-channel chunk, kx, 16-channel K-step) and the epilogue arithmetic are those
@@ -38,9 +44,10 @@
 // mask(px) * y[px][ch] in fp32 (exact products, fixed order) over the PAIR of rows (y, y + 1; y even in padded coordinates) the
 // wave has just computed -- no vector instruction per value, 8 accumulator registers that live for the last MFMAs of a pair only.  (Per-lane sums in registers cost 16 VGPRs the kernel does not have,
 // LDS float atomics 3 x the kernel's time, read-modify-write in LDS + a DPP reduction +50 us: profiles/README.md, round 4.)
-// The wave then writes the 32 sums: [pair of virtual rows][strip][64].  The pairs are image-relative units (row segments start at
-// even rows, images have an even number of padded rows), so the sums do not depend on where a workgroup's walk starts or where
-// an image sits in the batch; agp_bblock64_pool_finish adds an image's pairs and strips in a fixed order.
+// The wave then writes the 32 sums: [image][pair of the image, H / 2 + 1 entries][strip][64].  The pairs are image-relative units
+// (image rows (1, 2), (3, 4), ... in padded coordinates), so the sums do not depend on where a workgroup's walk starts or where
+// an image sits in the batch; agp_bblock64_pool_finish adds an image's pairs and strips in a fixed order.  (The buffer keeps the
+// (H + 2) / 2 entries per image of the walk over virtual rows: the last one is written as zeros with the image's last pair.)
 
 #include <type_traits>
 #include <utility>
@@ -55,18 +62,20 @@ constexpr int RING = 16;           // rows per ring
 constexpr int ROWB = 32 * 128;     // bytes of a ring row
 constexpr int TAB_OFF = 2 * RING * ROWB + 512;      // (512 B guard: slots 32, 33 of the last IR row)
 constexpr int STRIP_OFF = TAB_OFF + 4 * 64 * 4;    // conv2 waves: wave-private 32 pixels x 64 B output strips (accumulator -> line layout)
-template <bool POOL> constexpr int lds_bytes() { return STRIP_OFF + 4 * 2048; }
+constexpr int ZROW_OFF = STRIP_OFF + 4 * 2048;    // the zero row: 34 slots (a fragment read reaches slot 33)
+constexpr int ZROW_BYTES = ROWB + 512;
+template <bool POOL> constexpr int lds_bytes() { return ZROW_OFF + ZROW_BYTES; }
 
 struct Problem {
     const void* x; void* out;
     const void* w1; const void* w2;          // fp16 [64][3][3][64]
     const float *s1, *t1, *s2, *t2;          // folded BatchNorm: y = conv * s + t
-    float* pool;                             // optional [VR / 2][nstrips][64] pair sums of the stored output
+    float* pool;                             // optional [n][H / 2 + 1][nstrips][64] pair sums of the stored output
     uint32_t bytes;                          // bytes of one map
-    int VR, HP, W, pitch;                    // virtual rows n (H+2), H+2, interior width, bytes of a padded row
+    int VR, NP, J, W, pitch;                 // virtual rows n (H+2), pairs of image rows n H / 2, pairs per image H / 2, interior width, bytes of a padded row
     int nstrips, segs;                       // column strips; row segments per strip
     int dbg;                                 // timing-only experiments (AGP_FB_DBG), 0 in production
-    FastDiv d_hp, d_segs;
+    FastDiv d_j, d_segs;
 };
 struct Group {
     Problem p[MAXP];
@@ -104,16 +113,19 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         if (np > 3 && bid >= e2) { pid = 3; lb = bid - e2; }
     }
     const Problem& p = g.p[pid];
-    const int VR = p.VR, HP = p.HP, W = p.W, pitch = p.pitch, segs = p.segs;
-    const FastDiv d_hp = p.d_hp;
+    const int NP = p.NP, J = p.J, W = p.W, pitch = p.pitch, segs = p.segs;
+    const FastDiv d_j = p.d_j;
     const int dbg = p.dbg;
     const int strip = (int)fdiv((uint32_t)lb, p.d_segs);
     const int sk = lb - strip * segs;
-    // segment [Ra, Rb) of the strip's virtual rows, both even
-    const int Ra = (int)(((uint32_t)sk * (uint32_t)VR / (uint32_t)segs) & ~1u);         // (segs * VR < 2^32: checked by the host)
-    const int Rb = sk + 1 == segs ? VR : (int)(((uint32_t)(sk + 1) * (uint32_t)VR / (uint32_t)segs) & ~1u);
+    // segment [Pa, Pb) of the strip's pairs of image rows: the sizes differ by one pair at most
+    const int Pa = (int)((uint32_t)sk * (uint32_t)NP / (uint32_t)segs);                 // (segs * VR < 2^32: checked by the host)
+    const int Pb = sk + 1 == segs ? NP : (int)((uint32_t)(sk + 1) * (uint32_t)NP / (uint32_t)segs);
     const int x0 = strip * TW;                          // interior column of output slot 0
-    const int NS = (Rb - Ra + 3) >> 2;
+    const int NS = (Pb - Pa + 1) >> 1;
+    // conv1 also computes the seam pairs conv2 reads one row of: Pa - 1 and Pb, unless the segment starts / ends with an image
+    const bool seam_a = Pa != (int)fdiv((uint32_t)Pa, d_j) * J;
+    const int Pe1 = Pb != (int)fdiv((uint32_t)Pb, d_j) * J ? Pb : Pb - 1;               // conv1's last pair
 
     // ---- this wave's weights, 36 A fragments, in the K order igemm_kxr2 runs.
     // 32x32x16: w[((ky 2 + cc) 3 + kx) 2 + ks] = row perm23(l31) of the wave's 32 channels, K = 16 ks + 8 lh .. of the tap's chunk cc;
@@ -153,6 +165,7 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         tab[128 + tid] = p.s2[tid];
         tab[192 + tid] = p.t2[tid];
     }
+    if (tid < ZROW_BYTES / 16) *(u32x4*)(smem + ZROW_OFF + tid * 16) = u32x4{0u, 0u, 0u, 0u};
 
     // ---- LDS addressing.  Slot s of a ring row: 128 B at s * 128, its 16-byte chunk c stored at chunk c ^ ((s >> 1) & 7)
     // fragment reads: 32x32x16: slot l31 + kx, chunk lh + 4 cc + 2 ks (by XOR); 16x16x32: slot la + kx (+ 16: + 2048 B), chunk kq + 4 cc
@@ -200,19 +213,29 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         xp = xp < 0 ? 0 : (xp > W + 1 ? W + 1 : xp);     // clamped columns feed masked / unstored outputs only
         dvoff = xp * 128 + (((lane & 7) ^ ((s >> 1) & 7)) << 4);
     }
-    auto issue_rows = [&](int R0, int cnt) {
-#pragma unroll 4
+    // compact row c (pair c >> 1) -> virtual row: image i = pair / J, padded row 1 + c - i H
+    auto vrow = [&](int c) { return c + 2 * (int)fdiv((uint32_t)(c >> 1), d_j) + 1; };
+    auto issue_rows = [&](int c0, int cnt) {
+#pragma unroll 2
         for (int r = 0; r < cnt; ++r) {
-            const int R = R0 + r;
-            const int Rc = R < 0 ? 0 : (R >= VR ? VR - 1 : R);   // rows outside the batch feed zeroed intermediate rows only
-            const int so = __builtin_amdgcn_readfirstlane(Rc * pitch);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(XR + (R & (RING - 1)) * ROWB + pc * 1024), 16, dvoff, so, 0, 0);
+            const int c = c0 + r;
+            const int cc = c < 0 ? 0 : (c >= 2 * NP ? 2 * NP - 1 : c);   // rows outside the batch lie beyond an image border: never read
+            const int so = __builtin_amdgcn_readfirstlane(vrow(cc) * pitch);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, LDS_PTR(XR + (c & (RING - 1)) * ROWB + pc * 1024), 16, dvoff, so, 0, 0);
         }
     };
-    auto is_real = [&](int R) -> bool {                  // an image row (not a halo row, inside the batch); wave-uniform
-        if (R < 0 || R >= VR) return false;
-        const int yy = R - (int)fdiv((uint32_t)R, d_hp) * HP;
-        return yy >= 1 && yy <= HP - 2;
+    // pair P of the batch column: image, first / last pair of its image (wave-uniform)
+    struct Pair {
+        int img, j;
+        bool top, bot;
+    };
+    auto pair_of = [&](int P) {
+        Pair q;
+        q.img = (int)fdiv((uint32_t)P, d_j);
+        q.j = P - q.img * J;
+        q.top = q.j == 0;
+        q.bot = q.j == J - 1;
+        return q;
     };
     // The accumulators of one output row: 32 pixels x this wave's 32 channels (16 registers either way)
     struct Acc {
@@ -230,11 +253,12 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
                 for (int j = 0; j < 2; ++j) a.t[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
-    // Two rows at once: output rows R and R + 1 of `ring`'s convolution.  The rows share two of their input rows, so the pair reads
+    // Two rows at once: output rows c0 and c0 + 1 (compact, c0 even) of the convolution on the ring at byte `ring` of LDS; the row
+    // above / below them is the zero row where the pair is its image's first / last.  The rows share two of their input rows, so the pair reads
     // 4 x 12 KB-sized X fragments for its 72 (144) MFMAs instead of 6 x 12 (36 fragment reads per 36 MFMAs on two waves per SIMD
     // keep the LDS 60-75 % busy).  Each accumulator still sees its own MFMAs in igemm_kxr2's order.  `mid()` is issued among the
     // first MFMAs (deferred stores), `epi0()` when row R is complete, in front of the last MFMAs of row R + 1.
-    auto tile2 = [&](const char* ring, int R, Acc& a0, Acc& a1, auto&& mid, auto&& epi0) {
+    auto tile2 = [&](int ring, int c0, bool top, bool bot, Acc& a0, Acc& a1, auto&& mid, auto&& epi0) {
         acc_zero(a0);
         acc_zero(a1);
         // The fragment reads are SOFTWARE-PIPELINED by hand, PD read groups ahead of the MFMAs that use them (group = one
@@ -245,7 +269,10 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         constexpr int NG = M16 ? 24 : 48, PD = 2, NF = M16 ? 2 : 1;
         const char* rb[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) rb[q] = ring + __builtin_amdgcn_readfirstlane(((R - 1 + q) & (RING - 1)) * ROWB);
+        for (int q = 0; q < 4; ++q) {
+            const bool z = (q == 0 && top) || (q == 3 && bot);
+            rb[q] = smem + __builtin_amdgcn_readfirstlane(z ? ZROW_OFF : ring + ((c0 - 1 + q) & (RING - 1)) * ROWB);
+        }
         f16x8 fb[PD + 1][NF];
         auto load_group = [&](auto gc, auto slotc) {
             constexpr int g = decltype(gc)::value, sl = decltype(slotc)::value;
@@ -319,29 +346,23 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         for (int e = 0; e < 8; e += 2) { t0.pos2(v[e], v[e + 1]); t1.pos2(v[8 + e], v[9 + e]); }
         rg.pos2(ok0 ? t0.hi : 0.f, ok1 ? t1.hi : 0.f);
     };
-    // conv1: intermediate rows R, R + 1 (a row that is not an image row is conv2's zero padding)
-    auto write_ir = [&](int R, const Acc& acc, bool real) {
-        char* const dst = IR + __builtin_amdgcn_readfirstlane((R & (RING - 1)) * ROWB);
+    // conv1: intermediate row c of the IR ring
+    auto write_ir = [&](int c, const Acc& acc) {
+        char* const dst = IR + __builtin_amdgcn_readfirstlane((c & (RING - 1)) * ROWB);
         float v[16];
         bn(acc, v);
-        if constexpr (RG) track16(v, real && ctk0, real && ctk1);
+        if constexpr (RG) track16(v, ctk0, ctk1);
         u32x4 o0 = pack8_h_lo(v, 0.f), o1 = pack8_h_lo(v + 8, 0.f);
-        if (!(real && cin0)) o0 = u32x4{0u, 0u, 0u, 0u};
-        if (!(real && cin1)) o1 = u32x4{0u, 0u, 0u, 0u};
+        if (!cin0) o0 = u32x4{0u, 0u, 0u, 0u};
+        if (!cin1) o1 = u32x4{0u, 0u, 0u, 0u};
         *(u32x4*)(dst + wr0) = o0;
         *(u32x4*)(dst + wr1) = o1;
     };
-    auto conv1_pair = [&](int R) {
-        const bool real0 = is_real(R), real1 = is_real(R + 1);
+    auto conv1_pair = [&](int P) {
+        const Pair q = pair_of(P);
         Acc a0, a1;
-        if (real0 || real1) {
-            tile2(XR, R, a0, a1, [] {}, [&] { write_ir(R, a0, real0); });
-            write_ir(R + 1, a1, real1);
-        } else {
-            acc_zero(a0);
-            write_ir(R, a0, false);
-            write_ir(R + 1, a0, false);
-        }
+        tile2(0, 2 * P, q.top, q.bot, a0, a1, [] {}, [&] { write_ir(2 * P, a0); });
+        write_ir(2 * P + 1, a1);
     };
     // POOL: channel sums on the matrix pipe (see the header).  A = ones (the pixels that are not stored are zeroed on their way into
     // the strip), B = the strip read transposed: block (ct, hh) = pixels 8 (lane >> 4) + 4 hh + q, channels 16 ct + 4 p .. + 3,
@@ -364,8 +385,8 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
     };
     auto flush_pending = [&]() { store_lines(pl0, pl1, poff); poff = -1; };
     // BN + residual + ReLU of one row -> fp16 -> the wave's strip -> line layout registers (l0, l1)
-    auto epi2 = [&](int R, const Acc& acc, bool real, u32x4& l0, u32x4& l1, bool first) {
-        const char* const rsrc = XR + __builtin_amdgcn_readfirstlane((R & (RING - 1)) * ROWB);
+    auto epi2 = [&](int c, const Acc& acc, u32x4& l0, u32x4& l1, bool first) {
+        const char* const rsrc = XR + __builtin_amdgcn_readfirstlane((c & (RING - 1)) * ROWB);
         u32x4 r0 = {0u, 0u, 0u, 0u}, r1 = r0;
         if (!(dbg & 16)) { r0 = *(const u32x4*)(rsrc + rr0); r1 = *(const u32x4*)(rsrc + rr1); }
         float v[16], rf[16];
@@ -374,7 +395,7 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         unpack8_h(r1, rf + 8);
 #pragma unroll
         for (int e = 0; e < 16; ++e) v[e] += rf[e];
-        if constexpr (RG) track16(v, real && sok0, real && sok1);
+        if constexpr (RG) track16(v, sok0, sok1);
         u32x4 o0 = pack8_h_lo(v, 0.f), o1 = pack8_h_lo(v + 8, 0.f);
         // (LDS operations of one wave execute in order: the reads below see the writes above, and the next row's writes come
         // after these reads)
@@ -389,12 +410,11 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
         if constexpr (POOL) {
             if (first) { pacc[0] = f32x4{0.f, 0.f, 0.f, 0.f}; pacc[1] = pacc[0]; }
             {
-                // (no branch among the MFMAs, and the transposed reads need EXEC all ones: a row that is not an image row multiplies
-                // by A = 0 instead of being skipped)
+                // (the transposed reads need EXEC all ones)
                 const int tpx = 8 * (lane >> 4) + ((lane >> 2) & 3), pp = lane & 3;
                 const int tr0 = tpx * 64 + (((pp >> 1) ^ ((tpx >> 1) & 3)) << 4) + 8 * (pp & 1);      // hh = 1: 4 pixels on = (+ 256) ^ 32
                 typedef __attribute__((ext_vector_type(4))) short s16x4;
-                const uint32_t one2 = real ? 0x3C003C00u : 0u;
+                const uint32_t one2 = 0x3C003C00u;
                 const f16x8 ones = __builtin_bit_cast(f16x8, u32x4{one2, one2, one2, one2});
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
@@ -406,54 +426,48 @@ __global__ void __launch_bounds__(512, 2) fblock64_kernel(Group g, RF... rf) {
             }
         }
     };
-    auto conv2_pair = [&](int R) {
-        const bool real0 = is_real(R), real1 = is_real(R + 1);
-        if (!(real0 || real1)) {
-            if constexpr (POOL) { pacc[0] = f32x4{0.f, 0.f, 0.f, 0.f}; pacc[1] = pacc[0]; }
-            return;
-        }
+    // output rows 2 P, 2 P + 1, then the pair's channel sums leave (every row of the 16 x 16 result holds them: row 0)
+    auto conv2_pair = [&](int P) {
+        const Pair q = pair_of(P);
+        const int V = 2 * P + 2 * q.img + 1;             // virtual row of compact row 2 P
         Acc a0, a1;
         u32x4 q0, q1;
-        tile2(IR, R, a0, a1, flush_pending, [&] { epi2(R, a0, real0, q0, q1, true); });
-        epi2(R + 1, a1, real1, pl0, pl1, false);
-        store_lines(q0, q1, real0 ? __builtin_amdgcn_readfirstlane(R * pitch) : -1);
-        poff = real1 ? __builtin_amdgcn_readfirstlane((R + 1) * pitch) : -1;
-    };
-    // after the pair (R, R + 1): its channel sums leave (every row of the 16 x 16 result holds them: row 0)
-    auto pool_flush = [&](int R) {
+        tile2(RING * ROWB, 2 * P, q.top, q.bot, a0, a1, flush_pending, [&] { epi2(2 * P, a0, q0, q1, true); });
+        epi2(2 * P + 1, a1, pl0, pl1, false);
+        store_lines(q0, q1, __builtin_amdgcn_readfirstlane(V * pitch));
+        poff = __builtin_amdgcn_readfirstlane((V + 1) * pitch);
         if constexpr (POOL) {
             if (p.pool != nullptr && lane < 16) {
-                float* o = p.pool + ((size_t)(R >> 1) * p.nstrips + strip) * 64 + 32 * cA + lane;
+                const int es = p.nstrips * 64;           // floats of an entry
+                float* o = p.pool + (size_t)(q.img * (J + 1) + q.j) * es + strip * 64 + 32 * cA + lane;
                 o[0] = pacc[0][0];
                 o[16] = pacc[1][0];
+                if (q.bot) { o[es] = 0.f; o[es + 16] = 0.f; }
             }
         }
     };
 
-    // ---- prologue: input rows Ra - 2 .. Ra + 5, then the two intermediate rows in front of the first step
-    if (role == 0) issue_rows(Ra - 2, 8);
+    // ---- prologue: the input rows of conv1's pairs Pa - 1 .. Pa + 2, then the seam pair and the first pair on the four conv1 waves
+    if (role == 0) issue_rows(2 * Pa - 3, 10);
     // (the BUILTIN, not inline asm: the compiler's wait-count pass must see that the weight loads have landed, or it repeats the
     // vmcnt countdown of their first use inside the step loop)
     __builtin_amdgcn_s_waitcnt(0x0070);                  // vmcnt(0) lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
-    if (role == 0 && pA == 0) conv1_pair(Ra - 1);
+    if (role == 0 && (pA == 1 || seam_a)) conv1_pair(Pa - 1 + pA);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    // ---- steps: conv1 writes intermediate rows Ra + 1 + 4 t .. + 3 while conv2 turns rows Ra + 4 (t - 1) .. + 3 into output
+    // ---- steps: conv1 writes the intermediate pairs Pa + 2 t + 1, + 2 while conv2 turns pairs Pa + 2 (t - 1), + 1 into output
     for (int t = 0; t <= NS; ++t) {
         if (role == 0) {
             if (t < NS) {
-                if (t + 1 < NS && !(dbg & 2)) issue_rows(Ra + 4 * t + 6, 4);       // what conv1 reads in step t + 1
-                const int R = Ra + 1 + 4 * t + 2 * pA;
-                if (R <= Rb) conv1_pair(R);
+                if (t + 1 < NS && !(dbg & 2)) issue_rows(2 * Pa + 4 * t + 7, 4);   // what conv1 reads in step t + 1
+                const int P = Pa + 2 * t + 1 + pA;
+                if (P <= Pe1) conv1_pair(P);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else if (t >= 1) {
-            const int R = Ra + 4 * (t - 1) + 2 * pA;
-            if (R < Rb) {                                            // (Rb is even: R + 1 < Rb too)
-                conv2_pair(R);
-                pool_flush(R);
-            }
+            const int P = Pa + 2 * (t - 1) + pA;
+            if (P < Pb) conv2_pair(P);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (!(dbg & 4)) __builtin_amdgcn_s_barrier();
@@ -501,23 +515,46 @@ extern "C" int agp_bblock64_fwd_grouped(const agp_bblock64_desc* descs, int n, v
         p.s1 = d->scale1; p.t1 = d->shift1; p.s2 = d->scale2; p.t2 = d->shift2;
         p.pool = d->pool_partial;
         pool = pool || d->pool_partial;
-        p.HP = d->h + 2; p.VR = d->n * p.HP; p.W = d->w; p.pitch = (d->w + 2) * 128;
+        p.J = d->h / 2; p.NP = d->n * p.J; p.VR = d->n * (d->h + 2); p.W = d->w; p.pitch = (d->w + 2) * 128;
         p.bytes = (uint32_t)((int64_t)p.VR * p.pitch);
         p.nstrips = (d->w + TW - 1) / TW;
-        p.d_hp = make_fastdiv((uint32_t)p.HP);
+        p.d_j = make_fastdiv((uint32_t)p.J);
         p.dbg = AGP_TUNE("FB_DBG", 0);
-        total += (int64_t)p.nstrips * p.VR;
+        total += (int64_t)p.nstrips * p.NP;
     }
-    // row segments per strip: about one workgroup per CU, every workgroup the same number of rows (>= 16)
+    // row segments per strip, cut in pairs of image rows: one workgroup per CU where the rows allow it (>= 16 rows per segment),
+    // a problem's segments within one pair of each other.  First every problem's share of the CUs rounded down, then the CUs
+    // that are left go, one segment per strip at a time, to the problem whose segments are the longest (the launch ends with
+    // them; of equal ones the larger problem) as long as a whole set of its strips still fits.
     const int cus = fb_num_cus();
+    int64_t segs[MAXP], smax[MAXP];
+    int64_t rem = cus;
+    for (int i = 0; i < n; ++i) {
+        const Problem& p = g.p[i];
+        smax[i] = p.NP / 8 > 1 ? p.NP / 8 : 1;
+        while (smax[i] > 1 && smax[i] * (int64_t)p.VR >= (1ll << 32)) --smax[i];
+        const int64_t s = (int64_t)p.NP * cus / total;
+        segs[i] = s < 1 ? 1 : (s > smax[i] ? smax[i] : s);
+        rem -= p.nstrips * segs[i];
+    }
+    for (;;) {
+        int best = -1;
+        for (int i = 0; i < n; ++i) {
+            const Problem& p = g.p[i];
+            if (segs[i] >= smax[i] || p.nstrips > rem) continue;
+            if (best < 0) { best = i; continue; }
+            const Problem& b = g.p[best];
+            const int64_t li = (int64_t)p.NP * segs[best], lb = (int64_t)b.NP * segs[i];        // NP / segs, cross-multiplied
+            if (li > lb || (li == lb && (int64_t)p.nstrips * p.NP > (int64_t)b.nstrips * b.NP)) best = i;
+        }
+        if (best < 0) break;
+        ++segs[best];
+        rem -= g.p[best].nstrips;
+    }
     int wg = 0;
     for (int i = 0; i < n; ++i) {
         Problem& p = g.p[i];
-        int64_t s = (int64_t)p.VR * cus / total;
-        const int64_t smax = p.VR / 16 > 1 ? p.VR / 16 : 1;
-        s = s < 1 ? 1 : (s > smax ? smax : s);
-        while (s > 1 && s * (int64_t)p.VR >= (1ll << 32)) --s;
-        p.segs = (int)s;
+        p.segs = (int)segs[i];
         p.d_segs = make_fastdiv((uint32_t)p.segs);
         wg += p.nstrips * p.segs;
         g.wg_end[i] = wg;
