@@ -84,6 +84,11 @@ SIGNATURES = {
     "agp_pack_f32_to_nhwc": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "agp_pack_f32_to_nhwc4_h16": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "agp_pack_u8_cams_to_nhwc": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _I, _P, _P, _P]),
+    "agp_resize_ksize": (_I, [_I, _I]),
+    "agp_resize_coeffs": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "agp_resized_size": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "agp_resize_u8_cams": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "agp_resize_pack_u8_cams": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_F), C.POINTER(_F), _I, _P, _P, _P]),
     "agp_unpack_nhwc_to_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "agp_map_zero_halo": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "agp_map_absmax": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),

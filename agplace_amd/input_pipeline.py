@@ -27,6 +27,10 @@ handed to worker processes through shared memory); nothing here touches pixel va
 The lidar half of a query ships as raw scans (`points` [N,3] + `point_offsets` [B+1]; quantisation, deduplication and the
 augmentation rotation run on the device: SparseTensor.from_points_capacity); `random_z_rotation` draws the
 rotation the reference's collate function applies on the CPU.
+
+The camera half can ship one step earlier still: the DECODED frames as they leave the image decoder (`query_frames`
+[b,ncam,H0,W0,3], `db_frames`), resized on the device (ops.pack_cameras_resized_u8).  PinnedRing needs no change
+for that: a slot's tensors have whatever shapes the caller names, so a ring of frames is a ring with larger uint8 entries.
 """
 import math
 

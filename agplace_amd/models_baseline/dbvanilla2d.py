@@ -3,7 +3,8 @@
 `DBVanilla2D(mode='db', dim=args.features_dim)`; `model(data_dict, mode='db') -> {'embedding'}`.
 Per map type: ImageFE -> GeM -> MLP(Linear, LayerNorm, ReLU, Linear); stack over map types,
 F.normalize, mean over map types; db_map is [b,nmap,3,h,w] (cache/test) or [b,ndb,nmap,3,h,w]
-(train).  state_dict keys: dbimage_fes.{i}.fe.*, dbimage_pools.{i}.p, dbimage_mlps.{i}.seq.{0,1,3}.*
+(train), fp32, or the same tiles decoded as uint8 [...,h,w,3]; `db_frames` (uint8 [...,H0,W0,3]) instead of db_map: decoded
+frames, resized on the device by Resize(opt.db_resize).  state_dict keys: dbimage_fes.{i}.fe.*, dbimage_pools.{i}.p, dbimage_mlps.{i}.seq.{0,1,3}.*
 All arithmetic runs in libagplace_hip.so.  .eval()+no_grad = inference; .train() = end-to-end training
 (batch-statistics BatchNorm + conv backward on HIP kernels, train_fns.TrunkFn).
 """
@@ -94,24 +95,41 @@ class DBVanilla2D(nn.Module):
 
     def _forward_db(self, data_dict, train, trunk_maps, out_rows, defer_head):
         opt = self.opt
-        db_map = data_dict['db_map']
-        u8 = db_map.dtype == torch.uint8
-        if u8:
-            # decoded uint8 tiles [b,nmap,h,w,3] or [b,ndb,nmap,h,w,3] (HWC, as the image decoder leaves them): ToTensor +
-            # Normalize happen on the device inside the stem's input packing (ops.pack_cameras_u8, 4x fewer bytes over PCIe)
-            if db_map.shape[-1] != 3 or db_map.dim() not in (5, 6):
-                raise NotImplementedError("uint8 db_map must be [b,nmap,h,w,3] or [b,ndb,nmap,h,w,3]")
-            db_map = db_map.permute(*range(db_map.dim() - 3), -1, -3, -2)      # logical [...,3,h,w] view, no copy
-        if db_map.dim() == 5:      # [b,nmap,3,h,w]  caching / testing
-            mode = 'cachetest'
-            b, nmap, c, h, w = db_map.shape
-            db_map = db_map.unsqueeze(1)
-            ndb = 1
-        elif db_map.dim() == 6:    # [b,ndb,nmap,3,h,w]  training layout
-            mode = 'train'
-            b, ndb, nmap, c, h, w = db_map.shape
+        frames = data_dict.get('db_frames')
+        if frames is not None:
+            # decoded uint8 frames [b,nmap,H0,W0,3] or [b,ndb,nmap,H0,W0,3]: resized by torchvision's Resize(opt.db_resize) rule with
+            # PIL's arithmetic, normalised and packed in ONE launch in front of the stem (ops.RawFrames); the result
+            # is bit-identical to `db_map` = the resized uint8 tiles
+            if 'db_map' in data_dict:
+                raise ValueError("DBVanilla2D.forward_db: pass `db_frames` or `db_map`, not both")
+            if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() not in (5, 6) or frames.shape[-1] != 3:
+                raise ValueError("DBVanilla2D.forward_db: `db_frames` must be uint8 [b,nmap,H0,W0,3] or [b,ndb,nmap,H0,W0,3]")
+            h, w = ops.resized_size(frames.shape[-3], frames.shape[-2], opt.db_resize)
+            mode = 'cachetest' if frames.dim() == 5 else 'train'
+            if frames.dim() == 5:
+                frames = frames.unsqueeze(1)
+            b, ndb, nmap = frames.shape[:3]
+            c, u8, dev = 3, False, frames.device
         else:
-            raise NotImplementedError
+            db_map = data_dict['db_map']
+            dev = db_map.device
+            u8 = db_map.dtype == torch.uint8
+            if u8:
+                # decoded uint8 tiles [b,nmap,h,w,3] or [b,ndb,nmap,h,w,3] (HWC, as the image decoder leaves them): ToTensor +
+                # Normalize happen on the device inside the stem's input packing (ops.pack_cameras_u8, 4x fewer bytes over PCIe)
+                if db_map.shape[-1] != 3 or db_map.dim() not in (5, 6):
+                    raise NotImplementedError("uint8 db_map must be [b,nmap,h,w,3] or [b,ndb,nmap,h,w,3]")
+                db_map = db_map.permute(*range(db_map.dim() - 3), -1, -3, -2)      # logical [...,3,h,w] view, no copy
+            if db_map.dim() == 5:      # [b,nmap,3,h,w]  caching / testing
+                mode = 'cachetest'
+                b, nmap, c, h, w = db_map.shape
+                db_map = db_map.unsqueeze(1)
+                ndb = 1
+            elif db_map.dim() == 6:    # [b,ndb,nmap,3,h,w]  training layout
+                mode = 'train'
+                b, ndb, nmap, c, h, w = db_map.shape
+            else:
+                raise NotImplementedError
         assert c == 3
         prec = 3 if train else opt.mfma_precision
         if (not train and torch.is_grad_enabled() and getattr(self, "_frozen_backbone", False) and prec == 4
@@ -123,12 +141,16 @@ class DBVanilla2D(nn.Module):
         if not train and not torch.is_grad_enabled() and opt.fused_vector_path and nmap <= 4 and all(
                 m.seq[0].in_features <= 256 and m.seq[0].in_features % 32 == 0 and m.seq[0].out_features == 256
                 and m.seq[3].out_features == 256 for m in self.dbimage_mlps):
-            fused = VecProgram(b * ndb, db_map.device)
+            fused = VecProgram(b * ndb, dev)
         if True:
             vecs = []
             for i in range(nmap):
                 j = 0 if opt.share_dbfe is True else i
-                x = db_map[:, :, i].reshape(b * ndb, c, h, w)       # view when possible; strides are honoured
+                if frames is not None:
+                    f = frames[:, :, i]
+                    x = ops.RawFrames(f.reshape(b * ndb, 1, *f.shape[2:]), h, w)      # one "camera" per tile
+                else:
+                    x = db_map[:, :, i].reshape(b * ndb, c, h, w)       # view when possible; strides are honoured
                 if u8:
                     x = x.permute(0, 2, 3, 1).unsqueeze(1)          # uint8 [n,1,h,w,3]: one "camera" per tile (contiguous again)
                 if train:
@@ -162,7 +184,7 @@ class DBVanilla2D(nn.Module):
                 vecs.append(v)
             if fused is not None:
                 if nmap > 1:
-                    wmean = torch.full((1,), 1.0 / nmap, device=db_map.device)
+                    wmean = torch.full((1,), 1.0 / nmap, device=dev)
                     fused.wsum(2, [2 + i for i in range(nmap)], [wmean] * nmap)
                 if opt.final_l2 is True:
                     fused.l2norm(2, 2)

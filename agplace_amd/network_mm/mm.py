@@ -14,6 +14,9 @@ neither is present data_dict carries the voxel branch's dense outputs instead:
     vox_levels  [ [b,64], [b,128], [b,256] ]   globally pooled v1..v3  (fuse_block_toshallow.py:83)
     voxfeatvec  [b,256]                          MinkGeM(voxfeatmap)      (mm.py:89)
     stg2voxvec  [b,256], voxvec_fuse [b,256]     stage-2 voxel outputs    (stage2fuse_blockadd.py:201,207)
+The cameras enter as `query_image` -- the normalised fp32 panorama [b,3,h,w] or already resized uint8 tiles [b,ncam,h,w,3] -- or
+as `query_frames`: decoded uint8 frames [b,ncam,H0,W0,3], resized on the device by torchvision's Resize(opt.q_resize) rule with
+PIL's arithmetic and then handled exactly like the uint8 tiles.
 Execution modes:
   * .eval() under torch.no_grad(): inference, BatchNorm folded into the conv epilogues.
   * .train() with gradients enabled: end-to-end training.  Batch-statistics BatchNorm and the conv
@@ -176,7 +179,17 @@ class MM(nn.Module):
 
     # ==== query
     def query_image(self, data_dict):
-        """The image tensor the trunk sees (mm.py:70-75: drop='image' zeroes it)."""
+        """The image tensor the trunk sees (mm.py:70-75: drop='image' zeroes it); for `query_frames` the frames with the size
+        Resize(opt.q_resize) gives them (ops.RawFrames: resized, normalised and packed in one launch in front of the stem)."""
+        if 'query_frames' in data_dict:
+            if 'query_image' in data_dict:
+                raise ValueError("MM.forward_q: pass `query_frames` or `query_image`, not both")
+            frames = data_dict['query_frames']
+            if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+                raise ValueError("MM.forward_q: `query_frames` must be uint8 [b, ncam, H0, W0, 3]")
+            if self.drop == 'image':
+                raise NotImplementedError("drop='image' with uint8 camera frames")
+            return ops.RawFrames(frames, *ops.resized_size(frames.shape[2], frames.shape[3], self.opt.q_resize))
         image = data_dict['query_image']
         if self.drop == 'image':
             if image.dtype == torch.uint8:

@@ -257,6 +257,129 @@ def pack_cameras_u8(img_u8, prec, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None
     return out
 
 
+# ---- camera front end (csrc/camera.hip): the resize in front of the uint8 tiles, Pillow's arithmetic bit for bit
+def resized_size(h, w, size):
+    """(h, w) after torchvision's Resize(size) with an int size: the shorter edge becomes `size`, the longer
+    int(size * long / short) (agp_resized_size)."""
+    oh, ow = C.c_int(), C.c_int()
+    rc = _L().agp_resized_size(int(h), int(w), int(size), C.byref(oh), C.byref(ow))
+    if rc != 0:
+        raise ValueError(f"resized_size({h}, {w}, {size}): sizes must be positive")
+    return oh.value, ow.value
+
+
+def _resize_hw(H0, W0, size_or_hw):
+    if isinstance(size_or_hw, (tuple, list)):
+        h, w = size_or_hw
+        return int(h), int(w)
+    return resized_size(H0, W0, size_or_hw)
+
+
+_RESIZE_TABLES = {}      # (device, in, out) -> (k int32 [out, ksize], bounds int32 [out, 2]) on the device
+
+
+def resize_tables(n_in, n_out, device):
+    """The cached device tables of one axis (agp_resize_coeffs on the host, one upload).  Never built inside a stream capture:
+    a first use there raises RuntimeError -- call prepare_resize (or run one eager forward) before capturing."""
+    key = (str(torch.device(device)), int(n_in), int(n_out))
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"agplace_amd: the resize tables of {n_in} -> {n_out} pixels are not on {key[0]} yet and cannot be "
+                               "uploaded inside a stream capture; call ops.prepare_resize(H0, W0, h, w, device) first")
+        L = _L()
+        ks = L.agp_resize_ksize(int(n_in), int(n_out))
+        if ks < 0:
+            raise NotImplementedError(f"resize {n_in} -> {n_out}: sizes must lie in 1 .. 16384")
+        k = torch.empty((int(n_out), ks), dtype=torch.int32)
+        b = torch.empty((int(n_out), 2), dtype=torch.int32)
+        check(L.agp_resize_coeffs(int(n_in), int(n_out), C.cast(k.data_ptr(), C.POINTER(C.c_int32)),
+                                  C.cast(b.data_ptr(), C.POINTER(C.c_int32))), "agp_resize_coeffs")
+        t = _RESIZE_TABLES[key] = (k.to(device), b.to(device))
+    return t
+
+
+def prepare_resize(H0, W0, h, w, device):
+    """Build and upload the tables of (H0, W0) -> (h, w) on `device` (a no-op once cached): to be called before a stream capture
+    whose first use of this geometry would otherwise happen inside it."""
+    resize_tables(W0, w, device)
+    resize_tables(H0, h, device)
+
+
+def _check_frames(frames, what):
+    _need_cuda(frames, what)
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or 0 in frames.shape:
+        raise ValueError(f"{what} expects uint8 frames [n, ncam, H0, W0, 3]")
+
+
+def _resize_call(rc, what, H0, W0, h, w):
+    if rc == _lib.E_UNSUPPORTED:
+        raise NotImplementedError(f"{what}: {H0}x{W0} -> {h}x{w} is outside the supported geometry (every size in 1 .. 16384, "
+                                  "at most an 8-fold reduction per axis)")
+    check(rc, what)
+
+
+def resize_cameras_u8(frames, size_or_hw):
+    """uint8 [n, ncam, H0, W0, 3] decoded frames (HWC, on the GPU) -> uint8 [n, ncam, h, w, 3]: PIL's bilinear resize, the bytes
+    torchvision's Resize(size, antialias=True) gives for the PIL frame (reference datasets_ws_nuscenes.py:607-612).
+    size_or_hw: an int (Resize(int)'s rule, resized_size) or (h, w)."""
+    _check_frames(frames, "resize_cameras_u8")
+    frames = frames.contiguous()
+    n, ncam, H0, W0, _ = frames.shape
+    h, w = _resize_hw(H0, W0, size_or_hw)
+    if h < 1 or w < 1:
+        raise ValueError("resize_cameras_u8: the output size must be positive")
+    if H0 > 8 * h or W0 > 8 * w or max(H0, W0, h, w) > 16384:
+        _resize_call(_lib.E_UNSUPPORTED, "agp_resize_u8_cams", H0, W0, h, w)
+    (kx, bx), (ky, by) = resize_tables(W0, w, frames.device), resize_tables(H0, h, frames.device)
+    out = torch.empty((n, ncam, h, w, 3), dtype=torch.uint8, device=frames.device)
+    _resize_call(_L().agp_resize_u8_cams(ptr(frames), n, ncam, H0, W0, h, w, ptr(kx), ptr(bx), ptr(ky), ptr(by), ptr(out),
+                                         _lib.stream()), "agp_resize_u8_cams", H0, W0, h, w)
+    return out
+
+
+def pack_cameras_resized_u8(frames, size_or_hw, prec, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """uint8 [n, ncam, H0, W0, 3] decoded frames -> the stem's input map in ONE launch: resize_cameras_u8 + pack_cameras_u8
+    (bit-identical to that pair; the resized uint8 tiles are never written to memory)."""
+    _check_frames(frames, "pack_cameras_resized_u8")
+    frames = frames.contiguous()
+    n, ncam, H0, W0, _ = frames.shape
+    h, w = _resize_hw(H0, W0, size_or_hw)
+    if h < 1 or w < 1:
+        raise ValueError("pack_cameras_resized_u8: the output size must be positive")
+    if H0 > 8 * h or W0 > 8 * w or max(H0, W0, h, w) > 16384:
+        _resize_call(_lib.E_UNSUPPORTED, "agp_resize_pack_u8_cams", H0, W0, h, w)
+    (kx, bx), (ky, by) = resize_tables(W0, w, frames.device), resize_tables(H0, h, frames.device)
+    if out is None:
+        out = SplitMap.alloc(n, h, ncam * w, 4, 3, prec, frames.device)
+    elif (out.n, out.h, out.w, out.c, out.pad) != (n, h, ncam * w, 4, 3):
+        raise ValueError("pack_cameras_resized_u8: `out` must be the NHWC4 halo-3 map [n, h, ncam * w]")
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    _resize_call(_L().agp_resize_pack_u8_cams(ptr(frames), n, ncam, H0, W0, h, w, ptr(kx), ptr(bx), ptr(ky), ptr(by), m, s, 3,
+                                              ptr(out.hi), ptr(out.lo), _lib.stream()), "agp_resize_pack_u8_cams", H0, W0, h, w)
+    return out
+
+
+class RawFrames:
+    """Decoded uint8 frames [n, ncam, H0, W0, 3] that enter a trunk resized to (h, w): a stem input like the uint8 tiles, of
+    geometry (n, h, ncam * w), packed by pack_cameras_resized_u8 (ResNet._input_geometry / _stem_input).  The stem kernels that
+    read their input themselves do not take it (stem_walk_reads is False)."""
+    __slots__ = ("frames", "h", "w")
+
+    def __init__(self, frames, h, w):
+        _check_frames(frames, "RawFrames")
+        self.frames, self.h, self.w = frames, int(h), int(w)
+
+    @property
+    def shape(self):
+        return self.frames.shape
+
+    @property
+    def device(self):
+        return self.frames.device
+
+
 def split_weight(w, fmt=_lib.FMT_BF16, want_lo=True):
     """fp32 tensor -> (hi, lo) 16-bit planes (bf16 or fp16) on the same device (kernel: agp_split_f32)."""
     _need_cuda(w, "split_weight")

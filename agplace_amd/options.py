@@ -23,6 +23,11 @@ class Options:
     recall_values: List[int] = field(default_factory=lambda: [1, 5, 10, 20])
     # voxel size in metres of the lidar front end (reference tools/options.py:61); read when MM.forward_q gets raw `points`
     quant_size: float = 2.0
+    # shorter edge in pixels that the camera front end resizes decoded frames to (reference tools/options.py:64,66; torchvision
+    # Resize(int) on the PIL frame): read when MM.forward_q gets `query_frames` / DBVanilla2D.forward_db gets `db_frames`.  The
+    # reference's nuScenes loader hard-codes 192 for the cameras (datasets_ws_nuscenes.py:608): set q_resize=192 there
+    q_resize: int = 256
+    db_resize: int = 256
     # database model
     dbimage_fe: str = "resnet18"
     dbimage_fe_layers: str = "2_2_2"
@@ -130,6 +135,10 @@ class Options:
             raise ValueError(f"train_dgrad_products {self.train_dgrad_products!r}: 3 (tight) | 1 (one-product data gradients)")
         if not (isinstance(self.odeint_max_steps, int) and 1 <= self.odeint_max_steps <= 4096):
             raise ValueError(f"odeint_max_steps {self.odeint_max_steps!r}: an integer in 1 .. 4096")
+        for name in ("q_resize", "db_resize"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} {v!r}: a positive integer (the shorter edge after the resize)")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
 

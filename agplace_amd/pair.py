@@ -12,7 +12,7 @@ Outputs are bit-identical to calling the two models separately (tests/test_gpu_m
 import torch
 
 
-from . import range_guard, resnet
+from . import ops, range_guard, resnet
 
 RIDER = True      # False: the database head as a launch of its own behind the query network's tail
 
@@ -30,12 +30,38 @@ def can_pair(modelq, modeldb, qdata, dbdata):
     return all((f.fe_type, f.nstages) == (fq.fe_type, fq.nstages) for f in fdbs[:nmap])
 
 
+def _resized_tiles(modelq, modeldb, qdata, dbdata):
+    """Decoded frames (`query_frames` / `db_frames`) -> the resized uint8 tiles under `query_image` / `db_map`, which the pair
+    then embeds as it always has: one launch of the camera front end's uint8 mode per key (ops.resize_cameras_u8), bit-identical
+    to the fused resize + pack of the separate forwards (tests/test_gpu_camera.py)."""
+    if 'query_frames' in qdata:
+        if 'query_image' in qdata:
+            raise ValueError("embed_pair: pass `query_frames` or `query_image`, not both")
+        f = qdata['query_frames']
+        if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 5 or f.shape[-1] != 3:
+            raise ValueError("embed_pair: `query_frames` must be uint8 [b, ncam, H0, W0, 3]")
+        qdata = {k: v for k, v in qdata.items() if k != 'query_frames'}
+        qdata['query_image'] = ops.resize_cameras_u8(f, modelq.opt.q_resize)
+    if 'db_frames' in dbdata:
+        if 'db_map' in dbdata:
+            raise ValueError("embed_pair: pass `db_frames` or `db_map`, not both")
+        f = dbdata['db_frames']
+        if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() not in (5, 6) or f.shape[-1] != 3:
+            raise ValueError("embed_pair: `db_frames` must be uint8 [b,nmap,H0,W0,3] or [b,ndb,nmap,H0,W0,3]")
+        t = ops.resize_cameras_u8(f.reshape(-1, *f.shape[-4:]), modeldb.opt.db_resize)
+        dbdata = {k: v for k, v in dbdata.items() if k != 'db_frames'}
+        dbdata['db_map'] = t.view(*f.shape[:-3], *t.shape[-3:])
+    return qdata, dbdata
+
+
 def embed_pair(modelq, modeldb, qdata, dbdata):
     """(modelq(qdata, 'q'), modeldb(dbdata, 'db')) with the image trunks run in lock-step.  Falls back to the two
     separate forwards when the models cannot be paired (training, different trunk architectures).
+    Decoded frames (`query_frames`, `db_frames`) are resized to uint8 tiles first (_resized_tiles) and continue as tiles.
     fp16 range guard (Options.fp16_range_guard): the lock-step trunks of BOTH models report through the query model's word when
     its guard is on (else the database model's): a saturated database tile then shows in modelq.fp16_range_ok() /
     poll_fp16_range(), whose message names the database trunks as a possible source."""
+    qdata, dbdata = _resized_tiles(modelq, modeldb, qdata, dbdata)
     if not can_pair(modelq, modeldb, qdata, dbdata):
         return modelq(qdata, mode='q'), modeldb(dbdata, mode='db')
     # the fp16 range guard: the grouped trunk launches below run outside either model's forward and hold BOTH models' image trunks
@@ -161,7 +187,7 @@ class CapturedPair:
     changing the exponents afterwards invalidates the capture exactly like a weight reload does -- capture again."""
 
     def __init__(self, modelq, modeldb, qdata, dbdata, stream=None, warmup=2, poll_every=8):
-        dev = qdata['query_image'].device
+        dev = (qdata['query_frames'] if 'query_frames' in qdata else qdata['query_image']).device
         self.modelq, self.modeldb, self.qdata, self.dbdata = modelq, modeldb, qdata, dbdata
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
         self.poll_every, self._n = max(1, int(poll_every)), 0

@@ -166,9 +166,12 @@ class ResNet(nn.Module):
 
     @staticmethod
     def _input_geometry(x):
-        """(n, h, w, device) of a stem input: fp32 [n,3,h,w], uint8 camera tiles [n,ncam,h,w,3] or a packed SplitMap."""
+        """(n, h, w, device) of a stem input: fp32 [n,3,h,w], uint8 camera tiles [n,ncam,h,w,3], decoded frames to be resized
+        (ops.RawFrames) or a packed SplitMap."""
         if isinstance(x, ops.SplitMap):
             return x.n, x.h, x.w, x.hi.device
+        if isinstance(x, ops.RawFrames):
+            return x.shape[0], x.h, x.shape[1] * x.w, x.device
         if x.dtype == torch.uint8:
             n, ncam, h, w, _ = x.shape
             return n, h, ncam * w, x.device
@@ -177,7 +180,8 @@ class ResNet(nn.Module):
 
     def _stem_input(self, x, tag, prec, lo=0, hi=None, h16=False):
         """Images [lo, hi) of a stem input -- fp32 [n,3,h,w] image batch, uint8 [n,ncam,h,w,3] camera tiles (device-side
-        input pipeline, ops.pack_cameras_u8) or an already packed NHWC4 halo-3 SplitMap -- as the stem's input map (a
+        input pipeline, ops.pack_cameras_u8), decoded uint8 frames with their target size (ops.RawFrames: resized and packed in
+        one launch, ops.pack_cameras_resized_u8) or an already packed NHWC4 halo-3 SplitMap -- as the stem's input map (a
         slice of the full-batch workspace map)."""
         n, h, w, dev = self._input_geometry(x)
         hi = n if hi is None else hi
@@ -186,11 +190,14 @@ class ResNet(nn.Module):
                 raise ValueError("stem input map must be NHWC4 with halo 3 in the conv's storage format")
             return ops.slice_map(x, lo, hi)
         # h16 (training, fp32 images): the fp16 operand plane of the stem's one-pass weight gradient, written by the same pass
-        want16 = h16 and prec == 3 and x.dtype != torch.uint8
+        raw = isinstance(x, ops.RawFrames)
+        want16 = h16 and prec == 3 and not raw and x.dtype != torch.uint8
         xin = ops.slice_map(self._ws.map(tag, n, h, w, 4, 3, prec, dev, h16=want16), lo, hi)
         if not want16 and xin.h16 is not None:
             xin = ops.SplitMap(xin.hi, xin.lo, xin.n, xin.h, xin.w, xin.c, xin.pad)
-        if x.dtype == torch.uint8:
+        if raw:
+            ops.pack_cameras_resized_u8(x.frames[lo:hi], (x.h, x.w), prec, out=xin)
+        elif x.dtype == torch.uint8:
             ops.pack_cameras_u8(x[lo:hi], prec, out=xin)
         else:
             xin = ops.pack_f32(x[lo:hi], 4, 3, prec, out=xin)      # (a plane-less view of xin when the fp16 pack was refused)
@@ -471,7 +478,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
             h2, w2 = ops.conv_out_size(h1, 3, 2, 1), ops.conv_out_size(w1, 3, 2, 1)
             c = ops.slice_map(ws.map("pool", n, h2, w2, 64, 1, prec, dev), lo[r], hi[r])
             c.exp = prep["exp"]["stem"]
-            if prec == 4 and FUSE_STEM_POOL and STEM_READS_INPUT != "0" and not isinstance(x, ops.SplitMap) and (
+            if prec == 4 and FUSE_STEM_POOL and STEM_READS_INPUT != "0" and not isinstance(x, (ops.SplitMap, ops.RawFrames)) and (
                     STEM_READS_INPUT == "1" or ops.stem_walk_reads(x[lo[r]:hi[r]])):
                 # the stem kernel converts the raw input (fp32 image or uint8 tiles) on its way into LDS: no packed copy
                 ops.stem_pool_raw(x[lo[r]:hi[r]], prep["stem"], c)

@@ -140,6 +140,39 @@ int agp_pack_f32_to_nhwc4_h16(const float* x, int64_t sn, int64_t sc, int64_t sh
 int agp_pack_u8_cams_to_nhwc(const uint8_t* img, int n, int ncam, int h, int w, const float* mean3,
                              const float* std3, int pad, void* hi, void* lo, void* stream);
 
+/* Camera front end on the device: the resize in front of the tiles above.  The reference resizes PIL images
+ * (TVT.Resize(192, antialias=True), datasets/datasets_ws_nuscenes.py:607-612; Resize(opt.db_resize) on the aerial tiles,
+ * :284-303; the KITTI-360 twins, datasets_ws_kitti360.py:240-272), so the arithmetic is Pillow's ImagingResample for 8-bit
+ * channels with the bilinear filter, and the kernels reproduce it bit for bit:
+ *   per axis, out[xx] = min(255, (2^21 + sum_{t < count} k[xx][t] * in[first + t]) >> 22),
+ *   the horizontal pass first, its result rounded to uint8, the vertical pass on that.
+ * Tables per axis (made by agp_resize_coeffs on the host, uploaded by the caller): k = int32 [out][ksize] (taps >= count
+ * zero), bounds = int32 [out][2] = (first, count); ksize = agp_resize_ksize(in, out).  An axis whose size does not change has
+ * identity tables and goes through the same code.
+ *
+ * Pure host helpers (no device, no stream):
+ *   agp_resize_ksize(in, out)     taps per output pixel, 2 * ceil(max(in / out, 1)) + 1; -1 for a size outside 1 .. 16384
+ *   agp_resize_coeffs(...)        fills HOST arrays k [out][ksize] and bounds [out][2] (sizes 1 .. 16384, any ratio)
+ *   agp_resized_size(h, w, size)  torchvision Resize(int): shorter edge -> size, longer -> int(size * long / short)
+ *
+ * agp_resize_u8_cams:      frames uint8 [n][ncam][H0][W0][3] (HWC, contiguous, any byte alignment) -> out uint8 [n][ncam][h][w][3].
+ * agp_resize_pack_u8_cams: the same frames -> resize -> ToTensor + Normalize(mean3, std3: HOST pointers to 3 floats) ->
+ *                          tiles concatenated along W -> the stem's NHWC4 map [n][h+2*pad][ncam*w+2*pad][4] exactly as
+ *                          agp_pack_u8_cams_to_nhwc writes it (halo untouched, 4th channel zero, lo == NULL: one fp16 plane),
+ *                          in ONE launch; the resized uint8 image is never written to memory.
+ * kx / bx: the tables of (W0 -> w), ky / by: of (H0 -> h), DEVICE pointers.  The kernels clamp what they read from the bounds
+ * tables to the frame, so tables of another geometry give wrong pixels, never an access outside the buffers.
+ * Supported: every size in 1 .. 16384 and in / out <= 8 per axis (any enlargement), the axes independent, fewer than 2^31
+ * output tiles of 16 x 64 pixels; otherwise AGP_E_UNSUPPORTED.  AGP_E_BADARG: a null pointer, a size or count <= 0. */
+int agp_resize_ksize(int in, int out);
+int agp_resize_coeffs(int in, int out, int32_t* k, int32_t* bounds);
+int agp_resized_size(int h, int w, int size, int* oh, int* ow);
+int agp_resize_u8_cams(const uint8_t* frames, int n, int ncam, int H0, int W0, int h, int w, const int32_t* kx,
+                       const int32_t* bx, const int32_t* ky, const int32_t* by, uint8_t* out, void* stream);
+int agp_resize_pack_u8_cams(const uint8_t* frames, int n, int ncam, int H0, int W0, int h, int w, const int32_t* kx,
+                            const int32_t* bx, const int32_t* ky, const int32_t* by, const float* mean3,
+                            const float* std3, int pad, void* hi, void* lo, void* stream);
+
 /* halo-padded NHWC split planes -> dense fp32 NHWC [n][h][w][c] (a torch
  * channels_last tensor of logical shape [n,c,h,w]). */
 int agp_unpack_nhwc_to_f32(const void* hi, const void* lo, int n, int h, int w, int c,
