@@ -54,6 +54,12 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvStream2(C.Structure):
+    """struct agp_conv_stream2 (include/agplace_hip.h)."""
+    _fields_ = [("in_hi", C.c_void_p), ("w_cm", C.c_void_p),
+                ("n", C.c_int32), ("hin", C.c_int32), ("win", C.c_int32), ("cin", C.c_int32)]
+
+
 class BBlock64Desc(C.Structure):
     """struct agp_bblock64_desc (include/agplace_hip.h)."""
     _fields_ = [("inp", C.c_void_p), ("out", C.c_void_p), ("w1", C.c_void_p), ("w2", C.c_void_p),
@@ -95,6 +101,8 @@ SIGNATURES = {
     "agp_map_absmax_reset": (_I, [_P, _I, _P]),
     "agp_conv2d_fwd": (_I, [C.POINTER(ConvDesc), _P]),
     "agp_conv2d_fwd_grouped": (_I, [C.POINTER(ConvDesc), _I, _P]),
+    "agp_conv2d_s2_fwd": (_I, [C.POINTER(ConvDesc), _I, _P]),
+    "agp_conv2d_fwd_grouped2": (_I, [C.POINTER(ConvDesc), C.POINTER(ConvStream2), _I, _P]),
     "agp_bblock64_fwd_grouped": (_I, [C.POINTER(BBlock64Desc), _I, _P]),
     "agp_bblock64_pool_floats": (_L, [C.POINTER(BBlock64Desc)]),
     "agp_bblock64_pool_finish": (_I, [_P, _I, _I, _I, _P, _P]),

@@ -639,7 +639,8 @@ static int conv_fill_params(const agp_conv_desc* d, IgemmParams& p);
 void agp_internal_conv_kxr_geometry(agp_igemm::IgemmParams& p, const agp_conv_desc* d);
 bool agp_internal_use_kxr2(const agp_conv_desc* d);
 int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
-int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan);
+int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan, bool nods);
+int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan, const agp_igemm::KxrwStreams* ds);
 
 // Several convolutions of ONE channel shape (cin, cout, 3x3 stride 1) and precision as ONE launch: the tiles of
 // every problem form one grid (igemm_kxr2.hip).  Groups the kernel cannot take run as `n` launches, in order.
@@ -684,7 +685,7 @@ static int conv2d_fwd_group(const agp_conv_desc* descs, int n, void* stream, Til
                 const agp_conv_desc* d = descs + h + i;
                 ps[i].w2_hi = d->w_hi; ps[i].w2_cm = d->w_cm; ps[i].scale2 = d->scale; ps[i].shift2 = d->shift; ps[i].o2_hi = d->out_hi;
             }
-            return agp_internal_conv_s2(ps, descs, h, (hipStream_t)stream, plan);
+            return agp_internal_conv_s2(ps, descs, h, (hipStream_t)stream, plan, false);
         }
     }
     if (!group) {
@@ -728,6 +729,70 @@ extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* s
 }
 
 extern "C" int agp_conv2d_fwd(const agp_conv_desc* d, void* stream) { return conv2d_fwd_one(d, stream, nullptr); }
+
+// ---- the stage entry without a stored downsample map (include/agplace_hip.h)
+static bool s2_conv_ok(const agp_conv_desc* c, const agp_conv_desc* d0) {
+    return c->prec == AGP_PREC_F16 && c->in_hi && c->w_hi && c->out_hi && !c->in_lo && !c->w_lo && !c->out_lo && !c->res_hi && !c->res_lo &&
+           !c->stat_partial && !c->pool_partial && !c->hi_only &&
+           c->kh == 3 && c->kw == 3 && c->stride == 2 && c->pad == 1 && c->pin == 1 && c->pout == 1 && c->in_w_step == c->cin &&
+           c->hin > 0 && c->win > 0 && c->hout == (c->hin - 1) / 2 + 1 && c->wout == (c->win - 1) / 2 + 1 &&
+           c->cin % 32 == 0 && c->cout % 64 == 0 && c->n > 0 && c->cin == d0->cin && c->cout == d0->cout &&
+           (int64_t)c->n * (c->hin + 2) * (c->win + 2) * c->cin * 2 < (1ll << 31) &&
+           (int64_t)c->n * (c->hout + 2) * (c->wout + 2) * c->cout * 2 < (1ll << 31);
+}
+
+extern "C" int agp_conv2d_s2_fwd(const agp_conv_desc* descs, int n, void* stream) {
+    if (!descs) return AGP_E_BADARG;
+    if (n < 1 || n > 2 || AGP_TUNE("CONV_KERNEL", 0) || AGP_TUNE("NO_S2", 0)) return AGP_E_UNSUPPORTED;
+    for (int i = 0; i < n; ++i)
+        if (!s2_conv_ok(descs + i, descs)) return AGP_E_UNSUPPORTED;
+    IgemmParams ps[2];
+    for (int i = 0; i < n; ++i) {
+        ps[i] = IgemmParams{};
+        const int rc = conv_fill_params(descs + i, ps[i]);
+        if (rc != AGP_OK) return rc;
+    }
+    return agp_internal_conv_s2(ps, descs, n, (hipStream_t)stream, nullptr, true);
+}
+
+extern "C" int agp_conv2d_fwd_grouped2(const agp_conv_desc* descs, const agp_conv_stream2* s2, int n, void* stream) {
+    if (!descs || !s2) return AGP_E_BADARG;
+    if (n < 1 || n > 4 || AGP_TUNE("CONV_KERNEL", 0) || !AGP_TUNE("KXR_WIDE", 1)) return AGP_E_UNSUPPORTED;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const agp_conv_desc* d = descs + i;
+        const bool ok = d->prec == AGP_PREC_F16 && d->in_hi && d->w_hi && d->out_hi && !d->in_lo && !d->w_lo && !d->out_lo && !d->res_lo &&
+                        !d->hi_only && d->n > 0 && d->cin % 32 == 0 && d->cout % 128 == 0 && conv_kxr_ok(d) && agp_internal_use_kxr2(d) &&
+                        d->cin == descs[0].cin && d->cout == descs[0].cout;
+        if (!ok) return AGP_E_UNSUPPORTED;
+        const agp_conv_stream2* t = s2 + i;
+        if (!t->in_hi) continue;
+        any = true;
+        if (!t->w_cm || d->res_hi || d->pool_partial || t->n != d->n || t->cin <= 0 || t->cin % 32 || t->hin <= 0 || t->win <= 0 ||
+            (t->hin - 1) / 2 + 1 != d->hout || (t->win - 1) / 2 + 1 != d->wout ||
+            (int64_t)t->n * (t->hin + 2) * (t->win + 2) * t->cin * 2 >= (1ll << 31))
+            return AGP_E_UNSUPPORTED;
+    }
+    IgemmParams ps[4];
+    KxrwStreams ds = {};
+    for (int i = 0; i < n; ++i) {
+        ps[i] = IgemmParams{};
+        const int rc = conv_fill_params(descs + i, ps[i]);
+        if (rc != AGP_OK) return rc;
+        agp_internal_conv_kxr_geometry(ps[i], descs + i);
+        const agp_conv_stream2* t = s2 + i;
+        if (!t->in_hi) continue;
+        const int wp = t->win + 2, hp = t->hin + 2;
+        KxrwStream& k = ds.s[i];
+        k.x = t->in_hi; k.w = t->w_cm;
+        k.x_bytes = (uint32_t)((int64_t)t->n * hp * wp * t->cin * 2);
+        k.w_bytes = (uint32_t)((int64_t)t->cin * descs[i].cout * 2);
+        // raster row (img, y, xq) of the output reads input pixel (2 y, 2 (xq - 1)) = padded pixel (2 y + 1, 2 xq - 1)
+        k.sn = hp * wp * t->cin; k.sh = 2 * wp * t->cin; k.sw = 2 * t->cin; k.base = (wp - 1) * t->cin;
+        k.nc = t->cin / 32;
+    }
+    return agp_internal_conv_kxrw(ps, n, (hipStream_t)stream, nullptr, any ? &ds : nullptr);
+}
 
 // The tile plan of the launch that agp_conv2d_fwd (n == 1) / agp_conv2d_fwd_grouped (n > 1) would make for these descriptors:
 // the launch path itself, stopped in the launcher before anything touches the device.

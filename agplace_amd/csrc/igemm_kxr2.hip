@@ -522,14 +522,14 @@ int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
 
 }  // namespace agp_igemm
 
-int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
+int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan, const agp_igemm::KxrwStreams* ds);
 
 // `ps[i]` arrive with the padded-width raster geometry of agp_internal_conv_kxr_geometry; all share N, CK, prec F16.
 int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
     if (n < 1 || n > KXR2_MAXP) return AGP_E_BADARG;
     // layers with cout % 128 == 0 run on the wide form (256 x 128 tiles, igemm_kxrw.hip)
-    if (AGP_TUNE("KXR_WIDE", 1) && ps[0].N % 128 == 0) return agp_internal_conv_kxrw(ps, n, s, plan);
+    if (AGP_TUNE("KXR_WIDE", 1) && ps[0].N % 128 == 0) return agp_internal_conv_kxrw(ps, n, s, plan, nullptr);
     Kxr2Group g = {};
     g.nprob = n;
     for (int i = 0; i < n; ++i) {

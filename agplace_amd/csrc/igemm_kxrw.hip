@@ -37,6 +37,24 @@
 //   opens (L,2): W(L,2);  younger: R0[0..7]            -> vmcnt(8)
 //   tile row 0 reads its strip: R0; younger: R1        -> vmcnt(8)   (half tile: vmcnt(0))
 //   tile row 1 reads its strip: R1                     -> vmcnt(0), placed BEFORE tile row 0's stores (a store counts too)
+//
+// The residual COMPUTED from a second operand stream (RES = 2; the 1x1 / stride-2 downsample of a stage's first BasicBlock, whose
+// map is then never stored): raster row (img, y, xq) reads pixel (img, 2 y, 2 (xq - 1)) of the stage's INPUT map (KxrwStream) and
+// multiplies it with chunk-major 1x1 weights [cin2 / 32][N][32] that carry the downsample's BatchNorm scale (folded on the host,
+// rounded once to fp16).  After the 3x3 K loop the accumulators are rescaled in place, acc = acc * scale[n] + shift'[n] (the
+// epilogue's FMAs, moved earlier; shift' = the conv's shift + the downsample's), then nc2 = cin2 / 32 TRAILING phases T(0..nc2-1)
+// follow, each one X2 block (rows + 0 only: 128 TM rows, NX2 = 4 / 2 pieces per wave) on one 8 KB weight chunk D(j), 16 MFMAs per
+// wave into the SAME accumulators, and the epilogue runs without scale, shift or residual: the sum stays fp32 until the one store.
+// The downsample's values are therefore no longer rounded to fp16 or clamped on their own; the range guard sees the block output.
+// X2(j) lands in X buffer (xidle + j) & 1 (xidle = the buffer the last macro-step does not read), D(j) in ring slot j % 3:
+//     phase (L,0)       : W(L,2)[2]  X2(0)[NX2]        phase (L,1) : D(0)[2]          phase (L,2) : D(1)[2] (nc2 = 1: D(0) again)
+//     phase T(j)        : X2(j+1)[NX2]  D(j+2)[2]      (each only while it exists)
+//   opens (L,1): W(L,1);        younger: W(L,2) X2(0)   -> vmcnt(NX2+2)
+//   opens (L,2): W(L,2);        younger: X2(0) D(0)     -> vmcnt(NX2+2)
+//   opens T(0) : X2(0) D(0);    younger: D(1)           -> vmcnt(2)
+//   opens T(j+1): X2(j+1) D(j+1); younger: D(j+2)       -> vmcnt(2) while j + 2 < nc2, else vmcnt(0)
+//   the epilogue's strips overlay both X buffers and the W ring: vmcnt(0) before its barrier (nc2 = 1 leaves the second D(0) open)
+// Raster rows that are not stored (halo columns, rows >= M) read a neighbouring pixel of the plane or past its range (zeros).
 
 #include <type_traits>
 
@@ -44,7 +62,6 @@
 
 namespace agp_igemm {
 
-constexpr int KXRW_MAXP = 4;
 struct KxrwGroup {
     IgemmParams p[KXRW_MAXP];
     int mt_end[KXRW_MAXP];
@@ -56,6 +73,7 @@ struct KxrwGroup {
     uint32_t r_bytes[KXRW_MAXP];   // bytes of each problem's residual plane (the buffer range of its LDS-DMA)
 };
 constexpr uint32_t KXRW_ROOB = 0xffffff00u;      // a residual offset past every plane: the piece's lane reads zeros
+__device__ __forceinline__ const KxrwStreams& kxrw_streams(const KxrwStreams& s) { return s; }
 
 // Tile shapes (a wave = TM_ x TN_ MFMA tiles of 32 x 32, four waves stacked along the rows):
 //   TM_ = 2, TN_ = 4: 256 rows x 128 channels -- the full tile of the WIDE form, cout % 128 == 0;
@@ -75,8 +93,9 @@ template <int TM_, int TN_> struct KwShape {
 
 // One tile: rows [m0, m0 + 128 TM_) x columns [n0, n0 + 32 TN_) of problem g.p[pid]; RES: the problem has a residual (chosen per
 // tile, outside the tile's code: a branch around the last macro-step's MFMAs would cost the accumulators a trip through scratch).
-template <bool POOL, int TM_, int TN_, bool RG, bool RES>
-__device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, const int m0, const int n0) {
+// RES: 0 none, 1 a stored plane by LDS-DMA, 2 computed from the second operand stream *sp (file header).
+template <bool POOL, int TM_, int TN_, bool RG, int RES>
+__device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, const int m0, const int n0, const KxrwStream* sp = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using SH = KwShape<TM_, TN_>;
     constexpr int BN = SH::BN, NW = 4, TM = TM_, TN = TN_, ROWB = KW_ROWB;
@@ -86,6 +105,8 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     constexpr int NWP = BN / (NW * 16);                // 2 instructions per wave and W piece
     static_assert(TN == 4 && (TM == 2 || TM == 1), "the full tile (256 x 128) and its half tile (128 x 128)");
     static_assert(NWP == 2 && (NX == 5 || NX == 3), "the vmcnt counts exist for these");
+    constexpr int NX2 = SH::BM / (16 * NW);            // RES = 2: pieces per wave of an X2 block (rows + 0 only): 4 / 2
+    static_assert(!(POOL && RES == 2), "the computed residual is not instantiated with the pooling epilogue");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ws = smem + 2 * X_BUF;
     float* const tab = (float*)(ws + 3 * W_TAP);       // [scale 128][shift 128]
@@ -224,6 +245,24 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rr, LDS_PTR(strip + i * 1024), 16, off >= 0 ? off * 2 : (int)KXRW_ROOB, 0, 0, 0);
     };
 
+    // ---- the second operand stream (RES = 2): its per-lane offsets are filled in behind the main loop, when xoff[] / woff[] die
+    int x2off[RES == 2 ? NX2 : 1], doff[RES == 2 ? NWP : 1];
+    int nc2 = 0;
+    __amdgpu_buffer_rsrc_t rx2 = rx, rd2 = rw;
+    if constexpr (RES == 2) {
+        nc2 = __builtin_amdgcn_readfirstlane(sp->nc);
+        rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)sp->x, 0, sp->x_bytes, 0x00020000);
+        rd2 = __builtin_amdgcn_make_buffer_rsrc((void*)sp->w, 0, sp->w_bytes, 0x00020000);
+    }
+    auto load_x2 = [&](int buf, int j, int q) {         // piece q of this wave of X2(j): rows (wave + 4 q) * 16 .. of the tile
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, LDS_PTR(smem + buf * X_BUF + (wave + NW * q) * 1024), 16, x2off[q],
+                                                 __builtin_amdgcn_readfirstlane(j * 64), 0, 0);
+    };
+    auto load_d = [&](int slot, int j, int i) {         // instruction i of this wave of D(j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rd2, LDS_PTR(ws + slot * W_TAP + (wave + NW * i) * 1024), 16, doff[i],
+                                                 __builtin_amdgcn_readfirstlane(j * 64 * pN), 0, 0);
+    };
+
     int ky = 0, cc = 0;
     wait_vm_lgkm<NWP>();
     __builtin_amdgcn_s_barrier();
@@ -236,14 +275,15 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
     auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int nky_, int ncc_, int wcur_, int wnext_) {
         constexpr int kx = decltype(KX)::value;
         constexpr bool last = decltype(LAST)::value;
-        constexpr int nres = last && RES && kx < 2 ? NEI / 2 : 0;     // tile row 0's residual pieces of this phase
+        constexpr int nres = last && RES == 1 && kx < 2 ? NEI / 2 : 0;     // tile row 0's residual pieces of this phase
         const char* wb = ws + kx * W_TAP;
         bf16x8 xf[2][TM], wf[2][TN];
 #pragma unroll
         for (int t = 0; t < TM; ++t) xf[0][t] = *(const bf16x8*)(xb + xrd[kx][0] + t * (32 * ROWB));
 #pragma unroll
         for (int t = 0; t < TN; ++t) wf[0][t] = *(const bf16x8*)(wb + wrd[0] + t * (32 * ROWB));
-        constexpr int ndma = (kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : NWP)) + nres;
+        constexpr int nstr = last && RES == 2 ? (kx == 0 ? NX2 : NWP) : 0;      // the stream's pieces of this phase (file header)
+        constexpr int ndma = (kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : NWP)) + nres + nstr;
         static_assert(ndma <= 8, "one piece per MFMA pair");
 #pragma unroll
         for (int t = 0; t < TM; ++t) xf[1][t] = *(const bf16x8*)(xb + xrd[kx][1] + t * (32 * ROWB));
@@ -253,6 +293,10 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         auto piece = [&](int i) {
             if (nres && i >= ndma - nres) {
                 load_residual(strip0, 0, kx * (NEI / 2) + i - (ndma - nres));
+            } else if (nstr && i >= ndma - nstr) {
+                const int k = i - (ndma - nstr);
+                if (kx == 0) load_x2(xidle, 0, k);
+                else load_d(kx - 1, kx - 1 < nc2 ? kx - 1 : nc2 - 1, k);
             } else if (kx == 0) {
                 if (i < NWP) {
                     const int so = __builtin_amdgcn_readfirstlane((wcur_ + 2 * tapb) * wmul);
@@ -308,24 +352,114 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         __builtin_amdgcn_s_barrier();
         ky = nky; cc = ncc;
     }
+    if constexpr (RES == 2) {
+        const int s_sn = sp->sn, s_sh = sp->sh, s_sw = sp->sw, s_base = sp->base;
+#pragma unroll
+        for (int q = 0; q < NX2; ++q) {
+            const int row = (wave + NW * q) * 16 + lrow;
+            const int m = m0 + row;                     // not clamped: rows past the last image read zeros (buffer range check)
+            const uint32_t img = fdiv((uint32_t)m, d_howo);
+            const uint32_t rem = (uint32_t)m - img * d_howo.d;
+            const uint32_t y = fdiv(rem, d_wo);
+            const uint32_t xq = rem - y * d_wo.d;
+            const int el = (int)img * s_sn + (int)y * s_sh + (int)xq * s_sw + s_base;
+            x2off[q] = el * 2 + ((lpos ^ swz32(row)) << 4);
+        }
+#pragma unroll
+        for (int i = 0; i < NWP; ++i) {
+            const int row = (wave + NW * i) * 16 + lrow;
+            const int n = n0 + row < pN ? n0 + row : pN - 1;
+            doff[i] = n * 64 + ((lpos ^ swz32(row)) << 4);
+        }
+    }
     {
         const int st = nsteps - 1;
         const int wcur = (ky * 3 * CK + cc * 32) * 2;
         const char* xb = smem + (st & 1) * X_BUF;
         phase(I0{}, BT{}, xb, st, 0, 0, wcur, 0);
-        wait_vm_lgkm<NWP + (RES ? NEI / 2 : 0)>();
+        wait_vm_lgkm<NWP + (RES == 1 ? NEI / 2 : RES == 2 ? NX2 : 0)>();
         __builtin_amdgcn_s_barrier();
         phase(I1{}, BT{}, xb, st, 0, 0, wcur, 0);
-        wait_vm_lgkm<(RES ? NEI : 0)>();
+        wait_vm_lgkm<(RES == 1 ? NEI : RES == 2 ? NX2 + NWP : 0)>();
         __builtin_amdgcn_s_barrier();
         phase(I2{}, BT{}, xb, st, 0, 0, wcur, 0);
+    }
+    if constexpr (RES == 2) {
+        // ---- the accumulators take the conv's scale and the summed shift in place, then the trailing phases add the downsample
+        {
+            const float* tb = tab + 8 * lh;
+#pragma unroll
+            for (int jj = 0; jj < TN * 2; ++jj) {
+                const f32x4 s0 = *(const f32x4*)(tb + 16 * jj), s1 = *(const f32x4*)(tb + 16 * jj + 4);
+                const f32x4 h0 = *(const f32x4*)(tb + BN + 16 * jj), h1 = *(const f32x4*)(tb + BN + 16 * jj + 4);
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        acc[jj >> 1][tm][8 * (jj & 1) + e] =
+                            acc[jj >> 1][tm][8 * (jj & 1) + e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? h0[e & 3] : h1[e & 3]);
+            }
+        }
+        // MODE 2: X2(j + 1) and D(j + 2) go out among this phase's MFMAs, 1: X2(j + 1) only, 0: nothing (the last phase)
+        auto tphase = [&](auto MODE, int j) {
+            constexpr int mode = decltype(MODE)::value;
+            const char* xb = smem + ((xidle + j) & 1) * X_BUF;
+            const char* wb = ws + (j % 3) * W_TAP;
+            bf16x8 xf[2][TM], wf[2][TN];
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+                for (int t = 0; t < TM; ++t) xf[ks][t] = *(const bf16x8*)(xb + xrd[0][ks] + t * (32 * ROWB));
+#pragma unroll
+                for (int t = 0; t < TN; ++t) wf[ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
+            }
+            constexpr int ndma = mode == 2 ? NX2 + NWP : (mode == 1 ? NX2 : 0);
+            static_assert(ndma <= 8, "one piece per MFMA pair");
+            int ip = 0;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) {
+                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wf[ks][tn]),
+                                                                             __builtin_bit_cast(f16x8, xf[ks][tm]), acc[tn][tm], 0, 0, 0);
+                        if ((TM == 1 || (tm & 1)) && ip < ndma) {
+                            if (ip < NX2) load_x2((xidle + j + 1) & 1, j + 1, ip);
+                            else load_d((j + 2) % 3, j + 2, ip - NX2);
+                            ++ip;
+                        }
+                    }
+            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM + TN), 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, TM == 1 ? 1 : 2, 0);
+                if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        wait_vm_lgkm<NWP>();
+        __builtin_amdgcn_s_barrier();
+        int j = 0;
+        for (; j + 2 < nc2; ++j) {
+            tphase(I2{}, j);
+            wait_vm_lgkm<NWP>();
+            __builtin_amdgcn_s_barrier();
+        }
+        for (; j + 1 < nc2; ++j) {
+            tphase(I1{}, j);
+            wait_vm_lgkm<0>();
+            __builtin_amdgcn_s_barrier();
+        }
+        tphase(I0{}, j);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 
     // ---- epilogue: accumulator layout (a lane = one pixel, 8 x 8 consecutive channels) <-> line layout through the wave's strip of
     // 32 rows x 256 bytes (file header): row = pixel, 16-byte slot s of row r = chunk s ^ (r & 15) of the pixel's line.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if constexpr (RES) {
+    if constexpr (RES == 1) {
         if constexpr (TM == 2) {
 #pragma unroll
             for (int i = 0; i < NEI; ++i) load_residual(strip1, 1, i);
@@ -362,7 +496,7 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
             }
         }
         u32x4 rres[TN * 2];
-        if constexpr (RES) {
+        if constexpr (RES == 1) {
 #pragma unroll
             for (int jj = 0; jj < TN * 2; ++jj) rres[jj] = *(const u32x4*)(strip + a_off + ((jj ^ a_swz) << 5));
         }
@@ -373,9 +507,11 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
             const f32x4 h0 = *(const f32x4*)(tb + BN + 16 * jj), h1 = *(const f32x4*)(tb + BN + 16 * jj + 4);
             float v[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e)
-                v[e] = acc[jj >> 1][tm][8 * (jj & 1) + e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? h0[e & 3] : h1[e & 3]);
-            if constexpr (RES) {
+            for (int e = 0; e < 8; ++e) {
+                if constexpr (RES == 2) v[e] = acc[jj >> 1][tm][8 * (jj & 1) + e];      // scaled and shifted before the trailing phases
+                else v[e] = acc[jj >> 1][tm][8 * (jj & 1) + e] * (e < 4 ? s0[e & 3] : s1[e & 3]) + (e < 4 ? h0[e & 3] : h1[e & 3]);
+            }
+            if constexpr (RES == 1) {
                 float r[8];
                 unpack8_h(rres[jj], r);
 #pragma unroll
@@ -393,7 +529,7 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
         if constexpr (TM == 2) {
             // tile row 1's residual has had this tile row's arithmetic to land; the wait stands before the stores because a store
             // counts in vmcnt as well
-            if (tm == 0 && RES) wait_vm_lgkm<0>();
+            if (tm == 0 && RES == 1) wait_vm_lgkm<0>();
         }
 #pragma unroll
         for (int i = 0; i < NEI; ++i) {
@@ -486,8 +622,10 @@ __device__ __forceinline__ void kxrw_tile(const KxrwGroup& g, const int pid, con
 // block -> (problem, row tile, column tile).  XCD x owns a contiguous chunk of the global row tiles [0, MT_full); MIX: the blocks
 // from half_bid0 on are the HALF tiles (128 rows) of the row tiles [MT_full, MT) -- the launch's last, partial round of workgroups.
 // They carry the highest block ids, so they are dispatched last: the long tiles first, the short ones fill the end.
-template <bool POOL, bool MIX, bool RG>
-__global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
+// ds: the problems' second operand streams in the instantiations that hold the RES = 2 tile bodies (launch_kxrw_ds); the others
+// are the kernels of every launch without such a problem, unchanged.
+template <bool POOL, bool MIX, bool RG, class... DS>
+__global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g, DS... ds) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int TM_ = 2, TN_ = 4;
     constexpr int BM = KwShape<TM_, TN_>::BM, BN = KwShape<TM_, TN_>::BN;
@@ -516,13 +654,21 @@ __global__ void __launch_bounds__(256, 2) igemm_kxrw_kernel(KxrwGroup g) {
         if (half) {
             const int m0 = mt * BM + sub * (BM / 2);
             if (m0 >= g.p[pid].M) return;                  // the second half of a problem's last, partial row tile
-            if (g.p[pid].r_hi) kxrw_tile<POOL, 1, TN_, RG, true>(g, pid, m0, n0);
-            else kxrw_tile<POOL, 1, TN_, RG, false>(g, pid, m0, n0);
+            if constexpr (sizeof...(DS) != 0) {
+                const KxrwStream* sp = &kxrw_streams(ds...).s[pid];
+                if (sp->x) { kxrw_tile<POOL, 1, TN_, RG, 2>(g, pid, m0, n0, sp); return; }
+            }
+            if (g.p[pid].r_hi) kxrw_tile<POOL, 1, TN_, RG, 1>(g, pid, m0, n0);
+            else kxrw_tile<POOL, 1, TN_, RG, 0>(g, pid, m0, n0);
             return;
         }
     }
-    if (g.p[pid].r_hi) kxrw_tile<POOL, TM_, TN_, RG, true>(g, pid, mt * BM, n0);
-    else kxrw_tile<POOL, TM_, TN_, RG, false>(g, pid, mt * BM, n0);
+    if constexpr (sizeof...(DS) != 0) {
+        const KxrwStream* sp = &kxrw_streams(ds...).s[pid];
+        if (sp->x) { kxrw_tile<POOL, TM_, TN_, RG, 2>(g, pid, mt * BM, n0, sp); return; }
+    }
+    if (g.p[pid].r_hi) kxrw_tile<POOL, TM_, TN_, RG, 1>(g, pid, mt * BM, n0);
+    else kxrw_tile<POOL, TM_, TN_, RG, 0>(g, pid, mt * BM, n0);
 #endif
 }
 
@@ -567,11 +713,22 @@ int launch_kxrw(KxrwGroup& g, const KxrwPlan& k, hipStream_t s) {
     return AGP_OK;
 }
 
+template <bool MIX, bool RG>
+int launch_kxrw_ds(KxrwGroup& g, const KxrwStreams& ds, const KxrwPlan& k, hipStream_t s) {
+    constexpr int lds = KwShape<2, 4>::EPI_LDS;
+    static std::atomic<uint64_t> attr_done{0};
+    if (!agp_lds_attr((const void*)igemm_kxrw_kernel<false, MIX, RG, KxrwStreams>, lds, attr_done)) return AGP_E_LAUNCH;
+    AGP_LAUNCH((igemm_kxrw_kernel<false, MIX, RG, KxrwStreams>), dim3(MIX ? k.blocks : k.half_bid0), dim3(256), lds, s, g, ds);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
 }  // namespace agp_igemm
 
 // `ps[i]` arrive with the padded-width raster geometry of agp_internal_conv_kxr_geometry; all share N, CK, prec F16 and
-// N % 128 == 0 (256 x 128 tiles).
-int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
+// N % 128 == 0 (256 x 128 tiles).  ds != NULL: the problems' second operand streams (at least one with a plane; none of those
+// problems has a residual plane or pools).
+int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan, const agp_igemm::KxrwStreams* ds) {
     using namespace agp_igemm;
     if (n < 1 || n > KXRW_MAXP || ps[0].N % 128) return AGP_E_BADARG;
     constexpr int bm = KwShape<2, 4>::BM, bn = KwShape<2, 4>::BN;
@@ -602,6 +759,13 @@ int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
     g.mt_chunk = k.mt_chunk;
     g.half_bid0 = k.half_bid0;
     g.rflag = agp_range_flag_get();
+    if (ds) {
+        if (pool) return AGP_E_UNSUPPORTED;
+        return agp_rg_dispatch(g.rflag, [&](auto rg) {
+            constexpr bool RG = decltype(rg)::value;
+            return mix ? launch_kxrw_ds<true, RG>(g, *ds, k, s) : launch_kxrw_ds<false, RG>(g, *ds, k, s);
+        });
+    }
     return agp_rg_dispatch(g.rflag, [&](auto rg) {
         constexpr bool RG = decltype(rg)::value;
         if (mix) return pool ? launch_kxrw<true, true, RG>(g, k, s) : launch_kxrw<false, true, RG>(g, k, s);

@@ -130,6 +130,16 @@ __device__ __forceinline__ int group_problem(int& mt, int nprob, int e0, int e1,
     return pid;
 }
 
+constexpr int KXRW_MAXP = 4;     // problems of a grouped igemm_kxrw launch
+// igemm_kxrw RES = 2 (file header): per problem, the second operand stream of its computed residual; x == NULL: the problem has none
+struct KxrwStream {
+    const void* x; const void* w;      // the stage's input plane (fp16, 1-pixel halo); folded chunk-major 1x1 weights [nc][N][32]
+    uint32_t x_bytes, w_bytes;
+    int sn, sh, sw, base;              // elements: image, TWO input rows, TWO input pixels; padded pixel (1, -1) = raster (y 0, xq 0)
+    int nc;                            // cin2 / 32
+};
+struct KxrwStreams { KxrwStream s[KXRW_MAXP]; };
+
 constexpr int EPI_ROWB = 64 * 4 + 16;  // 64 fp32 channels + 16 B pad per pixel row
 
 // What a conv launcher decided on the host, in the order of agp_conv2d_tile_plan's plan[8].  The launchers take an optional

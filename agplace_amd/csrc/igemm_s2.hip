@@ -25,7 +25,10 @@
 //   opens (st+1,0): W(st+1,0) X(st+1); younger: W(st+1,1) D(st+1)       -> vmcnt(2)
 //   last macro-step L: (L,0) issues W(L,2) only -> opens (L,1): vmcnt(1); (L,1) issues nothing -> opens (L,2): vmcnt(0).
 // A phase's LDS-DMA pieces are issued among its MFMAs instead of in front of them, all of the phase's fragment reads first, the
-// last macro-step peeled (see igemm_kxrw.hip).  (The loop with the pieces at the head of a phase was retired: profiles/README.md,
+// last macro-step peeled (see igemm_kxrw.hip).
+// NODS (the 3x3 / stride-2 conv ALONE; the block's second conv then computes the downsample itself, igemm_kxrw.hip RES = 2): no second
+// accumulator set, no D slot, D loads, centre-tap MFMAs or second epilogue; the 3x3 arithmetic and its order are the same, so
+// its output is bit-identical.  Phase (st,2) issues W(st+1,1) only: (st+1,0) opens on vmcnt(1 piece) instead of vmcnt(2 pieces).  (The loop with the pieces at the head of a phase was retired: profiles/README.md,
 // round 3, "What was measured this round"; the code is in the history before the commit that removed it.)
 
 #include <type_traits>
@@ -45,14 +48,14 @@ constexpr int S2_BM = 128, S2_ROWB = 64;
 constexpr int S2_BMX = S2_BM + 16;                      // rows of a staged block (offsets 0 and 1 are read)
 constexpr int S2_XBLK = S2_BMX * S2_ROWB;               // one block (O or E)
 constexpr int S2_XBUF = 2 * S2_XBLK;                    // O then E
-template <int TN> constexpr int s2_lds() {              // X double buffer, W ring (3) + D slot, two scale / shift tables
-    return 2 * S2_XBUF + 4 * (32 * TN * S2_ROWB) + 4 * (32 * TN) * 4;
+template <int TN, bool NODS = false> constexpr int s2_lds() {      // X double buffer, W ring (3) + D slot, two scale / shift tables
+    return 2 * S2_XBUF + (NODS ? 3 : 4) * (32 * TN * S2_ROWB) + 4 * (32 * TN) * 4;
 }
 
 // TN = column tiles of 32 channels per wave: 2 = 128 x 64 tiles (54 KB LDS: three workgroups per CU, 4 MFMAs per phase and wave);
 // 4 = 128 x 128 tiles (71 KB: two per CU, 8 MFMAs per phase, the X blocks staged once per 128 channels).
 // rf: the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent otherwise
-template <int TN, class... RF>
+template <int TN, bool NODS, class... RF>
 __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group g, RF... rf) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr bool RG = sizeof...(RF) != 0;
@@ -64,7 +67,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
     static_assert(NX == 5, "the vmcnt counts below are written for NX = 5");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ws = smem + 2 * S2_XBUF;                // W ring slots 0..2, slot 3 = D (1x1 weights)
-    float* const tab = (float*)(ws + 4 * S2_WTAP);      // [conv scale 64][conv shift 64][ds scale 64][ds shift 64]
+    float* const tab = (float*)(ws + (NODS ? 3 : 4) * S2_WTAP);      // [conv scale 64][conv shift 64][ds scale 64][ds shift 64]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -86,7 +89,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
     const int pM = p.M, pN = p.N, pKtot = p.Ktot;
     const int x_sn = p.x_sn, x_sh_ = p.x_sh, x_sw = p.x_sw, x_base = p.x_base;
     const int o_sn = p.o_sn, o_sw = p.o_sw, o_base = p.o_base;
-    const bool has_ds = p.w2_hi != nullptr;
+    const bool has_ds = !NODS && p.w2_hi != nullptr;
 
     // ---- LDS-DMA source offsets (bytes).  Piece i < 9 is rows 16 i .. of the O block, piece 9 + i of the E block (one input
     // pixel = `cpix` bytes further: the E column is the O column + 1).  Rows past the map / before it read zeros (range check).
@@ -175,11 +178,14 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
         for (int ks = 0; ks < 2; ++ks) wrd[ks] = wrow * ROWB + (((2 * ks + lh) ^ swz32(wrow)) << 4);
     }
 
-    f32x16 acc[TN], acc2[TN];
+    f32x16 acc[TN], acc2[NODS ? 1 : TN];
 #pragma unroll
     for (int a = 0; a < TN; ++a)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[a][r] = 0.f; acc2[a][r] = 0.f; }
+        for (int r = 0; r < 16; ++r) {
+            acc[a][r] = 0.f;
+            if constexpr (!NODS) acc2[a][r] = 0.f;
+        }
 
     // ---- epilogue addressing, LINE layout (igemm_kxr2.hip): a pixel's BN channels are 2 BN bytes = LPP lanes of 16 bytes; one
     // store instruction covers 64 / LPP pixels of the wave's 32 rows
@@ -204,7 +210,10 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
     int ky = 0, cc = 0;
     wait_vm_lgkm<NWP>();
     __builtin_amdgcn_s_barrier();
-    if (tid < BN) { tab[tid] = tab_v[0]; tab[BN + tid] = tab_v[1]; tab[2 * BN + tid] = tab_v[2]; tab[3 * BN + tid] = tab_v[3]; }
+    if (tid < BN) {
+        tab[tid] = tab_v[0]; tab[BN + tid] = tab_v[1];
+        if constexpr (!NODS) { tab[2 * BN + tid] = tab_v[2]; tab[3 * BN + tid] = tab_v[3]; }
+    }
     auto phase = [&](auto KX, auto LAST, const char* xb, int st_, int ky_, int nky_, int ncc_, int wcur_, int wnext_) {
         constexpr int kx = decltype(KX)::value;
         constexpr bool last = decltype(LAST)::value;
@@ -217,7 +226,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
             for (int t = 0; t < TN; ++t) wf[ks][t] = *(const bf16x8*)(wb + wrd[ks] + t * (32 * ROWB));
         }
         // the phase's LDS-DMA list in the order the vmcnt counts assume
-        constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : (kx == 2 ? 2 * NWP : NWP));
+        constexpr int ndma = kx == 0 ? (last ? NWP : NWP + NX) : (last ? 0 : (kx == 2 && !NODS ? 2 * NWP : NWP));
         auto piece = [&](int i) {
             if (kx == 0) {
                 if (i < NWP) {
@@ -233,7 +242,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
             } else if (i < NWP) {
                 const int so = __builtin_amdgcn_readfirstlane((wnext_ + (kx - 1) * tapb) * wmul);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, LDS_PTR(ws + (kx - 1) * S2_WTAP + (wave + NW * i) * 1024), 16, woff_c[i], so, 0, 0);
-            } else {
+            } else if constexpr (!NODS) {
                 const int so = __builtin_amdgcn_readfirstlane((nky_ == 1 ? ncc_ : 0) * 64 * dmul);
                 const int k = i - NWP;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rd, LDS_PTR(ws + 3 * S2_WTAP + (wave + NW * k) * 1024), 16,
@@ -258,7 +267,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
             if (i < ndma) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (kx == 1 && ky_ == 1 && has_ds) {
+        if constexpr (!NODS) if (kx == 1 && ky_ == 1 && has_ds) {
             // the downsample: centre tap of the staged E block on the 1x1 weights (slot 3)
             const char* db = ws + 3 * S2_WTAP;
             bf16x8 df[2][TN];
@@ -287,7 +296,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
         wait_vm_lgkm<NX + NWP>();
         __builtin_amdgcn_s_barrier();
         phase(I2{}, std::false_type{}, xb, st, ky, nky, ncc, wcur, wnext);
-        wait_vm_lgkm<2 * NWP>();
+        wait_vm_lgkm<(NODS ? 1 : 2) * NWP>();
         __builtin_amdgcn_s_barrier();
         ky = nky; cc = ncc;
     }
@@ -338,7 +347,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     };
     epilogue(acc, tab, (bf16_t*)p.o_hi, p.relu ? 0.f : -65504.f, false);
-    if (has_ds) epilogue(acc2, tab + 2 * BN, (bf16_t*)p.o2_hi, -65504.f, true);
+    if constexpr (!NODS) if (has_ds) epilogue(acc2, tab + 2 * BN, (bf16_t*)p.o2_hi, -65504.f, true);
     rg.flush(rg_word(rf...), p.relu ? 0.f : -65504.f);
 #endif
 }
@@ -348,7 +357,8 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
 // ps[i]: the 3x3 / stride-2 conv of problem i in the generic geometry (conv_fill_params), with w2_hi / scale2 / shift2 / o2_hi
 // = its 1x1 / stride-2 downsample (or NULL); all problems share N and CK.  plan != NULL: the tile plan instead of the launch (MT = the
 // row tiles of all problems).
-int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan) {
+// nods: the instantiation without a downsample (every w2_hi NULL).
+int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan, bool nods) {
     using namespace agp_igemm;
     if (n < 1 || n > S2_MAXP) return AGP_E_BADARG;
     S2Group g = {};
@@ -389,9 +399,14 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
         return AGP_OK;
     }
     int rc;
-    if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, uint32_t*>, s2_lds<4>(), a4g, rflag)
-                       : launch(igemm_s2_kernel<2, uint32_t*>, s2_lds<2>(), a2g, rflag);
-    else rc = w4 ? launch(igemm_s2_kernel<4>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2>, s2_lds<2>(), a2s);
+    if (nods) {
+        static std::atomic<uint64_t> n4s{0}, n2s{0}, n4g{0}, n2g{0};
+        if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, true, uint32_t*>, s2_lds<4, true>(), n4g, rflag)
+                           : launch(igemm_s2_kernel<2, true, uint32_t*>, s2_lds<2, true>(), n2g, rflag);
+        else rc = w4 ? launch(igemm_s2_kernel<4, true>, s2_lds<4, true>(), n4s) : launch(igemm_s2_kernel<2, true>, s2_lds<2, true>(), n2s);
+    } else if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, false, uint32_t*>, s2_lds<4>(), a4g, rflag)
+                              : launch(igemm_s2_kernel<2, false, uint32_t*>, s2_lds<2>(), a2g, rflag);
+    else rc = w4 ? launch(igemm_s2_kernel<4, false>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2, false>, s2_lds<2>(), a2s);
     if (rc != AGP_OK) return rc;
     AGP_CHECK_LAUNCH();
     return AGP_OK;

@@ -774,6 +774,57 @@ def conv2d_grouped(jobs, prec):
     return [j[2] for j in jobs]
 
 
+class Stream2Weights:
+    """The 1x1 / stride-2 downsample of a stage's first BasicBlock as the SECOND OPERAND STREAM of the block's conv2
+    (agp_conv2d_fwd_grouped2): its BatchNorm scale folded into the weights (multiplied in fp32, rounded once to fp16) as a
+    chunk-major plane [cin / 32][cout][32], and its shift, which the caller adds to conv2's.  `fusable` is False when a folded
+    weight is not finite or leaves fp16's range: such a block keeps the stored downsample map."""
+    __slots__ = ("cin", "cout", "plane", "shift", "fusable")
+
+    def __init__(self, weight, scale, shift):
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        if tuple(weight.shape[2:]) != (1, 1) or cin % 32:
+            raise ValueError("Stream2Weights: a 1x1 conv with cin % 32 == 0")
+        wf = weight.detach().float().reshape(cout, cin) * scale.detach().float().reshape(cout, 1)
+        self.cin, self.cout = cin, cout
+        self.fusable = bool(torch.isfinite(wf).all()) and bool((wf.abs() < 65504.0).all())
+        self.plane = wf.half().view(cout, cin // 32, 32).permute(1, 0, 2).contiguous() if self.fusable else None
+        self.shift = shift.detach().float().contiguous()
+
+
+def conv2d_s2_nods(jobs):
+    """jobs: [(x, cw, out, relu), ...], 1..2 3x3 / stride-2 convs of one channel shape on fp16 maps (AGP_PREC_F16) as ONE launch of the
+    stage-entry kernel without its downsample part (agp_conv2d_s2_fwd).  Returns the output maps."""
+    arr = (_lib.ConvDesc * len(jobs))()
+    keep = []
+    for d, (x, cw, out, relu) in zip(arr, jobs):
+        keep.append(cw.planes(_lib.PREC_F16))
+        _fill_conv_desc(d, x, cw, out, None, relu, _lib.PREC_F16)
+    check(_L().agp_conv2d_s2_fwd(arr, len(jobs), _lib.stream()), "agp_conv2d_s2_fwd")
+    return [j[2] for j in jobs]
+
+
+def conv2d_grouped2(jobs):
+    """jobs: [(x, cw, out, residual, relu, stream2), ...], 1..4 3x3 / stride-1 convs of one channel shape (cout % 128 == 0) on fp16
+    maps (AGP_PREC_F16) as ONE launch (agp_conv2d_fwd_grouped2); stream2: None, or (x2, Stream2Weights) -- the job's residual is
+    then COMPUTED as the 1x1 / stride-2 conv of the map x2 (`residual` must be None, and cw.shift already holds the sum of the
+    two shifts).  Returns the output maps."""
+    arr = (_lib.ConvDesc * len(jobs))()
+    st = (_lib.ConvStream2 * len(jobs))()
+    keep = []
+    for d, t, (x, cw, out, residual, relu, stream2) in zip(arr, st, jobs):
+        keep.append(cw.planes(_lib.PREC_F16))
+        _fill_conv_desc(d, x, cw, out, residual, relu, _lib.PREC_F16)
+        if stream2 is not None:
+            x2, sw = stream2
+            if x2.lo is not None or x2.pad != 1 or x2.c != sw.cin or sw.plane is None:
+                raise ValueError("conv2d_grouped2: the second stream is a one-plane fp16 map with a 1-pixel halo and fusable weights")
+            t.in_hi, t.w_cm = ptr(x2.hi), ptr(sw.plane)
+            t.n, t.hin, t.win, t.cin = x2.n, x2.h, x2.w, sw.cin
+    check(_L().agp_conv2d_fwd_grouped2(arr, st, len(jobs), _lib.stream()), "agp_conv2d_fwd_grouped2")
+    return [j[2] for j in jobs]
+
+
 def conv2d(x: SplitMap, cw: ConvWeights, out: SplitMap, residual: SplitMap = None, relu=False, prec=3, stat_partial=None, pool=None,
            bstat=None, hi_only=False):
     """hi_only (prec 3, 3x3 stride-1 convs on 1-pixel-halo maps): ONE bf16 product on the hi planes (agp_conv_desc.hi_only)."""

@@ -68,6 +68,10 @@ class _Block(nn.Module):
 
 
 FUSE_STEM_POOL = True      # inference, fp16 maps: agp_stem_pool_fwd instead of conv + max-pool
+# Inference, precision mode 4: the 1x1 / stride-2 downsample of a stage's first BasicBlock is computed INSIDE the block's second
+# conv (ops.conv2d_grouped2: the block's input is that conv's second operand stream) instead of being written by the stage-entry
+# launch and read back as a residual plane; the sum stays fp32 until the one store.  False: the stored downsample map, as before.
+FUSE_DOWNSAMPLE = True
 
 
 class ResNet(nn.Module):
@@ -133,11 +137,13 @@ class ResNet(nn.Module):
         key = self._version_key()
         if key != self._prep_key:
             self._prep, self._prep_key = {}, key
+            self.__dict__["_prep_fuse"] = {}
         scaled = bool(scaled) and any(self._map_exp.values())
         if scaled in self._prep:
             return self._prep[scaled]
         prep = {}
         mexp = prep["exp"] = {}      # exponent of every map the prepared convs write: "stem", (li, bi, ci), ("ds", li, bi)
+        fuse = {}                    # (li, bi) -> _fused_downsample of the block (FUSE_DOWNSAMPLE), kept beside the set: _prepared_fuse
 
         def E(name):
             return int(self._map_exp.get(name, 0)) if scaled else 0
@@ -161,8 +167,40 @@ class ResNet(nn.Module):
                 # the downsample folds to the NEW stage's exponent: the residual operand is then stored like the output
                 mexp[("ds", li, bi)] = g_out
                 prep[(li, bi)] = (cws, fold(*ds, g_in, g_out) if ds else None)
+                fuse[(li, bi)] = self._fused_downsample(blk, ds, cws, g_in, g_out)
         self._prep[scaled] = prep
+        self.__dict__.setdefault("_prep_fuse", {})[scaled] = fuse
         return prep
+
+    def _prepared_fuse(self, scaled=False):
+        """{(li, bi): (ops.Stream2Weights, conv2 with the summed shift) or None} of the set _prepared(scaled) returns."""
+        self._prepared(scaled)
+        return self._prep_fuse[bool(scaled) and any(self._map_exp.values())]
+
+    @staticmethod
+    def _fused_downsample(blk, ds, cws, g_in, g_out):
+        """(ops.Stream2Weights, conv2 with the summed shift) of a BasicBlock with a 1x1 / stride-2 downsample whose conv2 the wide
+        3x3 kernel runs (FUSE_DOWNSAMPLE), else None.  Also None -- the block keeps its stored downsample map -- when a folded
+        weight leaves fp16's range; that is decided here, once per weight version, and needs one host read: weights prepared
+        for the first time inside a stream capture are not fused."""
+        if ds is None or blk.kind != "basic" or len(cws) != 2:
+            return None
+        dc, c1, c2 = ds[0], cws[0], cws[1]
+        if tuple(dc.kernel_size) != (1, 1) or dc.stride[0] != 2 or dc.padding[0] != 0 or dc.in_channels % 32 or \
+                (c1.kh, c1.kw, c1.stride, c1.pad) != (3, 3, 2, 1) or (c2.kh, c2.kw, c2.stride, c2.pad) != (3, 3, 1, 1) or c2.cout % 128 or \
+                c2.cin % 32:
+            return None
+        if dc.weight.is_cuda and torch.cuda.is_current_stream_capturing():
+            return None
+        bn = ds[1]
+        s_d, t_d = ops.fold_exp(*ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps), g_in, g_out)
+        sw = ops.Stream2Weights(dc.weight, s_d, t_d)
+        if not sw.fusable:
+            return None
+        import copy
+        c2f = copy.copy(c2)                  # the same weight planes (a shared dict), another shift
+        c2f.shift = (c2.shift + sw.shift).contiguous()
+        return sw, c2f
 
     @staticmethod
     def _input_geometry(x):
@@ -373,6 +411,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
         if (b.fe_type, b.nstages) != (a.fe_type, a.nstages):
             raise ValueError("forward_maps_multi: the trunks must share one architecture")
     preps = [net._prepared(scaled=prec != 3) for net in nets]
+    fuses = [net._prepared_fuse(scaled=prec != 3) for net in nets]
     geo = [net._input_geometry(x) for net, x in zip(nets, xs)]
     devs = [g[3] for g in geo]
     nchunks = max(1, -(-geo[0][0] // STAGE1_CHUNK))
@@ -401,8 +440,15 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
             mexp = {r: preps[r]["exp"] for r in act}
             lname = f"layer{li + 1}.{bi}"
             ds_jobs = []
+            # the downsample inside conv2 (FUSE_DOWNSAMPLE): decided per trunk from its channel shapes, the precision and the switch
+            # alone -- never from the batch, the chunking or the other trunks, so every grouping computes the same bits.  Such a
+            # trunk asks for no downsample map.
+            fz = {r: fuses[r].get((li, bi)) for r in act} if (prec == 4 and FUSE_DOWNSAMPLE and ops.MAP_PROBE is None) else {}
+            fused = [r for r in act if fz.get(r) is not None]
             if cws[act[0]][1] is not None:
                 for r in act:
+                    if r in fused:
+                        continue
                     dsw = cws[r][1]
                     ho = ops.conv_out_size(cur[r].h, 3, blks[r].stride, 1)
                     wo = ops.conv_out_size(cur[r].w, 3, blks[r].stride, 1)
@@ -431,6 +477,35 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
                 if ops.MAP_PROBE is not None:       # (a calibration runs in mode 3 and never takes the fused block; for completeness)
                     for r in act:
                         ops.probe_map(nets[r], f"{lname}.out", cur[r])
+                continue
+            if fused:
+                plain = [r for r in act if r not in fused]
+                o1, o2 = {}, {}
+                for r in act:
+                    c1 = cws[r][0][0]
+                    o1[r] = view(r, f"c{li}.{bi}.0", ops.conv_out_size(cur[r].h, 3, 2, 1), ops.conv_out_size(cur[r].w, 3, 2, 1), c1.cout,
+                                 mexp[r][(li, bi, 0)])
+                    o2[r] = view(r, f"c{li}.{bi}.1", o1[r].h, o1[r].w, cws[r][0][1].cout, mexp[r][(li, bi, 1)])
+                for k in range(0, len(fused), 2):
+                    ops.conv2d_s2_nods([(cur[r], cws[r][0][0], o1[r], True) for r in fused[k:k + 2]])
+                if plain:
+                    # (a trunk whose folded downsample weights leave fp16: its entry launch writes the downsample map as before)
+                    cj = [(cur[r], cws[r][0][0], o1[r], None, True) for r in plain]
+                    if len(cj) + len(ds_jobs) <= 4:
+                        ops.conv2d_grouped(cj + ds_jobs, prec)
+                    else:
+                        ops.conv2d_grouped(ds_jobs, prec)
+                        ops.conv2d_grouped(cj, prec)
+                for k in range(0, len(act), 4):
+                    ops.conv2d_grouped2([(o1[r], fz[r][1], o2[r], None, True, (cur[r], fz[r][0])) if r in fused else
+                                         (o1[r], cws[r][0][1], o2[r], idt[r], True, None) for r in act[k:k + 4]])
+                if bi == nblocks - 1 and (li > 0 or nchunks == 1):
+                    for r in act:                  # (a one-block stage: its output is pooled from the stored map)
+                        pool = stage_pool[r].get(li)
+                        if pool is not None:
+                            pool.fused = False
+                            pool.finish(o2[r])
+                cur = o2
                 continue
             for ci in range(nconv):
                 last = ci == nconv - 1

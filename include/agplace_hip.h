@@ -292,6 +292,29 @@ int agp_conv2d_fwd(const agp_conv_desc* d, void* stream);
  * agp_conv2d_fwd in order.  Results are bit-identical to separate launches. */
 int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* stream);
 
+/* The stage entry of a ResNet BasicBlock WITHOUT a stored downsample map (AGP_PREC_F16, fp16 maps with a 1-pixel halo):
+ *
+ * agp_conv2d_s2_fwd: 1..2 3x3 / stride-2 / pad-1 convs sharing (cin, cout) -- the block's first conv of every trunk -- as one
+ * launch of the stage-entry kernel without its 1x1 downsample part.  The outputs are bit-identical to the 3x3 outputs of
+ * agp_conv2d_fwd_grouped({3x3 ..., 1x1 ...}).
+ *
+ * agp_conv2d_fwd_grouped2: 1..4 3x3 / stride-1 / pad-1 convs sharing (cin, cout), cout % 128 == 0, as one launch; problem i
+ * with s2[i].in_hi != NULL adds, before the ReLU and in fp32, the 1x1 / stride-2 / pad-0 convolution of the map s2[i]
+ * (n images of hin x win x cin, cin % 32 == 0, 1-pixel halo; hout = (hin - 1) / 2 + 1 etc. must be the conv's map size) with the
+ * chunk-major fp16 weights w_cm [cin / 32][cout][32]: out = relu?(scale * conv3x3(in) + shift + conv1x1s2(s2)).  The caller
+ * folds the downsample's BatchNorm scale into w_cm and adds its shift to `shift`; the downsample's values are never rounded to
+ * fp16 or clamped on their own (the fp16 range guard sees the sum).  Such a problem has no res_hi and no pool_partial.
+ * s2[i].in_hi == NULL: the problem is what agp_conv2d_fwd_grouped would compute (res_hi or not), bit for bit.
+ *
+ * Both return AGP_E_UNSUPPORTED for anything else, before a launch is made. */
+typedef struct agp_conv_stream2 {
+    const void* in_hi;
+    const void* w_cm;
+    int32_t n, hin, win, cin;
+} agp_conv_stream2;
+int agp_conv2d_s2_fwd(const agp_conv_desc* descs, int n, void* stream);
+int agp_conv2d_fwd_grouped2(const agp_conv_desc* descs, const agp_conv_stream2* s2, int n, void* stream);
+
 /* The tile plan of the launch that agp_conv2d_fwd (n == 1) or agp_conv2d_fwd_grouped (n > 1) would make for `descs`, computed
  * on the host by the launch path itself (nothing is launched, no device is needed; pointers are looked at as NULL / non-NULL
  * only).  plan = { kernel (AGP_CONV_KERNEL_*), BM, BN (rows x channels of a tile), MT, NT (row x column tiles of all problems),
