@@ -95,6 +95,12 @@ SIGNATURES = {
     "agp_resized_size": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "agp_resize_u8_cams": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "agp_resize_pack_u8_cams": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_F), C.POINTER(_F), _I, _P, _P, _P]),
+    "agp_center_crop_origin": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "agp_resize_u8_cams_roi": (_I, [_P, _I, _I, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "agp_resize_pack_u8_cams_roi": (_I, [_P, _I, _I, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_F), C.POINTER(_F), _I,
+                                         _P, _P, _P]),
+    "agp_jitter_u8_cams": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "agp_jitter_pack_u8_cams": (_I, [_P, _I, _I, _I, _I, _P, _P, C.POINTER(_F), C.POINTER(_F), _I, _P, _P, _P]),
     "agp_unpack_nhwc_to_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "agp_map_zero_halo": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "agp_map_absmax": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),

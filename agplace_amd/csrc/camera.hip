@@ -40,8 +40,12 @@ __device__ __forceinline__ int wave_max_i(int v) {
 // kx / ky: int32 [out][ksx / ksy], bx / by: int32 [out][2] = (first tap, tap count).  Bounds are clamped to the frame when they
 // are loaded, and a tile whose patch would not fit the LDS buffers writes nothing: tables that do not belong to the geometry
 // (the host cannot see device memory) can give wrong pixels, never an access outside the frame or the buffers.
+// The kernel resizes a WINDOW of H0 x W0 pixels of every frame (torchvision's CenterCrop in front of the Resize; the whole frame
+// is the window at origin 0): frame f's window starts at frames + f * fstride + origin and its rows are gpitch bytes apart.  The
+// tables are those of the window's size, so the bounds, clamped to H0 x W0, never leave the window.
 template <bool PACK>
-__global__ __launch_bounds__(256) void resize_cams_kernel(const uint8_t* __restrict__ frames, int ncam, int H0, int W0, int h, int w,
+__global__ __launch_bounds__(256) void resize_cams_kernel(const uint8_t* __restrict__ frames, size_t fstride, size_t origin,
+                                                          int gpitch, int ncam, int H0, int W0, int h, int w,
                                                           const int32_t* __restrict__ kx, const int32_t* __restrict__ bx, int ksx,
                                                           const int32_t* __restrict__ ky, const int32_t* __restrict__ by, int ksy,
                                                           int tiles_x, int tiles_y, uint8_t* __restrict__ out8, float m0, float m1,
@@ -97,13 +101,13 @@ __global__ __launch_bounds__(256) void resize_cams_kernel(const uint8_t* __restr
     const int rowbytes = ncols * 3;
     const int pitch = (rowbytes + 15 + 15) & ~15;                      // a row may start up to 15 bytes into its first vector
     const int chunk = STAGE_BYTES / pitch;
-    const uint8_t* fbase = frames + (size_t)frame * H0 * W0 * 3;
+    const uint8_t* fbase = frames + (size_t)frame * fstride + origin;
 
     for (int c0 = 0; c0 < nrows; c0 += chunk) {
         const int nr = min(chunk, nrows - c0);
         // ---- stage rows [ry0 + c0, ry0 + c0 + nr) x columns [cx0, cx0 + ncols): a wave per row, 16 bytes per lane
         for (int i = wv; i < nr; i += 4) {
-            const uint8_t* g = fbase + ((size_t)(ry0 + c0 + i) * W0 + cx0) * 3;
+            const uint8_t* g = fbase + (size_t)(ry0 + c0 + i) * gpitch + (size_t)cx0 * 3;
             const int sh = (int)((uintptr_t)g & 15);
             const u32x4* ga = (const u32x4*)(g - sh);                  // aligned down: every vector loaded holds a byte of the row,
             const int nvec = (sh + rowbytes + 15) >> 4;                // so it lies in a page the frames own
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void resize_cams_kernel(const uint8_t* __restr
             const int mn = bxs[2 * lane], cnt = bxs[2 * lane + 1];
             const int32_t* kr = kxs + lane * KS_MAX;
             for (int i = wv; i < nr; i += 4) {
-                const uint8_t* g = fbase + ((size_t)(ry0 + c0 + i) * W0 + cx0) * 3;
+                const uint8_t* g = fbase + (size_t)(ry0 + c0 + i) * gpitch + (size_t)cx0 * 3;
                 const uint8_t* p = stage + i * pitch + (int)((uintptr_t)g & 15) + (mn - cx0) * 3;
                 int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
                 for (int t = 0; t < cnt; ++t) {
@@ -180,25 +184,32 @@ inline int ksize_of(int in, int out) {
     return (int)ceil(1.0 * fs) * 2 + 1;
 }
 
-int launch(bool pack, const uint8_t* frames, int n, int ncam, int H0, int W0, int h, int w, const int32_t* kx, const int32_t* bx,
-           const int32_t* ky, const int32_t* by, uint8_t* out8, const float* mean3, const float* std3, int pad, void* hi, void* lo,
-           void* stream) {
+// (H0, W0): the window's size; pitch / fstride: bytes between the rows / the frames of the full frames; (y0, x0): the window's origin
+int launch(bool pack, const uint8_t* frames, int n, int ncam, int64_t pitch, int64_t fstride, int y0, int x0, int H0, int W0, int h,
+           int w, const int32_t* kx, const int32_t* bx, const int32_t* ky, const int32_t* by, uint8_t* out8, const float* mean3,
+           const float* std3, int pad, void* hi, void* lo, void* stream) {
     if (!frames || !kx || !bx || !ky || !by || n <= 0 || ncam <= 0 || H0 <= 0 || W0 <= 0 || h <= 0 || w <= 0) return AGP_E_BADARG;
     if (pack ? (!hi || !mean3 || !std3 || pad < 0) : !out8) return AGP_E_BADARG;
     if (!dim_ok(H0, h) || !dim_ok(W0, w) || H0 > MAX_RATIO * h || W0 > MAX_RATIO * w) return AGP_E_UNSUPPORTED;
+    // the window lies inside a frame: its rows inside the frame's rows, its last row inside the frame
+    if (y0 < 0 || x0 < 0 || pitch <= 0 || fstride <= 0) return AGP_E_BADARG;
+    if (3 * ((int64_t)x0 + W0) > pitch || ((int64_t)y0 + H0) * pitch > fstride) return AGP_E_BADARG;
+    if (pitch > 3 * (int64_t)MAX_DIM) return AGP_E_UNSUPPORTED;
     const int ksx = ksize_of(W0, w), ksy = ksize_of(H0, h);
     if (ksx > KS_MAX || ksy > KS_MAX) return AGP_E_UNSUPPORTED;
     const int tiles_x = (w + TW - 1) / TW, tiles_y = (h + TH - 1) / TH;
     const int64_t blocks = (int64_t)n * ncam * tiles_x * tiles_y;
     if (blocks >= (1ll << 31) || (int64_t)n * ncam >= (1ll << 31)) return AGP_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
+    const size_t origin = (size_t)y0 * (size_t)pitch + (size_t)x0 * 3;
     if (pack) {
-        AGP_LAUNCH(resize_cams_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, frames, ncam, H0, W0, h, w, kx, bx, ksx, ky, by,
-                   ksy, tiles_x, tiles_y, (uint8_t*)nullptr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], pad, (bf16_t*)hi,
-                   (bf16_t*)lo);
+        AGP_LAUNCH(resize_cams_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, frames, (size_t)fstride, origin,
+                   (int)pitch, ncam, H0, W0, h, w, kx, bx, ksx, ky, by, ksy, tiles_x, tiles_y, (uint8_t*)nullptr, mean3[0], mean3[1],
+                   mean3[2], std3[0], std3[1], std3[2], pad, (bf16_t*)hi, (bf16_t*)lo);
     } else {
-        AGP_LAUNCH(resize_cams_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, frames, ncam, H0, W0, h, w, kx, bx, ksx, ky, by,
-                   ksy, tiles_x, tiles_y, out8, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 0, (bf16_t*)nullptr, (bf16_t*)nullptr);
+        AGP_LAUNCH(resize_cams_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, frames, (size_t)fstride, origin,
+                   (int)pitch, ncam, H0, W0, h, w, kx, bx, ksx, ky, by, ksy, tiles_x, tiles_y, out8, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 0,
+                   (bf16_t*)nullptr, (bf16_t*)nullptr);
     }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
@@ -259,11 +270,28 @@ extern "C" int agp_resized_size(int h, int w, int size, int* oh, int* ow) {
 
 extern "C" int agp_resize_u8_cams(const uint8_t* frames, int n, int ncam, int H0, int W0, int h, int w, const int32_t* kx,
                                   const int32_t* bx, const int32_t* ky, const int32_t* by, uint8_t* out, void* stream) {
-    return launch(false, frames, n, ncam, H0, W0, h, w, kx, bx, ky, by, out, nullptr, nullptr, 0, nullptr, nullptr, stream);
+    return launch(false, frames, n, ncam, 3 * (int64_t)W0, 3 * (int64_t)W0 * H0, 0, 0, H0, W0, h, w, kx, bx, ky, by, out, nullptr,
+                  nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int agp_resize_pack_u8_cams(const uint8_t* frames, int n, int ncam, int H0, int W0, int h, int w, const int32_t* kx,
                                        const int32_t* bx, const int32_t* ky, const int32_t* by, const float* mean3,
                                        const float* std3, int pad, void* hi, void* lo, void* stream) {
-    return launch(true, frames, n, ncam, H0, W0, h, w, kx, bx, ky, by, nullptr, mean3, std3, pad, hi, lo, stream);
+    return launch(true, frames, n, ncam, 3 * (int64_t)W0, 3 * (int64_t)W0 * H0, 0, 0, H0, W0, h, w, kx, bx, ky, by, nullptr, mean3,
+                  std3, pad, hi, lo, stream);
+}
+
+extern "C" int agp_resize_u8_cams_roi(const uint8_t* frames, int n, int ncam, int64_t pitch, int64_t frame_stride, int y0, int x0,
+                                      int ch, int cw, int h, int w, const int32_t* kx, const int32_t* bx, const int32_t* ky,
+                                      const int32_t* by, uint8_t* out, void* stream) {
+    return launch(false, frames, n, ncam, pitch, frame_stride, y0, x0, ch, cw, h, w, kx, bx, ky, by, out, nullptr, nullptr, 0, nullptr,
+                  nullptr, stream);
+}
+
+extern "C" int agp_resize_pack_u8_cams_roi(const uint8_t* frames, int n, int ncam, int64_t pitch, int64_t frame_stride, int y0, int x0,
+                                           int ch, int cw, int h, int w, const int32_t* kx, const int32_t* bx, const int32_t* ky,
+                                           const int32_t* by, const float* mean3, const float* std3, int pad, void* hi, void* lo,
+                                           void* stream) {
+    return launch(true, frames, n, ncam, pitch, frame_stride, y0, x0, ch, cw, h, w, kx, bx, ky, by, nullptr, mean3, std3, pad, hi, lo,
+                  stream);
 }

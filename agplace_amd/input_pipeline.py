@@ -53,6 +53,56 @@ def random_z_rotation(max_theta_deg=5.0, generator=None):
     return z_rotation((math.pi * max_theta_deg / 180.0) * 2.0 * (u - 0.5))
 
 
+def _jitter_range(name, value, center, lo_bound, hi_bound, clip_at_zero):
+    """torchvision's ColorJitter._check_input for a number: [center - v, center + v], the first three clamped at 0; None when the
+    range is the single point `center` (the op is then left out and draws nothing)."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 <= value < float("inf")):
+        raise ValueError(f"color_jitter: {name} {value!r} must be a finite number >= 0")
+    lo, hi = center - float(value), center + float(value)
+    if clip_at_zero:
+        lo = max(lo, 0.0)
+    if not (lo_bound <= lo <= hi <= hi_bound):
+        raise ValueError(f"color_jitter: {name} values must lie in [{lo_bound}, {hi_bound}], got [{lo}, {hi}]")
+    return None if lo == hi == center else (lo, hi)
+
+
+def color_jitter(n, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, generator=None):
+    """n parameter records of torchvision's ColorJitter(brightness, contrast, saturation, hue) as float32 [n, 8] on the CPU --
+    `.cuda()` it and pass it as data_dict['query_jitter'] / ['db_jitter'] beside the frames (one record per frame, in the
+    frames' memory order), or to ops.jitter_cameras_u8.  The reference's loaders call ColorJitter(j, j, j, hue=min(0.5, j))
+    (datasets_ws_kitti360.py:236-280; Options.q_jitter / db_jitter hold j).
+
+    A record: [0:4] the ops in the order they run (0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue), [4:7] the brightness,
+    contrast and saturation factors, [7] the hue byte shift.  Per frame the draws are ColorJitter.get_params', in its order and with
+    its torch calls: torch.randperm(4), then torch.empty(1).uniform_(lo, hi) for brightness, contrast, saturation and hue; an op whose
+    range is a single point draws nothing and is marked absent (0 in its slot of the order).  Ranges: a value v gives
+    [max(0, 1 - v), 1 + v] for the first three and [-v, v], 0 <= v <= 0.5, for hue.
+
+    The hue byte shift is int(hue_factor * 255) truncated toward zero, mod 256.  This is the PINNED definition of the wrap-around
+    in torchvision's PIL path, `np_h += np.uint8(hue_factor * 255)` on the uint8 H channel: a negative factor -f shifts by
+    256 - int(f * 255)."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"color_jitter: n {n!r} must be a non-negative integer")
+    ranges = [_jitter_range("brightness", brightness, 1.0, 0.0, float("inf"), True),
+              _jitter_range("contrast", contrast, 1.0, 0.0, float("inf"), True),
+              _jitter_range("saturation", saturation, 1.0, 0.0, float("inf"), True),
+              _jitter_range("hue", hue, 0.0, -0.5, 0.5, False)]
+    out = torch.zeros((n, 8), dtype=torch.float32)
+    out[:, 4:7] = 1.0
+    for i in range(n):
+        order = torch.randperm(4, generator=generator)
+        vals = [None if r is None else float(torch.empty(1).uniform_(r[0], r[1], generator=generator)) for r in ranges]
+        for k, fn in enumerate(order.tolist()):
+            if vals[fn] is not None:
+                out[i, k] = fn + 1
+        for fn in range(3):
+            if vals[fn] is not None:
+                out[i, 4 + fn] = vals[fn]
+        if vals[3] is not None:
+            out[i, 7] = int(vals[3] * 255) % 256
+    return out
+
+
 class PinnedRing:
     def __init__(self, spec, depth=2, device="cuda"):
         """spec: {name: (shape, dtype)} of one batch."""

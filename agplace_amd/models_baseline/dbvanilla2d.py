@@ -4,7 +4,8 @@
 Per map type: ImageFE -> GeM -> MLP(Linear, LayerNorm, ReLU, Linear); stack over map types,
 F.normalize, mean over map types; db_map is [b,nmap,3,h,w] (cache/test) or [b,ndb,nmap,3,h,w]
 (train), fp32, or the same tiles decoded as uint8 [...,h,w,3]; `db_frames` (uint8 [...,H0,W0,3]) instead of db_map: decoded
-frames, resized on the device by Resize(opt.db_resize).  state_dict keys: dbimage_fes.{i}.fe.*, dbimage_pools.{i}.p, dbimage_mlps.{i}.seq.{0,1,3}.*
+frames, centre-cropped (opt.db_cropsize) and resized on the device by Resize(opt.db_resize), with `db_jitter` colour-jittered
+(DESIGN.md 1d); uint8 inputs are normalised with opt.image_mean / opt.image_std.  state_dict keys: dbimage_fes.{i}.fe.*, dbimage_pools.{i}.p, dbimage_mlps.{i}.seq.{0,1,3}.*
 All arithmetic runs in libagplace_hip.so.  .eval()+no_grad = inference; .train() = end-to-end training
 (batch-statistics BatchNorm + conv backward on HIP kernels, train_fns.TrunkFn).
 """
@@ -45,6 +46,8 @@ class DBVanilla2D(nn.Module):
         if mode == 'db':
             maptype = opt.maptype.split('_')
             fes = [ImageFE(fe_type=opt.dbimage_fe, layers=opt.dbimage_fe_layers) for _ in maptype]
+            for e in fes:
+                e.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
             self.dbimage_fes = nn.ModuleList(fes)
             self.dbimage_pools = nn.ModuleList([GeM() for _ in maptype])
             self.dbimage_mlps = nn.ModuleList([MLP(e.last_dim, dim) for e in fes])
@@ -96,6 +99,9 @@ class DBVanilla2D(nn.Module):
     def _forward_db(self, data_dict, train, trunk_maps, out_rows, defer_head):
         opt = self.opt
         frames = data_dict.get('db_frames')
+        jitter = data_dict.get('db_jitter')
+        if jitter is not None and frames is None:
+            raise ValueError("DBVanilla2D.forward_db: `db_jitter` (colour jitter records) needs `db_frames`")
         if frames is not None:
             # decoded uint8 frames [b,nmap,H0,W0,3] or [b,ndb,nmap,H0,W0,3]: resized by torchvision's Resize(opt.db_resize) rule with
             # PIL's arithmetic, normalised and packed in ONE launch in front of the stem (ops.RawFrames); the result
@@ -104,11 +110,24 @@ class DBVanilla2D(nn.Module):
                 raise ValueError("DBVanilla2D.forward_db: pass `db_frames` or `db_map`, not both")
             if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() not in (5, 6) or frames.shape[-1] != 3:
                 raise ValueError("DBVanilla2D.forward_db: `db_frames` must be uint8 [b,nmap,H0,W0,3] or [b,ndb,nmap,H0,W0,3]")
-            h, w = ops.resized_size(frames.shape[-3], frames.shape[-2], opt.db_resize)
+            # opt.db_cropsize: CenterCrop in front of the Resize, a region of interest of the same launch; `db_jitter`: float32
+            # [number of frames, 8] colour jitter records on the device, in the frames' memory order (input_pipeline.color_jitter)
+            crop = opt.db_cropsize
+            if crop is not None:
+                ops.center_crop_origin(frames.shape[-3], frames.shape[-2], crop)       # (larger than the frame: NotImplementedError)
+                h, w = ops.resized_size(crop, crop, opt.db_resize)
+            else:
+                h, w = ops.resized_size(frames.shape[-3], frames.shape[-2], opt.db_resize)
             mode = 'cachetest' if frames.dim() == 5 else 'train'
             if frames.dim() == 5:
                 frames = frames.unsqueeze(1)
             b, ndb, nmap = frames.shape[:3]
+            if jitter is not None:
+                if (not torch.is_tensor(jitter) or jitter.dtype != torch.float32 or jitter.dim() < 2
+                        or jitter.shape[-1] != ops.JITTER_RECORD or jitter.numel() != b * ndb * nmap * ops.JITTER_RECORD):
+                    raise ValueError(f"DBVanilla2D.forward_db: `db_jitter` must be float32 [{b * ndb * nmap}, {ops.JITTER_RECORD}], "
+                                     "one record per frame")
+                jitter = jitter.reshape(b, ndb, nmap, ops.JITTER_RECORD)
             c, u8, dev = 3, False, frames.device
         else:
             db_map = data_dict['db_map']
@@ -148,7 +167,8 @@ class DBVanilla2D(nn.Module):
                 j = 0 if opt.share_dbfe is True else i
                 if frames is not None:
                     f = frames[:, :, i]
-                    x = ops.RawFrames(f.reshape(b * ndb, 1, *f.shape[2:]), h, w)      # one "camera" per tile
+                    x = ops.RawFrames(f.reshape(b * ndb, 1, *f.shape[2:]), h, w, crop=crop,      # one "camera" per tile
+                                      jitter=None if jitter is None else jitter[:, :, i].reshape(b * ndb, ops.JITTER_RECORD))
                 else:
                     x = db_map[:, :, i].reshape(b * ndb, c, h, w)       # view when possible; strides are honoured
                 if u8:

@@ -16,7 +16,9 @@ neither is present data_dict carries the voxel branch's dense outputs instead:
     stg2voxvec  [b,256], voxvec_fuse [b,256]     stage-2 voxel outputs    (stage2fuse_blockadd.py:201,207)
 The cameras enter as `query_image` -- the normalised fp32 panorama [b,3,h,w] or already resized uint8 tiles [b,ncam,h,w,3] -- or
 as `query_frames`: decoded uint8 frames [b,ncam,H0,W0,3], resized on the device by torchvision's Resize(opt.q_resize) rule with
-PIL's arithmetic and then handled exactly like the uint8 tiles.
+PIL's arithmetic and then handled exactly like the uint8 tiles; `query_jitter` beside them (float32 [b*ncam,8]
+records from input_pipeline.color_jitter) runs torchvision's ColorJitter on the resized frames, on the device.  uint8 inputs are
+normalised with opt.image_mean / opt.image_std.
 Execution modes:
   * .eval() under torch.no_grad(): inference, BatchNorm folded into the conv epilogues.
   * .train() with gradients enabled: end-to-end training.  Batch-statistics BatchNorm and the conv
@@ -46,6 +48,7 @@ class MM(nn.Module):
         self.opt = opt = opt or get_options()
         self.drop = drop
         self.image_fe = ImageFE(fe_type=opt.mm_imgfe, layers=opt.mm_imgfe_layers)
+        self.image_fe.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
         self.image_pool = GeM()
         planes = [int(x) for x in opt.mm_voxfe_planes.split('_')]
         layers = [int(x) for x in opt.mm_voxfe_layers.split('_')]
@@ -181,6 +184,8 @@ class MM(nn.Module):
     def query_image(self, data_dict):
         """The image tensor the trunk sees (mm.py:70-75: drop='image' zeroes it); for `query_frames` the frames with the size
         Resize(opt.q_resize) gives them (ops.RawFrames: resized, normalised and packed in one launch in front of the stem)."""
+        if 'query_jitter' in data_dict and 'query_frames' not in data_dict:
+            raise ValueError("MM.forward_q: `query_jitter` (colour jitter records) needs `query_frames`")
         if 'query_frames' in data_dict:
             if 'query_image' in data_dict:
                 raise ValueError("MM.forward_q: pass `query_frames` or `query_image`, not both")
@@ -189,7 +194,9 @@ class MM(nn.Module):
                 raise ValueError("MM.forward_q: `query_frames` must be uint8 [b, ncam, H0, W0, 3]")
             if self.drop == 'image':
                 raise NotImplementedError("drop='image' with uint8 camera frames")
-            return ops.RawFrames(frames, *ops.resized_size(frames.shape[2], frames.shape[3], self.opt.q_resize))
+            # `query_jitter`: float32 [b * ncam, 8] colour jitter records on the device (input_pipeline.color_jitter), one per frame
+            return ops.RawFrames(frames, *ops.resized_size(frames.shape[2], frames.shape[3], self.opt.q_resize),
+                                 jitter=data_dict.get('query_jitter'))
         image = data_dict['query_image']
         if self.drop == 'image':
             if image.dtype == torch.uint8:

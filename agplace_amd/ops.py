@@ -319,13 +319,50 @@ def _resize_call(rc, what, H0, W0, h, w):
     check(rc, what)
 
 
-def resize_cameras_u8(frames, size_or_hw):
+def center_crop_origin(H0, W0, c):
+    """(top, left) of torchvision's CenterCrop(c) window on an (H0, W0) PIL frame: round((H0 - c) / 2.0), round((W0 - c) / 2.0) with
+    Python's round, halves to even (agp_center_crop_origin).  A crop larger than the frame raises NotImplementedError: torchvision
+    pads with black there, which the front end does not build."""
+    if isinstance(c, bool) or not isinstance(c, int) or c < 1:
+        raise ValueError(f"center_crop_origin: crop {c!r} must be a positive integer")
+    top, left = C.c_int(), C.c_int()
+    rc = _L().agp_center_crop_origin(int(H0), int(W0), c, C.byref(top), C.byref(left))
+    if rc == _lib.E_UNSUPPORTED:
+        raise NotImplementedError(f"centre crop {c} of a {H0}x{W0} frame: a crop larger than the frame (torchvision pads with black) "
+                                  "is not supported")
+    if rc != 0:
+        raise ValueError(f"center_crop_origin({H0}, {W0}, {c}): sizes must be positive")
+    return top.value, left.value
+
+
+def _crop_geometry(frames, crop, size_or_hw, what):
+    """The window CenterCrop(crop) cuts out of contiguous frames and its resize: (top, left, h, w, x tables, y tables)."""
+    n, ncam, H0, W0, _ = frames.shape
+    top, left = center_crop_origin(H0, W0, crop)
+    h, w = _resize_hw(crop, crop, size_or_hw)
+    if h < 1 or w < 1:
+        raise ValueError(f"{what}: the output size must be positive")
+    if crop > 8 * h or crop > 8 * w or max(H0, W0, h, w) > 16384:
+        _resize_call(_lib.E_UNSUPPORTED, what, crop, crop, h, w)
+    return top, left, h, w, resize_tables(crop, w, frames.device), resize_tables(crop, h, frames.device)
+
+
+def resize_cameras_u8(frames, size_or_hw, crop=None):
     """uint8 [n, ncam, H0, W0, 3] decoded frames (HWC, on the GPU) -> uint8 [n, ncam, h, w, 3]: PIL's bilinear resize, the bytes
     torchvision's Resize(size, antialias=True) gives for the PIL frame (reference datasets_ws_nuscenes.py:607-612).
-    size_or_hw: an int (Resize(int)'s rule, resized_size) or (h, w)."""
+    size_or_hw: an int (Resize(int)'s rule, resized_size) or (h, w).
+    crop: an int c puts torchvision's CenterCrop(c) in front of the resize (reference datasets_ws_kitti360.py:257-262), as a
+    region of interest of the same launch (center_crop_origin); the size rule then applies to the c x c window."""
     _check_frames(frames, "resize_cameras_u8")
     frames = frames.contiguous()
     n, ncam, H0, W0, _ = frames.shape
+    if crop is not None:
+        top, left, h, w, (kx, bx), (ky, by) = _crop_geometry(frames, crop, size_or_hw, "agp_resize_u8_cams_roi")
+        out = torch.empty((n, ncam, h, w, 3), dtype=torch.uint8, device=frames.device)
+        _resize_call(_L().agp_resize_u8_cams_roi(ptr(frames), n, ncam, 3 * W0, 3 * W0 * H0, top, left, crop, crop, h, w, ptr(kx),
+                                                 ptr(bx), ptr(ky), ptr(by), ptr(out), _lib.stream()),
+                     "agp_resize_u8_cams_roi", crop, crop, h, w)
+        return out
     h, w = _resize_hw(H0, W0, size_or_hw)
     if h < 1 or w < 1:
         raise ValueError("resize_cameras_u8: the output size must be positive")
@@ -338,38 +375,117 @@ def resize_cameras_u8(frames, size_or_hw):
     return out
 
 
-def pack_cameras_resized_u8(frames, size_or_hw, prec, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+def pack_cameras_resized_u8(frames, size_or_hw, prec, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, crop=None):
     """uint8 [n, ncam, H0, W0, 3] decoded frames -> the stem's input map in ONE launch: resize_cameras_u8 + pack_cameras_u8
-    (bit-identical to that pair; the resized uint8 tiles are never written to memory)."""
+    (bit-identical to that pair; the resized uint8 tiles are never written to memory).  crop: as in resize_cameras_u8 -- still
+    one launch, the cropped image is never written either."""
     _check_frames(frames, "pack_cameras_resized_u8")
     frames = frames.contiguous()
     n, ncam, H0, W0, _ = frames.shape
-    h, w = _resize_hw(H0, W0, size_or_hw)
-    if h < 1 or w < 1:
-        raise ValueError("pack_cameras_resized_u8: the output size must be positive")
-    if H0 > 8 * h or W0 > 8 * w or max(H0, W0, h, w) > 16384:
-        _resize_call(_lib.E_UNSUPPORTED, "agp_resize_pack_u8_cams", H0, W0, h, w)
-    (kx, bx), (ky, by) = resize_tables(W0, w, frames.device), resize_tables(H0, h, frames.device)
+    if crop is not None:
+        top, left, h, w, (kx, bx), (ky, by) = _crop_geometry(frames, crop, size_or_hw, "agp_resize_pack_u8_cams_roi")
+    else:
+        h, w = _resize_hw(H0, W0, size_or_hw)
+        if h < 1 or w < 1:
+            raise ValueError("pack_cameras_resized_u8: the output size must be positive")
+        if H0 > 8 * h or W0 > 8 * w or max(H0, W0, h, w) > 16384:
+            _resize_call(_lib.E_UNSUPPORTED, "agp_resize_pack_u8_cams", H0, W0, h, w)
+        (kx, bx), (ky, by) = resize_tables(W0, w, frames.device), resize_tables(H0, h, frames.device)
     if out is None:
         out = SplitMap.alloc(n, h, ncam * w, 4, 3, prec, frames.device)
     elif (out.n, out.h, out.w, out.c, out.pad) != (n, h, ncam * w, 4, 3):
         raise ValueError("pack_cameras_resized_u8: `out` must be the NHWC4 halo-3 map [n, h, ncam * w]")
     m = (C.c_float * 3)(*mean)
     s = (C.c_float * 3)(*std)
+    if crop is not None:
+        _resize_call(_L().agp_resize_pack_u8_cams_roi(ptr(frames), n, ncam, 3 * W0, 3 * W0 * H0, top, left, crop, crop, h, w, ptr(kx),
+                                                      ptr(bx), ptr(ky), ptr(by), m, s, 3, ptr(out.hi), ptr(out.lo), _lib.stream()),
+                     "agp_resize_pack_u8_cams_roi", crop, crop, h, w)
+        return out
     _resize_call(_L().agp_resize_pack_u8_cams(ptr(frames), n, ncam, H0, W0, h, w, ptr(kx), ptr(bx), ptr(ky), ptr(by), m, s, 3,
                                               ptr(out.hi), ptr(out.lo), _lib.stream()), "agp_resize_pack_u8_cams", H0, W0, h, w)
+    return out
+
+
+# ---- colour jitter of the resized tiles (csrc/jitter.hip, DESIGN.md 1d): torchvision's ColorJitter on the PIL frame, Pillow's bytes
+JITTER_RECORD = 8      # floats per frame: 4 ops in order (0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue), 3 factors, hue shift
+
+
+def _check_jitter(tiles, params, what):
+    """tiles uint8 [n, ncam, h, w, 3] and their records float32 [..., 8], one per frame, both on the GPU -> (tiles, params [n * ncam, 8])"""
+    _need_cuda(tiles, what)
+    if tiles.dtype != torch.uint8 or tiles.dim() != 5 or tiles.shape[-1] != 3 or 0 in tiles.shape:
+        raise ValueError(f"{what} expects uint8 tiles [n, ncam, h, w, 3]")
+    if not torch.is_tensor(params) or params.dtype != torch.float32 or params.dim() < 2 or params.shape[-1] != JITTER_RECORD:
+        raise ValueError(f"{what}: the jitter parameters must be a float32 tensor [frames, {JITTER_RECORD}] "
+                         "(input_pipeline.color_jitter)")
+    _need_cuda(params, what)
+    nframes = tiles.shape[0] * tiles.shape[1]
+    if params.numel() != nframes * JITTER_RECORD:
+        raise ValueError(f"{what}: {params.numel() // JITTER_RECORD} jitter records for {nframes} frames")
+    if nframes > 65535 or tiles.shape[2] * tiles.shape[3] > (1 << 30):
+        raise NotImplementedError(f"{what}: at most 65535 frames of at most 2^30 pixels per call")
+    return tiles.contiguous(), params.contiguous().view(nframes, JITTER_RECORD)
+
+
+def jitter_cameras_u8(tiles, params):
+    """uint8 [n, ncam, h, w, 3] resized tiles + one parameter record per frame (float32 [n * ncam, 8] on the GPU, from
+    input_pipeline.color_jitter) -> the jittered uint8 tiles: torchvision's ColorJitter on the PIL frame, byte for byte.  Nothing
+    is read on the host, so a captured call replays with the records rewritten in place."""
+    tiles, params = _check_jitter(tiles, params, "jitter_cameras_u8")
+    n, ncam, h, w, _ = tiles.shape
+    sums = torch.empty((n * ncam,), dtype=torch.int64, device=tiles.device)
+    out = torch.empty_like(tiles)
+    check(_L().agp_jitter_u8_cams(ptr(tiles), n, ncam, h, w, ptr(params), ptr(sums), ptr(out), _lib.stream()), "agp_jitter_u8_cams")
+    return out
+
+
+def pack_cameras_jittered_u8(tiles, params, prec, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """jitter_cameras_u8 + pack_cameras_u8 with the jittered bytes never stored: the same planes, bit for bit."""
+    tiles, params = _check_jitter(tiles, params, "pack_cameras_jittered_u8")
+    n, ncam, h, w, _ = tiles.shape
+    if out is None:
+        out = SplitMap.alloc(n, h, ncam * w, 4, 3, prec, tiles.device)
+    elif (out.n, out.h, out.w, out.c, out.pad) != (n, h, ncam * w, 4, 3):
+        raise ValueError("pack_cameras_jittered_u8: `out` must be the NHWC4 halo-3 map [n, h, ncam * w]")
+    sums = torch.empty((n * ncam,), dtype=torch.int64, device=tiles.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    check(_L().agp_jitter_pack_u8_cams(ptr(tiles), n, ncam, h, w, ptr(params), ptr(sums), m, s, 3, ptr(out.hi), ptr(out.lo),
+                                       _lib.stream()), "agp_jitter_pack_u8_cams")
     return out
 
 
 class RawFrames:
     """Decoded uint8 frames [n, ncam, H0, W0, 3] that enter a trunk resized to (h, w): a stem input like the uint8 tiles, of
     geometry (n, h, ncam * w), packed by pack_cameras_resized_u8 (ResNet._input_geometry / _stem_input).  The stem kernels that
-    read their input themselves do not take it (stem_walk_reads is False)."""
-    __slots__ = ("frames", "h", "w")
+    read their input themselves do not take it (stem_walk_reads is False).
+    crop: optional CenterCrop size in front of the resize ((h, w) is then the resized WINDOW's size).  jitter: optional colour
+    jitter records float32 [n * ncam, 8] on the frames' device (input_pipeline.color_jitter); the frames are then cropped and
+    resized to uint8 tiles, which pack_cameras_jittered_u8 jitters and packs."""
+    __slots__ = ("frames", "h", "w", "crop", "jitter")
 
-    def __init__(self, frames, h, w):
+    def __init__(self, frames, h, w, crop=None, jitter=None):
         _check_frames(frames, "RawFrames")
         self.frames, self.h, self.w = frames, int(h), int(w)
+        if crop is not None:
+            center_crop_origin(frames.shape[2], frames.shape[3], crop)
+        if jitter is not None:
+            nframes = frames.shape[0] * frames.shape[1]
+            if (not torch.is_tensor(jitter) or jitter.dtype != torch.float32 or jitter.dim() < 2 or jitter.shape[-1] != JITTER_RECORD
+                    or jitter.numel() != nframes * JITTER_RECORD):
+                raise ValueError(f"RawFrames: the jitter parameters must be float32 [{nframes}, {JITTER_RECORD}], one record per frame")
+            jitter = jitter.reshape(nframes, JITTER_RECORD)
+        self.crop, self.jitter = crop, jitter
+
+    def stem_map(self, lo, hi, prec, mean, std, out):
+        """Images [lo, hi) as the stem's input map `out`: crop + resize + pack in one launch, or with jitter crop + resize to
+        uint8 tiles -> statistics -> jitter + pack."""
+        if self.jitter is None:
+            return pack_cameras_resized_u8(self.frames[lo:hi], (self.h, self.w), prec, mean, std, out=out, crop=self.crop)
+        ncam = self.frames.shape[1]
+        tiles = resize_cameras_u8(self.frames[lo:hi], (self.h, self.w), crop=self.crop)
+        return pack_cameras_jittered_u8(tiles, self.jitter[lo * ncam:hi * ncam], prec, mean, std, out=out)
 
     @property
     def shape(self):

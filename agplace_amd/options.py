@@ -8,7 +8,7 @@ the process-wide default that modules pick up when no explicit `opt` is passed, 
 the reference's zero-argument constructors (`MM()`, `GeM()`, `DiffBlock(dim, ode_dim)`).
 """
 from dataclasses import dataclass, field, fields
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 
 @dataclass
@@ -28,6 +28,19 @@ class Options:
     # reference's nuScenes loader hard-codes 192 for the cameras (datasets_ws_nuscenes.py:608): set q_resize=192 there
     q_resize: int = 256
     db_resize: int = 256
+    # torchvision CenterCrop(db_cropsize) on the aerial tile in front of Resize(db_resize) (reference tools/options.py,
+    # datasets_ws_kitti360.py:257-262): applied to `db_frames` as a region of interest of the resize launch.  None = no crop (the
+    # nuScenes loader has it commented out)
+    db_cropsize: Optional[int] = None
+    # torchvision ColorJitter(j, j, j, hue=min(0.5, j)) strengths of the training loaders (datasets_ws_kitti360.py:236-280): what
+    # input_pipeline.color_jitter is called with for the `query_jitter` / `db_jitter` records; 0 = no jitter.  The models apply the
+    # records they are handed and never draw any themselves
+    q_jitter: float = 0.0
+    db_jitter: float = 0.0
+    # Normalize(mean, std) of every uint8 camera route (tiles, frames, the walking stem); fp32 `query_image` / `db_map` arrive
+    # normalised.  ImageNet's constants (the nuScenes loader); the KITTI-360 loader uses 0.5 / 0.22 (from_reference_opt)
+    image_mean: Tuple[float, float, float] = (0.485, 0.456, 0.406)
+    image_std: Tuple[float, float, float] = (0.229, 0.224, 0.225)
     # database model
     dbimage_fe: str = "resnet18"
     dbimage_fe_layers: str = "2_2_2"
@@ -139,6 +152,21 @@ class Options:
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} {v!r}: a positive integer (the shorter edge after the resize)")
+        v = self.db_cropsize
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+            raise ValueError(f"db_cropsize {v!r}: None or a positive integer (the side of the centre crop)")
+        for name in ("q_jitter", "db_jitter"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 <= v < float("inf")):
+                raise ValueError(f"{name} {v!r}: a finite number >= 0 (the ColorJitter strength)")
+        for name in ("image_mean", "image_std"):
+            v = getattr(self, name)
+            if (not isinstance(v, (tuple, list)) or len(v) != 3
+                    or any(isinstance(c, bool) or not isinstance(c, (int, float)) or not (abs(c) < float("inf")) for c in v)):
+                raise ValueError(f"{name} {v!r}: three finite numbers")
+            setattr(self, name, tuple(float(c) for c in v))
+        if any(c <= 0.0 for c in self.image_std):
+            raise ValueError(f"image_std {self.image_std!r}: every component must be positive")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
 
@@ -157,6 +185,12 @@ def from_reference_opt(ns) -> Options:
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")
             setattr(o, f.name, v)
+    if getattr(ns, "dataset", None) == "kitti360":
+        # the KITTI-360 loader's Normalize (datasets_ws_kitti360.py:236-280); every other loader uses ImageNet's constants
+        o.image_mean, o.image_std = (0.5,) * 3, (0.22,) * 3
+    else:
+        # db_cropsize is only live in the KITTI-360 loader (the nuScenes one has the crop commented out)
+        o.db_cropsize = Options.__dataclass_fields__["db_cropsize"].default
     o.validate()
     return o
 

@@ -33,23 +33,34 @@ def can_pair(modelq, modeldb, qdata, dbdata):
 def _resized_tiles(modelq, modeldb, qdata, dbdata):
     """Decoded frames (`query_frames` / `db_frames`) -> the resized uint8 tiles under `query_image` / `db_map`, which the pair
     then embeds as it always has: one launch of the camera front end's uint8 mode per key (ops.resize_cameras_u8), bit-identical
-    to the fused resize + pack of the separate forwards (tests/test_gpu_camera.py)."""
+    to the fused resize + pack of the separate forwards (tests/test_gpu_camera.py).  The database frames are centre-cropped
+    (opt.db_cropsize) in that launch; `query_jitter` / `db_jitter` records jitter the tiles (ops.jitter_cameras_u8)."""
+    if 'query_jitter' in qdata and 'query_frames' not in qdata:
+        raise ValueError("embed_pair: `query_jitter` (colour jitter records) needs `query_frames`")
+    if 'db_jitter' in dbdata and 'db_frames' not in dbdata:
+        raise ValueError("embed_pair: `db_jitter` (colour jitter records) needs `db_frames`")
     if 'query_frames' in qdata:
         if 'query_image' in qdata:
             raise ValueError("embed_pair: pass `query_frames` or `query_image`, not both")
         f = qdata['query_frames']
         if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() != 5 or f.shape[-1] != 3:
             raise ValueError("embed_pair: `query_frames` must be uint8 [b, ncam, H0, W0, 3]")
-        qdata = {k: v for k, v in qdata.items() if k != 'query_frames'}
-        qdata['query_image'] = ops.resize_cameras_u8(f, modelq.opt.q_resize)
+        t = ops.resize_cameras_u8(f, modelq.opt.q_resize)
+        if 'query_jitter' in qdata:
+            t = ops.jitter_cameras_u8(t, qdata['query_jitter'])
+        qdata = {k: v for k, v in qdata.items() if k not in ('query_frames', 'query_jitter')}
+        qdata['query_image'] = t
     if 'db_frames' in dbdata:
         if 'db_map' in dbdata:
             raise ValueError("embed_pair: pass `db_frames` or `db_map`, not both")
         f = dbdata['db_frames']
         if not torch.is_tensor(f) or f.dtype != torch.uint8 or f.dim() not in (5, 6) or f.shape[-1] != 3:
             raise ValueError("embed_pair: `db_frames` must be uint8 [b,nmap,H0,W0,3] or [b,ndb,nmap,H0,W0,3]")
-        t = ops.resize_cameras_u8(f.reshape(-1, *f.shape[-4:]), modeldb.opt.db_resize)
-        dbdata = {k: v for k, v in dbdata.items() if k != 'db_frames'}
+        # (the records of `db_jitter` are in the frames' memory order)
+        t = ops.resize_cameras_u8(f.reshape(-1, *f.shape[-4:]), modeldb.opt.db_resize, crop=modeldb.opt.db_cropsize)
+        if 'db_jitter' in dbdata:
+            t = ops.jitter_cameras_u8(t, dbdata['db_jitter'])
+        dbdata = {k: v for k, v in dbdata.items() if k not in ('db_frames', 'db_jitter')}
         dbdata['db_map'] = t.view(*f.shape[:-3], *t.shape[-3:])
     return qdata, dbdata
 

@@ -106,6 +106,8 @@ class ResNet(nn.Module):
         self._prep = {}
         self._prep_key = None
         self._ws = ops.Workspace()
+        # ToTensor + Normalize of uint8 inputs (tiles, frames); the owning model sets them from its Options (set_image_norm)
+        self.image_mean, self.image_std = ops.IMAGENET_MEAN, ops.IMAGENET_STD
         # map exponents (agplace_amd/map_exponents.py): {map name: e}, a plain attribute -- not a parameter or a buffer, so
         # state_dict() keeps the reference's keys.  Names: "layer{L}" = the residual group of stage L (its incoming identity and
         # every block output; for layer1 also the pooled stem output), "layer{L}.{b}.conv{k}" = a block-internal map.
@@ -202,6 +204,11 @@ class ResNet(nn.Module):
         c2f.shift = (c2.shift + sw.shift).contiguous()
         return sw, c2f
 
+    def set_image_norm(self, mean, std):
+        """Normalize(mean, std) of this trunk's uint8 inputs (Options.image_mean / image_std)."""
+        self.image_mean, self.image_std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        return self
+
     @staticmethod
     def _input_geometry(x):
         """(n, h, w, device) of a stem input: fp32 [n,3,h,w], uint8 camera tiles [n,ncam,h,w,3], decoded frames to be resized
@@ -218,8 +225,8 @@ class ResNet(nn.Module):
 
     def _stem_input(self, x, tag, prec, lo=0, hi=None, h16=False):
         """Images [lo, hi) of a stem input -- fp32 [n,3,h,w] image batch, uint8 [n,ncam,h,w,3] camera tiles (device-side
-        input pipeline, ops.pack_cameras_u8), decoded uint8 frames with their target size (ops.RawFrames: resized and packed in
-        one launch, ops.pack_cameras_resized_u8) or an already packed NHWC4 halo-3 SplitMap -- as the stem's input map (a
+        input pipeline, ops.pack_cameras_u8), decoded uint8 frames with their target size (ops.RawFrames: cropped, resized and
+        packed in one launch, ops.pack_cameras_resized_u8; with colour jitter through uint8 tiles, RawFrames.stem_map) or an already packed NHWC4 halo-3 SplitMap -- as the stem's input map (a
         slice of the full-batch workspace map)."""
         n, h, w, dev = self._input_geometry(x)
         hi = n if hi is None else hi
@@ -233,10 +240,11 @@ class ResNet(nn.Module):
         xin = ops.slice_map(self._ws.map(tag, n, h, w, 4, 3, prec, dev, h16=want16), lo, hi)
         if not want16 and xin.h16 is not None:
             xin = ops.SplitMap(xin.hi, xin.lo, xin.n, xin.h, xin.w, xin.c, xin.pad)
+        # Normalize's constants of every uint8 route (Options.image_mean / image_std, set_image_norm); fp32 images arrive normalised
         if raw:
-            ops.pack_cameras_resized_u8(x.frames[lo:hi], (x.h, x.w), prec, out=xin)
+            x.stem_map(lo, hi, prec, self.image_mean, self.image_std, xin)
         elif x.dtype == torch.uint8:
-            ops.pack_cameras_u8(x[lo:hi], prec, out=xin)
+            ops.pack_cameras_u8(x[lo:hi], prec, self.image_mean, self.image_std, out=xin)
         else:
             xin = ops.pack_f32(x[lo:hi], 4, 3, prec, out=xin)      # (a plane-less view of xin when the fp16 pack was refused)
         return xin
@@ -556,7 +564,7 @@ def forward_maps_multi(nets, xs, prec=3, level_means=None, final_pools=None):
             if prec == 4 and FUSE_STEM_POOL and STEM_READS_INPUT != "0" and not isinstance(x, (ops.SplitMap, ops.RawFrames)) and (
                     STEM_READS_INPUT == "1" or ops.stem_walk_reads(x[lo[r]:hi[r]])):
                 # the stem kernel converts the raw input (fp32 image or uint8 tiles) on its way into LDS: no packed copy
-                ops.stem_pool_raw(x[lo[r]:hi[r]], prep["stem"], c)
+                ops.stem_pool_raw(x[lo[r]:hi[r]], prep["stem"], c, net.image_mean, net.image_std)
                 cur[r] = c
                 continue
             xin = net._stem_input(x, "in", prec, lo[r], hi[r])

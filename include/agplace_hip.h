@@ -173,6 +173,39 @@ int agp_resize_pack_u8_cams(const uint8_t* frames, int n, int ncam, int H0, int 
                             const int32_t* bx, const int32_t* ky, const int32_t* by, const float* mean3,
                             const float* std3, int pad, void* hi, void* lo, void* stream);
 
+/* Centre crop in front of the resize (torchvision's CenterCrop(int) on the PIL frame, reference
+ * datasets/datasets_ws_kitti360.py:257-280), as a region of interest of the same kernel: the cropped image is never written.
+ *   agp_center_crop_origin(H0, W0, c)  host helper: top = round((H0 - c) / 2), left = round((W0 - c) / 2) with Python's round
+ *                                      (halves to even); AGP_E_UNSUPPORTED when c exceeds the frame (torchvision pads: not built)
+ * agp_resize_u8_cams_roi / agp_resize_pack_u8_cams_roi: the two entry points above for the window of ch x cw pixels at (y0, x0)
+ * of every frame.  pitch / frame_stride: BYTES between the rows / the frames of the full frames (3 * W0 and 3 * W0 * H0 for
+ * contiguous frames); the window must lie inside a frame (AGP_E_BADARG otherwise).  kx / bx: the tables of (cw -> w), ky / by:
+ * of (ch -> h); the supported sizes are those above, for the window.  The window at (0, 0) of the frame's size is the
+ * uncropped call: same kernel, same bytes. */
+int agp_center_crop_origin(int H0, int W0, int c, int* top, int* left);
+int agp_resize_u8_cams_roi(const uint8_t* frames, int n, int ncam, int64_t pitch, int64_t frame_stride, int y0, int x0, int ch,
+                           int cw, int h, int w, const int32_t* kx, const int32_t* bx, const int32_t* ky, const int32_t* by,
+                           uint8_t* out, void* stream);
+int agp_resize_pack_u8_cams_roi(const uint8_t* frames, int n, int ncam, int64_t pitch, int64_t frame_stride, int y0, int x0, int ch,
+                                int cw, int h, int w, const int32_t* kx, const int32_t* bx, const int32_t* ky, const int32_t* by,
+                                const float* mean3, const float* std3, int pad, void* hi, void* lo, void* stream);
+
+/* Colour jitter of the resized tiles (torchvision's ColorJitter on the PIL frame = Pillow's ImageEnhance blends and its
+ * RGB <-> HSV conversions, byte for byte; DESIGN.md 1d, csrc/jitter.hip).
+ * tiles: uint8 [n][ncam][h][w][3].  params: DEVICE float [n * ncam][8], one record per frame:
+ *   [0..3] the ops in the order they run: 0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue
+ *   [4..6] the brightness, contrast and saturation factors;  [7] the hue byte shift 0 .. 255
+ * sums: DEVICE workspace of n * ncam 64-bit words (sum of L per frame for the contrast op; zeroed by a kernel of the call).
+ * Nothing is read on the host: the calls can be captured and replayed with the records rewritten in place.
+ * agp_jitter_u8_cams:      -> out uint8 [n][ncam][h][w][3] (not the input buffer).
+ * agp_jitter_pack_u8_cams: -> the stem's NHWC4 map exactly as agp_pack_u8_cams_to_nhwc writes the jittered tiles; the jittered
+ *                          bytes are never stored.
+ * Supported: n * ncam <= 65535 frames of at most 2^30 pixels. */
+int agp_jitter_u8_cams(const uint8_t* tiles, int n, int ncam, int h, int w, const float* params, void* sums, uint8_t* out,
+                       void* stream);
+int agp_jitter_pack_u8_cams(const uint8_t* tiles, int n, int ncam, int h, int w, const float* params, void* sums,
+                            const float* mean3, const float* std3, int pad, void* hi, void* lo, void* stream);
+
 /* halo-padded NHWC split planes -> dense fp32 NHWC [n][h][w][c] (a torch
  * channels_last tensor of logical shape [n,c,h,w]). */
 int agp_unpack_nhwc_to_f32(const void* hi, const void* lo, int n, int h, int w, int c,

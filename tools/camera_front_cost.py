@@ -9,6 +9,10 @@ figure, not the others):
   pack      ops.pack_cameras_u8 alone on tiles that are already resized: the pass the library had before the front end
   host      Pillow's Image.resize(BILINEAR) of the same frames on the host (if Pillow imports): wall clock of one pass over all
             frames on a thread pool of `--host-threads` threads (Pillow releases the GIL while it resamples)
+Opt-in legs of the KITTI-360 chain (nobody has measured them yet; figures go to profiles/README.md when someone does):
+  --crop C    crop_fused  ops.pack_cameras_resized_u8(..., crop=C): CenterCrop(C) + Resize(size) + normalise + pack, one launch
+  --jitter J  jitter_pack ops.pack_cameras_jittered_u8 on the resized tiles with ColorJitter(J, J, J, hue=min(0.5, J)) records
+              (zero + statistics + apply launches); jitter_bcs: the same without the hue op (its HSV round trip is the fp64 part)
 Device figures: HIP events around `steps` back-to-back calls, the median of `windows` windows, after a warm-up; the map is the
 fp16 plane of precision mode 4.  Prints one JSON line per measurement and a summary line with the fused kernel's byte floor
 (frames in + packed map out) / --hbm-tbs."""
@@ -52,7 +56,20 @@ def measure_device(which, args):
     out = ops.SplitMap.alloc(args.batch, h, args.ncam * w, 4, 3, 4, dev)
     ops.prepare_resize(H0, W0, h, w, dev)
     tiles = ops.resize_cameras_u8(frames, (h, w))
+    if which == "crop_fused":
+        ch, cw = ops.resized_size(args.crop, args.crop, args.size)
+        cout = ops.SplitMap.alloc(args.batch, ch, args.ncam * cw, 4, 3, 4, dev)
+        ops.prepare_resize(args.crop, args.crop, ch, cw, dev)
+        h, w = ch, cw
+    if which in ("jitter_pack", "jitter_bcs"):
+        from agplace_amd import input_pipeline
+        j = args.jitter
+        recs = input_pipeline.color_jitter(args.batch * args.ncam, j, j, j, min(0.5, j) if which == "jitter_pack" else 0.0,
+                                           generator=torch.Generator().manual_seed(1)).to(dev)
     fns = {"fused": lambda: ops.pack_cameras_resized_u8(frames, (h, w), 4, out=out),
+           "crop_fused": lambda: ops.pack_cameras_resized_u8(frames, args.size, 4, out=cout, crop=args.crop),
+           "jitter_pack": lambda: ops.pack_cameras_jittered_u8(tiles, recs, 4, out=out),
+           "jitter_bcs": lambda: ops.pack_cameras_jittered_u8(tiles, recs, 4, out=out),
            "two_pass": lambda: ops.pack_cameras_u8(ops.resize_cameras_u8(frames, (h, w)), 4, out=out),
            "pack": lambda: ops.pack_cameras_u8(tiles, 4, out=out)}
     fn = fns[which]
@@ -104,14 +121,17 @@ def main():
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per measurement")
     ap.add_argument("--hbm-tbs", type=float, default=6.3, help="achievable HBM rate the byte floor is quoted at")
-    ap.add_argument("--only", choices=["fused", "two_pass", "pack", "host"], help="(internal) run ONE measurement in this process")
+    ap.add_argument("--crop", type=int, default=None, help="also time CenterCrop(C) in front of the resize")
+    ap.add_argument("--jitter", type=float, default=None, help="also time ColorJitter(J, J, J, min(0.5, J)) on the resized tiles")
+    ap.add_argument("--only", choices=["fused", "two_pass", "pack", "host", "crop_fused", "jitter_pack", "jitter_bcs"], help="(internal) run ONE measurement in this process")
     args = ap.parse_args()
     if args.only:
         res = measure_host(args) if args.only == "host" else measure_device(args.only, args)
         print(json.dumps(dict({"metric": "camera_front_cost", "what": args.only}, **res)), flush=True)
         return 0
     got = {}
-    for what in ("fused", "two_pass", "pack", "host"):
+    extra = (["crop_fused"] if args.crop else []) + (["jitter_pack", "jitter_bcs"] if args.jitter else [])
+    for what in ["fused", "two_pass", "pack", "host"] + extra:
         cmd = [sys.executable, os.path.abspath(__file__), "--only", what] + [a for a in sys.argv[1:]]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
@@ -134,7 +154,8 @@ def main():
                       "fused_ms": got["fused"]["ms"], "two_pass_ms": got["two_pass"]["ms"], "pack_ms": got["pack"]["ms"],
                       "host_ms": got["host"]["ms"], "bytes_in": bytes_in, "bytes_out": bytes_out, "hbm_tbs": args.hbm_tbs,
                       "byte_floor_ms": round(floor_ms, 4), "fused_over_floor": round(got["fused"]["ms"] / floor_ms, 2),
-                      "fused_over_two_pass": round(got["fused"]["ms"] / got["two_pass"]["ms"], 3)}), flush=True)
+                      "fused_over_two_pass": round(got["fused"]["ms"] / got["two_pass"]["ms"], 3),
+                      **{w + "_ms": got[w]["ms"] for w in extra}}), flush=True)
     return 0
 
 
