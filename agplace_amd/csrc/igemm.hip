@@ -19,12 +19,14 @@
 //   (folded BN / bias), residual, ReLU, re-split, full-line 16-byte stores.
 //   Epilogue GMIN: dist = |w|^2 + acc (queries pre-scaled by -2), min over the 16
 //   database rows a lane holds per 32x32 tile -> gmin[group][query].
+// Host side: the launchers, and the entries of this kernel alone: agp_internal_conv_generic / _generic_group (the dense convs
+// that conv_dispatch.hip routes here), agp_internal_gmin (kNN coarse pass), agp_sparse_conv_fwd.
 
 #ifndef AGP_SCHED
 #define AGP_SCHED 0
 #endif
 
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 namespace agp_igemm {
 
@@ -587,325 +589,9 @@ int launch_igemm(IgemmParams& p, int prec, hipStream_t s, TilePlan* plan = nullp
 }  // namespace agp_igemm
 using namespace agp_igemm;
 
-int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s, agp_igemm::TilePlan* plan);
-int agp_internal_conv_d16_pool(agp_igemm::IgemmParams& p, int prec, hipStream_t s);
-int agp_internal_stem_raw(agp_igemm::IgemmParams& p, int kind, const void* x, long long sn, long long sc, long long sh, long long sw,
-                          int h, int w, int ncam, const float* mean3, const float* std3, hipStream_t s);
-int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hipStream_t s, agp_igemm::TilePlan* plan);
-
-// Row tiles of the kernel that would run `d`, if that kernel can emit per-tile channel statistics
-// (agp_conv_desc::stat_partial): the 3x3 stride-1 kernel on bf16-pair maps.  Must mirror agp_internal_conv_kxr.
-extern "C" int agp_conv2d_stat_tiles(const agp_conv_desc* d) {
-    if (!d || d->prec != AGP_PREC_BF16X3) return 0;
-    // the packed stem on the direct-X kernel (igemm_d16: 256-row tiles of the plain [n][hout][wout] raster)
-    const int force = AGP_TUNE("CONV_KERNEL", 0);          // development build: 1 = generic LDS-staged, 2 = direct-X, 3 = 3x3 kernel
-    if (d->in_w_step != d->cin && !force && d->cout % 64 == 0)
-        return (int)(((int64_t)d->n * d->hout * d->wout + 255) / 256);
-    // everything else the generic kernel runs (1x1 and stride-2 convs): 128-row tiles for cout % 128 == 0, else 256
-    if (d->in_w_step == d->cin && !force && !AGP_TUNE("IGEMM_VARIANT", 0) && d->cin % 32 == 0 && d->cout % 64 == 0 &&
-        !(d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1)) {
-        const int bm = (d->cout % 128 == 0) ? 128 : 256;
-        return (int)(((int64_t)d->n * d->hout * d->wout + bm - 1) / bm);
-    }
-    const bool kxr_ok = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->pin == 1 &&
-                        d->pout == 1 && d->in_w_step == d->cin && d->hout == d->hin && d->wout == d->win &&
-                        (int64_t)d->n * (d->hin + 2) * (d->win + 2) * d->cin * 2 < (1ll << 31);
-    if (!kxr_ok || d->cin % 32 || d->cout % 64 || (force && force != 3)) return 0;
-    const int64_t m = (int64_t)d->n * d->hin * (d->win + 2);
-    const int bm = (d->cout % 128 == 0 && !d->hi_only) ? 128 : 256;      // (the one-product form: 256-row tiles at every width)
-    return (int)((m + bm - 1) / bm);
-}
-
-static bool conv_kxr_ok(const agp_conv_desc* d);
-bool agp_internal_use_kxr2(const agp_conv_desc* d);
-
-// 64-row blocks of agp_conv_desc::pool_partial: the AGP_PREC_F16 3x3 stride-1 kernel (igemm_kxr2, 256-row tiles of four
-// 64-row wave blocks) over a raster that gives every image a multiple of 64 rows.
-extern "C" int agp_conv2d_pool_blocks(const agp_conv_desc* d) {
-    if (!d || d->prec != AGP_PREC_F16 || d->in_lo || d->out_lo || d->cin % 32 || d->cout % 64 || d->n <= 0) return 0;
-    if (!conv_kxr_ok(d) || !agp_internal_use_kxr2(d) || AGP_TUNE("CONV_KERNEL", 0) || AGP_TUNE("NO_CONV_POOL", 0)) return 0;
-    const int64_t rp = ((int64_t)d->hin * (d->win + 2) + 63) / 64 * 64;
-    if ((int64_t)d->n * rp >= (1ll << 31)) return 0;
-    return (int)(((int64_t)d->n * rp + 511) / 512 * 8);      // (64-row blocks of 256- or 512-row tiles: the larger count)
-}
-
-static bool conv_kxr_ok(const agp_conv_desc* d) {
-    return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->pin == 1 &&
-           d->pout == 1 && d->in_w_step == d->cin && d->hout == d->hin && d->wout == d->win &&
-           (int64_t)d->n * (d->hin + 2) * (d->win + 2) * d->cin * 2 < (1ll << 31);
-}
-
-static int conv_fill_params(const agp_conv_desc* d, IgemmParams& p);
-void agp_internal_conv_kxr_geometry(agp_igemm::IgemmParams& p, const agp_conv_desc* d);
-bool agp_internal_use_kxr2(const agp_conv_desc* d);
-int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
-int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs, int n, hipStream_t s, agp_igemm::TilePlan* plan, bool nods);
-int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan, const agp_igemm::KxrwStreams* ds);
-
-// Several convolutions of ONE channel shape (cin, cout, 3x3 stride 1) and precision as ONE launch: the tiles of
-// every problem form one grid (igemm_kxr2.hip).  Groups the kernel cannot take run as `n` launches, in order.
-static int conv2d_fwd_one(const agp_conv_desc* d, void* stream, TilePlan* plan);
-
-// `plan` != NULL (agp_conv2d_tile_plan): the same decisions, reported instead of launched.
-static int conv2d_fwd_group(const agp_conv_desc* descs, int n, void* stream, TilePlan* plan) {
-    if (!descs || n <= 0) return AGP_E_BADARG;
-    bool group = n >= 2 && n <= 4;
-    for (int i = 0; i < n && group; ++i) {
-        const agp_conv_desc* d = descs + i;
-        group = d->in_hi && d->w_hi && d->out_hi && !d->in_lo && !d->out_lo && !d->res_lo && d->n > 0 &&
-                d->cin % 32 == 0 && d->cout % 64 == 0 && conv_kxr_ok(d) && agp_internal_use_kxr2(d) &&
-                d->cin == descs[0].cin && d->cout == descs[0].cout && !AGP_TUNE("CONV_KERNEL", 0);
-    }
-    if (!group && !AGP_TUNE("CONV_KERNEL", 0) && !AGP_TUNE("NO_S2", 0)) {
-        // the stride-2 entry of a ResNet stage: [3x3/s2 conv of every trunk ..., its 1x1/s2 downsample of every trunk ...] on fp16
-        // maps with one product -> ONE launch of igemm_s2.hip (the downsample rides on the 3x3's staged centre tap)
-        const int h = n / 2;
-        bool s2 = (n == 2 || n == 4);
-        for (int i = 0; i < h && s2; ++i) {
-            const agp_conv_desc* c = descs + i;
-            const agp_conv_desc* d = descs + h + i;
-            s2 = c->prec == AGP_PREC_F16 && d->prec == AGP_PREC_F16 && c->in_hi && c->w_hi && c->out_hi && d->w_hi && d->out_hi &&
-                 !c->in_lo && !c->out_lo && !d->in_lo && !d->out_lo && !c->res_hi && !d->res_hi && !c->stat_partial && !d->stat_partial &&
-                 !c->pool_partial && !d->pool_partial &&
-                 c->kh == 3 && c->kw == 3 && c->stride == 2 && c->pad == 1 && c->pin == 1 && c->pout == 1 && c->in_w_step == c->cin &&
-                 d->kh == 1 && d->kw == 1 && d->stride == 2 && d->pad == 0 && d->pin == 1 && d->pout == 1 && d->in_w_step == d->cin &&
-                 d->in_hi == c->in_hi && d->n == c->n && d->hin == c->hin && d->win == c->win && d->cin == c->cin &&
-                 d->cout == c->cout && d->hout == c->hout && d->wout == c->wout && !d->relu &&
-                 c->hout == (c->hin - 1) / 2 + 1 && c->wout == (c->win - 1) / 2 + 1 &&
-                 c->cin % 32 == 0 && c->cout % 64 == 0 && c->n > 0 && c->cin == descs[0].cin && c->cout == descs[0].cout &&
-                 (int64_t)c->n * (c->hin + 2) * (c->win + 2) * c->cin * 2 < (1ll << 31) &&
-                 (int64_t)c->n * (c->hout + 2) * (c->wout + 2) * c->cout * 2 < (1ll << 31);
-        }
-        if (s2) {
-            IgemmParams ps[2];
-            for (int i = 0; i < h; ++i) {
-                ps[i] = IgemmParams{};
-                const int rc = conv_fill_params(descs + i, ps[i]);
-                if (rc != AGP_OK) return rc;
-                const agp_conv_desc* d = descs + h + i;
-                ps[i].w2_hi = d->w_hi; ps[i].w2_cm = d->w_cm; ps[i].scale2 = d->scale; ps[i].shift2 = d->shift; ps[i].o2_hi = d->out_hi;
-            }
-            return agp_internal_conv_s2(ps, descs, h, (hipStream_t)stream, plan, false);
-        }
-    }
-    if (!group) {
-        // second grouping: fp16 single-product convs of the generic kernel (1x1 and stride-2 convs) of one tile
-        // configuration -- the stride-2 entry of a ResNet stage (3x3/s2 + 1x1/s2 downsample of every trunk)
-        bool g2 = n >= 2 && n <= 4 && !AGP_TUNE("CONV_KERNEL", 0) && !AGP_TUNE("NO_IGEMM_GROUP", 0);
-        for (int i = 0; i < n && g2; ++i) {
-            const agp_conv_desc* d = descs + i;
-            g2 = d->in_hi && d->w_hi && d->out_hi && !d->in_lo && !d->out_lo && !d->res_lo && d->n > 0 &&
-                 d->prec == AGP_PREC_F16 && !d->stat_partial && d->cin % 64 == 0 && d->cout % 128 == 0 &&
-                 !conv_kxr_ok(d) && d->in_w_step == d->cin && !(d->pin < d->pad);
-        }
-        if (g2) {
-            IgemmParams ps[4];
-            for (int i = 0; i < n; ++i) {
-                ps[i] = IgemmParams{};
-                const int rc = conv_fill_params(descs + i, ps[i]);
-                if (rc != AGP_OK) return rc;
-            }
-            return launch_group_f16(ps, n, (hipStream_t)stream, plan);
-        }
-        if (plan && n > 1) return AGP_E_UNSUPPORTED;      // `n` launches: ask for each descriptor's plan
-        for (int i = 0; i < n; ++i) {
-            const int rc = conv2d_fwd_one(descs + i, stream, plan);
-            if (rc != AGP_OK) return rc;
-        }
-        return AGP_OK;
-    }
-    IgemmParams ps[4];
-    for (int i = 0; i < n; ++i) {
-        ps[i] = IgemmParams{};
-        const int rc = conv_fill_params(descs + i, ps[i]);
-        if (rc != AGP_OK) return rc;
-        agp_internal_conv_kxr_geometry(ps[i], descs + i);
-    }
-    return agp_internal_conv_kxr2(ps, n, (hipStream_t)stream, plan);
-}
-
-extern "C" int agp_conv2d_fwd_grouped(const agp_conv_desc* descs, int n, void* stream) {
-    return conv2d_fwd_group(descs, n, stream, nullptr);
-}
-
-extern "C" int agp_conv2d_fwd(const agp_conv_desc* d, void* stream) { return conv2d_fwd_one(d, stream, nullptr); }
-
-// ---- the stage entry without a stored downsample map (include/agplace_hip.h)
-static bool s2_conv_ok(const agp_conv_desc* c, const agp_conv_desc* d0) {
-    return c->prec == AGP_PREC_F16 && c->in_hi && c->w_hi && c->out_hi && !c->in_lo && !c->w_lo && !c->out_lo && !c->res_hi && !c->res_lo &&
-           !c->stat_partial && !c->pool_partial && !c->hi_only &&
-           c->kh == 3 && c->kw == 3 && c->stride == 2 && c->pad == 1 && c->pin == 1 && c->pout == 1 && c->in_w_step == c->cin &&
-           c->hin > 0 && c->win > 0 && c->hout == (c->hin - 1) / 2 + 1 && c->wout == (c->win - 1) / 2 + 1 &&
-           c->cin % 32 == 0 && c->cout % 64 == 0 && c->n > 0 && c->cin == d0->cin && c->cout == d0->cout &&
-           (int64_t)c->n * (c->hin + 2) * (c->win + 2) * c->cin * 2 < (1ll << 31) &&
-           (int64_t)c->n * (c->hout + 2) * (c->wout + 2) * c->cout * 2 < (1ll << 31);
-}
-
-extern "C" int agp_conv2d_s2_fwd(const agp_conv_desc* descs, int n, void* stream) {
-    if (!descs) return AGP_E_BADARG;
-    if (n < 1 || n > 2 || AGP_TUNE("CONV_KERNEL", 0) || AGP_TUNE("NO_S2", 0)) return AGP_E_UNSUPPORTED;
-    for (int i = 0; i < n; ++i)
-        if (!s2_conv_ok(descs + i, descs)) return AGP_E_UNSUPPORTED;
-    IgemmParams ps[2];
-    for (int i = 0; i < n; ++i) {
-        ps[i] = IgemmParams{};
-        const int rc = conv_fill_params(descs + i, ps[i]);
-        if (rc != AGP_OK) return rc;
-    }
-    return agp_internal_conv_s2(ps, descs, n, (hipStream_t)stream, nullptr, true);
-}
-
-extern "C" int agp_conv2d_fwd_grouped2(const agp_conv_desc* descs, const agp_conv_stream2* s2, int n, void* stream) {
-    if (!descs || !s2) return AGP_E_BADARG;
-    if (n < 1 || n > 4 || AGP_TUNE("CONV_KERNEL", 0) || !AGP_TUNE("KXR_WIDE", 1)) return AGP_E_UNSUPPORTED;
-    bool any = false;
-    for (int i = 0; i < n; ++i) {
-        const agp_conv_desc* d = descs + i;
-        const bool ok = d->prec == AGP_PREC_F16 && d->in_hi && d->w_hi && d->out_hi && !d->in_lo && !d->w_lo && !d->out_lo && !d->res_lo &&
-                        !d->hi_only && d->n > 0 && d->cin % 32 == 0 && d->cout % 128 == 0 && conv_kxr_ok(d) && agp_internal_use_kxr2(d) &&
-                        d->cin == descs[0].cin && d->cout == descs[0].cout;
-        if (!ok) return AGP_E_UNSUPPORTED;
-        const agp_conv_stream2* t = s2 + i;
-        if (!t->in_hi) continue;
-        any = true;
-        if (!t->w_cm || d->res_hi || d->pool_partial || t->n != d->n || t->cin <= 0 || t->cin % 32 || t->hin <= 0 || t->win <= 0 ||
-            (t->hin - 1) / 2 + 1 != d->hout || (t->win - 1) / 2 + 1 != d->wout ||
-            (int64_t)t->n * (t->hin + 2) * (t->win + 2) * t->cin * 2 >= (1ll << 31))
-            return AGP_E_UNSUPPORTED;
-    }
-    IgemmParams ps[4];
-    KxrwStreams ds = {};
-    for (int i = 0; i < n; ++i) {
-        ps[i] = IgemmParams{};
-        const int rc = conv_fill_params(descs + i, ps[i]);
-        if (rc != AGP_OK) return rc;
-        agp_internal_conv_kxr_geometry(ps[i], descs + i);
-        const agp_conv_stream2* t = s2 + i;
-        if (!t->in_hi) continue;
-        const int wp = t->win + 2, hp = t->hin + 2;
-        KxrwStream& k = ds.s[i];
-        k.x = t->in_hi; k.w = t->w_cm;
-        k.x_bytes = (uint32_t)((int64_t)t->n * hp * wp * t->cin * 2);
-        k.w_bytes = (uint32_t)((int64_t)t->cin * descs[i].cout * 2);
-        // raster row (img, y, xq) of the output reads input pixel (2 y, 2 (xq - 1)) = padded pixel (2 y + 1, 2 xq - 1)
-        k.sn = hp * wp * t->cin; k.sh = 2 * wp * t->cin; k.sw = 2 * t->cin; k.base = (wp - 1) * t->cin;
-        k.nc = t->cin / 32;
-    }
-    return agp_internal_conv_kxrw(ps, n, (hipStream_t)stream, nullptr, any ? &ds : nullptr);
-}
-
-// The tile plan of the launch that agp_conv2d_fwd (n == 1) / agp_conv2d_fwd_grouped (n > 1) would make for these descriptors:
-// the launch path itself, stopped in the launcher before anything touches the device.
-extern "C" int agp_conv2d_tile_plan(const agp_conv_desc* descs, int n, int32_t plan[8]) {
-    if (!descs || !plan || n <= 0) return AGP_E_BADARG;
-    TilePlan tp = {};
-    const int rc = n == 1 ? conv2d_fwd_one(descs, nullptr, &tp) : conv2d_fwd_group(descs, n, nullptr, &tp);
-    if (rc != AGP_OK) return rc;
-    const int32_t v[8] = {tp.kernel, tp.BM, tp.BN, tp.MT, tp.NT, tp.MT_full, tp.half_tiles, tp.grid};
-    for (int i = 0; i < 8; ++i) plan[i] = v[i];
-    return AGP_OK;
-}
-
-static int conv2d_fwd_one(const agp_conv_desc* d, void* stream, TilePlan* plan) {
-    if (!d || !d->in_hi || !d->w_hi || !d->out_hi) return AGP_E_BADARG;
-    // storage format follows the precision: BF16X3 = bf16 plane pairs everywhere; F16W2 / F16 = one
-    // fp16 activation plane (lo pointers NULL) and an fp16 weight pair / single plane
-    if (d->prec == AGP_PREC_BF16X3) {
-        if ((!d->hi_only && (!d->in_lo || !d->w_lo)) || !d->out_lo || (d->res_hi && !d->res_lo)) return AGP_E_BADARG;
-    } else if (d->prec == AGP_PREC_F16W2 || d->prec == AGP_PREC_F16) {
-        if (d->in_lo || d->out_lo || d->res_lo) return AGP_E_BADARG;
-        if (d->prec == AGP_PREC_F16W2 && !d->w_lo) return AGP_E_BADARG;
-    } else {
-        return AGP_E_BADARG;
-    }
-    if (d->cin % 32 || d->cout % 64 || d->n <= 0) return AGP_E_BADARG;
-    if (d->pin < d->pad && d->in_w_step == d->cin) return AGP_E_BADARG;
-    IgemmParams p = {};
-    {
-        const int rc = conv_fill_params(d, p);
-        if (rc != AGP_OK) return rc;
-    }
-    // Kernel choice (development build: CONV_KERNEL = 1 generic / 2 direct-X / 3 3x3 kernel forces one where it is applicable):
-    //   3x3 stride-1 pad-1 on 1-pixel-halo planes -> igemm_kxr.hip / igemm_kxr2.hip (horizontal-tap reuse in LDS)
-    //   packed stem (in_w_step != cin)             -> igemm_d16.hip (X straight into registers)
-    //   everything else (1x1, stride 2)            -> the generic LDS-staged kernel of this file
-    const int force = AGP_TUNE("CONV_KERNEL", 0);
-    const bool kxr_ok = conv_kxr_ok(d);
-    const bool stem = d->in_w_step != d->cin;
-#if defined(AGP_TUNING)
-    if (p.dbg & 0x1000000) {   // census experiment (tools/census.py): the record buffer's address as two switch words
-        const uint64_t a = ((uint64_t)(uint32_t)AGP_TUNE("CENSUS_BUF_HI", 0) << 32) | (uint32_t)AGP_TUNE("CENSUS_BUF_LO", 0);
-        p.gmin = (float*)(uintptr_t)a;
-        if (!p.gmin) p.dbg &= ~0x1000000;
-    }
-#endif
-    int which = force ? force : (kxr_ok ? 3 : (stem ? 2 : 1));
-    if (which == 3 && !kxr_ok) which = stem ? 2 : 1;
-    if (d->hi_only && (d->prec != AGP_PREC_BF16X3 || which != 3)) return AGP_E_BADARG;      // the 3x3 stride-1 kernel's one-product form only
-    // w_cm == w_hi: the caller holds chunk-major planes ONLY (training planes written that way): every kernel but the 3x3 stride-1
-    // one would read them as row-major -- refuse instead
-    if (d->w_cm && d->w_cm == d->w_hi && (which != 3 || !p.w_cm)) return AGP_E_BADARG;
-    if (which == 3) return agp_internal_conv_kxr(p, d, (hipStream_t)stream, plan);
-    if (which == 2) return agp_internal_conv_d16(p, d->prec, (hipStream_t)stream, plan);
-    return launch_igemm<EPI_CONV>(p, d->prec, (hipStream_t)stream, plan);
-}
-
-// The generic geometry of `d` (every conv kernel starts from it).
-static int conv_fill_params(const agp_conv_desc* d, IgemmParams& p) {
-    const int hp = d->hin + 2 * d->pin, wp = d->win + 2 * d->pin;
-    const int wstep = d->in_w_step;
-    // bytes of one plane; for the packed stem (in_w_step < cin) rows overlap, the plane
-    // still has hp*wp pixels of in_w_step elements.
-    const int64_t x_elems = (int64_t)d->n * hp * wp * wstep;
-    const int64_t w_elems = (int64_t)d->cout * d->kh * d->kw * d->cin;
-    if (x_elems * 2 >= (1ll << 32) || w_elems * 2 >= (1ll << 31)) return AGP_E_BADARG;
-    p.x_hi = d->in_hi; p.x_lo = d->in_lo; p.x_bytes = (uint32_t)(x_elems * 2);
-    p.w_hi = d->w_hi; p.w_lo = d->w_lo; p.w_bytes = (uint32_t)(w_elems * 2);
-    if (d->prec == AGP_PREC_F16W2 && d->w_q8) { p.w_q8 = d->w_q8; p.w_q8_exp = d->w_q8_exp; }
-    if (d->prec == AGP_PREC_F16 && d->w_cm) p.w_cm = d->w_cm;
-    // the two-plane modes (igemm_kxr: 3x3 stride-1 convs): both planes chunk-major
-    if ((d->prec == AGP_PREC_F16W2 || d->prec == AGP_PREC_BF16X3) && d->w_cm && d->kh == 3 && d->kw == 3 &&
-        d->stride == 1 && d->pad == 1 && d->in_w_step == d->cin && (d->w_cm_lo || (d->hi_only && d->prec == AGP_PREC_BF16X3))) {
-        p.w_cm = d->w_cm; p.w_cm_lo = d->w_cm_lo;
-    }
-    if (d->stat_partial) {
-        if (agp_conv2d_stat_tiles(d) <= 0) return AGP_E_BADARG;      // only the kernels that can produce them
-        p.stat_partial = d->stat_partial;
-        if (d->bstat_z_hi) {
-            // backward mode: the 3x3 stride-1 kernel only (the other kernels' tiles carry forward sums)
-            // (bstat_z_lo NULL: z is ONE fp16 plane -- the output of a forward conv that ran as one fp16 product)
-            if (!d->bstat_mean || !d->bstat_rstd || d->in_w_step != d->cin ||
-                !(d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1))
-                return AGP_E_BADARG;
-            p.bs_z_hi = d->bstat_z_hi; p.bs_z_lo = d->bstat_z_lo; p.bs_y_hi = d->bstat_y_hi;
-            p.bs_mean = d->bstat_mean; p.bs_rstd = d->bstat_rstd;
-        }
-    } else if (d->bstat_z_hi) {
-        return AGP_E_BADARG;
-    }
-    if (d->pool_partial) {
-        if (agp_conv2d_pool_blocks(d) <= 0) return AGP_E_BADARG;
-        if (d->pool_stat != 0 && d->pool_stat != 1) return AGP_E_BADARG;
-        p.pool_partial = d->pool_partial; p.pool_p = d->pool_stat ? nullptr : d->pool_p; p.pool_eps = d->pool_eps; p.pool_sq = d->pool_stat;
-    }
-    p.M = d->n * d->hout * d->wout;
-    p.N = d->cout;
-    p.KW = d->kw; p.CK = d->cin; p.ntaps = d->kh * d->kw;
-    p.Ktot = d->kh * d->kw * d->cin;
-    p.d_howo = make_fastdiv((uint32_t)(d->hout * d->wout));
-    p.d_wo = make_fastdiv((uint32_t)d->wout);
-    p.x_sw = wstep; p.x_sh = wp * wstep; p.x_sn = hp * wp * wstep;
-    p.x_base = ((d->pin - d->pad) * wp + (d->pin - d->pad)) * wstep;
-    p.sy = d->stride; p.sx = d->stride;
-    const int hop = d->hout + 2 * d->pout, wop = d->wout + 2 * d->pout;
-    p.o_hi = d->out_hi; p.o_lo = d->out_lo;
-    p.o_sw = d->cout; p.o_sh = wop * d->cout; p.o_sn = hop * wop * d->cout;
-    p.o_base = (d->pout * wop + d->pout) * d->cout;
-    p.r_hi = d->res_hi; p.r_lo = d->res_lo;
-    p.scale = d->scale; p.shift = d->shift; p.relu = d->relu;
-    p.dbg = AGP_TUNE("IGEMM_DBG", 0);
-    return AGP_OK;
-}
+// The dense convs that conv_dispatch.hip routes to this kernel: one, or 2..4 as one grid (launch_group_f16_cfg); generic geometry.
+int agp_internal_conv_generic(IgemmParams& p, int prec, hipStream_t s, TilePlan* plan) { return launch_igemm<EPI_CONV>(p, prec, s, plan); }
+int agp_internal_conv_generic_group(IgemmParams* ps, int n, hipStream_t s, TilePlan* plan) { return launch_group_f16(ps, n, s, plan); }
 
 // Coarse kNN pass, called from knn.hip: W = database rows, X = queries (1x1 "conv").
 int agp_internal_gmin(const void* q_hi, const void* q_lo, int64_t nq, const void* db_hi,
@@ -947,51 +633,4 @@ extern "C" int agp_sparse_conv_fwd(const void* f_hi, const void* f_lo, int64_t n
     p.o_hi = out_hi; p.o_lo = out_lo; p.o_sn = 0; p.o_sh = 0; p.o_sw = cout; p.o_base = 0;
     p.r_hi = res_hi; p.r_lo = res_lo; p.scale = scale; p.shift = shift; p.relu = relu;
     return launch_igemm<EPI_CONV>(p, prec, (hipStream_t)stream);
-}
-
-// ---- packed 7x7/2 stem conv + BatchNorm + ReLU + MaxPool2d(3, 2, 1) in one kernel (fp16 maps).
-// `d` describes the stem conv as for agp_conv2d_fwd (cin = 32, in_w_step = 4, kw = 1, stride 2, pad 3,
-// cout = 64, relu = 1) except that out_* is the POOLED map [n][hp2][wp2][64] with halo d->pout and
-// hout / wout are the POOLED sizes.
-static int stem_pool_impl(const agp_conv_desc* d, int kind, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int ncam,
-                          const float* mean3, const float* std3, void* stream) {
-    if (!d || !d->in_hi || !d->w_hi || !d->out_hi || d->in_lo || d->out_lo || d->res_hi) return AGP_E_BADARG;
-    if (d->prec != AGP_PREC_F16W2 && d->prec != AGP_PREC_F16) return AGP_E_BADARG;
-    if (d->prec == AGP_PREC_F16W2 && !d->w_lo) return AGP_E_BADARG;
-    if (d->cin != 32 || d->in_w_step != 4 || d->kw != 1 || d->kh != 7 || d->stride != 2 || d->pad != 3 || d->pin != 3 ||
-        d->cout != 64 || !d->relu || d->n <= 0)
-        return AGP_E_BADARG;
-    const int h1 = (d->hin + 2 * 3 - 7) / 2 + 1, w1 = (d->win + 2 * 3 - 7) / 2 + 1;
-    const int h2 = (h1 + 2 - 3) / 2 + 1, w2 = (w1 + 2 - 3) / 2 + 1;
-    if (d->hout != h2 || d->wout != w2) return AGP_E_BADARG;
-    IgemmParams p = {};
-    const int hp = d->hin + 6, wp = d->win + 6;
-    const int64_t x_elems = (int64_t)d->n * hp * wp * 4;
-    const int64_t w_elems = (int64_t)64 * 7 * 32;
-    if (kind == 0 && x_elems * 2 >= (1ll << 32)) return AGP_E_BADARG;
-    p.x_hi = d->in_hi; p.x_lo = nullptr; p.x_bytes = (uint32_t)(x_elems * 2);
-    p.w_hi = d->w_hi; p.w_lo = d->w_lo; p.w_bytes = (uint32_t)(w_elems * 2);
-    p.M = d->n * h1 * w1; p.N = 64; p.Ktot = 7 * 32; p.KW = 1; p.CK = 32; p.ntaps = 7;
-    p.d_howo = make_fastdiv((uint32_t)(h1 * w1)); p.d_wo = make_fastdiv((uint32_t)w1);
-    p.x_sw = 4; p.x_sh = wp * 4; p.x_sn = hp * wp * 4; p.x_base = 0; p.sy = 2; p.sx = 2;
-    const int hop = h2 + 2 * d->pout, wop = w2 + 2 * d->pout;
-    p.o_hi = d->out_hi; p.o_lo = nullptr;
-    p.o_sw = 64; p.o_sh = wop * 64; p.o_sn = hop * wop * 64; p.o_base = (d->pout * wop + d->pout) * 64;
-    p.scale = d->scale; p.shift = d->shift; p.relu = 1;
-    p.pool_h1 = h1; p.pool_w1 = w1; p.pool_h2 = h2; p.pool_w2 = w2;
-    p.pool_ty = (h2 + 6) / 7; p.pool_tx = (w2 + 6) / 7;
-    if (kind == 0) return agp_internal_conv_d16_pool(p, d->prec, (hipStream_t)stream);
-    if (d->prec != AGP_PREC_F16) return AGP_E_BADARG;
-    if (kind == 2 && (ncam <= 0 || d->win % ncam)) return AGP_E_BADARG;
-    return agp_internal_stem_raw(p, kind, d->in_hi, sn, sc, sh, sw, d->hin, d->win, ncam, mean3, std3, (hipStream_t)stream);
-}
-
-extern "C" int agp_stem_pool_fwd(const agp_conv_desc* d, void* stream) {
-    return stem_pool_impl(d, 0, 0, 0, 0, 0, 1, nullptr, nullptr, stream);
-}
-
-extern "C" int agp_stem_pool_raw_fwd(const agp_conv_desc* d, int kind, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int ncam,
-                                     const float* mean3, const float* std3, void* stream) {
-    if (kind != 1 && kind != 2) return AGP_E_BADARG;
-    return stem_pool_impl(d, kind, sn, sc, sh, sw, ncam, mean3, std3, stream);
 }

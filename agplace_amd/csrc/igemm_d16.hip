@@ -17,7 +17,7 @@
 //   * Split-bf16 (NPREC 3): hi*hi + hi*lo + lo*hi into one fp32 accumulator.
 //   * Epilogue as in igemm.hip: LDS transpose -> scale/shift, residual, ReLU, hi/lo split,
 //     whole-line stores.
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 namespace agp_igemm {
 
@@ -552,10 +552,6 @@ int launch_d16_pool(IgemmParams& p, hipStream_t s) {
 
 }  // namespace agp_igemm
 
-int agp_internal_stem_walk(agp_igemm::IgemmParams& p, int kind, agp_igemm::StemRaw raw, hipStream_t s);     // stem_walk.hip
-bool agp_internal_stem_walk_reads(const agp_igemm::StemRaw& raw, int n);
-bool agp_internal_stem_walk_reads_u8(const agp_igemm::StemRaw& raw, int n);
-
 // development build, STEM_WALK = 0: the one-workgroup-per-block stem kernels of this file instead of stem_walk.hip
 static bool stem_walk_enabled() { return AGP_TUNE("STEM_WALK", 1) != 0; }
 
@@ -574,7 +570,7 @@ int agp_internal_conv_d16_pool(agp_igemm::IgemmParams& p, int prec, hipStream_t 
     return AGP_E_BADARG;
 }
 
-// Conv dispatch for the direct-X kernel (called from igemm.hip's agp_conv2d_fwd).
+// Conv dispatch for the direct-X kernel (called from conv_dispatch.hip's agp_conv2d_fwd).
 int agp_internal_conv_d16(agp_igemm::IgemmParams& p, int prec, hipStream_t s, agp_igemm::TilePlan* plan) {
     using namespace agp_igemm;
     const bool wide = (p.N % 128 == 0);

@@ -19,7 +19,7 @@
 
 #include <type_traits>
 
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 namespace agp_igemm {
 
@@ -709,8 +709,6 @@ int launch_kxr(IgemmParams& p, hipStream_t s, TilePlan* plan) {
 
 }  // namespace agp_igemm
 
-int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan);
-
 // Rewrites the generic geometry of `p` for the padded-width raster of the 3x3 stride-1 kernels.
 void agp_internal_conv_kxr_geometry(agp_igemm::IgemmParams& p, const agp_conv_desc* d) {
     using namespace agp_igemm;
@@ -743,7 +741,7 @@ int agp_internal_conv_kxr(agp_igemm::IgemmParams& p, const agp_conv_desc* d, hip
     const bool wide = (p.N % 128 == 0);
     if (d->prec == AGP_PREC_BF16X3 && d->hi_only) {
         // one bf16 product on the hi planes, the split-pair epilogue (residual, statistics, out_hi / out_lo) of the three-product
-        // form; 256-row tiles at every width (agp_conv2d_stat_tiles mirrors it)
+        // form; 256-row tiles at every width
         // wide: a wave owns 64 rows x 128 columns -- 16 MFMAs per phase and barrier, the inference kernel's shape (8 on 128 x 128
         // tiles of four waves: 0.20 MFMA-busy at 2.2 TB/s, bound by neither)
         return wide ? launch_kxr<256, 128, 4, 1, 1, 3, true>(p, s, plan) : launch_kxr<256, 64, 4, 1, 1, 3, true>(p, s, plan);

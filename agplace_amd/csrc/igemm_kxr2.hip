@@ -54,7 +54,7 @@
 
 #include <type_traits>
 
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 // -DAGP_CENSUS=1: per-workgroup time stamps (100 MHz) into the buffer of tools/census.py (p.gmin, dbg bit 0x1000000)
 #ifndef AGP_CENSUS
@@ -521,8 +521,6 @@ int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
 }
 
 }  // namespace agp_igemm
-
-int agp_internal_conv_kxrw(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan, const agp_igemm::KxrwStreams* ds);
 
 // `ps[i]` arrive with the padded-width raster geometry of agp_internal_conv_kxr_geometry; all share N, CK, prec F16.
 int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp_igemm::TilePlan* plan) {

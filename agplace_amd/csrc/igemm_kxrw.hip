@@ -58,7 +58,7 @@
 
 #include <type_traits>
 
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 namespace agp_igemm {
 

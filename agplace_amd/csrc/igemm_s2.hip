@@ -33,7 +33,7 @@
 
 #include <type_traits>
 
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 namespace agp_igemm {
 
@@ -354,7 +354,7 @@ __global__ void __launch_bounds__(256, TN == 2 ? 3 : 2) igemm_s2_kernel(S2Group 
 
 }  // namespace agp_igemm
 
-// ps[i]: the 3x3 / stride-2 conv of problem i in the generic geometry (conv_fill_params), with w2_hi / scale2 / shift2 / o2_hi
+// ps[i]: the 3x3 / stride-2 conv of problem i in the generic geometry (conv_dispatch.hip conv_fill_params), with w2_hi / scale2 / shift2 / o2_hi
 // = its 1x1 / stride-2 downsample (or NULL); all problems share N and CK.  plan != NULL: the tile plan instead of the launch (MT = the
 // row tiles of all problems).
 // nods: the instantiation without a downsample (every w2_hi NULL).

@@ -26,7 +26,7 @@
 //
 // Arithmetic: the same operand layout, tap order and MFMA as stem_pool_lds_kernel, so the conv sums are bit-identical to
 // that kernel's, and the maximum of post-ReLU fp16 values is exact in any order: outputs are bit-identical.
-#include "igemm_params.hpp"
+#include "conv_internal.hpp"
 
 namespace agp_igemm {
 

@@ -555,7 +555,7 @@ class ConvWeights:
             # planes of a 3x3 / stride-1 / pad-1 conv, the data-gradient planes of any 3x3 conv (its dgrad is such a conv)
             fs = stride if (not dgrad and fwd_stride is None) else fwd_stride
             cm_ok = kh == 3 and kw == 3 and CHUNK_MAJOR_TRAIN
-            # (exactly the convs agp_conv2d_fwd hands to that kernel -- igemm.hip conv_kxr_ok: cin % 32 == 0 and cout % 64 == 0 of the
+            # (exactly the convs agp_conv2d_fwd hands to that kernel -- conv_dispatch.hip conv_kxr_ok: cin % 32 == 0 and cout % 64 == 0 of the
             # conv that reads the pair, and its input plane below 2 GiB: `plane_pixels` = padded pixels n (h+2) (w+2) of the forward
             # conv's input map, which bounds the data-gradient conv's input too; a plane the 3x3 kernel cannot address goes to the
             # generic kernel, which reads row-major planes)
