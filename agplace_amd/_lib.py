@@ -204,6 +204,11 @@ SIGNATURES = {
     "agp_knn_workspace_bytes": (_L, [_L, _L, _I, _I]),
     "agp_knn_search": (_I, [_P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _L, _P]),
     "agp_knn_coarse_pass": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _P, _L, _P]),
+    "agp_cnx_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "agp_cnx_stem_fwd": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _F, _P, _P]),
+    "agp_cnx_dwconv_ln_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _L, _P]),
+    "agp_cnx_mlp_fwd": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "agp_cnx_downsample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

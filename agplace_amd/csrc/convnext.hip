@@ -1,0 +1,464 @@
+// ConvNeXt-tiny inference kernels (agplace_amd/convnext.py): stem, depthwise 7x7 + LayerNorm, the fused
+// Linear -> GELU -> Linear block, and the LayerNorm + 2x2/s2 downsample.
+//
+// The residual stream is a plain fp32 [n][h][w][C] tensor (C = 96, 192 or 384).  Arithmetic follows the project's mode 3
+// (AGP_PREC_BF16X3): every MFMA operand is a bf16 (hi, lo) pair and a product is hi*hi + hi*lo + lo*hi accumulated in fp32;
+// LayerNorm statistics, GELU and the residual add are fp32; nothing is stored in fp16.
+//
+// The matrix kernels compute TRANSPOSED products with mfma_f32_32x32x16_bf16: the weights are the A operand (output feature on
+// the row), 32 pixels are the B operand (pixel on the column = on the lane).  A 32x32 result then has its pixel on the lane and
+// its 32 features in the lane's 16 registers -- which is already the B-operand layout of a following MFMA that sums over those
+// features.  agp_cnx_mlp_fwd uses this: a 32-wide slice of the hidden map leaves the first GEMM in registers, goes through
+// bias + GELU + the bf16 split there and is consumed at once by the second GEMM.  The hidden map [P][4C] never exists in memory,
+// LDS included.  The register r of lane (col, h = lane >> 5) holds feature row (r & 3) + 8 (r >> 2) + 4 h; the MFMA that takes
+// registers 8t .. 8t+7 as its K slots 8h .. 8h+7 needs W2's columns in that order, which is how convnext.py lays them out.
+#include "common.hpp"
+
+namespace {
+
+constexpr int CNX_TP = 32;         // pixels per tile of the matrix kernels (one MFMA column block)
+constexpr int CNX_KPAD = 8;        // bf16 elements of padding per LDS operand row (16 B: spreads the rows over the banks)
+
+// sum over the 32 lanes of a half wave (lanes that share lane >> 5)
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// sum over 8 consecutive lanes
+__device__ __forceinline__ float oct_sum(float v) {
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+
+__device__ __forceinline__ void mfma3(f32x16& acc, const bf16x8& wh, const bf16x8& wl, const bf16x8& xh, const bf16x8& xl) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc, 0, 0, 0);
+}
+
+// feature row (inside a 32-row block) of accumulator register `reg` of a lane in half `h`
+__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+// ------------------------------------------------------------------------------------------------------------------ stem
+// Conv2d(3, 96, k=4, s=4, bias) + LayerNorm over the 96 channels.  32 output pixels per block; a thread owns 3 channels
+// (cl, cl + 32, cl + 64) of 4 pixels, the 32 lanes of a half wave hold one pixel's 96 channels.  wt: [48][96], 48 = (ci, ky, kx).
+__global__ __launch_bounds__(256) void cnx_stem_kernel(const float* __restrict__ x, long long sn, long long sc, long long sh,
+                                                       long long sw, int ho, int wo, long long P, const float* __restrict__ wt,
+                                                       const float* __restrict__ bias, const float* __restrict__ g,
+                                                       const float* __restrict__ b, float eps, float* __restrict__ out) {
+    __shared__ float xin[32][48];
+    const int t = threadIdx.x, cl = t & 31, pg = t >> 5;
+    const long long p0 = (long long)blockIdx.x * 32;
+    for (int e = t; e < 32 * 48; e += 256) {
+        const int px = e / 48, idx = e % 48;
+        const long long p = p0 + px;
+        float v = 0.f;
+        if (p < P) {
+            const int ci = idx >> 4, ky = (idx >> 2) & 3, kx = idx & 3;
+            const long long img = p / ((long long)ho * wo);
+            const int rem = (int)(p - img * ho * wo), oy = rem / wo, ox = rem - oy * wo;
+            v = x[img * sn + ci * sc + (long long)(4 * oy + ky) * sh + (long long)(4 * ox + kx) * sw];
+        }
+        xin[px][idx] = v;
+    }
+    __syncthreads();
+    float acc[4][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float bv = bias[cl + 32 * k];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i][k] = bv;
+    }
+    for (int idx = 0; idx < 48; ++idx) {
+        float w[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = wt[idx * 96 + cl + 32 * k];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float xv = xin[pg * 4 + i][idx];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc[i][k] = fmaf(xv, w[k], acc[i][k]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float mean = half_sum(acc[i][0] + acc[i][1] + acc[i][2]) * (1.f / 96.f);
+        float d[3], q = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = acc[i][k] - mean;
+            q = fmaf(d[k], d[k], q);
+        }
+        const float rstd = 1.f / sqrtf(half_sum(q) * (1.f / 96.f) + eps);
+        const long long p = p0 + pg * 4 + i;
+        if (p < P) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int c = cl + 32 * k;
+                out[p * 96 + c] = fmaf(d[k] * rstd, g[c], b[c]);
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- depthwise 7x7 + LayerNorm
+// One block per 4 x 8 tile of output pixels of one image, all C channels.  The channels are walked in chunks of 32: the chunk's
+// 10 x 14 input window (3-pixel halo, zeros outside the image: the window is addressed by (image, y, x), never by the flattened
+// pixel index, so it cannot reach into a neighbouring image) and its 49 x 32 weights go to LDS; thread (cl = t & 31,
+// col = t >> 5) computes the 4 outputs of its column for channel cl of the chunk.  Its C / 32 x 4 conv results stay in
+// registers; the 32 lanes of a half wave then hold one pixel's C channels for the LayerNorm.  wt: [49][C].
+template <int C>
+__global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restrict__ x, int h, int w, int tiles_y, int tiles_x,
+                                                            const float* __restrict__ wt, const float* __restrict__ bias,
+                                                            const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                            bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo) {
+    constexpr int NK = C / 32;
+    __shared__ __attribute__((aligned(16))) float tile[10][14][32];
+    __shared__ float wl[49][32];
+    const int t = threadIdx.x, cl = t & 31, col = t >> 5;
+    int bid = blockIdx.x;
+    const int tx = bid % tiles_x;
+    bid /= tiles_x;
+    const int ty = bid % tiles_y, img = bid / tiles_y;
+    const int y0 = ty * 4, x0 = tx * 8;
+    const float* ximg = x + (size_t)img * h * w * C;
+    float conv[4][NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        __syncthreads();
+        for (int e = t; e < 140 * 8; e += 256) {
+            const int q = e & 7, pxi = e >> 3, yy = pxi / 14, xx = pxi - yy * 14;
+            const int gy = y0 + yy - 3, gx = x0 + xx - 3;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (gy >= 0 && gy < h && gx >= 0 && gx < w) v = *(const f32x4*)(ximg + ((size_t)gy * w + gx) * C + k * 32 + q * 4);
+            *(f32x4*)&tile[yy][xx][q * 4] = v;
+        }
+        for (int e = t; e < 49 * 32; e += 256) wl[e >> 5][e & 31] = wt[(e >> 5) * C + k * 32 + (e & 31)];
+        __syncthreads();
+        float acc[4];
+        const float bv = bias[k * 32 + cl];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = bv;
+#pragma unroll 1
+        for (int kx = 0; kx < 7; ++kx) {
+            float v[10];
+#pragma unroll
+            for (int r = 0; r < 10; ++r) v[r] = tile[r][col + kx][cl];
+#pragma unroll
+            for (int ky = 0; ky < 7; ++ky) {
+                const float wv = wl[ky * 7 + kx][cl];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = fmaf(wv, v[i + ky], acc[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) conv[i][k] = acc[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) s += conv[i][k];
+        const float mean = half_sum(s) * (1.f / C);
+        float q = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            conv[i][k] -= mean;
+            q = fmaf(conv[i][k], conv[i][k], q);
+        }
+        const float rstd = 1.f / sqrtf(half_sum(q) * (1.f / C) + eps);
+        const int gy = y0 + i, gx = x0 + col;
+        if (gy < h && gx < w) {
+            const size_t p = ((size_t)img * h + gy) * w + gx;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int c = k * 32 + cl;
+                bf16_t hi, lo;
+                split_bf16(fmaf(conv[i][k] * rstd, g[c], b[c]), hi, lo);
+                o_hi[p * C + c] = hi;
+                o_lo[p * C + c] = lo;
+            }
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------------- Linear -> GELU -> Linear, fused
+// out[p][c] = resid[p][c] + ls[c] * (sum_j GELU(sum_k xn[p][k] W1[j][k] + b1[j]) W2[c][j] + b2[c]) for 32 pixels per block.
+// The tile's operand planes sit in LDS ([32][C + 8] bf16 each).  The four waves split the hidden dimension: wave v takes the
+// 32-wide hidden blocks v, v + 4, ...; per block: C / 16 k-steps of the first GEMM into one 32x32 accumulator, bias + GELU +
+// split in registers, then 2 k-steps into each of the C / 32 output accumulators.  The waves' partial [C][32] sums are added in
+// wave order through LDS (the operand planes' space, free by then), 32 channels at a time, with the epilogue: every output
+// element is read (resid) and written (out) by the same thread, so `out` may alias `resid`.
+//   w1 planes: [4C / 32][C / 16][64 lanes][8]     lane (r, h) of block jb, step kk: W1[jb * 32 + r][kk * 16 + 8 h + e]
+//   w2 planes: [4C / 32][2][C / 32][64 lanes][8]  lane (r, h) of block jb, half t, tile ct: W2[ct * 32 + r][jb * 32 + acc_row(8 t + e, h)]
+template <int C>
+__global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo, long long P,
+                                                      const bf16x8* __restrict__ w1_hi, const bf16x8* __restrict__ w1_lo,
+                                                      const float* __restrict__ b1, const bf16x8* __restrict__ w2_hi,
+                                                      const bf16x8* __restrict__ w2_lo, const float* __restrict__ b2,
+                                                      const float* __restrict__ ls, const float* resid, float* out) {
+    constexpr int LD = C + CNX_KPAD, KK = C / 16, CT = C / 32, JB = C / 8, VR = C / 8;
+    constexpr int XBYTES = 2 * CNX_TP * LD * 2, RBYTES = 4 * 32 * 36 * 4;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[XBYTES > RBYTES ? XBYTES : RBYTES];
+    bf16_t* const sx_hi = (bf16_t*)smem;
+    bf16_t* const sx_lo = sx_hi + CNX_TP * LD;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
+    const long long p0 = (long long)blockIdx.x * CNX_TP;
+    for (int e = t; e < CNX_TP * VR; e += 256) {
+        const int row = e / VR, v = e - row * VR;
+        u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
+        if (p0 + row < P) {
+            vh = *(const u32x4*)(x_hi + (size_t)(p0 + row) * C + v * 8);
+            vl = *(const u32x4*)(x_lo + (size_t)(p0 + row) * C + v * 8);
+        }
+        *(u32x4*)(sx_hi + row * LD + v * 8) = vh;
+        *(u32x4*)(sx_lo + row * LD + v * 8) = vl;
+    }
+    __syncthreads();
+    f32x16 y[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) y[ct][i] = 0.f;
+    const bf16_t* const bx_hi = sx_hi + r * LD + 8 * h;
+    const bf16_t* const bx_lo = sx_lo + r * LD + 8 * h;
+#pragma unroll 1
+    for (int jb = wave; jb < JB; jb += 4) {
+        f32x16 hacc;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 bv = *(const f32x4*)(b1 + jb * 32 + 8 * q + 4 * h);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hacc[4 * q + i] = bv[i];
+        }
+        const bf16x8* const a_hi = w1_hi + (size_t)jb * KK * 64 + lane;
+        const bf16x8* const a_lo = w1_lo + (size_t)jb * KK * 64 + lane;
+#pragma unroll 4
+        for (int kk = 0; kk < KK; ++kk)
+            mfma3(hacc, a_hi[kk * 64], a_lo[kk * 64], *(const bf16x8*)(bx_hi + kk * 16), *(const bf16x8*)(bx_lo + kk * 16));
+        bf16x8 g_hi[2], g_lo[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            bf16_t hi, lo;
+            split_bf16(gelu_exact(hacc[i]), hi, lo);
+            g_hi[i >> 3][i & 7] = (short)hi;
+            g_lo[i >> 3][i & 7] = (short)lo;
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            const bf16x8* const c_hi = w2_hi + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
+            const bf16x8* const c_lo = w2_lo + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) mfma3(y[ct], c_hi[ct * 64], c_lo[ct * 64], g_hi[tt], g_lo[tt]);
+        }
+    }
+    float* const red = (float*)smem;       // [4 waves][32 pixels][36]: 32 channels + 4 floats of padding
+    const int epx = t >> 3, ec = (t & 7) * 4;
+    const long long ep = p0 + epx;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        __syncthreads();                   // the operand planes (first round) / the previous round's sums have been read
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 v = {y[ct][4 * q], y[ct][4 * q + 1], y[ct][4 * q + 2], y[ct][4 * q + 3]};
+            *(f32x4*)(red + (wave * 32 + r) * 36 + 8 * q + 4 * h) = v;
+        }
+        __syncthreads();
+        if (ep < P) {
+            const f32x4 s0 = *(const f32x4*)(red + (0 * 32 + epx) * 36 + ec), s1 = *(const f32x4*)(red + (1 * 32 + epx) * 36 + ec);
+            const f32x4 s2 = *(const f32x4*)(red + (2 * 32 + epx) * 36 + ec), s3 = *(const f32x4*)(red + (3 * 32 + epx) * 36 + ec);
+            const int c = ct * 32 + ec;
+            const f32x4 rv = *(const f32x4*)(resid + (size_t)ep * C + c);
+            const f32x4 bv = *(const f32x4*)(b2 + c), lv = *(const f32x4*)(ls + c);
+            f32x4 o;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] = fmaf(lv[i], (((s0[i] + s1[i]) + s2[i]) + s3[i]) + bv[i], rv[i]);
+            *(f32x4*)(out + (size_t)ep * C + c) = o;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------- LayerNorm + Conv2d(C, 2C, k=2, s=2)
+// A GEMM with K = 4C (k = (ky * 2 + kx) * C + c) and N = 2C over the floor(h/2) x floor(w/2) output pixels, 32 per block, on
+// the MLP kernel's MFMA core.  K is walked in chunks of 384 = 384 / C whole input pixels: eight lanes normalise one input
+// pixel (fp32 statistics, two passes in registers) and write its operand planes to LDS, then wave v accumulates the output
+// feature blocks v, v + 4, ... over the chunk.  w planes: [2C / 32][4C / 16][64 lanes][8] as w1 above.
+template <int C>
+__global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __restrict__ x, int h, int w, int ho, int wo, long long P,
+                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                             const bf16x8* __restrict__ w_hi, const bf16x8* __restrict__ w_lo,
+                                                             const float* __restrict__ bias, float* __restrict__ out) {
+    constexpr int KC = 384, LD = KC + CNX_KPAD, IPP = KC / C, NCH = 4 * C / KC, NT = 2 * C / 32, NTW = (NT + 3) / 4, KKT = 4 * C / 16;
+    constexpr int NV = C / 32;             // float4 per lane of a pixel's eight
+    __shared__ __attribute__((aligned(16))) bf16_t sx_hi[CNX_TP * LD];
+    __shared__ __attribute__((aligned(16))) bf16_t sx_lo[CNX_TP * LD];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, r = lane & 31, hh = lane >> 5;
+    const long long p0 = (long long)blockIdx.x * CNX_TP;
+    const int lpx = t >> 3, sl = t & 7;
+    const long long lp = p0 + lpx;
+    long long img = 0;
+    int oy = 0, ox = 0;
+    if (lp < P) {
+        img = lp / ((long long)ho * wo);
+        const int rem = (int)(lp - img * ho * wo);
+        oy = rem / wo;
+        ox = rem - oy * wo;
+    }
+    f32x16 y[NTW];
+#pragma unroll
+    for (int n = 0; n < NTW; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) y[n][i] = 0.f;
+    const bf16_t* const bx_hi = sx_hi + r * LD + 8 * hh;
+    const bf16_t* const bx_lo = sx_lo + r * LD + 8 * hh;
+#pragma unroll 1
+    for (int ch = 0; ch < NCH; ++ch) {
+        __syncthreads();
+#pragma unroll 1
+        for (int sub = 0; sub < IPP; ++sub) {
+            const int kp = ch * IPP + sub, ky = kp >> 1, kx = kp & 1;
+            f32x4 v[NV];
+            float s = 0.f;
+            if (lp < P) {
+                const float* src = x + (((size_t)img * h + (2 * oy + ky)) * w + (2 * ox + kx)) * C;
+#pragma unroll
+                for (int m = 0; m < NV; ++m) {
+                    v[m] = *(const f32x4*)(src + (sl + 8 * m) * 4);
+                    s += (v[m][0] + v[m][1]) + (v[m][2] + v[m][3]);
+                }
+            } else {
+#pragma unroll
+                for (int m = 0; m < NV; ++m) v[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            const float mean = oct_sum(s) * (1.f / C);
+            float q = 0.f;
+#pragma unroll
+            for (int m = 0; m < NV; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    v[m][i] -= mean;
+                    q = fmaf(v[m][i], v[m][i], q);
+                }
+            const float rstd = 1.f / sqrtf(oct_sum(q) * (1.f / C) + eps);
+#pragma unroll
+            for (int m = 0; m < NV; ++m) {
+                const int c = (sl + 8 * m) * 4;
+                const f32x4 gv = *(const f32x4*)(g + c), bv = *(const f32x4*)(b + c);
+                bf16_t hi[4], lo[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) split_bf16(lp < P ? fmaf(v[m][i] * rstd, gv[i], bv[i]) : 0.f, hi[i], lo[i]);
+                *(u32x2*)(sx_hi + lpx * LD + sub * C + c) = u32x2{pack2(hi[0], hi[1]), pack2(hi[2], hi[3])};
+                *(u32x2*)(sx_lo + lpx * LD + sub * C + c) = u32x2{pack2(lo[0], lo[1]), pack2(lo[2], lo[3])};
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int n = 0; n < NTW; ++n) {
+            const int nt = wave + 4 * n;
+            if (nt < NT) {
+                const bf16x8* const a_hi = w_hi + ((size_t)nt * KKT + ch * (KC / 16)) * 64 + lane;
+                const bf16x8* const a_lo = w_lo + ((size_t)nt * KKT + ch * (KC / 16)) * 64 + lane;
+#pragma unroll 4
+                for (int kk = 0; kk < KC / 16; ++kk)
+                    mfma3(y[n], a_hi[kk * 64], a_lo[kk * 64], *(const bf16x8*)(bx_hi + kk * 16), *(const bf16x8*)(bx_lo + kk * 16));
+            }
+        }
+    }
+    const long long op = p0 + r;
+    if (op < P) {
+#pragma unroll
+        for (int n = 0; n < NTW; ++n) {
+            const int nt = wave + 4 * n;
+            if (nt < NT) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = nt * 32 + 8 * q + 4 * hh;
+                    const f32x4 bv = *(const f32x4*)(bias + c);
+                    const f32x4 o = {y[n][4 * q] + bv[0], y[n][4 * q + 1] + bv[1], y[n][4 * q + 2] + bv[2], y[n][4 * q + 3] + bv[3]};
+                    *(f32x4*)(out + (size_t)op * (2 * C) + c) = o;
+                }
+            }
+        }
+    }
+}
+
+inline long long cnx_pad(long long P) { return (P + CNX_TP - 1) / CNX_TP * CNX_TP; }
+inline bool cnx_c_host_ok(int C) { return C == 96 || C == 192 || C == 384; }
+inline bool cnx_map_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long long)n * h * w < (1ll << 31) / 32; }
+
+}  // namespace
+
+extern "C" {
+
+int64_t agp_cnx_workspace_bytes(int n, int h, int w, int C) {
+    if (!cnx_map_ok(n, h, w) || !cnx_c_host_ok(C)) return -1;
+    return 2 * cnx_pad((long long)n * h * w) * C * 2;      // the normalised operand: two bf16 planes [P_pad][C]
+}
+
+int agp_cnx_stem_fwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int n, int h, int w, const float* wt,
+                     const float* bias, const float* ln_w, const float* ln_b, float eps, float* out, void* stream) {
+    if (!x || !wt || !bias || !ln_w || !ln_b || !out || n <= 0 || h < 4 || w < 4) return AGP_E_BADARG;
+    const int ho = (h - 4) / 4 + 1, wo = (w - 4) / 4 + 1;
+    if (!cnx_map_ok(n, ho, wo)) return AGP_E_BADARG;
+    const long long P = (long long)n * ho * wo;
+    AGP_LAUNCH(cnx_stem_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x, (long long)sn, (long long)sc,
+               (long long)sh, (long long)sw, ho, wo, P, wt, bias, ln_w, ln_b, eps, out);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_dwconv_ln_fwd(const float* x, int n, int h, int w, int C, const float* wt, const float* bias, const float* ln_w,
+                          const float* ln_b, float eps, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!x || !wt || !bias || !ln_w || !ln_b || !workspace || !cnx_map_ok(n, h, w) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    if (workspace_bytes < agp_cnx_workspace_bytes(n, h, w, C) || ((uintptr_t)workspace & 15)) return AGP_E_BADARG;
+    bf16_t* const hi = (bf16_t*)workspace;
+    bf16_t* const lo = hi + cnx_pad((long long)n * h * w) * C;
+    const int ty = (h + 3) / 4, tx = (w + 7) / 8;
+    const dim3 grid((unsigned)((long long)n * ty * tx));
+    hipStream_t s = (hipStream_t)stream;
+    if (C == 96) { AGP_LAUNCH(cnx_dwconv_ln_kernel<96>, grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, hi, lo); }
+    else if (C == 192) { AGP_LAUNCH(cnx_dwconv_ln_kernel<192>, grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, hi, lo); }
+    else { AGP_LAUNCH(cnx_dwconv_ln_kernel<384>, grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, hi, lo); }
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_mlp_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1_hi, const void* w1_lo,
+                    const float* b1, const void* w2_hi, const void* w2_lo, const float* b2, const float* layer_scale,
+                    const float* resid, float* out, void* stream) {
+    if (!workspace || !w1_hi || !w1_lo || !b1 || !w2_hi || !w2_lo || !b2 || !layer_scale || !resid || !out) return AGP_E_BADARG;
+    if (P <= 0 || P >= (1ll << 31) / 32 || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    if (workspace_bytes < 2 * cnx_pad(P) * C * 2 || ((uintptr_t)workspace & 15)) return AGP_E_BADARG;
+    const bf16_t* const hi = (const bf16_t*)workspace;
+    const bf16_t* const lo = hi + cnx_pad(P) * C;
+    const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
+    hipStream_t s = (hipStream_t)stream;
+    const bf16x8 *a = (const bf16x8*)w1_hi, *b = (const bf16x8*)w1_lo, *c = (const bf16x8*)w2_hi, *d = (const bf16x8*)w2_lo;
+    if (C == 96) { AGP_LAUNCH(cnx_mlp_kernel<96>, grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out); }
+    else if (C == 192) { AGP_LAUNCH(cnx_mlp_kernel<192>, grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out); }
+    else { AGP_LAUNCH(cnx_mlp_kernel<384>, grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out); }
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_downsample_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
+                           const void* w_hi, const void* w_lo, const float* bias, float* out, void* stream) {
+    if (!x || !ln_w || !ln_b || !w_hi || !w_lo || !bias || !out || !cnx_map_ok(n, h, w) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    const int ho = h / 2, wo = w / 2;
+    if (ho < 1 || wo < 1) return AGP_E_BADARG;
+    const long long P = (long long)n * ho * wo;
+    const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
+    hipStream_t s = (hipStream_t)stream;
+    const bf16x8 *a = (const bf16x8*)w_hi, *b = (const bf16x8*)w_lo;
+    if (C == 96) { AGP_LAUNCH(cnx_downsample_kernel<96>, grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, b, bias, out); }
+    else if (C == 192) { AGP_LAUNCH(cnx_downsample_kernel<192>, grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, b, bias, out); }
+    else { AGP_LAUNCH(cnx_downsample_kernel<384>, grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, b, bias, out); }
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+}  // extern "C"

@@ -17,6 +17,7 @@ import torch.nn as nn
 from .. import autograd_ops, ops, range_guard, train_fns
 from ..network.image_fe import ImageFE
 from ..network.image_pooling import GeM
+from ..network_mm.image_pooling import gem_op
 from ..network_mm.ffns import _PreparedLinear
 from ..options import get_options
 from ..vecprog import VecProgram
@@ -46,8 +47,10 @@ class DBVanilla2D(nn.Module):
         if mode == 'db':
             maptype = opt.maptype.split('_')
             fes = [ImageFE(fe_type=opt.dbimage_fe, layers=opt.dbimage_fe_layers) for _ in maptype]
+            self._convnext = opt.dbimage_fe == "convnext_tiny"
             for e in fes:
-                e.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
+                if not self._convnext:      # Normalize of the uint8 routes (tiles, frames), which the ResNets alone have
+                    e.fe.set_image_norm(opt.image_mean, opt.image_std)
             self.dbimage_fes = nn.ModuleList(fes)
             self.dbimage_pools = nn.ModuleList([GeM() for _ in maptype])
             self.dbimage_mlps = nn.ModuleList([MLP(e.last_dim, dim) for e in fes])
@@ -82,6 +85,8 @@ class DBVanilla2D(nn.Module):
         caller lets it ride in another program's launch (VecProgram.run(rider=...), agplace_amd.pair) -- the returned embedding
         is written when that launch runs."""
         opt = self.opt
+        if getattr(self, "_convnext", False):
+            return self._forward_db_convnext(data_dict, trunk_maps)
         # .train() under torch.no_grad() (train.py:315 with --train_modeldb False): batch-statistics BatchNorm with
         # running-stat updates and no tape -- the train-mode kernels run, the autograd Functions record nothing.
         # .eval() with gradients enabled and trainable parameters: the training graph on frozen BatchNorm statistics
@@ -226,6 +231,54 @@ class DBVanilla2D(nn.Module):
             if opt.final_l2 is True:
                 shp = out.shape
                 out = autograd_ops.l2normalize(out.reshape(-1, shp[-1])).view(shp)
+        return {'embedding': out}
+
+    def _forward_db_convnext(self, data_dict, trunk_maps):
+        """dbimage_fe='convnext_tiny' (agplace_amd/convnext.py): inference over fp32 `db_map`.  Per map type: the trunk's last map
+        (fp32, 384 channels) -> the dense-fp32 GeM -> the per-op MLP(384, dim) -> F.normalize; then the mean over map types.  The
+        heads may train on a frozen trunk (freeze_backbone) through the ops' own backward kernels."""
+        opt = self.opt
+        what = "DBVanilla2D with dbimage_fe='convnext_tiny' (inference only)"
+        if self.training:
+            raise NotImplementedError(f"{what}: .train() is not built; call .eval()")
+        if 'db_frames' in data_dict or 'db_jitter' in data_dict:
+            raise NotImplementedError(f"{what}: `db_frames` (decoded uint8 frames) is not built; pass fp32 `db_map`")
+        if trunk_maps is not None:
+            raise NotImplementedError(f"{what}: lock-step trunks (pair.embed_pair) are not built")
+        db_map = data_dict['db_map']
+        if db_map.dtype == torch.uint8:
+            raise NotImplementedError(f"{what}: uint8 `db_map` is not built; pass fp32 tiles")
+        if torch.is_grad_enabled() and any(p.requires_grad for e in self.dbimage_fes for p in e.fe.features.parameters()):
+            raise NotImplementedError(f"{what}: gradients into the trunk are not built; run under torch.no_grad() or "
+                                      "freeze_backbone()")
+        if db_map.dim() == 5:      # [b,nmap,3,h,w]  caching / testing
+            mode = 'cachetest'
+            b, nmap, c, h, w = db_map.shape
+            db_map = db_map.unsqueeze(1)
+            ndb = 1
+        elif db_map.dim() == 6:    # [b,ndb,nmap,3,h,w]  training layout
+            mode = 'train'
+            b, ndb, nmap, c, h, w = db_map.shape
+        else:
+            raise NotImplementedError
+        assert c == 3
+        vecs = []
+        for i in range(nmap):
+            j = 0 if opt.share_dbfe is True else i
+            x = db_map[:, :, i].reshape(b * ndb, c, h, w).float()
+            last, _ = self.dbimage_fes[j](x)
+            v = gem_op(last, self.dbimage_pools[j].p, self.dbimage_pools[j].eps)
+            v = self.dbimage_mlps[j](v)
+            if opt.output_l2 is True:
+                v = autograd_ops.l2normalize(v)
+            vecs.append(v)
+        out = vecs[0] if nmap == 1 else autograd_ops.wsum(vecs, [torch.full((1,), 1.0 / nmap, device=vecs[0].device)] * nmap)
+        out = out.view(b, ndb, -1)
+        if mode == 'cachetest':
+            out = out.view(b, -1)
+        if opt.final_l2 is True:
+            shp = out.shape
+            out = autograd_ops.l2normalize(out.reshape(-1, shp[-1])).view(shp)
         return {'embedding': out}
 
     def forward(self, data_dict, mode: List[str]):

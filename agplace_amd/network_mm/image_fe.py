@@ -1,20 +1,26 @@
-"""ImageFE, drop-in for reference network_mm/image_fe.py (ResNet18/34 branches, :10-46,97-113,153-174).
+"""ImageFE, drop-in for reference network_mm/image_fe.py (ResNet18/34 branches, :10-46,97-113,153-174; the
+convnext_tiny branch, :59-88,118-150).
 
 Constructor `ImageFE(fe_type, layers)` with layers like '2_2_2': only the COUNT of entries matters
 for ResNets (reference :15-30).  forward(x[b,3,H,W]) -> (last_map, [l1, l2, l3(, l4)]) as fp32
 tensors of logical shape [b,C,h,w] (channels_last memory).  `forward_maps` returns the same
 stages as ops.SplitMap without the fp32 export (the fused MM / DBVanilla2D paths use it).
-ConvNeXt / SqueezeNet branches of the reference are not built (never selected by its defaults).
+
+'convnext_tiny' (agplace_amd/convnext.py) is inference only and takes exactly three `layers` entries, which are BLOCK COUNTS
+there: features[6:] are dropped and stage i keeps its first layers[i] blocks, last_dim = 384, the list holds the outputs of
+features[1], [3], [5].  It runs in the mode-3 arithmetic only (prec None or 3) and has no ops.SplitMap form: `forward_maps`
+with pool requests raises NotImplementedError.  The SqueezeNet branch of the reference is not built.
 """
 import torch.nn as nn
 
 from .. import range_guard
 from ..options import get_options
+from ..convnext import ConvNeXt
 from ..resnet import ResNet
 
 
 class ImageFE(nn.Module):
-    _ALLOWED = ("resnet18", "resnet34")
+    _ALLOWED = ("resnet18", "resnet34", "convnext_tiny")
     _LAST_DIM = {"resnet18": {2: 128, 3: 256, 4: 512}, "resnet34": {2: 128, 3: 256, 4: 512},
                  "resnet50": {2: 512, 3: 1024, 4: 2048}}
 
@@ -26,12 +32,25 @@ class ImageFE(nn.Module):
         self.layers = layers
         if fe_type not in self._ALLOWED or len(layers) not in (2, 3, 4):
             raise NotImplementedError
+        if fe_type == "convnext_tiny":
+            if len(layers) == 2:
+                raise NotImplementedError      # as the reference (image_fe.py:72-76)
+            if len(layers) == 4:
+                raise NotImplementedError("ImageFE('convnext_tiny') with four `layers` entries: the reference returns the three maps of "
+                                          "features[1], [3], [5] under last_dim = 768, which breaks its own head (the last map has "
+                                          "384 channels); use three entries")
+            self.last_dim = 384
+            self.fe = ConvNeXt(layers)
+            return
         self.last_dim = self._LAST_DIM[fe_type][len(layers)]
         self.fe = ResNet(fe_type, nstages=len(layers))
 
     def forward_maps(self, x, prec=None, level_means=None, final_pool=None):
         """prec: MFMA precision mode (include/agplace_hip.h); None = the process-wide Options.mfma_precision, i.e. the
         precision MM / DBVanilla2D run this trunk at."""
+        if self.fe_type == "convnext_tiny":
+            raise NotImplementedError("ImageFE('convnext_tiny').forward_maps: the ConvNeXt trunk has no ops.SplitMap form (plain fp32 "
+                                      "maps, no pool requests); use forward(x) or fe.forward_maps(x)")
         if len(self.layers) not in (3, 4):
             raise NotImplementedError      # reference forward_resnet raises for 2 entries too
         prec = get_options().mfma_precision if prec is None else prec
@@ -46,6 +65,11 @@ class ImageFE(nn.Module):
         return 2 if p == 4 else p
 
     def forward(self, x, prec=None):
+        if self.fe_type == "convnext_tiny":
+            if prec not in (None, 3):
+                raise ValueError(f"ImageFE('convnext_tiny'): prec must be None or 3 (three bf16 products, fp32 maps), got {prec}")
+            x_list = self.fe.forward_maps(x)
+            return x_list[-1], x_list
         prec = self.export_precision() if prec is None else prec
         # the fp16 range guard of the op-level drop-in (Options.fp16_range_guard): around its own forward only -- inside MM /
         # DBVanilla2D the trunk's maps report through the model that runs it

@@ -47,6 +47,9 @@ class MM(nn.Module):
         super().__init__()
         self.opt = opt = opt or get_options()
         self.drop = drop
+        if opt.mm_imgfe == "convnext_tiny":
+            raise NotImplementedError("MM with mm_imgfe='convnext_tiny' is not built: the fusion blocks need the 384-wide stage 2 and "
+                                      "matching voxel planes; the ConvNeXt trunk serves ImageFE and DBVanilla2D")
         self.image_fe = ImageFE(fe_type=opt.mm_imgfe, layers=opt.mm_imgfe_layers)
         self.image_fe.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
         self.image_pool = GeM()

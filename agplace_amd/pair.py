@@ -72,6 +72,9 @@ def embed_pair(modelq, modeldb, qdata, dbdata):
     fp16 range guard (Options.fp16_range_guard): the lock-step trunks of BOTH models report through the query model's word when
     its guard is on (else the database model's): a saturated database tile then shows in modelq.fp16_range_ok() /
     poll_fp16_range(), whose message names the database trunks as a possible source."""
+    if any(getattr(e, "fe_type", None) == "convnext_tiny" for e in getattr(modeldb, "dbimage_fes", ())):
+        raise NotImplementedError("pair.embed_pair with a ConvNeXt database model (dbimage_fe='convnext_tiny') is not built; call "
+                                  "modelq(qdata, 'q') and modeldb(dbdata, 'db') separately")
     qdata, dbdata = _resized_tiles(modelq, modeldb, qdata, dbdata)
     if not can_pair(modelq, modeldb, qdata, dbdata):
         return modelq(qdata, mode='q'), modeldb(dbdata, mode='db')

@@ -989,6 +989,33 @@ int agp_seg_pool_bwd(const void* x_hi, const void* x_lo, const int32_t* bidx, co
                      const void* b_hi, const void* b_lo, int64_t n, int c, void* o_hi, void* o_lo, float* gp,
                      void* stream);
 
+/* ---- ConvNeXt-tiny trunk, inference (csrc/convnext.hip, agplace_amd/convnext.py).  The residual stream is a plain fp32
+ * [n][h][w][C] tensor, C = 96, 192 or 384.  MFMA operands are bf16 (hi, lo) pairs with three products (the arithmetic of
+ * AGP_PREC_BF16X3), accumulation, LayerNorm statistics, GELU and the residual add are fp32; nothing is stored in fp16.  The
+ * entries allocate nothing and never synchronise.  workspace: 16-byte aligned, agp_cnx_workspace_bytes(n, h, w, C) bytes = the
+ * normalised operand of ONE block as two bf16 planes [P_pad][C], P = n h w, P_pad = P rounded up to 32 (no P x 4C term: the
+ * hidden map of the block's MLP exists only in registers); -1 for an unsupported shape. */
+int64_t agp_cnx_workspace_bytes(int n, int h, int w, int C);
+/* Conv2d(3, 96, k=4, s=4, bias) + LayerNorm over channels.  x: fp32 [n][3][h][w] with element strides (sn, sc, sh, sw);
+ * wt fp32 [48][96] = the conv weight [96][3][4][4] transposed; out fp32 [n][(h-4)/4+1][(w-4)/4+1][96]. */
+int agp_cnx_stem_fwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int n, int h, int w, const float* wt,
+                     const float* bias, const float* ln_w, const float* ln_b, float eps, float* out, void* stream);
+/* Depthwise Conv2d(C, C, 7, padding=3, groups=C, bias) + LayerNorm over channels of the stream x; wt fp32 [49][C] = the conv
+ * weight [C][1][7][7] transposed.  Writes the normalised operand into the workspace. */
+int agp_cnx_dwconv_ln_fwd(const float* x, int n, int h, int w, int C, const float* wt, const float* bias, const float* ln_w,
+                          const float* ln_b, float eps, void* workspace, int64_t workspace_bytes, void* stream);
+/* out = resid + layer_scale * (GELU(xn W1^T + b1) W2^T + b2) for the P pixels whose operand agp_cnx_dwconv_ln_fwd left in the
+ * workspace; resid / out fp32 [P][C], out may alias resid.  w1_* / w2_*: bf16 planes of Linear(C, 4C) / Linear(4C, C) in the
+ * kernel's fragment order (convnext.hip: cnx_mlp_kernel; agplace_amd/convnext.py prepares them). */
+int agp_cnx_mlp_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1_hi, const void* w1_lo,
+                    const float* b1, const void* w2_hi, const void* w2_lo, const float* b2, const float* layer_scale,
+                    const float* resid, float* out, void* stream);
+/* LayerNorm over channels + Conv2d(C, 2C, k=2, s=2, bias): x fp32 [n][h][w][C] -> out fp32 [n][h/2][w/2][2C] (sizes floored: an
+ * odd last row / column is dropped).  w_*: bf16 planes of the weight as a [2C][4C] matrix, k = (ky * 2 + kx) * C + c, in fragment
+ * order. */
+int agp_cnx_downsample_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
+                           const void* w_hi, const void* w_lo, const float* bias, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

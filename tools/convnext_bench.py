@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""ConvNeXt-tiny trunk at the database tile size: time per kernel and of the whole trunk, with the ResNet18 trunk in mode 3 on
+the same batch for context.
+
+python tools/convnext_bench.py [--batch 64] [--size 256] [--reps 10] [--windows 5] [--json out.json]
+Events on the launch stream around `reps` back-to-back calls, the median of `windows` such windows after a warm-up.  GMAC are
+algorithmic (one multiply-accumulate per weight use, whatever the three bf16 products cost); the fraction of peak is
+2 * MAC / time over the 2.5 PFLOP/s dense bf16 peak.  Weights are seeded random values (zeros would flatter the clock)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import bench_inputs  # noqa: E402
+from agplace_amd import convnext as cnx  # noqa: E402
+from agplace_amd.network.image_fe import ImageFE  # noqa: E402
+
+PEAK = 2.5e15
+
+
+def convnext_macs(layers, h, w):
+    """Algorithmic MACs of the truncated trunk on one h x w image, and per kernel kind and stage."""
+    sizes = cnx.ConvNeXt.map_sizes(h, w)
+    per = {"stem": sizes[0][0] * sizes[0][1] * 96 * 48}
+    for s, (hh, ww) in enumerate(sizes):
+        c, px = cnx.DIMS[s], hh * ww
+        per[("dwconv", c)] = px * c * 49
+        per[("mlp", c)] = px * 8 * c * c
+        if s > 0:
+            per[("down", cnx.DIMS[s - 1])] = px * c * 4 * cnx.DIMS[s - 1]
+    total = per["stem"] + sum(per[("down", cnx.DIMS[s])] for s in range(2))
+    total += sum(min(layers[s], cnx.DEPTHS[s]) * (per[("dwconv", cnx.DIMS[s])] + per[("mlp", cnx.DIMS[s])]) for s in range(3))
+    return total, per
+
+
+def timed(fn, reps, windows):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(windows):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / reps)
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def randomize(fe, seed):
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in fe.named_parameters():
+            if name.endswith("layer_scale"):
+                p.copy_(torch.rand(p.shape, generator=g) * 0.9 + 0.3)
+            elif p.dim() > 1:
+                p.copy_(torch.randn(p.shape, generator=g) / (p[0].numel() ** 0.5))
+            elif name.endswith("bias"):
+                p.copy_(0.2 * torch.randn(p.shape, generator=g))
+            else:
+                p.copy_(0.5 + torch.rand(p.shape, generator=g))
+    return fe
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.set_grad_enabled(False)
+    n, hw = a.batch, a.size
+    x = torch.randn(n, 3, hw, hw, generator=torch.Generator().manual_seed(1)).to(dev)
+    rows = []
+
+    def report(name, macs, t):
+        med, lo, hi = t
+        rows.append({"name": name, "gmac": macs / 1e9, "ms": med, "ms_min": lo, "ms_max": hi, "frac_peak": 2 * macs / (med * 1e-3) / PEAK})
+        print(f"{name:34s} {macs / 1e9:9.2f} GMAC {med:9.3f} ms (min {lo:.3f} max {hi:.3f})  {2 * macs / med / 1e9:8.1f} TFLOP/s "
+              f"algorithmic = {100 * rows[-1]['frac_peak']:5.2f} % of peak")
+
+    # ---- per kernel, at the map sizes of this input
+    fe = randomize(ImageFE("convnext_tiny", "3_3_9"), 0).to(dev).eval()
+    sizes = cnx.ConvNeXt.map_sizes(hw, hw)
+    _, per = convnext_macs([3, 3, 9], hw, hw)
+    prep = fe.fe._prepared()
+    report("stem", n * per["stem"], timed(lambda: cnx.stem_fwd(x, prep["stem"]), a.reps, a.windows))
+    for s, (h, w) in enumerate(sizes):
+        c = cnx.DIMS[s]
+        cur = torch.randn(n, h, w, c, device=dev)
+        ws = torch.empty(cnx.workspace_bytes(n, h, w, c), dtype=torch.uint8, device=dev)
+        p = prep[("blocks", s)][0]
+        out = torch.empty_like(cur)
+        report(f"dwconv+ln C={c} {h}x{w}", n * per[("dwconv", c)], timed(lambda: cnx.dwconv_ln_fwd(cur, p, ws), a.reps, a.windows))
+        report(f"fused mlp C={c} {h}x{w}", n * per[("mlp", c)], timed(lambda: cnx.mlp_fwd(ws, p, cur, out), a.reps, a.windows))
+        if s < 2:
+            d = prep[("down", s)]
+            report(f"ln+downsample C={c} {h}x{w}", n * per[("down", c)], timed(lambda: cnx.downsample_fwd(cur, d), a.reps, a.windows))
+        del cur, ws, out
+    # ---- whole trunks
+    for layers in ("2_2_2", "3_3_9"):
+        fe = randomize(ImageFE("convnext_tiny", layers), 0).to(dev).eval()
+        macs, _ = convnext_macs([int(v) for v in layers.split("_")], hw, hw)
+        report(f"convnext_tiny {layers} trunk", n * macs, timed(lambda: fe(x), max(2, a.reps // 2), a.windows))
+        del fe
+    r18 = ImageFE("resnet18", "2_2_2").to(dev).eval()
+    report("resnet18 2_2_2 trunk, mode 3", n * bench_inputs.resnet_gmacs("resnet18", 3, hw, hw),
+           timed(lambda: r18(x, prec=3), max(2, a.reps // 2), a.windows))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump({"batch": n, "size": hw, "reps": a.reps, "windows": a.windows, "rows": rows}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
