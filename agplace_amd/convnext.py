@@ -1,4 +1,4 @@
-"""ConvNeXt-tiny image trunk, inference only: the parameter container of torchvision.models.convnext_tiny after the reference's
+"""ConvNeXt-tiny image trunk: the parameter container of torchvision.models.convnext_tiny after the reference's
 truncation (network_mm/image_fe.py:59-88) and its forward on the kernels of csrc/convnext.hip.
 
 State_dict keys are torchvision's: features.0.{0,1}.*, features.{1,3,5}.{b}.{layer_scale, block.{0,2,3,5}.*},
@@ -11,6 +11,17 @@ format, map exponent, conv dispatch or precision mode 2 / 4.  Arithmetic is the 
 accumulation); LayerNorm statistics, GELU and the residual add are fp32 and nothing is stored in fp16, so there is no fp16 range
 to guard.  Per block: agp_cnx_dwconv_ln_fwd writes the normalised operand, agp_cnx_mlp_fwd runs Linear -> GELU -> Linear with the
 4C-wide hidden map in registers only and adds the scaled result to the stream in place.
+
+Training is OPT-IN (`ConvNeXt.enable_training()`, Options.convnext_train): without it .train() and gradients into the trunk are
+refused as before and the inference path is untouched.  With it, `forward_maps_train` runs the same kernels out of place (every
+block writes a new stream tensor), applies stochastic depth in .train(), and records ONE autograd node (`_TrunkFn`) whose saved
+state is the stream tensors plus the per-block stochastic-depth scales; the backward (csrc/convnext_bwd.hip) recomputes the
+normalised operand with agp_cnx_dwconv_ln_fwd and never stores the hidden map either.
+
+Stochastic depth restates torchvision's StochasticDepth(p, "row") (torchvision is not a dependency): block k of the FULL
+18-block network has p_k = stochastic_depth_prob * k / 17 (the truncation happens after construction, so a kept block keeps its
+k); in .train() each image draws scale = bernoulli(1 - p_k) / (1 - p_k) and out = x + scale[n] * layer_scale * branch(x);
+p_k == 0 and .eval() apply no scale.
 """
 import torch
 import torch.nn as nn
@@ -21,6 +32,8 @@ from ._lib import check, ptr
 DIMS = (96, 192, 384, 768)
 DEPTHS = (3, 3, 9, 3)
 LN_EPS = 1e-6
+STAGE_FIRST_BLOCK = (0, 3, 6)          # index k of a stage's first block in the full network
+TRAIN_SWITCH = "opt in with ConvNeXt.enable_training() / Options.convnext_train"
 
 
 class LayerNorm2d(nn.LayerNorm):
@@ -83,6 +96,28 @@ def prep_down(ln, conv):
     return dict(c=c, g=_f32(ln.weight), b=_f32(ln.bias), w=_split(_frag_rows(wk)), bias=_f32(conv.bias))
 
 
+def prep_block_bwd(blk):
+    """The backward's extra planes of one CNBlock: (layer_scale * W2)^T and W1^T in fragment order, W2 itself in fp32."""
+    l1, l2 = blk.block[3], blk.block[5]
+    c = l1.weight.shape[1]
+    w2 = _f32(l2.weight)
+    return dict(w2t=_split(_frag_rows((_f32(blk.layer_scale).reshape(c, 1) * w2).t().contiguous())),
+                w1t=_split(_frag_acc(_f32(l1.weight).t().contiguous())), w2f=w2)
+
+
+def prep_down_bwd(ln, conv):
+    c = conv.weight.shape[1]
+    wk = _f32(conv.weight).permute(0, 2, 3, 1).reshape(2 * c, 4 * c)
+    return dict(wt=_split(_frag_rows(wk.t().contiguous())))
+
+
+def bwd_workspace_bytes(n, h, w, c):
+    b = _lib.load().agp_cnx_bwd_workspace_bytes(n, h, w, c)
+    if b <= 0:
+        raise ValueError(f"ConvNeXt: unsupported map [{n},{h},{w},{c}]")
+    return b
+
+
 def workspace_bytes(n, h, w, c):
     b = _lib.load().agp_cnx_workspace_bytes(n, h, w, c)
     if b <= 0:
@@ -126,6 +161,76 @@ def mlp_fwd(ws, p, resid, out):
     return out
 
 
+def mlp_fwd_rows(ws, p, resid, out, row_scale=None):
+    """mlp_fwd with a per-image factor: out = resid + row_scale[image] * layer_scale * MLP(operand); row_scale fp32 [n] or None."""
+    _stream_ok(resid, p["c"])
+    _stream_ok(out, p["c"])
+    if out.shape != resid.shape:
+        raise ValueError("ConvNeXt.mlp_fwd_rows: out and resid differ in shape")
+    n, h, w, c = resid.shape
+    _rows_ok(row_scale, n, resid.device)
+    check(_lib.load().agp_cnx_mlp_fwd_rows(ptr(ws), ws.numel(), n * h * w, c, ptr(p["w1"][0]), ptr(p["w1"][1]), ptr(p["b1"]),
+                                           ptr(p["w2"][0]), ptr(p["w2"][1]), ptr(p["b2"]), ptr(p["ls"]), ptr(resid), ptr(out),
+                                           ptr(row_scale), h * w, _lib.stream()), "agp_cnx_mlp_fwd_rows")
+    return out
+
+
+def _rows_ok(row_scale, n, device):
+    if row_scale is not None and not (torch.is_tensor(row_scale) and row_scale.dtype == torch.float32 and row_scale.is_contiguous()
+                                      and tuple(row_scale.shape) == (n,) and row_scale.device == device):
+        raise ValueError("ConvNeXt: row_scale must be a contiguous fp32 [n] tensor on the stream's device, or None")
+
+
+def mlp_bwd(ws, p, pb, gy, row_scale, grads, bws):
+    """Backward of mlp_fwd_rows for the operand in `ws`: returns gxn [n,h,w,C]; adds into grads = (g_w1 [4C,C], g_b1, g_w2 [C,4C],
+    g_b2, g_layer_scale), fp32 buffers in parameter layout.  bws: uint8, >= bwd_workspace_bytes(*gy.shape)."""
+    _stream_ok(gy, p["c"])
+    n, h, w, c = gy.shape
+    _rows_ok(row_scale, n, gy.device)
+    gxn = torch.empty_like(gy)
+    check(_lib.load().agp_cnx_mlp_bwd(ptr(ws), ws.numel(), n * h * w, c, ptr(gy), ptr(row_scale), h * w, ptr(p["w1"][0]),
+                                      ptr(p["w1"][1]), ptr(p["b1"]), ptr(pb["w2t"][0]), ptr(pb["w2t"][1]), ptr(pb["w1t"][0]),
+                                      ptr(pb["w1t"][1]), ptr(pb["w2f"]), ptr(p["b2"]), ptr(p["ls"]), ptr(gxn), *[ptr(g) for g in grads],
+                                      ptr(bws), bws.numel(), _lib.stream()), "agp_cnx_mlp_bwd")
+    return gxn
+
+
+def dwconv_ln_bwd(x, gxn, gy, p, grads, bws):
+    """Backward of dwconv_ln_fwd plus the residual: returns gx = gy + dL/dx through the branch; adds into grads = (g_dw [C,1,7,7],
+    g_dwbias, g_ln_w, g_ln_b)."""
+    _stream_ok(x, p["c"])
+    _stream_ok(gxn, p["c"])
+    _stream_ok(gy, p["c"])
+    n, h, w, c = x.shape
+    gx = torch.empty_like(x)
+    check(_lib.load().agp_cnx_dwconv_ln_bwd(ptr(x), ptr(gxn), ptr(gy), n, h, w, c, ptr(p["dw"]), ptr(p["dwb"]), ptr(p["g"]), LN_EPS,
+                                            ptr(gx), *[ptr(g) for g in grads], ptr(bws), bws.numel(), _lib.stream()),
+          "agp_cnx_dwconv_ln_bwd")
+    return gx
+
+
+def downsample_bwd(x, gout, p, pb, grads, bws):
+    """Backward of downsample_fwd: returns gx [n,h,w,C] (exactly 0 on a dropped odd last row / column); adds into grads =
+    (g_ln_w, g_ln_b, g_w [2C,C,2,2], g_bias)."""
+    _stream_ok(x, p["c"])
+    _stream_ok(gout, 2 * p["c"])
+    n, h, w, c = x.shape
+    gx = torch.empty_like(x)
+    g_ln_w, g_ln_b, g_w, g_bias = grads
+    check(_lib.load().agp_cnx_downsample_bwd(ptr(x), ptr(gout), n, h, w, c, ptr(p["g"]), ptr(p["b"]), LN_EPS, ptr(pb["wt"][0]),
+                                             ptr(pb["wt"][1]), ptr(gx), ptr(g_w), ptr(g_bias), ptr(g_ln_w), ptr(g_ln_b), ptr(bws),
+                                             bws.numel(), _lib.stream()), "agp_cnx_downsample_bwd")
+    return gx
+
+
+def stem_bwd(x, gout, p, grads, bws):
+    """Backward of stem_fwd (no input gradient): adds into grads = (g_w [96,3,4,4], g_bias, g_ln_w, g_ln_b)."""
+    _stream_ok(gout, DIMS[0])
+    n, _, H, W = x.shape
+    check(_lib.load().agp_cnx_stem_bwd(ptr(x), *x.stride(), n, H, W, ptr(p["w"]), ptr(p["bias"]), ptr(p["g"]), LN_EPS, ptr(gout),
+                                       *[ptr(g) for g in grads], ptr(bws), bws.numel(), _lib.stream()), "agp_cnx_stem_bwd")
+
+
 def downsample_fwd(x, p):
     """LayerNorm + 2x2 / stride-2 conv of the stream x -> a new stream [n, h//2, w//2, 2C]."""
     _stream_ok(x, p["c"])
@@ -136,8 +241,31 @@ def downsample_fwd(x, p):
     return out
 
 
+class _TrunkFn(torch.autograd.Function):
+    """The training forward of the whole trunk as one node.  Inputs: the trunk, the input image, the per-block scales, then every
+    parameter of `features` (so that autograd accumulates into their .grad: a trunk applied twice adds up).  Outputs: the three
+    exported maps; gradients arriving at all three are added into the stream's gradient at their taps."""
+
+    @staticmethod
+    def forward(ctx, fe, x, scales, *params):
+        maps, saved = fe._run_train(x, scales, keep=True)
+        ctx.fe, ctx.x, ctx.scales, ctx.saved = fe, x, scales, saved
+        ctx.key = fe._version_key()
+        return tuple(m.permute(0, 3, 1, 2) for m in maps)
+
+    @staticmethod
+    def backward(ctx, *gmaps):
+        fe = ctx.fe
+        if fe._version_key() != ctx.key:
+            raise RuntimeError("ConvNeXt: a parameter changed between the training forward and its backward")
+        grads = fe._run_backward(ctx.x, ctx.scales, ctx.saved, gmaps)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
 class ConvNeXt(nn.Module):
     """`layers`: the three block counts of the reference's 'a_b_c'."""
+
+    stochastic_depth_prob = 0.1        # torchvision's convnext_tiny; a module attribute, not a parameter
 
     def __init__(self, layers):
         super().__init__()
@@ -160,7 +288,24 @@ class ConvNeXt(nn.Module):
         # registered and unused, as in the reference (never part of a forward: frozen like ResNet.fc)
         self.classifier.requires_grad_(False)
         self._prep, self._prep_key = None, None
+        self._prep_bwd, self._prep_bwd_key = None, None
+        self._train_enabled = False
+        self.last_row_scales = None
         self._ws = ops.Workspace()
+
+    # ------------------------------------------------------------------ training switch
+    def enable_training(self, flag=True):
+        """Opt in to (or out of) the training path: .train() and gradients into the trunk.  Off by default; while off both are
+        refused and nothing changes for inference."""
+        self._train_enabled = bool(flag)
+        return self
+
+    def sd_probs(self):
+        """Per stage, the stochastic-depth probability p_k of each kept block: stochastic_depth_prob * k / 17 with k the block's
+        index in the full 18-block network (torchvision sets them before the reference truncates)."""
+        total = sum(DEPTHS) - 1.0
+        return [[self.stochastic_depth_prob * (STAGE_FIRST_BLOCK[s] + b) / total for b in range(len(self.features[1 + 2 * s]))]
+                for s in range(3)]
 
     # ------------------------------------------------------------------ weights
     def _version_key(self):
@@ -179,6 +324,18 @@ class ConvNeXt(nn.Module):
             self._prep, self._prep_key = prep, key
         return self._prep
 
+    def _prepared_bwd(self):
+        key = self._version_key()
+        if key != self._prep_bwd_key:
+            with torch.no_grad():
+                prep = {}
+                for s in range(3):
+                    prep[("blocks", s)] = [prep_block_bwd(blk) for blk in self.features[1 + 2 * s]]
+                    if s < 2:
+                        prep[("down", s)] = prep_down_bwd(*self.features[2 + 2 * s])
+            self._prep_bwd, self._prep_bwd_key = prep, key
+        return self._prep_bwd
+
     # ------------------------------------------------------------------ forward
     @staticmethod
     def map_sizes(h, w):
@@ -195,12 +352,17 @@ class ConvNeXt(nn.Module):
     def forward_maps(self, x):
         """fp32 [n,3,H,W] on the GPU (any strides) -> the outputs of features[1], [3], [5] as fp32 tensors of logical shape
         [n,C,h,w] in channels_last memory.  Inference only; allocates the three maps, launches on the current stream and never
-        synchronises (capturable after one eager call has prepared the weights)."""
+        synchronises (capturable after one eager call has prepared the weights).  With the training switch on, .train() or
+        trainable trunk parameters under enabled gradients go through `forward_maps_train` instead."""
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters())
+        if self._train_enabled and (self.training or wants_grad):
+            return self.forward_maps_train(x)
         if self.training:
-            raise NotImplementedError("ConvNeXt: .train() is not built (inference only); call .eval()")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.features.parameters())):
-            raise NotImplementedError("ConvNeXt: gradients into the trunk are not built (inference only): run under "
-                                      "torch.no_grad() or freeze the trunk (requires_grad_(False) / freeze_backbone())")
+            raise NotImplementedError(f"ConvNeXt: .train() is not enabled (inference only; {TRAIN_SWITCH}); call .eval()")
+        if torch.is_grad_enabled() and (x.requires_grad or wants_grad):
+            raise NotImplementedError("ConvNeXt: gradients into the trunk are not enabled (inference only): run under "
+                                      "torch.no_grad() or freeze the trunk (requires_grad_(False) / freeze_backbone()), or "
+                                      + TRAIN_SWITCH)
         if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
             raise ValueError("ConvNeXt.forward_maps: x must be an fp32 [n,3,H,W] tensor on the GPU")
         n, _, H, W = x.shape
@@ -216,3 +378,97 @@ class ConvNeXt(nn.Module):
                 mlp_fwd(ws, p, cur, cur)
             maps.append(cur.permute(0, 3, 1, 2))
         return maps
+
+    # ------------------------------------------------------------------ training
+    def forward_maps_train(self, x, row_scales=None):
+        """The training forward (needs enable_training()): the three maps of `forward_maps`, out of place, as one autograd node.
+
+        row_scales: None = in .train() draw, per block with p_k > 0 and per image, scale = bernoulli(1 - p_k) / (1 - p_k) on the
+        device from torch's current CUDA generator; in .eval() no scale.  Or a list with one entry per block (stage by stage):
+        an fp32 [n] tensor used in place of the draw, or None for no scale.  Under torch.no_grad(), or with no trainable trunk
+        parameter, nothing is saved.  An input that requires a gradient is refused: the stem returns no image gradient."""
+        if not self._train_enabled:
+            raise NotImplementedError(f"ConvNeXt: training (.train(), gradients) is not enabled; {TRAIN_SWITCH}")
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
+            raise ValueError("ConvNeXt.forward_maps_train: x must be an fp32 [n,3,H,W] tensor on the GPU")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("ConvNeXt: the gradient of the input image is not built (the stem returns none)")
+        n = x.shape[0]
+        nblocks = sum(len(self.features[1 + 2 * s]) for s in range(3))
+        if row_scales is None:
+            row_scales = [None] * nblocks
+            if self.training:
+                probs = [p for stage in self.sd_probs() for p in stage]
+                row_scales = [None if p == 0.0 else torch.bernoulli(torch.full((n,), 1.0 - p, dtype=torch.float32, device=x.device))
+                              * (1.0 / (1.0 - p)) for p in probs]
+        elif len(row_scales) != nblocks:
+            raise ValueError(f"ConvNeXt.forward_maps_train: row_scales needs {nblocks} entries (one per block), got {len(row_scales)}")
+        scales = tuple(None if r is None else r.detach().contiguous() for r in row_scales)
+        self.last_row_scales = scales          # what this forward applied (drawn or given), for inspection
+        params = [p for p in self.features.parameters()]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return list(_TrunkFn.apply(self, x.detach(), scales, *params))
+        with torch.no_grad():
+            maps, _ = self._run_train(x, scales, keep=False)
+        return [m.permute(0, 3, 1, 2) for m in maps]
+
+    def _ws_bytes(self, n, sizes, fn):
+        return max(fn(n, h, w, DIMS[s]) for s, (h, w) in enumerate(sizes))
+
+    def _run_train(self, x, scales, keep):
+        """keep: every block writes a new stream tensor and the block inputs are returned (the saved state); else in place."""
+        n, _, H, W = x.shape
+        sizes = self.map_sizes(H, W)
+        prep = self._prepared()
+        ws = self._ws.tensor("cnx_ws", (self._ws_bytes(n, sizes, workspace_bytes),), torch.uint8, x.device)
+        maps, saved, cur, k = [], [], None, 0
+        for s in range(3):
+            cur = stem_fwd(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)])
+            inputs = []
+            for p in prep[("blocks", s)]:
+                dwconv_ln_fwd(cur, p, ws)
+                out = torch.empty_like(cur) if keep else cur
+                mlp_fwd_rows(ws, p, cur, out, scales[k])
+                inputs.append(cur)
+                cur, k = out, k + 1
+            saved.append(inputs)
+            maps.append(cur)
+        return maps, (saved, maps) if keep else None
+
+    def _run_backward(self, x, scales, saved, gmaps):
+        """Gradients of every parameter of `features`, in parameters() order, as fp32 tensors in parameter layout."""
+        inputs, maps = saved
+        n, _, H, W = x.shape
+        sizes = self.map_sizes(H, W)
+        prep, pb = self._prepared(), self._prepared_bwd()
+        dev = x.device
+        ws = self._ws.tensor("cnx_ws", (self._ws_bytes(n, sizes, workspace_bytes),), torch.uint8, dev)
+        bws = self._ws.tensor("cnx_bws", (self._ws_bytes(n, sizes, bwd_workspace_bytes),), torch.uint8, dev)
+        params = list(self.features.parameters())
+        grads = {id(p): torch.zeros(p.shape, dtype=torch.float32, device=dev) for p in params}
+        G = lambda *ps: [grads[id(p)] for p in ps]
+        nb = [len(b) for b in inputs]
+        g = None
+        for s in (2, 1, 0):
+            gm = gmaps[s]
+            if gm is not None:
+                gm = gm.permute(0, 2, 3, 1).float().contiguous()
+                g = gm if g is None else g + gm
+            elif g is None:
+                g = torch.zeros_like(maps[s])
+            k0 = sum(nb[:s])
+            for b in reversed(range(nb[s])):
+                blk, p, xin = self.features[1 + 2 * s][b], prep[("blocks", s)][b], inputs[s][b]
+                dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
+                dwconv_ln_fwd(xin, p, ws)                  # the operand, recomputed
+                gxn = mlp_bwd(ws, p, pb[("blocks", s)][b], g, scales[k0 + b],
+                              G(l1.weight, l1.bias, l2.weight, l2.bias, blk.layer_scale), bws)
+                g = dwconv_ln_bwd(xin, gxn, g, p, G(dw.weight, dw.bias, ln.weight, ln.bias), bws)
+            if s > 0:
+                ln, conv = self.features[2 * s]
+                g = downsample_bwd(maps[s - 1], g, prep[("down", s - 1)], pb[("down", s - 1)], G(ln.weight, ln.bias, conv.weight, conv.bias),
+                                   bws)
+            else:
+                conv, ln = self.features[0]
+                stem_bwd(x, g, prep["stem"], G(conv.weight, conv.bias, ln.weight, ln.bias), bws)
+        return [grads[id(p)] for p in params]

@@ -1,5 +1,6 @@
-// ConvNeXt-tiny inference kernels (agplace_amd/convnext.py): stem, depthwise 7x7 + LayerNorm, the fused
-// Linear -> GELU -> Linear block, and the LayerNorm + 2x2/s2 downsample.
+// ConvNeXt-tiny forward kernels (agplace_amd/convnext.py): stem, depthwise 7x7 + LayerNorm, the fused
+// Linear -> GELU -> Linear block (with an optional per-image factor for the training forward), and the LayerNorm + 2x2/s2
+// downsample.  The backward kernels are in convnext_bwd.hip.
 //
 // The residual stream is a plain fp32 [n][h][w][C] tensor (C = 96, 192 or 384).  Arithmetic follows the project's mode 3
 // (AGP_PREC_BF16X3): every MFMA operand is a bf16 (hi, lo) pair and a product is hi*hi + hi*lo + lo*hi accumulated in fp32;
@@ -12,36 +13,9 @@
 // bias + GELU + the bf16 split there and is consumed at once by the second GEMM.  The hidden map [P][4C] never exists in memory,
 // LDS included.  The register r of lane (col, h = lane >> 5) holds feature row (r & 3) + 8 (r >> 2) + 4 h; the MFMA that takes
 // registers 8t .. 8t+7 as its K slots 8h .. 8h+7 needs W2's columns in that order, which is how convnext.py lays them out.
-#include "common.hpp"
+#include "convnext_common.hpp"
 
 namespace {
-
-constexpr int CNX_TP = 32;         // pixels per tile of the matrix kernels (one MFMA column block)
-constexpr int CNX_KPAD = 8;        // bf16 elements of padding per LDS operand row (16 B: spreads the rows over the banks)
-
-// sum over the 32 lanes of a half wave (lanes that share lane >> 5)
-__device__ __forceinline__ float half_sum(float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// sum over 8 consecutive lanes
-__device__ __forceinline__ float oct_sum(float v) {
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ void mfma3(f32x16& acc, const bf16x8& wh, const bf16x8& wl, const bf16x8& xh, const bf16x8& xl) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc, 0, 0, 0);
-}
-
-// feature row (inside a 32-row block) of accumulator register `reg` of a lane in half `h`
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // ------------------------------------------------------------------------------------------------------------------ stem
 // Conv2d(3, 96, k=4, s=4, bias) + LayerNorm over the 96 channels.  32 output pixels per block; a thread owns 3 channels
@@ -193,14 +167,18 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
 // split in registers, then 2 k-steps into each of the C / 32 output accumulators.  The waves' partial [C][32] sums are added in
 // wave order through LDS (the operand planes' space, free by then), 32 channels at a time, with the epilogue: every output
 // element is read (resid) and written (out) by the same thread, so `out` may alias `resid`.
+// ROWS (the training forward, agp_cnx_mlp_fwd_rows): layer_scale is multiplied by row_scale[p / ppi], the stochastic-depth
+// factor of the pixel's image -- per pixel, since a tile may straddle two images.  ROWS = false is the inference kernel, whose
+// arithmetic does not change.
 //   w1 planes: [4C / 32][C / 16][64 lanes][8]     lane (r, h) of block jb, step kk: W1[jb * 32 + r][kk * 16 + 8 h + e]
 //   w2 planes: [4C / 32][2][C / 32][64 lanes][8]  lane (r, h) of block jb, half t, tile ct: W2[ct * 32 + r][jb * 32 + acc_row(8 t + e, h)]
-template <int C>
+template <int C, bool ROWS>
 __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo, long long P,
                                                       const bf16x8* __restrict__ w1_hi, const bf16x8* __restrict__ w1_lo,
                                                       const float* __restrict__ b1, const bf16x8* __restrict__ w2_hi,
                                                       const bf16x8* __restrict__ w2_lo, const float* __restrict__ b2,
-                                                      const float* __restrict__ ls, const float* resid, float* out) {
+                                                      const float* __restrict__ ls, const float* resid, float* out,
+                                                      const float* __restrict__ row_scale, long long ppi) {
     constexpr int LD = C + CNX_KPAD, KK = C / 16, CT = C / 32, JB = C / 8, VR = C / 8;
     constexpr int XBYTES = 2 * CNX_TP * LD * 2, RBYTES = 4 * 32 * 36 * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem[XBYTES > RBYTES ? XBYTES : RBYTES];
@@ -259,6 +237,8 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
     float* const red = (float*)smem;       // [4 waves][32 pixels][36]: 32 channels + 4 floats of padding
     const int epx = t >> 3, ec = (t & 7) * 4;
     const long long ep = p0 + epx;
+    float rs = 1.f;
+    if (ROWS && ep < P) rs = row_scale[ep / ppi];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
         __syncthreads();                   // the operand planes (first round) / the previous round's sums have been read
@@ -273,7 +253,9 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
             const f32x4 s2 = *(const f32x4*)(red + (2 * 32 + epx) * 36 + ec), s3 = *(const f32x4*)(red + (3 * 32 + epx) * 36 + ec);
             const int c = ct * 32 + ec;
             const f32x4 rv = *(const f32x4*)(resid + (size_t)ep * C + c);
-            const f32x4 bv = *(const f32x4*)(b2 + c), lv = *(const f32x4*)(ls + c);
+            const f32x4 bv = *(const f32x4*)(b2 + c);
+            f32x4 lv = *(const f32x4*)(ls + c);
+            if (ROWS) lv *= rs;
             f32x4 o;
 #pragma unroll
             for (int i = 0; i < 4; ++i) o[i] = fmaf(lv[i], (((s0[i] + s1[i]) + s2[i]) + s3[i]) + bv[i], rv[i]);
@@ -386,10 +368,6 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
     }
 }
 
-inline long long cnx_pad(long long P) { return (P + CNX_TP - 1) / CNX_TP * CNX_TP; }
-inline bool cnx_c_host_ok(int C) { return C == 96 || C == 192 || C == 384; }
-inline bool cnx_map_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long long)n * h * w < (1ll << 31) / 32; }
-
 }  // namespace
 
 extern "C" {
@@ -427,22 +405,35 @@ int agp_cnx_dwconv_ln_fwd(const float* x, int n, int h, int w, int C, const floa
     return AGP_OK;
 }
 
-int agp_cnx_mlp_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1_hi, const void* w1_lo,
-                    const float* b1, const void* w2_hi, const void* w2_lo, const float* b2, const float* layer_scale,
-                    const float* resid, float* out, void* stream) {
+int agp_cnx_mlp_fwd_rows(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1_hi, const void* w1_lo,
+                         const float* b1, const void* w2_hi, const void* w2_lo, const float* b2, const float* layer_scale,
+                         const float* resid, float* out, const float* row_scale, int64_t pixels_per_image, void* stream) {
     if (!workspace || !w1_hi || !w1_lo || !b1 || !w2_hi || !w2_lo || !b2 || !layer_scale || !resid || !out) return AGP_E_BADARG;
     if (P <= 0 || P >= (1ll << 31) / 32 || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    if (row_scale && (pixels_per_image <= 0 || P % pixels_per_image)) return AGP_E_BADARG;
     if (workspace_bytes < 2 * cnx_pad(P) * C * 2 || ((uintptr_t)workspace & 15)) return AGP_E_BADARG;
     const bf16_t* const hi = (const bf16_t*)workspace;
     const bf16_t* const lo = hi + cnx_pad(P) * C;
     const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
     hipStream_t s = (hipStream_t)stream;
     const bf16x8 *a = (const bf16x8*)w1_hi, *b = (const bf16x8*)w1_lo, *c = (const bf16x8*)w2_hi, *d = (const bf16x8*)w2_lo;
-    if (C == 96) { AGP_LAUNCH(cnx_mlp_kernel<96>, grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out); }
-    else if (C == 192) { AGP_LAUNCH(cnx_mlp_kernel<192>, grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out); }
-    else { AGP_LAUNCH(cnx_mlp_kernel<384>, grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out); }
+    const long long ppi = pixels_per_image;
+#define CNX_MLP(CC, RR) AGP_LAUNCH((cnx_mlp_kernel<CC, RR>), grid, dim3(256), 0, s, hi, lo, (long long)P, a, b, b1, c, d, b2, layer_scale, resid, out, row_scale, ppi)
+    if (row_scale) {
+        if (C == 96) { CNX_MLP(96, true); } else if (C == 192) { CNX_MLP(192, true); } else { CNX_MLP(384, true); }
+    } else {
+        if (C == 96) { CNX_MLP(96, false); } else if (C == 192) { CNX_MLP(192, false); } else { CNX_MLP(384, false); }
+    }
+#undef CNX_MLP
     AGP_CHECK_LAUNCH();
     return AGP_OK;
+}
+
+int agp_cnx_mlp_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1_hi, const void* w1_lo,
+                    const float* b1, const void* w2_hi, const void* w2_lo, const float* b2, const float* layer_scale,
+                    const float* resid, float* out, void* stream) {
+    return agp_cnx_mlp_fwd_rows(workspace, workspace_bytes, P, C, w1_hi, w1_lo, b1, w2_hi, w2_lo, b2, layer_scale, resid, out, nullptr,
+                                0, stream);
 }
 
 int agp_cnx_downsample_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,

@@ -1,0 +1,38 @@
+// Shared by convnext.hip (forward) and convnext_bwd.hip (backward): tile constants, wave reductions, the three-product MFMA.
+#pragma once
+#include "common.hpp"
+
+namespace {
+
+constexpr int CNX_TP = 32;         // pixels per tile of the matrix kernels (one MFMA column block)
+constexpr int CNX_KPAD = 8;        // bf16 elements of padding per LDS operand row (16 B: spreads the rows over the banks)
+
+// sum over the 32 lanes of a half wave (lanes that share lane >> 5)
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// sum over 8 consecutive lanes
+__device__ __forceinline__ float oct_sum(float v) {
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+
+__device__ __forceinline__ void mfma3(f32x16& acc, const bf16x8& wh, const bf16x8& wl, const bf16x8& xh, const bf16x8& xl) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc, 0, 0, 0);
+}
+
+// feature row (inside a 32-row block) of accumulator register `reg` of a lane in half `h`
+__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+inline long long cnx_pad(long long P) { return (P + CNX_TP - 1) / CNX_TP * CNX_TP; }
+inline bool cnx_c_host_ok(int C) { return C == 96 || C == 192 || C == 384; }
+inline bool cnx_map_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long long)n * h * w < (1ll << 31) / 32; }
+
+}  // namespace

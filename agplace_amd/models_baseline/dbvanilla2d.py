@@ -51,6 +51,8 @@ class DBVanilla2D(nn.Module):
             for e in fes:
                 if not self._convnext:      # Normalize of the uint8 routes (tiles, frames), which the ResNets alone have
                     e.fe.set_image_norm(opt.image_mean, opt.image_std)
+                elif opt.convnext_train:    # the opt-in training path of the ConvNeXt trunk (agplace_amd/convnext.py)
+                    e.fe.enable_training()
             self.dbimage_fes = nn.ModuleList(fes)
             self.dbimage_pools = nn.ModuleList([GeM() for _ in maptype])
             self.dbimage_mlps = nn.ModuleList([MLP(e.last_dim, dim) for e in fes])
@@ -234,13 +236,17 @@ class DBVanilla2D(nn.Module):
         return {'embedding': out}
 
     def _forward_db_convnext(self, data_dict, trunk_maps):
-        """dbimage_fe='convnext_tiny' (agplace_amd/convnext.py): inference over fp32 `db_map`.  Per map type: the trunk's last map
+        """dbimage_fe='convnext_tiny' (agplace_amd/convnext.py) over fp32 `db_map`.  Per map type: the trunk's last map
         (fp32, 384 channels) -> the dense-fp32 GeM -> the per-op MLP(384, dim) -> F.normalize; then the mean over map types.  The
-        heads may train on a frozen trunk (freeze_backbone) through the ops' own backward kernels."""
+        heads may train on a frozen trunk (freeze_backbone) through the ops' own backward kernels.  Inference only unless
+        Options.convnext_train enabled the trunks' training path: then .train() (stochastic depth; under torch.no_grad() nothing is
+        saved) and gradients into the trunk run through ConvNeXt.forward_maps_train; with share_dbfe the one trunk is applied per
+        map type, each application with its own saved state, and its parameter gradients accumulate."""
         opt = self.opt
-        what = "DBVanilla2D with dbimage_fe='convnext_tiny' (inference only)"
-        if self.training:
-            raise NotImplementedError(f"{what}: .train() is not built; call .eval()")
+        enabled = all(e.fe._train_enabled for e in self.dbimage_fes)
+        what = "DBVanilla2D with dbimage_fe='convnext_tiny'" + ("" if enabled else " (inference only; Options.convnext_train opts in)")
+        if self.training and not enabled:
+            raise NotImplementedError(f"{what}: .train() is not enabled; call .eval()")
         if 'db_frames' in data_dict or 'db_jitter' in data_dict:
             raise NotImplementedError(f"{what}: `db_frames` (decoded uint8 frames) is not built; pass fp32 `db_map`")
         if trunk_maps is not None:
@@ -248,8 +254,8 @@ class DBVanilla2D(nn.Module):
         db_map = data_dict['db_map']
         if db_map.dtype == torch.uint8:
             raise NotImplementedError(f"{what}: uint8 `db_map` is not built; pass fp32 tiles")
-        if torch.is_grad_enabled() and any(p.requires_grad for e in self.dbimage_fes for p in e.fe.features.parameters()):
-            raise NotImplementedError(f"{what}: gradients into the trunk are not built; run under torch.no_grad() or "
+        if not enabled and torch.is_grad_enabled() and any(p.requires_grad for e in self.dbimage_fes for p in e.fe.features.parameters()):
+            raise NotImplementedError(f"{what}: gradients into the trunk are not enabled; run under torch.no_grad() or "
                                       "freeze_backbone()")
         if db_map.dim() == 5:      # [b,nmap,3,h,w]  caching / testing
             mode = 'cachetest'

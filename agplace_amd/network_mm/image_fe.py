@@ -6,7 +6,8 @@ for ResNets (reference :15-30).  forward(x[b,3,H,W]) -> (last_map, [l1, l2, l3(,
 tensors of logical shape [b,C,h,w] (channels_last memory).  `forward_maps` returns the same
 stages as ops.SplitMap without the fp32 export (the fused MM / DBVanilla2D paths use it).
 
-'convnext_tiny' (agplace_amd/convnext.py) is inference only and takes exactly three `layers` entries, which are BLOCK COUNTS
+'convnext_tiny' (agplace_amd/convnext.py) is inference only unless `fe.enable_training()` opted in (then .train() and gradients
+into the trunk run through ConvNeXt.forward_maps_train); it takes exactly three `layers` entries, which are BLOCK COUNTS
 there: features[6:] are dropped and stage i keeps its first layers[i] blocks, last_dim = 384, the list holds the outputs of
 features[1], [3], [5].  It runs in the mode-3 arithmetic only (prec None or 3) and has no ops.SplitMap form: `forward_maps`
 with pool requests raises NotImplementedError.  The SqueezeNet branch of the reference is not built.

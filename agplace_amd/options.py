@@ -119,6 +119,12 @@ class Options:
     # 3 (default) | 1 = opt-in: the data gradients of the 3x3 convs as ONE bf16 product of the hi planes (train_graph.DGRAD_HI_ONLY),
     # usually together with train_precision = 16; measured error: tests/test_gpu_train.py, timing: bench.py train.fast_mode
     train_dgrad_products: int = 3
+    # Opt-in training of the ConvNeXt-tiny trunk (dbimage_fe = "convnext_tiny"): DBVanilla2D then calls
+    # ConvNeXt.enable_training() on its trunks, so .train() (torchvision's stochastic depth, p_k = 0.1 k / 17) and gradients into
+    # the trunk run on the kernels of csrc/convnext_bwd.hip (mode-3 products, fixed-order sums: repeatable bit for bit).  False
+    # (default): the trunk is inference only and refuses both, as before.  A reference namespace does not carry this field:
+    # from_reference_opt(args).copy(convnext_train=True).
+    convnext_train: bool = False
     # inference: MM.forward embeds a batch as this many sub-batches on as many HIP streams (1 = off)
     query_substreams: int = 1
     # inference: the vector path (everything after the backbones) as two program launches (agplace_amd/vecprog.py) instead
@@ -167,6 +173,8 @@ class Options:
             setattr(self, name, tuple(float(c) for c in v))
         if any(c <= 0.0 for c in self.image_std):
             raise ValueError(f"image_std {self.image_std!r}: every component must be positive")
+        if not isinstance(self.convnext_train, bool):
+            raise ValueError(f"convnext_train {self.convnext_train!r}: True | False")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
 

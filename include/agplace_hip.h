@@ -1016,6 +1016,44 @@ int agp_cnx_mlp_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, i
 int agp_cnx_downsample_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
                            const void* w_hi, const void* w_lo, const float* bias, float* out, void* stream);
 
+/* ---- ConvNeXt-tiny trunk, training (csrc/convnext.hip: the scaled forward; csrc/convnext_bwd.hip: the backward).  Same
+ * arithmetic; no atomics: every sum over pixels or workgroups has a fixed order, two runs give the same bits.  Nothing allocates
+ * or synchronises.  Every g_* argument is a caller-owned fp32 buffer in the PARAMETER's layout that the entry adds to (+=).
+ * bwd_workspace: 16-byte aligned, agp_cnx_bwd_workspace_bytes(n, h, w, C) bytes for the map [n][h][w][C] the entry differentiates
+ * at (stem: its OUTPUT map, C = 96; downsample: its INPUT map): per-slice partial planes (a slice = agp_cnx_bwd_slice_pixels()
+ * pixels of the weight-gradient sweeps) and one stream-sized map; no P x 4C term. */
+int64_t agp_cnx_bwd_workspace_bytes(int n, int h, int w, int C);
+int64_t agp_cnx_bwd_slice_pixels(void);
+/* agp_cnx_mlp_fwd with a per-image factor (torchvision's StochasticDepth(p, "row")): out = resid + row_scale[p / pixels_per_image]
+ * * layer_scale * MLP(xn).  row_scale: fp32 [P / pixels_per_image] or NULL (= agp_cnx_mlp_fwd, bit for bit). */
+int agp_cnx_mlp_fwd_rows(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1_hi, const void* w1_lo,
+                         const float* b1, const void* w2_hi, const void* w2_lo, const float* b2, const float* layer_scale,
+                         const float* resid, float* out, const float* row_scale, int64_t pixels_per_image, void* stream);
+/* Backward of agp_cnx_mlp_fwd_rows for the operand in `workspace` (recomputed by agp_cnx_dwconv_ln_fwd) and gy = dL/dout [P][C]:
+ * gxn [P][C] (overwritten) = dL/d operand; g_w1 [4C][C], g_b1 [4C], g_w2 [C][4C], g_b2 [C], g_layer_scale [C] are added to.
+ * w1_*: the forward's planes; w2t_*: (layer_scale * W2)^T [4C][C] and w1t_*: W1^T [C][4C] in fragment order (convnext.py:
+ * prep_block_bwd); w2: Linear(4C, C).weight fp32 [C][4C].  The residual path (dL/dresid = gy) is the caller's. */
+int agp_cnx_mlp_bwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const float* gy, const float* row_scale,
+                    int64_t pixels_per_image, const void* w1_hi, const void* w1_lo, const float* b1, const void* w2t_hi,
+                    const void* w2t_lo, const void* w1t_hi, const void* w1t_lo, const float* w2, const float* b2,
+                    const float* layer_scale, float* gxn, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_layer_scale,
+                    void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
+/* Backward of agp_cnx_dwconv_ln_fwd plus the block's residual: x the block input, gxn = dL/d operand, gy = dL/dout;
+ * gx [n][h][w][C] (overwritten) = gy + dL/dx through the branch; g_dw [C][49], g_dwbias, g_ln_w, g_ln_b [C] are added to. */
+int agp_cnx_dwconv_ln_bwd(const float* x, const float* gxn, const float* gy, int n, int h, int w, int C, const float* wt,
+                          const float* bias, const float* ln_w, float eps, float* gx, float* g_dw, float* g_dwbias, float* g_ln_w,
+                          float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
+/* Backward of agp_cnx_downsample_fwd: gout [n][h/2][w/2][2C]; gx [n][h][w][C] (overwritten; the pixels of a dropped odd last row /
+ * column get exactly 0); g_w [2C][C][2][2], g_bias [2C], g_ln_w, g_ln_b [C] are added to.  wt_*: the weight matrix transposed,
+ * [4C][2C], in fragment order. */
+int agp_cnx_downsample_bwd(const float* x, const float* gout, int n, int h, int w, int C, const float* ln_w, const float* ln_b,
+                           float eps, const void* wt_hi, const void* wt_lo, float* gx, float* g_w, float* g_bias, float* g_ln_w,
+                           float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
+/* Backward of agp_cnx_stem_fwd (no input gradient): gout [n][ho][wo][96]; g_w [96][48], g_bias, g_ln_w, g_ln_b [96] are added to. */
+int agp_cnx_stem_bwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int n, int h, int w, const float* wt,
+                     const float* bias, const float* ln_w, float eps, const float* gout, float* g_w, float* g_bias, float* g_ln_w,
+                     float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

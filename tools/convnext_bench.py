@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """ConvNeXt-tiny trunk at the database tile size: time per kernel and of the whole trunk, with the ResNet18 trunk in mode 3 on
-the same batch for context.
+the same batch for context; then one training forward + backward of '2_2_2' (the opt-in training path, .eval() with gradients:
+no stochastic depth) and each backward entry alone.
 
-python tools/convnext_bench.py [--batch 64] [--size 256] [--reps 10] [--windows 5] [--json out.json]
+python tools/convnext_bench.py [--batch 64] [--size 256] [--reps 10] [--windows 5] [--json out.json] [--train-only]
 Events on the launch stream around `reps` back-to-back calls, the median of `windows` such windows after a warm-up.  GMAC are
 algorithmic (one multiply-accumulate per weight use, whatever the three bf16 products cost); the fraction of peak is
 2 * MAC / time over the 2.5 PFLOP/s dense bf16 peak.  Weights are seeded random values (zeros would flatter the clock)."""
@@ -68,6 +69,55 @@ def randomize(fe, seed):
     return fe
 
 
+def train_leg(a, dev, x, report, rows):
+    """'2_2_2' with the training switch on: the forward that keeps its tape, its backward (gradients fed into all three maps), and
+    every backward entry alone at the map sizes of this input.  MACs: the backward of a GEMM costs two of them (data and weight
+    gradient), the recomputed operand and hidden map are not counted."""
+    n, hw = x.shape[0], x.shape[2]
+    sizes = cnx.ConvNeXt.map_sizes(hw, hw)
+    macs, per = convnext_macs([2, 2, 2], hw, hw)
+    torch.set_grad_enabled(True)
+    fe = randomize(ImageFE("convnext_tiny", "2_2_2"), 0).to(dev).eval()
+    fe.fe.enable_training()
+    reps = max(2, a.reps // 2)
+    t_f = timed(lambda: fe(x), reps, a.windows)
+    report("train fwd 2_2_2 (tape kept)", n * macs, t_f)
+    maps = fe(x)[1]
+    gs = [torch.randn(m.shape, device=dev).contiguous(memory_format=torch.channels_last) for m in maps]
+    t_b = timed(lambda: torch.autograd.backward(maps, grad_tensors=gs, retain_graph=True), reps, a.windows)
+    report("train bwd 2_2_2", 2 * n * macs, t_b)
+    rows.append({"name": "train bwd / fwd", "ratio": t_b[0] / t_f[0]})
+    print(f"backward / forward = {t_b[0] / t_f[0]:.2f}")
+    del maps, gs
+    torch.set_grad_enabled(False)
+    prep, pb = fe.fe._prepared(), fe.fe._prepared_bwd()
+    feats = fe.fe.features
+    for s, (h, w) in enumerate(sizes):
+        c = cnx.DIMS[s]
+        cur, g = torch.randn(n, h, w, c, device=dev), torch.randn(n, h, w, c, device=dev)
+        ws = torch.empty(cnx.workspace_bytes(n, h, w, c), dtype=torch.uint8, device=dev)
+        bws = torch.empty(cnx.bwd_workspace_bytes(n, h, w, c), dtype=torch.uint8, device=dev)
+        blk, p = feats[1 + 2 * s][0], prep[("blocks", s)][0]
+        zeros = lambda *ps: [torch.zeros(q.shape, device=dev) for q in ps]
+        cnx.dwconv_ln_fwd(cur, p, ws)
+        gm = zeros(blk.block[3].weight, blk.block[3].bias, blk.block[5].weight, blk.block[5].bias, blk.layer_scale)
+        report(f"mlp bwd C={c} {h}x{w}", 2 * n * per[("mlp", c)],
+               timed(lambda: cnx.mlp_bwd(ws, p, pb[("blocks", s)][0], g, None, gm, bws), a.reps, a.windows))
+        gd = zeros(blk.block[0].weight, blk.block[0].bias, blk.block[2].weight, blk.block[2].bias)
+        report(f"ln+dwconv bwd C={c} {h}x{w}", 2 * n * per[("dwconv", c)],
+               timed(lambda: cnx.dwconv_ln_bwd(cur, g, g, p, gd, bws), a.reps, a.windows))
+        if s < 2:
+            ln, conv = feats[2 + 2 * s]
+            go = torch.randn(n, h // 2, w // 2, 2 * c, device=dev)
+            gw = zeros(ln.weight, ln.bias, conv.weight, conv.bias)
+            report(f"ln+downsample bwd C={c} {h}x{w}", 2 * n * per[("down", c)],
+                   timed(lambda: cnx.downsample_bwd(cur, go, prep[("down", s)], pb[("down", s)], gw, bws), a.reps, a.windows))
+        if s == 0:
+            gst = zeros(feats[0][0].weight, feats[0][0].bias, feats[0][1].weight, feats[0][1].bias)
+            report("stem bwd", n * per["stem"], timed(lambda: cnx.stem_bwd(x, g, prep["stem"], gst, bws), a.reps, a.windows))
+        del cur, g, ws, bws
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -75,6 +125,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--train-only", action="store_true", help="skip the inference legs")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
@@ -88,33 +139,35 @@ def main():
         print(f"{name:34s} {macs / 1e9:9.2f} GMAC {med:9.3f} ms (min {lo:.3f} max {hi:.3f})  {2 * macs / med / 1e9:8.1f} TFLOP/s "
               f"algorithmic = {100 * rows[-1]['frac_peak']:5.2f} % of peak")
 
-    # ---- per kernel, at the map sizes of this input
-    fe = randomize(ImageFE("convnext_tiny", "3_3_9"), 0).to(dev).eval()
-    sizes = cnx.ConvNeXt.map_sizes(hw, hw)
-    _, per = convnext_macs([3, 3, 9], hw, hw)
-    prep = fe.fe._prepared()
-    report("stem", n * per["stem"], timed(lambda: cnx.stem_fwd(x, prep["stem"]), a.reps, a.windows))
-    for s, (h, w) in enumerate(sizes):
-        c = cnx.DIMS[s]
-        cur = torch.randn(n, h, w, c, device=dev)
-        ws = torch.empty(cnx.workspace_bytes(n, h, w, c), dtype=torch.uint8, device=dev)
-        p = prep[("blocks", s)][0]
-        out = torch.empty_like(cur)
-        report(f"dwconv+ln C={c} {h}x{w}", n * per[("dwconv", c)], timed(lambda: cnx.dwconv_ln_fwd(cur, p, ws), a.reps, a.windows))
-        report(f"fused mlp C={c} {h}x{w}", n * per[("mlp", c)], timed(lambda: cnx.mlp_fwd(ws, p, cur, out), a.reps, a.windows))
-        if s < 2:
-            d = prep[("down", s)]
-            report(f"ln+downsample C={c} {h}x{w}", n * per[("down", c)], timed(lambda: cnx.downsample_fwd(cur, d), a.reps, a.windows))
-        del cur, ws, out
-    # ---- whole trunks
-    for layers in ("2_2_2", "3_3_9"):
-        fe = randomize(ImageFE("convnext_tiny", layers), 0).to(dev).eval()
-        macs, _ = convnext_macs([int(v) for v in layers.split("_")], hw, hw)
-        report(f"convnext_tiny {layers} trunk", n * macs, timed(lambda: fe(x), max(2, a.reps // 2), a.windows))
-        del fe
-    r18 = ImageFE("resnet18", "2_2_2").to(dev).eval()
-    report("resnet18 2_2_2 trunk, mode 3", n * bench_inputs.resnet_gmacs("resnet18", 3, hw, hw),
-           timed(lambda: r18(x, prec=3), max(2, a.reps // 2), a.windows))
+    if not a.train_only:
+        # ---- per kernel, at the map sizes of this input
+        fe = randomize(ImageFE("convnext_tiny", "3_3_9"), 0).to(dev).eval()
+        sizes = cnx.ConvNeXt.map_sizes(hw, hw)
+        _, per = convnext_macs([3, 3, 9], hw, hw)
+        prep = fe.fe._prepared()
+        report("stem", n * per["stem"], timed(lambda: cnx.stem_fwd(x, prep["stem"]), a.reps, a.windows))
+        for s, (h, w) in enumerate(sizes):
+            c = cnx.DIMS[s]
+            cur = torch.randn(n, h, w, c, device=dev)
+            ws = torch.empty(cnx.workspace_bytes(n, h, w, c), dtype=torch.uint8, device=dev)
+            p = prep[("blocks", s)][0]
+            out = torch.empty_like(cur)
+            report(f"dwconv+ln C={c} {h}x{w}", n * per[("dwconv", c)], timed(lambda: cnx.dwconv_ln_fwd(cur, p, ws), a.reps, a.windows))
+            report(f"fused mlp C={c} {h}x{w}", n * per[("mlp", c)], timed(lambda: cnx.mlp_fwd(ws, p, cur, out), a.reps, a.windows))
+            if s < 2:
+                d = prep[("down", s)]
+                report(f"ln+downsample C={c} {h}x{w}", n * per[("down", c)], timed(lambda: cnx.downsample_fwd(cur, d), a.reps, a.windows))
+            del cur, ws, out
+        # ---- whole trunks
+        for layers in ("2_2_2", "3_3_9"):
+            fe = randomize(ImageFE("convnext_tiny", layers), 0).to(dev).eval()
+            macs, _ = convnext_macs([int(v) for v in layers.split("_")], hw, hw)
+            report(f"convnext_tiny {layers} trunk", n * macs, timed(lambda: fe(x), max(2, a.reps // 2), a.windows))
+            del fe
+        r18 = ImageFE("resnet18", "2_2_2").to(dev).eval()
+        report("resnet18 2_2_2 trunk, mode 3", n * bench_inputs.resnet_gmacs("resnet18", 3, hw, hw),
+               timed(lambda: r18(x, prec=3), max(2, a.reps // 2), a.windows))
+    train_leg(a, dev, x, report, rows)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
