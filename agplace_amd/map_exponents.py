@@ -142,6 +142,9 @@ def calibrate(model, batches, headroom_bits=2):
     ImageFE / ResNet.  The model must be in .eval() mode.  Returns the installed dict (get_exponents)."""
     from .network_mm.image_fe import ImageFE
     from .network_mm.mm import MM
+    if isinstance(model, MM) and model._convnext:
+        raise NotImplementedError("map_exponents.calibrate on MM with mm_imgfe='convnext_tiny': its image side runs in the mode-3 "
+                                  "arithmetic (fp32 range), there are no map exponents to calibrate")
     if model.training:
         raise RuntimeError("map_exponents.calibrate: put the model in .eval() mode (exponents act on inference only)")
     if ops.MAP_PROBE is not None:

@@ -3,7 +3,9 @@
 FCODE.forward(x[b,D]) = odeint(f, x, t=[0,1], method=opt.odeint_method,
 options={'step_size': opt.odeint_size})[-1] with f(t, y) = act(Linear(y)).  torchdiffeq is not
 used: the whole fixed-grid solve (all steps, all stages) is ONE persistent HIP kernel
-(agp_fcode_fwd) that keeps W's MFMA fragments in registers.  The time grid follows
+(agp_fcode_fwd) that keeps W's MFMA fragments in registers.  dim = 384 in inference (no gradient wanted) is one launch as well
+(agp_fcode_wide_fwd: W's `hi` plane in registers, the `lo` plane streamed from L2); every other width, and
+384 with a gradient wanted, runs the same steps as a sequence of differentiable launches (_forward_any_width).  The time grid follows
 torchdiffeq's constructor exactly (niters = ceil(1/step + 1), arange * step, last point forced
 to 1) and is kept in fp32 (the reference builds t with .float().type_as(x)).
 'rk4' is torchdiffeq's 3/8-rule variant.  rtol/atol (opt.tol) are ignored by fixed-grid solvers.
@@ -105,6 +107,11 @@ class FCODE(nn.Module):
         fc = self.func.func.fc
         if fc.in_features == 256:
             return autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, self, add1, add2)
+        if fc.in_features == ops.FCODE_WIDE_DIM and not self.adaptive and not (torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad for t in (x, add1, add2, fc.weight, fc.bias))):
+            # inference at 384 columns: the whole solve in one launch (csrc/fusion_wide.hip); with a gradient wanted the
+            # any-width route below, whose launches are differentiable
+            return ops.fcode_wide(x, self._prep.get(), self.act_name, self.method, self.dts, add1=add1, add2=add2)
         return self._forward_any_width(x, add1, add2)
 
     def solver_stats(self):

@@ -47,11 +47,12 @@ class MM(nn.Module):
         super().__init__()
         self.opt = opt = opt or get_options()
         self.drop = drop
-        if opt.mm_imgfe == "convnext_tiny":
-            raise NotImplementedError("MM with mm_imgfe='convnext_tiny' is not built: the fusion blocks need the 384-wide stage 2 and "
-                                      "matching voxel planes; the ConvNeXt trunk serves ImageFE and DBVanilla2D")
+        self._convnext = opt.mm_imgfe == "convnext_tiny"
+        if self._convnext:
+            _check_convnext_options(opt)
         self.image_fe = ImageFE(fe_type=opt.mm_imgfe, layers=opt.mm_imgfe_layers)
-        self.image_fe.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
+        if not self._convnext:
+            self.image_fe.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
         self.image_pool = GeM()
         planes = [int(x) for x in opt.mm_voxfe_planes.split('_')]
         layers = [int(x) for x in opt.mm_voxfe_layers.split('_')]
@@ -223,6 +224,8 @@ class MM(nn.Module):
         fused inference path launches it inside its first program's launch and empties the list; a caller that still finds it
         there (per-op path taken) runs it itself."""
         opt = self.opt
+        if self._convnext:
+            return self._forward_q_convnext(data_dict, image_maps, out_rows)
         # .train() under torch.no_grad() is a live reference configuration (`with torch.set_grad_enabled(args.train_modelq)`
         # around a model in train mode, train.py:307): batch-statistics BatchNorm with running-stat updates, no tape.
         # The train-mode kernels run; the autograd Functions record nothing when no input requires grad.
@@ -239,6 +242,30 @@ class MM(nn.Module):
         # forward only, the process-wide switches restored when it returns
         with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1):
             return self._forward_q(data_dict, train, image_maps, out_rows, rider)
+
+    def _forward_q_convnext(self, data_dict, image_maps, out_rows):
+        """mm_imgfe='convnext_tiny' (inference only): the trunk's three fp32 maps (96 / 192 / 384 channels) are pooled by
+        ops.pool_f32 -- the last one ONCE, for its mean (fusion level 3) and its GeM (the image descriptor) -- the vector path is
+        the per-op one (the fused vector programs are 256 columns wide; FCODE(384) is one launch per solve, csrc/fusion_wide.hip),
+        and stage 2 packs the last map into the 384-wide BasicBlock.  The image side runs in the mode-3 arithmetic whatever
+        Options.mfma_precision says (the ConvNeXt trunk's contract: fp32 range, so neither map exponents nor the fp16 range guard
+        have work on it); the voxel branch runs at Options.mfma_precision as in the ResNet model.  No host synchronisation:
+        capturable after one eager warm-up."""
+        what = "MM with mm_imgfe='convnext_tiny' (inference only)"
+        if self.training:
+            raise NotImplementedError(f"{what}: .train() is not built; call .eval()")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(f"{what}: gradients are not built (a parameter requires one); run under torch.no_grad()")
+        if 'query_frames' in data_dict or 'query_jitter' in data_dict:
+            raise NotImplementedError(f"{what}: `query_frames` (decoded uint8 frames) is not built; pass the fp32 `query_image`")
+        if data_dict['query_image'].dtype == torch.uint8:
+            raise NotImplementedError(f"{what}: uint8 `query_image` is not built; pass the normalised fp32 panorama")
+        if image_maps is not None or out_rows:
+            raise NotImplementedError(f"{what}: lock-step trunks and row-sliced outputs (pair.embed_pair, query sub-streams) are "
+                                      "not built")
+        # (the guard, when Options.fp16_range_guard is on, covers the voxel branch's fp16 maps as in the ResNet model)
+        with range_guard.guarded(self, self.opt, self.opt.mfma_precision, False):
+            return self._forward_q(data_dict, False, None, None, None)
 
     def _forward_q(self, data_dict, train, image_maps, out_rows, rider):
         opt = self.opt
@@ -311,16 +338,24 @@ class MM(nn.Module):
             else:
                 # the level means, l3's GeM (image descriptor) and l3's mean (fusion level 3) come out of the epilogues of
                 # the convs that write those maps (ops.PoolReq): no pass re-reads a stage output
-                if image_maps is not None:
+                fpool = None
+                if self._convnext:
+                    # fp32 maps, no conv epilogue to pool in: one pass over each map, the last one for both of its poolings
+                    maps = self.image_fe.fe.forward_maps(image)
+                    levels = [_Pooled(ops.pool_f32(m, None, want_mean=True, want_gem=False)[0]) for m in maps[:-1]]
+                    mean3, imagefeatvec = ops.pool_f32(maps[-1], self.image_pool.p, want_mean=True, want_gem=True, eps=self.image_pool.eps)
+                    levels.append(_Pooled(mean3))
+                elif image_maps is not None:
                     maps, lvl_means, fpool = image_maps
                 else:
                     lvl_means, fpool = [], self.final_pool_request()
                     maps = self.image_fe.forward_maps(image, prec=prec, level_means=lvl_means, final_pool=fpool)
                 imagefeatmap = maps[-1]
-                # (maps stored with an exponent: the pooled vectors are the stored maps', times 2^-e; the fused vector path
-                # restores the factor where its programs load them, the per-op path below with a small launch each)
-                mean3, imagefeatvec = fpool.mean, fpool.gem
-                levels = [_Pooled(m, mp.exp) for m, mp in zip(lvl_means, maps)] + [_Pooled(mean3, fpool.exp)]
+                if fpool is not None:
+                    # (maps stored with an exponent: the pooled vectors are the stored maps', times 2^-e; the fused vector path
+                    # restores the factor where its programs load them, the per-op path below with a small launch each)
+                    mean3, imagefeatvec = fpool.mean, fpool.gem
+                    levels = [_Pooled(m, mp.exp) for m, mp in zip(lvl_means, maps)] + [_Pooled(mean3, fpool.exp)]
             if vox_side is not None:
                 cur = torch.cuda.current_stream(image.device)
                 with torch.cuda.stream(vox_side):
@@ -341,13 +376,13 @@ class MM(nn.Module):
                         t.record_stream(cur)
                 self._publish_voxel_flag(vox_flag)
             # ---- inference: the whole vector path as two launches (vecprog.hip) around the stage-2 conv block
-            if not train and not torch.is_grad_enabled() and opt.fused_vector_path:
+            if not train and not torch.is_grad_enabled() and opt.fused_vector_path and not self._convnext:
                 try:
                     return self._vector_path_fused(data_dict, imagefeatmap, levels, imagefeatvec, voxmap, prec, out_rows or {}, rider,
                                                    gem3_exp=fpool.exp)
                 except VecProgramUnfit:
                     pass                      # an option set the program cannot express: the per-op path below
-            if not train:
+            if not train and fpool is not None:
                 imagefeatvec = fpool.true_gem()
             if opt.output_l2 is True:
                 imagefeatvec = autograd_ops.l2normalize(imagefeatvec)
@@ -369,7 +404,8 @@ class MM(nn.Module):
             stg2fusevec, stg2imagevec, _, stg2voxvec = self.stg2fuseblock(
                 imagefeatmap, None,
                 voxmap if voxmap is not None else (data_dict['stg2voxvec'].float(), data_dict['voxvec_fuse'].float()),
-                output[-1], type='vox', prec=prec, train_ctx=train_ctx, vox_train_ctx=vox_train_ctx)
+                output[-1], type='vox', prec=prec, train_ctx=train_ctx, vox_train_ctx=vox_train_ctx,
+                img_prec=3 if self._convnext else None)
             stg2fusevec = autograd_ops.linear(stg2fusevec, self.stg2fusefc, self._prep_fc)
             # ---- final output
             terms, weights = [], []
@@ -518,6 +554,8 @@ class MM(nn.Module):
 
     def forward(self, data_dict, mode):
         if mode == 'q':
+            if self._convnext:
+                return self.forward_q(data_dict)        # (no sub-stream split for this trunk)
             k = self.opt.query_substreams
             img = data_dict.get('query_image')
             if (k > 1 and not self.training and not torch.is_grad_enabled() and 'coords' not in data_dict and 'points' not in data_dict
@@ -572,6 +610,30 @@ class MM(nn.Module):
             for st in substreams:
                 t.record_stream(st)
         return {name: ops.join_rows([o[name] for o in outs]) for name in outs[0]}
+
+
+def _check_convnext_options(opt):
+    """mm_imgfe='convnext_tiny' is built for the one configuration in which the reference's own wiring is consistent: the last
+    fusion level is nn.Identity() for the image and the voxel vector (fuse_block_toshallow.py:25-30), so the trunk's last plane
+    (384), the last voxel plane and the fusion width must agree."""
+    def refuse(field, why):
+        raise NotImplementedError(f"MM with mm_imgfe='convnext_tiny': {field}={getattr(opt, field)!r} is not built: {why}; the "
+                                  "supported configuration is mm_imgfe_layers='a_b_c', mm_imgfe_planes='96_192_384', mm_imgfe_dim=384, "
+                                  "mm_stg2fuse_dim=384, mm_voxfe_planes='X_Y_384' (X, Y multiples of 64), mm_voxfe_dim=384")
+    if len(opt.mm_imgfe_layers.split('_')) != 3:
+        refuse("mm_imgfe_layers", "the ConvNeXt trunk takes exactly three block counts")
+    if opt.mm_imgfe_planes != "96_192_384":
+        refuse("mm_imgfe_planes", "the trunk's maps have 96, 192 and 384 channels")
+    if opt.mm_imgfe_dim != 384:
+        refuse("mm_imgfe_dim", "the trunk's last map has 384 channels")
+    if opt.mm_stg2fuse_dim != 384:
+        refuse("mm_stg2fuse_dim", "the last fusion level is an identity, so the fusion width is the last image plane, 384")
+    vox = opt.mm_voxfe_planes.split('_')
+    if len(vox) != 3 or not all(v.isdigit() for v in vox) or int(vox[2]) != 384 or any(int(v) % 64 or int(v) <= 0 for v in vox[:2]):
+        refuse("mm_voxfe_planes", "the last fusion level is an identity, so the last voxel plane is 384, and the two lower planes "
+                                  "are multiples of 64")
+    if opt.mm_voxfe_dim != 384:
+        refuse("mm_voxfe_dim", "the stage-2 voxel block runs on the last voxel plane, 384")
 
 
 class _Pooled:

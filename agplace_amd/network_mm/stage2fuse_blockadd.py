@@ -226,14 +226,17 @@ class Stage2FuseBlockAdd(nn.Module):
                               for m in self.projsfusevox]
         self._ws = ops.Workspace()
 
-    def forward_imgvox(self, imgmap, bevmap, voxmap, fusevec, prec=3, train_ctx=None, vox_train_ctx=None):
+    def forward_imgvox(self, imgmap, bevmap, voxmap, fusevec, prec=3, train_ctx=None, vox_train_ctx=None, img_prec=None):
         # imgmap: ops.SplitMap or fp32 [b,c,h,w]; voxmap: (stg2voxvec [b,C], voxvec_fuse [b,D])
         # train_ctx = (MapSink, token tensor, stage index): train-mode path through train_fns.Stage2ImgFn
+        # img_prec: the image side's precision mode when it differs from the sparse side's (the ConvNeXt trunk: mode 3); None = prec
         opt = self.opt
+        img_prec = prec if img_prec is None else img_prec
         if opt.stg2_type != 'full':
             raise NotImplementedError
         if not isinstance(imgmap, ops.SplitMap):
-            imgmap = ops.pack_f32(imgmap, imgmap.shape[1], 1, prec)
+            n_, c_, h_, w_ = imgmap.shape
+            imgmap = ops.pack_f32(imgmap, c_, 1, img_prec, out=self._ws.map("in", n_, h_, w_, c_, 1, img_prec, imgmap.device))
         sparse_vox = isinstance(voxmap, sparse.SparseTensor)
         if not sparse_vox:
             voxoutvec, voxvec_fuse = voxmap
@@ -271,12 +274,12 @@ class Stage2FuseBlockAdd(nn.Module):
                                                   sink, stage if i == 0 else ("s2", i - 1), prec, want_fuse, ("s2", i))
                 mean, imgoutvec = res if want_fuse else (None, res)
             else:
-                m = self._ws.map(f"add{i}", imgmap.n, imgmap.h, imgmap.w, imgmap.c, 1, prec, imgmap.hi.device)
+                m = self._ws.map(f"add{i}", imgmap.n, imgmap.h, imgmap.w, imgmap.c, 1, img_prec, imgmap.hi.device)
                 # (a map with an exponent takes the vector times 2^-e; the per-op path spends a small launch on it, the fused
                 # vector path folds it into the projection: MM._vector_path_fused)
                 ops.bcast_add(imgmap, ops.scale_pow2(fusevec_img.detach().contiguous().float(), -imgmap.exp) if imgmap.exp else fusevec_img, m)
                 req = ops.PoolReq(self.poolimage.p, eps=self.poolimage.eps, want_mean=want_fuse, want_gem=True)
-                imgmap = self.ffnsimg[i].forward_map(m, prec, pool=req)
+                imgmap = self.ffnsimg[i].forward_map(m, img_prec, pool=req)
                 mean, imgoutvec = (req.true_mean() if want_fuse else None), req.true_gem()
             if want_fuse:
                 if opt.stg2_useproj is True:
@@ -287,8 +290,8 @@ class Stage2FuseBlockAdd(nn.Module):
                 fusevec = self.ffnsfuse[i](fusevec)
         return fusevec, imgoutvec, None, voxoutvec
 
-    def forward(self, imagemap, bevmap, voxmap, fusevec, type, prec=3, train_ctx=None, vox_train_ctx=None):
+    def forward(self, imagemap, bevmap, voxmap, fusevec, type, prec=3, train_ctx=None, vox_train_ctx=None, img_prec=None):
         if type == 'vox':
             return self.forward_imgvox(imagemap, bevmap, voxmap, fusevec, prec=prec, train_ctx=train_ctx,
-                                       vox_train_ctx=vox_train_ctx)
+                                       vox_train_ctx=vox_train_ctx, img_prec=img_prec)
         raise NotImplementedError   # 'bev': ffnsbev / poolbev are never built in the reference

@@ -1265,6 +1265,51 @@ def fcode(x, lw: LinearWeights, act, method, dts, add1=None, add2=None, want_tra
     return (y, traj) if want_traj else y
 
 
+FCODE_WIDE_DIM = 384       # the one width of agp_fcode_wide_fwd
+FCODE_WIDE_ROWS = 16       # batch rows per workgroup of that kernel
+
+
+def fcode_wide_planes(lw: LinearWeights):
+    """The planes of a [384, 384] Linear in the fragment order agp_fcode_wide_fwd reads (include/agplace_hip.h): for wave w
+    (48 output features), K-step ks and tile t the 64 lanes' 16-byte MFMA A-fragments are contiguous.  Built once per
+    LinearWeights, i.e. once per parameter version (_PreparedLinear), and never inside a stream capture: the permuting copies
+    would become nodes of the graph and the planes memory of its pool."""
+    if lw._frag is None:
+        d = FCODE_WIDE_DIM
+        if lw.n != d or lw.k != d:
+            raise NotImplementedError(f"fcode_wide is built for dim={d}, got a [{lw.n}, {lw.k}] Linear")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fcode_wide: the weight planes are prepared on the first call: run the forward once before "
+                               "capturing it (and again after a parameter update)")
+
+        def frag(t):        # [npad, 384] -> (w, t, row, ks, q, e) -> (w, ks, t, q, row, e)
+            return t[:d].view(8, 3, 16, d // 32, 4, 8).permute(0, 3, 1, 4, 2, 5).contiguous()
+        lw._frag = (frag(lw.w_hi), frag(lw.w_lo))
+    return lw._frag
+
+
+def fcode_wide(x, lw: LinearWeights, act, method, dts, add1=None, add2=None):
+    """y(1) of y' = act(y W^T + b), y(0) = x + add1 + add2 at 384 columns on the fixed grid `dts`: ONE launch
+    (agp_fcode_wide_fwd), no host synchronisation, capturable; no trajectory -- the inference kernel of FCODE(384)."""
+    _need_cuda(x, "fcode_wide")
+    x = x.contiguous().float()
+    b, d = x.shape
+    add1, add2 = _vec_operand(add1, x, "fcode_wide add1"), _vec_operand(add2, x, "fcode_wide add2")
+    if d != FCODE_WIDE_DIM:
+        raise NotImplementedError(f"fcode_wide is built for dim={FCODE_WIDE_DIM}, got {d}")
+    if method not in _lib.ODE:
+        raise NotImplementedError(method)
+    if act not in _lib.ACT:
+        raise NotImplementedError(act)
+    f_hi, f_lo = fcode_wide_planes(lw)
+    n = len(dts)
+    arr = (C.c_float * n)(*dts)
+    y = torch.empty_like(x)
+    check(_L().agp_fcode_wide_fwd(ptr(x), ptr(add1), ptr(add2), ptr(f_hi), ptr(f_lo), ptr(lw.bias), b, d, _lib.ACT[act],
+                                  _lib.ODE[method], arr, n, ptr(y), _lib.stream()), "agp_fcode_wide_fwd")
+    return y
+
+
 def fcode_bwd(traj, gy, lw: LinearWeights, act, method, dts):
     """(gx, gw, gb) of FCODE given the trajectory recorded by fcode(..., want_traj=True)."""
     gy = gy.contiguous().float()

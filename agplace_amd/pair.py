@@ -75,6 +75,9 @@ def embed_pair(modelq, modeldb, qdata, dbdata):
     if any(getattr(e, "fe_type", None) == "convnext_tiny" for e in getattr(modeldb, "dbimage_fes", ())):
         raise NotImplementedError("pair.embed_pair with a ConvNeXt database model (dbimage_fe='convnext_tiny') is not built; call "
                                   "modelq(qdata, 'q') and modeldb(dbdata, 'db') separately")
+    if getattr(modelq, "_convnext", False):
+        raise NotImplementedError("pair.embed_pair with a ConvNeXt query model (mm_imgfe='convnext_tiny') is not built; call "
+                                  "modelq(qdata, 'q') and modeldb(dbdata, 'db') separately")
     qdata, dbdata = _resized_tiles(modelq, modeldb, qdata, dbdata)
     if not can_pair(modelq, modeldb, qdata, dbdata):
         return modelq(qdata, mode='q'), modeldb(dbdata, mode='db')

@@ -490,6 +490,17 @@ int agp_fcode_fwd(const float* x, const float* add1, const float* add2, const vo
                   const void* w_lo, const float* bias, int b, int act, int method,
                   const float* dt, int nsteps, float* y, float* traj, void* stream);
 
+/* FCODE forward at d = 384 (the inference kernel of FCODE(384), csrc/fusion_wide.hip): y(1) as agp_fcode_fwd computes it -- the
+ * same methods, time grid, activations and split-bf16 x3 / fp32-state arithmetic, a fixed summation order -- in ONE launch, no
+ * host synchronisation, no trajectory.  One workgroup of 8 waves owns 16 batch rows for the whole solve (no workgroup waits for
+ * another); W's `hi` plane stays in registers, the `lo` plane is read from L2 once per f-evaluation.  wf_hi / wf_lo: the two
+ * split-bf16 planes of W [384][384] in the kernel's FRAGMENT order, 16 bytes per entry:
+ *   [wave 0..7][ks 0..11][tile 0..2][q 0..3][row 0..15][8] = W[48 wave + 16 tile + row][32 ks + 8 q .. + 7].
+ * d != 384: AGP_E_UNSUPPORTED.  AGP_E_BADARG: a null pointer, b <= 0, nsteps outside 1..64, an unknown act or method. */
+int agp_fcode_wide_fwd(const float* x, const float* add1, const float* add2, const void* wf_hi, const void* wf_lo,
+                       const float* bias, int b, int d, int act, int method, const float* dt, int nsteps, float* y,
+                       void* stream);
+
 /* FCODE backward (discretise-then-optimise, like autograd through odeint at ffns.py:84): given
  * gy = dL/dy(1) and the recorded trajectory, produce gx = dL/dx (also the gradient of add1/add2)
  * and OVERWRITE gw[256][256] = dL/dW, gb[256] = dL/db.  wt_hi/wt_lo are the split planes of W^T.
