@@ -126,6 +126,8 @@ SIGNATURES = {
     "agp_pool_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P]),
     "agp_pool_f32_fwd": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P]),
     "agp_gem_f32_bwd": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P]),
+    "agp_bcast_add_f32_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "agp_pool_f32_bwd": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "agp_linear_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "agp_fcode_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, _P, _P, _P]),
     "agp_fcode_traj_floats": (_L, [_I, _I, _I]),

@@ -16,7 +16,9 @@ Training is OPT-IN (`ConvNeXt.enable_training()`, Options.convnext_train): witho
 refused as before and the inference path is untouched.  With it, `forward_maps_train` runs the same kernels out of place (every
 block writes a new stream tensor), applies stochastic depth in .train(), and records ONE autograd node (`_TrunkFn`) whose saved
 state is the stream tensors plus the per-block stochastic-depth scales; the backward (csrc/convnext_bwd.hip) recomputes the
-normalised operand with agp_cnx_dwconv_ln_fwd and never stores the hidden map either.
+normalised operand with agp_cnx_dwconv_ln_fwd and never stores the hidden map either.  DBVanilla2D consumes the node's last map
+through the dense-fp32 GeM; MM wraps it in train_fns.CnxTrunkFn, which pools the three maps, lends the last stream tensor to the
+stage-2 block (ops.bcast_add_f32) and returns one fp32 gradient per map to this node (ops.pool_f32_bwd).
 
 Stochastic depth restates torchvision's StochasticDepth(p, "row") (torchvision is not a dependency): block k of the FULL
 18-block network has p_k = stochastic_depth_prob * k / 17 (the truncation happens after construction, so a kept block keeps its
@@ -351,7 +353,7 @@ class ConvNeXt(nn.Module):
 
     def forward_maps(self, x):
         """fp32 [n,3,H,W] on the GPU (any strides) -> the outputs of features[1], [3], [5] as fp32 tensors of logical shape
-        [n,C,h,w] in channels_last memory.  Inference only; allocates the three maps, launches on the current stream and never
+        [n,C,h,w] in channels_last memory.  The inference path: allocates the three maps, launches on the current stream and never
         synchronises (capturable after one eager call has prepared the weights).  With the training switch on, .train() or
         trainable trunk parameters under enabled gradients go through `forward_maps_train` instead."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters())

@@ -223,6 +223,111 @@ __global__ __launch_bounds__(256) void gem_f32_bwd_kernel(const float* __restric
     }
 }
 
+// ---- the bridge between the ConvNeXt trunk's fp32 stream tensors and the split-bf16 maps of the training graph.  Both are
+// streaming kernels over (pixel, 8-channel group) items, channel groups fastest (a wave reads and writes contiguous rows), every
+// access 16 bytes; items are counted in 32 bits (the launchers refuse larger maps) so that the index split is three FastDivs.
+
+// out (halo `pout`, interior only) = split_bf16(x + vec[n][c]): 2 x 16 B of x and of vec in, 16 B per plane out.
+__global__ __launch_bounds__(256) void bcast_add_f32_kernel(const float* __restrict__ x, const float* __restrict__ vec, int h, int w,
+                                                            int c, uint32_t total, FastDiv dg, FastDiv dw, FastDiv dh,
+                                                            bf16_t* __restrict__ ohi, bf16_t* __restrict__ olo, int pout) {
+    const int hop = h + 2 * pout, wop = w + 2 * pout;
+    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < total; t += gridDim.x * 256u) {
+        const uint32_t pix = fdiv(t, dg), g = t - pix * dg.d;
+        const uint32_t row = fdiv(pix, dw), px = pix - row * dw.d;
+        const uint32_t im = fdiv(row, dh), py = row - im * dh.d;
+        const f32x4* src = (const f32x4*)(x + (size_t)t * 8);
+        const f32x4* vv = (const f32x4*)(vec + (size_t)im * c + g * 8);
+        const f32x4 a0 = src[0], a1 = src[1], b0 = vv[0], b1 = vv[1];
+        float s[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { s[e] = a0[e] + b0[e]; s[4 + e] = a1[e] + b1[e]; }
+        u32x4 hh, ll;
+        split8(s, hh, ll);
+        const size_t off = (((size_t)im * hop + py + pout) * wop + px + pout) * c + g * 8;
+        *(u32x4*)(ohi + off) = hh;
+        *(u32x4*)(olo + off) = ll;
+    }
+}
+
+// out[n][h][w][c] (fp32, overwritten) = base? + gmean[n][c] / HW ? + ggem[n][c] * dGeM/dx ?   with the derivative of
+// gem_f32_bwd_kernel:  g * y^(1-p) * max(x, eps)^(p-1) * [x >= eps] / HW.  dL/dp is summed elementwise as pool_bwd_kernel
+// (train.hip) does -- sum over pixels of r * xc * ln(xc) / p, minus g * y * ln(y) / p once per (image, channel) -- per thread over
+// its grid-stride items, then over the block in wave order (common.hpp); gp_finish_kernel adds the block partials in block
+// order: no atomics, the same bits every run.
+__global__ __launch_bounds__(256) void pool_f32_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gmean,
+                                                           const float* __restrict__ ggem, const float* __restrict__ gem_y,
+                                                           const float* __restrict__ pptr, float eps, const bf16_t* __restrict__ bhi,
+                                                           const bf16_t* __restrict__ blo, int pb, int h, int w, int c, uint32_t total,
+                                                           FastDiv dg, FastDiv dw, FastDiv dh, float* __restrict__ out, float* gp) {
+    const float inv_hw = 1.f / (float)(h * w);
+    const float p = ggem ? pptr[0] : 1.f;
+    const int hbp = h + 2 * pb, wbp = w + 2 * pb;
+    float dp = 0.f;
+    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < total; t += gridDim.x * 256u) {
+        const uint32_t pix = fdiv(t, dg), g = t - pix * dg.d;
+        const uint32_t row = fdiv(pix, dw), px = pix - row * dw.d;
+        const uint32_t im = fdiv(row, dh), py = row - im * dh.d;
+        const size_t vi = (size_t)im * c + g * 8;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        if (bhi) map_load8(bhi, blo, (((size_t)im * hbp + py + pb) * wbp + px + pb) * c + g * 8, v);
+        if (gmean) {
+            const f32x4 m0 = *(const f32x4*)(gmean + vi), m1 = *(const f32x4*)(gmean + vi + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] += m0[e] * inv_hw; v[4 + e] += m1[e] * inv_hw; }
+        }
+        if (ggem) {
+            const f32x4 x0 = *(const f32x4*)(x + (size_t)t * 8), x1 = *(const f32x4*)(x + (size_t)t * 8 + 4);
+            const f32x4 y0 = *(const f32x4*)(gem_y + vi), y1 = *(const f32x4*)(gem_y + vi + 4);
+            const f32x4 g0 = *(const f32x4*)(ggem + vi), g1 = *(const f32x4*)(ggem + vi + 4);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float xe = e < 4 ? x0[e] : x1[e - 4], yy = e < 4 ? y0[e] : y1[e - 4], ge = e < 4 ? g0[e] : g1[e - 4];
+                const float l2y = __builtin_log2f(yy);
+                const float xc = fmaxf(xe, eps), l2x = __builtin_log2f(xc);
+                const float r = ge * inv_hw * __builtin_exp2f((1.f - p) * l2y + (p - 1.f) * l2x);
+                if (xe >= eps) v[e] += r;
+                if (gp) {                                   // (in units of log2 / p: the block total takes ln 2 / p)
+                    dp += r * xc * l2x;
+                    if (px == 0 && py == 0) dp -= ge * yy * l2y;
+                }
+            }
+        }
+        f32x4* o = (f32x4*)(out + (size_t)t * 8);
+        o[0] = f32x4{v[0], v[1], v[2], v[3]};
+        o[1] = f32x4{v[4], v[5], v[6], v[7]};
+    }
+    // this block's share of dL/dp, in block order (every thread of every block gets here: the branch is uniform)
+    if (gp) {
+        const float tot = agp_block_sum_ordered(dp) * (0.6931471805599453f / p);
+        if (threadIdx.x == 0) gp[1 + blockIdx.x] = tot;
+    }
+}
+
+// gp[0] += the block partials pool_f32_bwd_kernel left in gp[1 .. 1 + nblocks), in the order of agp_grid_sum_ordered's last
+// block.  A launch of its own, not that in-kernel hand-off: its release fence at agent scope makes every block wait until the
+// dirty lines of its L2 are written back, and this kernel's blocks have just stored their share of the map there (measured at
+// [16,14,84,384] on an MI355X: 78 us with the in-kernel sum, 25 us with this launch, 17 us without dL/dp; the same bits).
+__global__ __launch_bounds__(64) void gp_finish_kernel(float* gp, int nblocks) {
+    float t = 0.f;
+    for (int i = threadIdx.x; i < nblocks; i += 64) t += gp[1 + i];
+    t = wave_sum(t);
+    if (threadIdx.x == 0) gp[0] += t;
+}
+
+// items of a [n][h][w][c] tensor in 8-channel groups, or 0 when they do not fit the kernels' 32-bit counters
+inline uint32_t f32_bridge_items(int n, int h, int w, int c) {
+    const int64_t items = (int64_t)n * h * w * (c / 8);
+    return items < ((int64_t)1 << 31) && (int64_t)n * h < ((int64_t)1 << 31) ? (uint32_t)items : 0u;
+}
+// four items per thread, at most 8192 blocks (< AGP_GP_SLOTS: one dL/dp partial per block), as train.hip's element-wise passes
+inline int f32_bridge_grid(uint32_t items) {
+    const uint32_t g = (items + 1023u) / 1024u;
+    return (int)(g < 1u ? 1u : (g > 8192u ? 8192u : g));
+}
+
 }  // namespace agp_pool
 using namespace agp_pool;
 
@@ -275,5 +380,38 @@ extern "C" int agp_gem_f32_bwd(const float* x, int64_t sn, int64_t sc, int64_t s
     AGP_LAUNCH(gem_f32_bwd_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0,
                        (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, p, eps, y, gy, gx, gp);
     AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+extern "C" int agp_bcast_add_f32_fwd(const float* x, const float* vec, int n, int h, int w, int c, void* out_hi, void* out_lo,
+                                     int pout, void* stream) {
+    if (!x || !vec || !out_hi || !out_lo || n <= 0 || h <= 0 || w <= 0 || c <= 0 || pout < 0) return AGP_E_BADARG;
+    if (c % 64) return AGP_E_UNSUPPORTED;
+    const uint32_t items = f32_bridge_items(n, h, w, c);
+    if (!items) return AGP_E_UNSUPPORTED;
+    AGP_LAUNCH(bcast_add_f32_kernel, dim3(f32_bridge_grid(items)), dim3(256), 0, (hipStream_t)stream, x, vec, h, w, c, items,
+               make_fastdiv((uint32_t)(c / 8)), make_fastdiv((uint32_t)w), make_fastdiv((uint32_t)h), (bf16_t*)out_hi, (bf16_t*)out_lo,
+               pout);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+extern "C" int agp_pool_f32_bwd(const float* x, const float* gmean, const float* ggem, const float* gem_y, const float* p, float eps,
+                                const void* b_hi, const void* b_lo, int pb, int n, int h, int w, int c, float* out, float* gp,
+                                void* stream) {
+    if (!out || n <= 0 || h <= 0 || w <= 0 || c <= 0 || pb < 0) return AGP_E_BADARG;
+    if (!gmean && !ggem && !b_hi) return AGP_E_BADARG;
+    if ((ggem && (!x || !gem_y || !p)) || (gp && !ggem) || (!b_hi != !b_lo)) return AGP_E_BADARG;
+    if (c % 8) return AGP_E_UNSUPPORTED;
+    const uint32_t items = f32_bridge_items(n, h, w, c);
+    if (!items) return AGP_E_UNSUPPORTED;
+    AGP_LAUNCH(pool_f32_bwd_kernel, dim3(f32_bridge_grid(items)), dim3(256), 0, (hipStream_t)stream, x, gmean, ggem, gem_y, p, eps,
+               (const bf16_t*)b_hi, (const bf16_t*)b_lo, pb, h, w, c, items, make_fastdiv((uint32_t)(c / 8)),
+               make_fastdiv((uint32_t)w), make_fastdiv((uint32_t)h), out, gp);
+    AGP_CHECK_LAUNCH();
+    if (gp) {
+        AGP_LAUNCH(gp_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, gp, f32_bridge_grid(items));
+        AGP_CHECK_LAUNCH();
+    }
     return AGP_OK;
 }

@@ -28,6 +28,9 @@ Execution modes:
   * .eval() with gradients enabled and trainable parameters: the same training graph on FROZEN BatchNorm
     statistics (train_graph.bn_frozen: running statistics read, not updated, constants of the backward).
   * .eval() + freeze_backbone(): train the fusion path only, on frozen image features.
+With mm_imgfe='convnext_tiny' (the 384-wide configuration of _check_convnext_options) the first mode is the default and the other
+three are behind Options.convnext_train: the same training graph with train_fns.CnxTrunkFn in TrunkFn's place
+(_forward_q_convnext).
 """
 import torch
 import torch.nn as nn
@@ -53,6 +56,8 @@ class MM(nn.Module):
         self.image_fe = ImageFE(fe_type=opt.mm_imgfe, layers=opt.mm_imgfe_layers)
         if not self._convnext:
             self.image_fe.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
+        elif opt.convnext_train:            # the opt-in training path of the ConvNeXt trunk (agplace_amd/convnext.py)
+            self.image_fe.fe.enable_training()
         self.image_pool = GeM()
         planes = [int(x) for x in opt.mm_voxfe_planes.split('_')]
         layers = [int(x) for x in opt.mm_voxfe_layers.split('_')]
@@ -244,17 +249,23 @@ class MM(nn.Module):
             return self._forward_q(data_dict, train, image_maps, out_rows, rider)
 
     def _forward_q_convnext(self, data_dict, image_maps, out_rows):
-        """mm_imgfe='convnext_tiny' (inference only): the trunk's three fp32 maps (96 / 192 / 384 channels) are pooled by
+        """mm_imgfe='convnext_tiny': the trunk's three fp32 maps (96 / 192 / 384 channels) are pooled by
         ops.pool_f32 -- the last one ONCE, for its mean (fusion level 3) and its GeM (the image descriptor) -- the vector path is
         the per-op one (the fused vector programs are 256 columns wide; FCODE(384) is one launch per solve, csrc/fusion_wide.hip),
         and stage 2 packs the last map into the 384-wide BasicBlock.  The image side runs in the mode-3 arithmetic whatever
         Options.mfma_precision says (the ConvNeXt trunk's contract: fp32 range, so neither map exponents nor the fp16 range guard
         have work on it); the voxel branch runs at Options.mfma_precision as in the ResNet model.  No host synchronisation:
-        capturable after one eager warm-up."""
-        what = "MM with mm_imgfe='convnext_tiny' (inference only)"
-        if self.training:
+        capturable after one eager warm-up.
+        Inference only unless Options.convnext_train opted in.  Then `train` is derived as in forward_q and the training graph of
+        the ResNet model runs with train_fns.CnxTrunkFn in TrunkFn's place: the trunk trains through its own node
+        (ConvNeXt.forward_maps_train, stochastic depth in .train()), stage 2 reads the last fp32 map through ops.bcast_add_f32
+        and hands its map gradient back through ops.pool_f32_bwd.  Options.train_precision / train_dgrad_products act on the
+        stage-2 block only: the trunk is mode 3 whatever they say."""
+        enabled = self.image_fe.fe._train_enabled
+        what = "MM with mm_imgfe='convnext_tiny'" + ("" if enabled else " (inference only)")
+        if self.training and not enabled:
             raise NotImplementedError(f"{what}: .train() is not built; call .eval()")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        if not enabled and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError(f"{what}: gradients are not built (a parameter requires one); run under torch.no_grad()")
         if 'query_frames' in data_dict or 'query_jitter' in data_dict:
             raise NotImplementedError(f"{what}: `query_frames` (decoded uint8 frames) is not built; pass the fp32 `query_image`")
@@ -263,9 +274,17 @@ class MM(nn.Module):
         if image_maps is not None or out_rows:
             raise NotImplementedError(f"{what}: lock-step trunks and row-sliced outputs (pair.embed_pair, query sub-streams) are "
                                       "not built")
-        # (the guard, when Options.fp16_range_guard is on, covers the voxel branch's fp16 maps as in the ResNet model)
-        with range_guard.guarded(self, self.opt, self.opt.mfma_precision, False):
-            return self._forward_q(data_dict, False, None, None, None)
+        train = enabled and (self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
+                                               and any(p.requires_grad for p in self.parameters())))
+        if not train:
+            # (the guard, when Options.fp16_range_guard is on, covers the voxel branch's fp16 maps as in the ResNet model)
+            with range_guard.guarded(self, self.opt, self.opt.mfma_precision, False):
+                return self._forward_q(data_dict, False, None, None, None)
+        if torch.is_grad_enabled() and data_dict['query_image'].requires_grad:
+            raise NotImplementedError("ConvNeXt: the gradient of the input image is not built (the stem returns none)")
+        from .. import train_graph
+        with train_graph.training_mode(self.opt.train_precision == 16, self.opt.train_dgrad_products == 1):
+            return self._forward_q(data_dict, True, None, None, None)
 
     def _forward_q(self, data_dict, train, image_maps, out_rows, rider):
         opt = self.opt
@@ -330,8 +349,14 @@ class MM(nn.Module):
             if train:
                 # feature maps stay inside the HIP graph; autograd sees the pooled vectors (train_fns.py)
                 sink = train_fns.MapSink()
-                *means, imagefeatvec = train_fns.TrunkFn.apply(
-                    train_fns.anchor_of(self.image_fe.fe, self.image_pool.p), image, self.image_fe.fe, self.image_pool, sink, prec, True)
+                if self._convnext:
+                    # fp32 stream tensors in the sink; the bridge kernels of csrc/pool.hip on either side of stage 2
+                    fe = self.image_fe.fe
+                    *means, imagefeatvec = train_fns.CnxTrunkFn.apply(train_fns.anchor_of(fe.features, self.image_pool.p), image, fe,
+                                                                       self.image_pool, sink)
+                else:
+                    *means, imagefeatvec = train_fns.TrunkFn.apply(
+                        train_fns.anchor_of(self.image_fe.fe, self.image_pool.p), image, self.image_fe.fe, self.image_pool, sink, prec, True)
                 levels = [_Pooled(m) for m in means]
                 imagefeatmap = sink.maps[-1]
                 train_ctx = (sink, means[-1], len(means) - 1)

@@ -228,13 +228,14 @@ class Stage2FuseBlockAdd(nn.Module):
 
     def forward_imgvox(self, imgmap, bevmap, voxmap, fusevec, prec=3, train_ctx=None, vox_train_ctx=None, img_prec=None):
         # imgmap: ops.SplitMap or fp32 [b,c,h,w]; voxmap: (stg2voxvec [b,C], voxvec_fuse [b,D])
-        # train_ctx = (MapSink, token tensor, stage index): train-mode path through train_fns.Stage2ImgFn
+        # train_ctx = (MapSink, token tensor, stage index): train-mode path through train_fns.Stage2ImgFn (the sink's entry is a
+        # SplitMap, or the ConvNeXt trunk's fp32 stream tensor)
         # img_prec: the image side's precision mode when it differs from the sparse side's (the ConvNeXt trunk: mode 3); None = prec
         opt = self.opt
         img_prec = prec if img_prec is None else img_prec
         if opt.stg2_type != 'full':
             raise NotImplementedError
-        if not isinstance(imgmap, ops.SplitMap):
+        if train_ctx is None and not isinstance(imgmap, ops.SplitMap):      # (train mode reads the map from the sink)
             n_, c_, h_, w_ = imgmap.shape
             imgmap = ops.pack_f32(imgmap, c_, 1, img_prec, out=self._ws.map("in", n_, h_, w_, c_, 1, img_prec, imgmap.device))
         sparse_vox = isinstance(voxmap, sparse.SparseTensor)

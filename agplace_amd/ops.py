@@ -1116,6 +1116,54 @@ def bcast_add(x: SplitMap, vec, out: SplitMap):
     return out
 
 
+def _stream_f32(t, what):
+    """A ConvNeXt stream tensor: contiguous fp32 [n,h,w,c] on the GPU (of the trunk's exported [n,c,h,w] view: permute(0, 2, 3, 1))."""
+    _need_cuda(t, what)
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{what}: needs a contiguous, 16-byte aligned fp32 [n,h,w,c] stream tensor")
+    return t
+
+
+def _vec_f32(v, n, c, device, what):
+    """fp32 [n, c] operand of the stream kernels: contiguous and 16-byte aligned (a copy when it is not)."""
+    if v is None:
+        return None
+    if tuple(v.shape) != (n, c) or v.device != device:
+        raise RuntimeError(f"{what}: vector of shape {tuple(v.shape)} on {v.device} for a map [{n}, {c}, ...] on {device}")
+    v = v.detach().contiguous().float()
+    return v.clone() if v.data_ptr() % 16 else v
+
+
+def bcast_add_f32(x, vec, out: SplitMap):
+    """out (split-bf16 SplitMap, interior) = split_bf16(x + vec[n, :]) for an fp32 stream tensor x [n,h,w,c] (or its [n,c,h,w]
+    channels_last view): the training-side pack_f32 + bcast_add in one pass, without rounding x to a bf16 pair first."""
+    x = _stream_f32(x, "bcast_add_f32")
+    n, h, w, c = x.shape
+    if (out.n, out.h, out.w, out.c) != (n, h, w, c) or out.lo is None:
+        raise RuntimeError(f"bcast_add_f32: a split-bf16 map [{n},{h},{w},{c}] is needed, got [{out.n},{out.h},{out.w},{out.c}]"
+                           + ("" if out.lo is not None else " in one fp16 plane"))
+    vec = _vec_f32(vec, n, c, x.device, "bcast_add_f32")
+    check(_L().agp_bcast_add_f32_fwd(ptr(x), ptr(vec), n, h, w, c, ptr(out.hi), ptr(out.lo), out.pad, _lib.stream()),
+          "agp_bcast_add_f32_fwd")
+    out.exp = 0
+    return out
+
+
+def pool_f32_bwd(x, gmean=None, ggem=None, gem_y=None, p=None, eps=GEM_EPS, base: SplitMap = None, gp=None):
+    """Backward of pool_f32 on a stream tensor x [n,h,w,c] (or its channels_last view) into a NEW fp32 [n,h,w,c] gradient:
+    base (a split-bf16 SplitMap gradient, optional) + gmean / (h w) + ggem * dGeM/dx, one pass; gp (ops.new_gp): [0] += dL/dp."""
+    x = _stream_f32(x, "pool_f32_bwd")
+    n, h, w, c = x.shape
+    if base is not None and ((base.n, base.h, base.w, base.c) != (n, h, w, c) or base.lo is None):
+        raise RuntimeError("pool_f32_bwd: base must be a split-bf16 map of the stream's shape")
+    gmean, ggem, gem_y = (_vec_f32(v, n, c, x.device, "pool_f32_bwd") for v in (gmean, ggem, gem_y))
+    out = torch.empty_like(x)
+    check(_L().agp_pool_f32_bwd(ptr(x), ptr(gmean), ptr(ggem), ptr(gem_y), ptr(p), eps, ptr(base.hi) if base is not None else None,
+                                ptr(base.lo) if base is not None else None, base.pad if base is not None else 0, n, h, w, c, ptr(out),
+                                ptr(gp), _lib.stream()), "agp_pool_f32_bwd")
+    return out
+
+
 # ------------------------------------------------------------------------- pooling
 def pool_map(x: SplitMap, p=None, want_mean=True, want_gem=True, eps=GEM_EPS, gem_out=None, raw=False):
     """(mean [n,c] or None, gem [n,c] or None) of a SplitMap in one pass.  A map with an exponent (x.exp != 0) is pooled with

@@ -119,7 +119,7 @@ class Options:
     # 3 (default) | 1 = opt-in: the data gradients of the 3x3 convs as ONE bf16 product of the hi planes (train_graph.DGRAD_HI_ONLY),
     # usually together with train_precision = 16; measured error: tests/test_gpu_train.py, timing: bench.py train.fast_mode
     train_dgrad_products: int = 3
-    # Opt-in training of the ConvNeXt-tiny trunk (dbimage_fe = "convnext_tiny"): DBVanilla2D then calls
+    # Opt-in training of the ConvNeXt-tiny trunk (dbimage_fe / mm_imgfe = "convnext_tiny"): DBVanilla2D and MM then call
     # ConvNeXt.enable_training() on its trunks, so .train() (torchvision's stochastic depth, p_k = 0.1 k / 17) and gradients into
     # the trunk run on the kernels of csrc/convnext_bwd.hip (mode-3 products, fixed-order sums: repeatable bit for bit).  False
     # (default): the trunk is inference only and refuses both, as before.  A reference namespace does not carry this field:

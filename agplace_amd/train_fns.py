@@ -8,6 +8,7 @@ of the small [b,256] vectors:
 
     TrunkFn      image -> (mean(l1), mean(l2), mean(l3), GeM(l3))      (ImageFE + GeM + level pools)
     Stage2ImgFn  (l3, Linear(fusevec)) -> (mean(o), GeM(o)),  o = BasicBlock(l3 + vec[:, :, None, None])
+    CnxTrunkFn   TrunkFn's role for the ConvNeXt-tiny trunk, whose maps are fp32 stream tensors (MM with Options.convnext_train)
 
 Stage2ImgFn consumes the l3 MAP of TrunkFn.  Its gradient w.r.t. that map is handed over through a
 `MapSink` side channel; autograd's topological order guarantees Stage2ImgFn.backward runs before
@@ -100,19 +101,77 @@ class TrunkFn(torch.autograd.Function):
         return (None,) * 8
 
 
+class CnxTrunkFn(torch.autograd.Function):
+    """TrunkFn's role for the ConvNeXt-tiny trunk (agplace_amd/convnext.py): image -> (mean(map 0), mean(map 1), mean(map 2),
+    GeM(map 2)).  The trunk's maps are plain fp32 [n,h,w,C] stream tensors and its training forward is an autograd node of its
+    own (convnext._TrunkFn, recorded here under enable_grad and run from this node's backward, so the trunk's parameter gradients
+    accumulate through autograd as in DBVanilla2D's ConvNeXt training).  The sink carries the STREAM tensors; Stage2ImgFn adds
+    its vector to the last one with ops.bcast_add_f32 and returns its SplitMap gradient through `sink.extra`, which
+    ops.pool_f32_bwd folds into the fp32 gradient handed to the trunk -- one pass over the last map in each direction."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, trunk, gem, sink):
+        ctx.set_materialize_grads(False)
+        want = ctx.needs_input_grad[0]
+        with torch.set_grad_enabled(bool(want)):
+            maps = trunk.forward_maps_train(x)          # logical [n,C,h,w] views of the stream tensors
+        streams = [m.detach().permute(0, 2, 3, 1) for m in maps]
+        p = gem.p.detach().float()
+        means = [ops.pool_f32(m.detach(), None, want_mean=True, want_gem=False)[0] for m in maps[:-1]]
+        mean_last, gemvec = ops.pool_f32(maps[-1].detach(), p, want_mean=True, want_gem=True, eps=gem.eps)
+        means.append(mean_last)
+        sink.maps = streams
+        if want:
+            train_graph.expect_grads([gem.p])
+        ctx.gem, ctx.sink, ctx.p, ctx.streams = gem, sink, p, streams
+        ctx.maps = maps if want else None
+        ctx.save_for_backward(gemvec)
+        return (*means, gemvec)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        gem, sink, streams = ctx.gem, ctx.sink, ctx.streams
+        (gemvec,) = ctx.saved_tensors
+        S = len(streams)
+        ggem = _c(gs[-1])
+        gp = ops.new_gp(gemvec.device) if (ggem is not None and gem.p.requires_grad) else None
+        outs, grads = [], []
+        for i, xs in enumerate(streams):
+            gm, gg, base = _c(gs[i]), ggem if i == S - 1 else None, sink.extra.pop(i, None)
+            if (gm is None and gg is None and base is None) or not ctx.maps[i].requires_grad:
+                continue
+            g = ops.pool_f32_bwd(xs, gmean=gm, ggem=gg, gem_y=gemvec if gg is not None else None,
+                                 p=ctx.p if gg is not None else None, eps=gem.eps, base=base, gp=gp if gg is not None else None)
+            outs.append(ctx.maps[i])
+            grads.append(g.permute(0, 3, 1, 2))
+        if gp is not None and not any(m is ctx.maps[-1] for m in outs):
+            # a frozen trunk under a trainable exponent: dL/dp alone
+            ops.pool_f32_bwd(streams[-1], ggem=ggem, gem_y=gemvec, p=ctx.p, eps=gem.eps, gp=gp)
+        if outs:
+            torch.autograd.backward(outs, grads)
+        if gp is not None:
+            train_graph._acc_grad(gem.p, gp[:1])
+        train_graph.notify_grads_ready([gem.p])
+        return (None,) * 5
+
+
 class Stage2ImgFn(torch.autograd.Function):
     """One image-side layer of Stage2FuseBlockAdd (reference stage2fuse_blockadd.py:212-216): map `stage` of the sink
     (a trunk stage index, or ("s2", i-1): the previous layer's output) + vec broadcast -> BasicBlock -> (mean, GeM).
     The output map is left in the sink under `out_key`; `token` is any tensor produced by the node that owns the input
-    map (it orders that node's backward after this one's)."""
+    map (it orders that node's backward after this one's).  A sink entry that is an fp32 [n,h,w,C] stream tensor (CnxTrunkFn)
+    is added and split in one pass (ops.bcast_add_f32); the gradient left in `sink.extra` is a SplitMap either way."""
 
     @staticmethod
     def forward(ctx, token, vec, block, gem, sink, stage, prec, want_mean, out_key=None):
         ctx.set_materialize_grads(False)
         l3 = sink.get(stage)
-        dev = l3.hi.device
-        y0 = block._ws.map("t.add", l3.n, l3.h, l3.w, l3.c, 1, prec, dev)
-        ops.bcast_add(l3, vec.contiguous().float(), y0)
+        if torch.is_tensor(l3):
+            n_, h_, w_, c_ = l3.shape
+            y0 = ops.bcast_add_f32(l3, vec, block._ws.map("t.add", n_, h_, w_, c_, 1, prec, l3.device))
+        else:
+            y0 = block._ws.map("t.add", l3.n, l3.h, l3.w, l3.c, 1, prec, l3.hi.device)
+            ops.bcast_add(l3, vec.contiguous().float(), y0)
         o = block.forward_map_train(y0, prec=prec)
         if out_key is not None:
             sink.layers[out_key] = o

@@ -467,6 +467,28 @@ int agp_gem_f32_bwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t 
                     int c, int h, int w, const float* p, float eps, const float* y,
                     const float* gy, float* gx, float* gp, void* stream);
 
+/* The bridge between the ConvNeXt trunk's fp32 stream tensors and the split-bf16 maps of the training graph (train_fns.py:
+ * CnxTrunkFn, Stage2ImgFn), one pass over the map each.
+ *
+ * agp_bcast_add_f32_fwd: x contiguous fp32 [n][h][w][c], vec fp32 [n][c] -> the INTERIOR of a halo-`pout` split-bf16 map
+ * (out_hi, out_lo; both required) = split_bf16(x + vec[n][c]): one fp32 add, then hi = rn(s), lo = rn(s - hi).  The halo is not
+ * touched (agp_bcast_add_fwd's rule).  x is NOT rounded to a bf16 pair before the add, so the result is not bit-equal to
+ * agp_pack_f32_to_nhwc + agp_bcast_add_fwd (which inference keeps).  c % 64 == 0 (else AGP_E_UNSUPPORTED, as is a map of 2^31 or
+ * more 8-channel groups); a null pointer or a size <= 0: AGP_E_BADARG.  x, vec 16-byte aligned. */
+int agp_bcast_add_f32_fwd(const float* x, const float* vec, int n, int h, int w, int c, void* out_hi, void* out_lo, int pout,
+                          void* stream);
+/* agp_pool_f32_bwd, the fp32 twin of agp_pool_bwd: out[n][h][w][c] (contiguous fp32, OVERWRITTEN) =
+ *     base ? + gmean[n][c] / (h * w) ? + ggem[n][c] * dGeM/dx ?
+ * x: the pooled tensor, contiguous fp32 [n][h][w][c] (read only with ggem).  base (b_hi, b_lo; both or neither): a split-bf16
+ * map of halo `pb`, read as hi + lo.  Every term is optional (NULL); all three NULL is AGP_E_BADARG, as are ggem without x, gem_y
+ * or p, gp without ggem, a null `out` and sizes <= 0.  The GeM derivative is agp_gem_f32_bwd's: g * y^(1-p) * max(x, eps)^(p-1)
+ * / (h * w) where x >= eps and 0 elsewhere, gem_y = the forward's output [n][c].  gp (optional): agp_gem_f32_bwd's contract --
+ * AGP_GP_FLOATS floats, [0] += dL/dp, a fixed-order sum over the grid, left ready for the next call (the block partials are
+ * added by a second, one-workgroup launch on the same stream).  No atomics: two calls give the same bits.  c % 8 == 0 (96, 192, 384 ...; else AGP_E_UNSUPPORTED).  All fp32 pointers 16-byte
+ * aligned. */
+int agp_pool_f32_bwd(const float* x, const float* gmean, const float* ggem, const float* gem_y, const float* p, float eps,
+                     const void* b_hi, const void* b_lo, int pb, int n, int h, int w, int c, float* out, float* gp, void* stream);
+
 /* ------------------------------------------------- fusion MLPs and Neural ODE */
 
 /* y = act(x W^T + b) for a [b,k] fp32 matrix, W [n][k] as split planes; n % 256 == 0,
