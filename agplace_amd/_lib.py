@@ -219,6 +219,9 @@ SIGNATURES = {
     "agp_cnx_dwconv_ln_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _L, _P]),
     "agp_cnx_downsample_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "agp_cnx_stem_bwd": (_I, [_P, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "agp_normalize_u8_cams": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
+    "agp_cnx_stem_u8_fwd": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _P, _F, _P, _P]),
+    "agp_cnx_stem_u8_bwd": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _L, _P]),
 }
 
 _lib = None

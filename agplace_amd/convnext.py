@@ -20,11 +20,19 @@ normalised operand with agp_cnx_dwconv_ln_fwd and never stores the hidden map ei
 through the dense-fp32 GeM; MM wraps it in train_fns.CnxTrunkFn, which pools the three maps, lends the last stream tensor to the
 stage-2 block (ops.bcast_add_f32) and returns one fp32 gradient per map to this node (ops.pool_f32_bwd).
 
+uint8 inputs are OPT-IN too (`ConvNeXt.enable_u8_inputs()`, Options.convnext_u8): the forwards then also take uint8 camera tiles
+[n,ncam,h,w,3] or decoded frames (ops.RawFrames: cropped, resized and jittered to such tiles first).  The image they stand for is the
+panorama [n,3,h,ncam*w] with v = (u8 / 255 - mean[c]) / std[c] (`set_image_norm`); the stem kernels read the bytes through a second
+loader of the same kernel body, so the maps and gradients are, bit for bit, those of the fp32 route on
+ops.normalize_cameras_u8(tiles, mean, std), and the training node saves the uint8 tiles instead of an fp32 image.
+
 Stochastic depth restates torchvision's StochasticDepth(p, "row") (torchvision is not a dependency): block k of the FULL
 18-block network has p_k = stochastic_depth_prob * k / 17 (the truncation happens after construction, so a kept block keeps its
 k); in .train() each image draws scale = bernoulli(1 - p_k) / (1 - p_k) and out = x + scale[n] * layer_scale * branch(x);
 p_k == 0 and .eval() apply no scale.
 """
+import ctypes as C
+
 import torch
 import torch.nn as nn
 
@@ -233,6 +241,39 @@ def stem_bwd(x, gout, p, grads, bws):
                                        *[ptr(g) for g in grads], ptr(bws), bws.numel(), _lib.stream()), "agp_cnx_stem_bwd")
 
 
+def _norm3(v):
+    return (C.c_float * 3)(*v)
+
+
+def _tiles_ok(tiles, what):
+    if not (torch.is_tensor(tiles) and tiles.is_cuda and tiles.dtype == torch.uint8 and tiles.dim() == 5 and tiles.shape[-1] == 3
+            and tiles.is_contiguous() and 0 not in tiles.shape):
+        raise ValueError(f"ConvNeXt.{what}: tiles must be a contiguous uint8 [n,ncam,h,w,3] tensor on the GPU")
+
+
+def stem_u8_fwd(tiles, mean, std, p):
+    """stem_fwd on the panorama [n,3,h,ncam*w] of uint8 tiles [n,ncam,h,w,3] (ops.normalize_cameras_u8), which is never written:
+    the same bits."""
+    _tiles_ok(tiles, "stem_u8_fwd")
+    n, ncam, h, w, _ = tiles.shape
+    if h < 4 or ncam * w < 4:
+        raise ValueError(f"ConvNeXt.stem_u8_fwd: a {h}x{ncam * w} panorama is smaller than the 4x4 stem")
+    out = torch.empty((n, (h - 4) // 4 + 1, (ncam * w - 4) // 4 + 1, DIMS[0]), dtype=torch.float32, device=tiles.device)
+    check(_lib.load().agp_cnx_stem_u8_fwd(ptr(tiles), n, ncam, h, w, _norm3(mean), _norm3(std), ptr(p["w"]), ptr(p["bias"]), ptr(p["g"]),
+                                          ptr(p["b"]), LN_EPS, ptr(out), _lib.stream()), "agp_cnx_stem_u8_fwd")
+    return out
+
+
+def stem_u8_bwd(tiles, mean, std, gout, p, grads, bws):
+    """stem_bwd on the panorama of uint8 tiles: the same workspace, partial order and bits."""
+    _tiles_ok(tiles, "stem_u8_bwd")
+    _stream_ok(gout, DIMS[0])
+    n, ncam, h, w, _ = tiles.shape
+    check(_lib.load().agp_cnx_stem_u8_bwd(ptr(tiles), n, ncam, h, w, _norm3(mean), _norm3(std), ptr(p["w"]), ptr(p["bias"]), ptr(p["g"]),
+                                          LN_EPS, ptr(gout), *[ptr(g) for g in grads], ptr(bws), bws.numel(), _lib.stream()),
+          "agp_cnx_stem_u8_bwd")
+
+
 def downsample_fwd(x, p):
     """LayerNorm + 2x2 / stride-2 conv of the stream x -> a new stream [n, h//2, w//2, 2C]."""
     _stream_ok(x, p["c"])
@@ -292,6 +333,9 @@ class ConvNeXt(nn.Module):
         self._prep, self._prep_key = None, None
         self._prep_bwd, self._prep_bwd_key = None, None
         self._train_enabled = False
+        self._u8_enabled = False
+        # ToTensor + Normalize of uint8 inputs (tiles, frames); the owning model sets them from its Options (set_image_norm)
+        self.image_mean, self.image_std = ops.IMAGENET_MEAN, ops.IMAGENET_STD
         self.last_row_scales = None
         self._ws = ops.Workspace()
 
@@ -301,6 +345,46 @@ class ConvNeXt(nn.Module):
         refused and nothing changes for inference."""
         self._train_enabled = bool(flag)
         return self
+
+    # ------------------------------------------------------------------ uint8 inputs
+    def enable_u8_inputs(self, flag=True):
+        """Opt in to (or out of) uint8 inputs (Options.convnext_u8): `forward_maps` / `forward_maps_train` then also take uint8
+        camera tiles [n,ncam,h,w,3] or decoded frames (ops.RawFrames), which the stem reads with ToTensor + Normalize
+        (set_image_norm) on the fly.  Off by default; while off only the fp32 image is accepted, as before."""
+        self._u8_enabled = bool(flag)
+        return self
+
+    def set_image_norm(self, mean, std):
+        """Normalize(mean, std) of this trunk's uint8 inputs (Options.image_mean / image_std)."""
+        self.image_mean, self.image_std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        return self
+
+    def _input(self, x, what):
+        """The stem's input: an fp32 [n,3,H,W] image as it is; with uint8 inputs enabled, uint8 tiles [n,ncam,h,w,3] made
+        contiguous, and an ops.RawFrames cropped and resized (ops.resize_cameras_u8) and jittered (ops.jitter_cameras_u8) to such
+        tiles.  Anything else: ValueError."""
+        if self._u8_enabled:
+            if isinstance(x, ops.RawFrames):
+                tiles = ops.resize_cameras_u8(x.frames, (x.h, x.w), crop=x.crop)
+                return tiles if x.jitter is None else ops.jitter_cameras_u8(tiles, x.jitter)
+            if torch.is_tensor(x) and x.dtype == torch.uint8:
+                if not (x.is_cuda and x.dim() == 5 and x.shape[-1] == 3 and 0 not in x.shape):
+                    raise ValueError(f"ConvNeXt.{what}: uint8 input must be [n,ncam,h,w,3] camera tiles on the GPU")
+                return x.contiguous()
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
+            raise ValueError(f"ConvNeXt.{what}: x must be an fp32 [n,3,H,W] tensor on the GPU")
+        return x
+
+    @staticmethod
+    def _geometry(x):
+        """(n, H, W) of a stem input: the fp32 image's, or the panorama's (h, ncam * w) of uint8 tiles."""
+        if x.dtype == torch.uint8:
+            n, ncam, h, w, _ = x.shape
+            return n, h, ncam * w
+        return x.shape[0], x.shape[2], x.shape[3]
+
+    def _stem(self, x, p):
+        return stem_u8_fwd(x, self.image_mean, self.image_std, p) if x.dtype == torch.uint8 else stem_fwd(x, p)
 
     def sd_probs(self):
         """Per stage, the stochastic-depth probability p_k of each kept block: stochastic_depth_prob * k / 17 with k the block's
@@ -355,26 +439,27 @@ class ConvNeXt(nn.Module):
         """fp32 [n,3,H,W] on the GPU (any strides) -> the outputs of features[1], [3], [5] as fp32 tensors of logical shape
         [n,C,h,w] in channels_last memory.  The inference path: allocates the three maps, launches on the current stream and never
         synchronises (capturable after one eager call has prepared the weights).  With the training switch on, .train() or
-        trainable trunk parameters under enabled gradients go through `forward_maps_train` instead."""
+        trainable trunk parameters under enabled gradients go through `forward_maps_train` instead.  With uint8 inputs enabled
+        (enable_u8_inputs) x may also be uint8 tiles [n,ncam,h,w,3] or an ops.RawFrames: H, W are then the panorama's (h, ncam*w);
+        frames need their resize tables on the device before a capture (one eager call, or ops.prepare_resize)."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters())
         if self._train_enabled and (self.training or wants_grad):
             return self.forward_maps_train(x)
         if self.training:
             raise NotImplementedError(f"ConvNeXt: .train() is not enabled (inference only; {TRAIN_SWITCH}); call .eval()")
-        if torch.is_grad_enabled() and (x.requires_grad or wants_grad):
+        if torch.is_grad_enabled() and (getattr(x, "requires_grad", False) or wants_grad):
             raise NotImplementedError("ConvNeXt: gradients into the trunk are not enabled (inference only): run under "
                                       "torch.no_grad() or freeze the trunk (requires_grad_(False) / freeze_backbone()), or "
                                       + TRAIN_SWITCH)
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
-            raise ValueError("ConvNeXt.forward_maps: x must be an fp32 [n,3,H,W] tensor on the GPU")
-        n, _, H, W = x.shape
+        x = self._input(x, "forward_maps")
+        n, H, W = self._geometry(x)
         sizes = self.map_sizes(H, W)
         prep = self._prepared()
         ws = self._ws.tensor("cnx_ws", (max(workspace_bytes(n, h, w, DIMS[s]) for s, (h, w) in enumerate(sizes)),), torch.uint8,
                              x.device)
         maps, cur = [], None
         for s in range(3):
-            cur = stem_fwd(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)])
+            cur = self._stem(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)])
             for p in prep[("blocks", s)]:
                 dwconv_ln_fwd(cur, p, ws)
                 mlp_fwd(ws, p, cur, cur)
@@ -388,11 +473,11 @@ class ConvNeXt(nn.Module):
         row_scales: None = in .train() draw, per block with p_k > 0 and per image, scale = bernoulli(1 - p_k) / (1 - p_k) on the
         device from torch's current CUDA generator; in .eval() no scale.  Or a list with one entry per block (stage by stage):
         an fp32 [n] tensor used in place of the draw, or None for no scale.  Under torch.no_grad(), or with no trainable trunk
-        parameter, nothing is saved.  An input that requires a gradient is refused: the stem returns no image gradient."""
+        parameter, nothing is saved.  An input that requires a gradient is refused: the stem returns no image gradient.
+        x: as in `forward_maps`; from uint8 tiles or frames the node saves the uint8 tiles, not an fp32 image."""
         if not self._train_enabled:
             raise NotImplementedError(f"ConvNeXt: training (.train(), gradients) is not enabled; {TRAIN_SWITCH}")
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3):
-            raise ValueError("ConvNeXt.forward_maps_train: x must be an fp32 [n,3,H,W] tensor on the GPU")
+        x = self._input(x, "forward_maps_train")
         if torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError("ConvNeXt: the gradient of the input image is not built (the stem returns none)")
         n = x.shape[0]
@@ -419,13 +504,13 @@ class ConvNeXt(nn.Module):
 
     def _run_train(self, x, scales, keep):
         """keep: every block writes a new stream tensor and the block inputs are returned (the saved state); else in place."""
-        n, _, H, W = x.shape
+        n, H, W = self._geometry(x)
         sizes = self.map_sizes(H, W)
         prep = self._prepared()
         ws = self._ws.tensor("cnx_ws", (self._ws_bytes(n, sizes, workspace_bytes),), torch.uint8, x.device)
         maps, saved, cur, k = [], [], None, 0
         for s in range(3):
-            cur = stem_fwd(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)])
+            cur = self._stem(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)])
             inputs = []
             for p in prep[("blocks", s)]:
                 dwconv_ln_fwd(cur, p, ws)
@@ -440,7 +525,7 @@ class ConvNeXt(nn.Module):
     def _run_backward(self, x, scales, saved, gmaps):
         """Gradients of every parameter of `features`, in parameters() order, as fp32 tensors in parameter layout."""
         inputs, maps = saved
-        n, _, H, W = x.shape
+        n, H, W = self._geometry(x)
         sizes = self.map_sizes(H, W)
         prep, pb = self._prepared(), self._prepared_bwd()
         dev = x.device
@@ -472,5 +557,8 @@ class ConvNeXt(nn.Module):
                                    bws)
             else:
                 conv, ln = self.features[0]
-                stem_bwd(x, g, prep["stem"], G(conv.weight, conv.bias, ln.weight, ln.bias), bws)
+                if x.dtype == torch.uint8:      # the saved uint8 tiles, normalised on the fly as in the forward
+                    stem_u8_bwd(x, self.image_mean, self.image_std, g, prep["stem"], G(conv.weight, conv.bias, ln.weight, ln.bias), bws)
+                else:
+                    stem_bwd(x, g, prep["stem"], G(conv.weight, conv.bias, ln.weight, ln.bias), bws)
         return [grads[id(p)] for p in params]

@@ -20,8 +20,9 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------------ stem
 // Conv2d(3, 96, k=4, s=4, bias) + LayerNorm over the 96 channels.  32 output pixels per block; a thread owns 3 channels
 // (cl, cl + 32, cl + 64) of 4 pixels, the 32 lanes of a half wave hold one pixel's 96 channels.  wt: [48][96], 48 = (ci, ky, kx).
-__global__ __launch_bounds__(256) void cnx_stem_kernel(const float* __restrict__ x, long long sn, long long sc, long long sh,
-                                                       long long sw, int ho, int wo, long long P, const float* __restrict__ wt,
+// LOAD: the image source (convnext_common.hpp: CnxLoadF32 strided fp32, CnxLoadU8 uint8 camera tiles normalised on the fly).
+template <class LOAD>
+__global__ __launch_bounds__(256) void cnx_stem_kernel(const LOAD ld, int ho, int wo, long long P, const float* __restrict__ wt,
                                                        const float* __restrict__ bias, const float* __restrict__ g,
                                                        const float* __restrict__ b, float eps, float* __restrict__ out) {
     __shared__ float xin[32][48];
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(256) void cnx_stem_kernel(const float* __restrict__
             const int ci = idx >> 4, ky = (idx >> 2) & 3, kx = idx & 3;
             const long long img = p / ((long long)ho * wo);
             const int rem = (int)(p - img * ho * wo), oy = rem / wo, ox = rem - oy * wo;
-            v = x[img * sn + ci * sc + (long long)(4 * oy + ky) * sh + (long long)(4 * ox + kx) * sw];
+            v = ld(img, ci, 4 * oy + ky, 4 * ox + kx);
         }
         xin[px][idx] = v;
     }
@@ -76,6 +77,20 @@ __global__ __launch_bounds__(256) void cnx_stem_kernel(const float* __restrict__
                 out[p * 96 + c] = fmaf(d[k] * rstd, g[c], b[c]);
             }
         }
+    }
+}
+
+// uint8 camera tiles -> the fp32 panorama [n][3][h][W = ncam * w] they stand for (contiguous NCHW): the image the uint8 stems
+// read, element for element the same expression (CnxLoadU8).  Streaming: one element per thread and step, coalesced stores.
+__global__ void cnx_normalize_u8_kernel(const CnxLoadU8 ld, int W, long long total, float* __restrict__ out) {
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+        long long r = e;
+        const int X = (int)(r % W);
+        r /= W;
+        const int y = (int)(r % ld.h);
+        r /= ld.h;
+        const int ci = (int)(r % 3);
+        out[e] = ld(r / 3, ci, y, X);
     }
 }
 
@@ -383,8 +398,38 @@ int agp_cnx_stem_fwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t
     const int ho = (h - 4) / 4 + 1, wo = (w - 4) / 4 + 1;
     if (!cnx_map_ok(n, ho, wo)) return AGP_E_BADARG;
     const long long P = (long long)n * ho * wo;
-    AGP_LAUNCH(cnx_stem_kernel, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x, (long long)sn, (long long)sc,
-               (long long)sh, (long long)sw, ho, wo, P, wt, bias, ln_w, ln_b, eps, out);
+    const CnxLoadF32 ld = {x, (long long)sn, (long long)sc, (long long)sh, (long long)sw};
+    AGP_LAUNCH(cnx_stem_kernel<CnxLoadF32>, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, (hipStream_t)stream, ld, ho, wo, P, wt, bias,
+               ln_w, ln_b, eps, out);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_stem_u8_fwd(const uint8_t* tiles, int n, int ncam, int h, int w, const float* mean3, const float* std3, const float* wt,
+                        const float* bias, const float* ln_w, const float* ln_b, float eps, float* out, void* stream) {
+    if (!tiles || !mean3 || !std3 || !wt || !bias || !ln_w || !ln_b || !out || n <= 0 || ncam <= 0 || h < 4 || w <= 0) return AGP_E_BADARG;
+    const long long W = (long long)ncam * w;
+    if (W < 4 || W >= (1ll << 31)) return AGP_E_BADARG;
+    const int ho = (h - 4) / 4 + 1, wo = (int)((W - 4) / 4 + 1);
+    if (!cnx_map_ok(n, ho, wo)) return AGP_E_BADARG;
+    const long long P = (long long)n * ho * wo;
+    const CnxLoadU8 ld = {tiles, ncam, h, w, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]};
+    AGP_LAUNCH(cnx_stem_kernel<CnxLoadU8>, dim3((unsigned)((P + 31) / 32)), dim3(256), 0, (hipStream_t)stream, ld, ho, wo, P, wt, bias,
+               ln_w, ln_b, eps, out);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_normalize_u8_cams(const uint8_t* tiles, int n, int ncam, int h, int w, const float* mean3, const float* std3, float* out,
+                          void* stream) {
+    if (!tiles || !mean3 || !std3 || !out || n <= 0 || ncam <= 0 || h < 4 || w <= 0) return AGP_E_BADARG;
+    const long long W = (long long)ncam * w;
+    if (W < 4 || W >= (1ll << 31)) return AGP_E_BADARG;      // (an image the stem takes: at least one 4x4 patch)
+    const CnxLoadU8 ld = {tiles, ncam, h, w, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]};
+    const long long total = (long long)n * 3 * h * W;
+    const long long blocks = (total + 255) / 256;
+    AGP_LAUNCH(cnx_normalize_u8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, ld, (int)W,
+               total, out);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }

@@ -768,8 +768,9 @@ __global__ __launch_bounds__(256) void cnx_down_wgrad_kernel(const float* __rest
 // The forward's conv and LayerNorm statistics recomputed per 32-pixel tile, LayerNorm backward -> gz (LDS), then
 // gW[o][idx] += sum_px gz[px][o] patch[px][idx]: thread t owns the 18 outputs t + 256 u.  A workgroup sweeps CNX_STEM_TILES
 // tiles and writes one partial: [96 x 48 gW][96 g_bias][96 g_gamma][96 g_beta].
-__global__ __launch_bounds__(256) void cnx_stem_bwd_kernel(const float* __restrict__ x, long long sn, long long sc, long long sh,
-                                                           long long sw, int ho, int wo, long long P, const float* __restrict__ wt,
+// LOAD: the image source, as in cnx_stem_kernel (convnext_common.hpp).
+template <class LOAD>
+__global__ __launch_bounds__(256) void cnx_stem_bwd_kernel(const LOAD ld, int ho, int wo, long long P, const float* __restrict__ wt,
                                                            const float* __restrict__ bias, const float* __restrict__ g, float eps,
                                                            const float* __restrict__ gout, float* __restrict__ part) {
     __shared__ float xin[32][48];
@@ -795,7 +796,7 @@ __global__ __launch_bounds__(256) void cnx_stem_bwd_kernel(const float* __restri
                 const int ci = idx >> 4, ky = (idx >> 2) & 3, kx = idx & 3;
                 const long long img = p / ((long long)ho * wo);
                 const int rem = (int)(p - img * ho * wo), oy = rem / wo, ox = rem - oy * wo;
-                v = x[img * sn + ci * sc + (long long)(4 * oy + ky) * sh + (long long)(4 * ox + kx) * sw];
+                v = ld(img, ci, 4 * oy + ky, 4 * ox + kx);
             }
             xin[px][idx] = v;
         }
@@ -1034,8 +1035,32 @@ int agp_cnx_stem_bwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t
     if (bwd_workspace_bytes < stem_bwd_floats(P) * 4) return AGP_E_BADARG;
     float* const part = (float*)bwd_workspace;
     hipStream_t s = (hipStream_t)stream;
-    AGP_LAUNCH(cnx_stem_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, s, x, (long long)sn, (long long)sc, (long long)sh, (long long)sw,
-               ho, wo, P, wt, bias, ln_w, eps, gout, part);
+    const CnxLoadF32 ld = {x, (long long)sn, (long long)sc, (long long)sh, (long long)sw};
+    AGP_LAUNCH(cnx_stem_bwd_kernel<CnxLoadF32>, dim3((unsigned)nb), dim3(256), 0, s, ld, ho, wo, P, wt, bias, ln_w, eps, gout, part);
+    reduce_into(s, part, nb, CNX_STEM_PART, 96 * 48, g_w);
+    reduce_into(s, part + 96 * 48, nb, CNX_STEM_PART, 96, g_bias);
+    reduce_into(s, part + 96 * 48 + 96, nb, CNX_STEM_PART, 96, g_ln_w);
+    reduce_into(s, part + 96 * 48 + 192, nb, CNX_STEM_PART, 96, g_ln_b);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_stem_u8_bwd(const uint8_t* tiles, int n, int ncam, int h, int w, const float* mean3, const float* std3, const float* wt,
+                        const float* bias, const float* ln_w, float eps, const float* gout, float* g_w, float* g_bias, float* g_ln_w,
+                        float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream) {
+    if (!tiles || !mean3 || !std3 || !wt || !bias || !ln_w || !gout || !g_w || !g_bias || !g_ln_w || !g_ln_b || !bwd_workspace || n <= 0 ||
+        ncam <= 0 || h < 4 || w <= 0)
+        return AGP_E_BADARG;
+    const long long W = (long long)ncam * w;
+    if (W < 4 || W >= (1ll << 31)) return AGP_E_BADARG;
+    const int ho = (h - 4) / 4 + 1, wo = (int)((W - 4) / 4 + 1);
+    if (!cnx_map_ok(n, ho, wo)) return AGP_E_BADARG;
+    const long long P = (long long)n * ho * wo, nb = ceil_div(ceil_div(P, 32), CNX_STEM_TILES);
+    if (bwd_workspace_bytes < stem_bwd_floats(P) * 4) return AGP_E_BADARG;
+    float* const part = (float*)bwd_workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const CnxLoadU8 ld = {tiles, ncam, h, w, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]};
+    AGP_LAUNCH(cnx_stem_bwd_kernel<CnxLoadU8>, dim3((unsigned)nb), dim3(256), 0, s, ld, ho, wo, P, wt, bias, ln_w, eps, gout, part);
     reduce_into(s, part, nb, CNX_STEM_PART, 96 * 48, g_w);
     reduce_into(s, part + 96 * 48, nb, CNX_STEM_PART, 96, g_bias);
     reduce_into(s, part + 96 * 48 + 96, nb, CNX_STEM_PART, 96, g_ln_w);

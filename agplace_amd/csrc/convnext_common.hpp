@@ -31,6 +31,31 @@ __device__ __forceinline__ void mfma3(f32x16& acc, const bf16x8& wh, const bf16x
 // feature row (inside a 32-row block) of accumulator register `reg` of a lane in half `h`
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
+// ---- the stem's two image sources (cnx_stem_kernel, cnx_stem_bwd_kernel: templated on the loader).  A loader returns element
+// (image, channel, row y, panorama column X) of the logical fp32 image [n][3][h][W]; everything after the load is shared.
+struct CnxLoadF32 {            // fp32 [n][3][h][W] with element strides
+    const float* x;
+    long long sn, sc, sh, sw;
+    __device__ __forceinline__ float operator()(long long img, int ci, int y, int X) const {
+        return x[img * sn + ci * sc + (long long)y * sh + (long long)X * sw];
+    }
+};
+// ToTensor + Normalize of one byte: pack_u8_cams_kernel's expression (pack.hip).  The ONE definition behind agp_normalize_u8_cams
+// and the uint8 stems, so the three give the same bits.
+__device__ __forceinline__ float cnx_norm_u8(uint8_t u, float mean, float stdv) { return ((float)u / 255.f - mean) / stdv; }
+struct CnxLoadU8 {             // uint8 camera tiles [n][ncam][h][w][3]; the image is the panorama [n][3][h][ncam * w]
+    const uint8_t* t;
+    int ncam, h, w;
+    float m0, m1, m2, s0, s1, s2;
+    // one byte per load, addressed per element by panorama column (a 4x4 patch may straddle cameras): cam < ncam, x < w, y < h
+    // for every (y, X) inside the panorama, so no load leaves the n * ncam * h * w * 3 bytes
+    __device__ __forceinline__ float operator()(long long img, int ci, int y, int X) const {
+        const int cam = X / w, x = X - cam * w;
+        const uint8_t u = t[((((long long)img * ncam + cam) * h + y) * w + x) * 3 + ci];
+        return cnx_norm_u8(u, ci == 0 ? m0 : ci == 1 ? m1 : m2, ci == 0 ? s0 : ci == 1 ? s1 : s2);
+    }
+};
+
 inline long long cnx_pad(long long P) { return (P + CNX_TP - 1) / CNX_TP * CNX_TP; }
 inline bool cnx_c_host_ok(int C) { return C == 96 || C == 192 || C == 384; }
 inline bool cnx_map_ok(int n, int h, int w) { return n > 0 && h > 0 && w > 0 && (long long)n * h * w < (1ll << 31) / 32; }

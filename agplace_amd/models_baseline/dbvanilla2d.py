@@ -51,8 +51,11 @@ class DBVanilla2D(nn.Module):
             for e in fes:
                 if not self._convnext:      # Normalize of the uint8 routes (tiles, frames), which the ResNets alone have
                     e.fe.set_image_norm(opt.image_mean, opt.image_std)
-                elif opt.convnext_train:    # the opt-in training path of the ConvNeXt trunk (agplace_amd/convnext.py)
-                    e.fe.enable_training()
+                else:
+                    if opt.convnext_train:  # the opt-in training path of the ConvNeXt trunk (agplace_amd/convnext.py)
+                        e.fe.enable_training()
+                    if opt.convnext_u8:     # its opt-in uint8 routes: tiles and frames, normalised by the stem as it reads
+                        e.fe.enable_u8_inputs().set_image_norm(opt.image_mean, opt.image_std)
             self.dbimage_fes = nn.ModuleList(fes)
             self.dbimage_pools = nn.ModuleList([GeM() for _ in maptype])
             self.dbimage_mlps = nn.ModuleList([MLP(e.last_dim, dim) for e in fes])
@@ -105,6 +108,103 @@ class DBVanilla2D(nn.Module):
 
     def _forward_db(self, data_dict, train, trunk_maps, out_rows, defer_head):
         opt = self.opt
+        frames, jitter, crop, db_map, u8, mode, (b, ndb, nmap, c, h, w), dev = self._db_inputs(data_dict)
+        assert c == 3
+        prec = 3 if train else opt.mfma_precision
+        if (not train and torch.is_grad_enabled() and getattr(self, "_frozen_backbone", False) and prec == 4
+                and any(p.requires_grad for p in self.parameters())):
+            prec = 2          # heads trained on frozen features: the tight mode, as in MM.forward_q
+        # inference: the MLP heads, F.normalize and the mean over map types as ONE program launch (vecprog.hip) when the
+        # heads fit it (Linear(<=256, 256): a ResNet18/34 trunk; a ResNet50 head, Linear(1024, dim), runs per op)
+        fused = None
+        if not train and not torch.is_grad_enabled() and opt.fused_vector_path and nmap <= 4 and all(
+                m.seq[0].in_features <= 256 and m.seq[0].in_features % 32 == 0 and m.seq[0].out_features == 256
+                and m.seq[3].out_features == 256 for m in self.dbimage_mlps):
+            fused = VecProgram(b * ndb, dev)
+        if True:
+            vecs = []
+            for i in range(nmap):
+                j = 0 if opt.share_dbfe is True else i
+                x = self._db_tile_input(i, frames, jitter, crop, db_map, u8, (b, ndb, nmap, c, h, w))
+                if train:
+                    # share_dbfe: ONE trunk over every map type (reference :69-72); each application keeps its own
+                    # activations and tape (slot i), the parameter gradients of all of them accumulate
+                    fe = self.dbimage_fes[j].fe
+                    v = train_fns.TrunkFn.apply(train_fns.anchor_of(fe, self.dbimage_pools[j].p), x, fe, self.dbimage_pools[j], train_fns.MapSink(),
+                                                prec, False, i if opt.share_dbfe is True else 0)[0]
+                else:
+                    if trunk_maps is not None and i in trunk_maps:
+                        fpool = trunk_maps[i][1]
+                    else:
+                        fpool = self.final_pool_request(i)
+                        self.dbimage_fes[j].forward_maps(x, prec=prec, final_pool=fpool)
+                    # (a last map stored with an exponent: the stored map's GeM; the fused head multiplies by 2^e where it loads
+                    # the vector, the per-op head with a small launch)
+                    v, vscale = (fpool.gem, fpool.scale) if fused is not None else (fpool.true_gem(), None)
+                if fused is not None:
+                    # MLP + F.normalize of this map type; register 2 + i holds its vector
+                    mlp = self.dbimage_mlps[j]
+                    fused.linear(0, mlp._p0.get(), v, scale=vscale)
+                    fused.layernorm(0, mlp.seq[1], 0, relu=True)
+                    fused.linear(2 + i, mlp._p3.get(), 0)
+                    if opt.output_l2 is True:
+                        fused.l2norm(2 + i, 2 + i)
+                    vecs.append(v)
+                    continue
+                v = self.dbimage_mlps[j](v)
+                if opt.output_l2 is True:
+                    v = autograd_ops.l2normalize(v)
+                vecs.append(v)
+            if fused is not None:
+                if nmap > 1:
+                    wmean = torch.full((1,), 1.0 / nmap, device=dev)
+                    fused.wsum(2, [2 + i for i in range(nmap)], [wmean] * nmap)
+                if opt.final_l2 is True:
+                    fused.l2norm(2, 2)
+                out = fused.store(2, out_rows)
+                if defer_head is not None:
+                    defer_head.append(fused)
+                else:
+                    fused.run()
+                out = out.view(b, ndb, -1)
+                if mode == 'cachetest':
+                    out = out.view(b, -1)
+                return {'embedding': out}
+        return {'embedding': self._mean_over_maps(vecs, b, ndb, mode)}
+
+    def _mean_over_maps(self, vecs, b, ndb, mode):
+        """The mean over map types of the per-map vectors [b * ndb, dim], in the input's layout, then final_l2."""
+        opt, nmap = self.opt, len(vecs)
+        if True:
+            out = vecs[0] if nmap == 1 else autograd_ops.wsum(
+                vecs, [torch.full((1,), 1.0 / nmap, device=vecs[0].device)] * nmap)
+            out = out.view(b, ndb, -1)
+            if mode == 'cachetest':
+                out = out.view(b, -1)
+            if opt.final_l2 is True:
+                shp = out.shape
+                out = autograd_ops.l2normalize(out.reshape(-1, shp[-1])).view(shp)
+        return out
+
+    def _db_tile_input(self, i, frames, jitter, crop, db_map, u8, dims):
+        """Map type i of a parsed input (_db_inputs) as one trunk input of b * ndb images: ops.RawFrames, uint8 [n,1,h,w,3] tiles
+        or a [n,3,h,w] view."""
+        b, ndb, nmap, c, h, w = dims
+        if frames is not None:
+            f = frames[:, :, i]
+            return ops.RawFrames(f.reshape(b * ndb, 1, *f.shape[2:]), h, w, crop=crop,      # one "camera" per tile
+                                 jitter=None if jitter is None else jitter[:, :, i].reshape(b * ndb, ops.JITTER_RECORD))
+        x = db_map[:, :, i].reshape(b * ndb, c, h, w)       # view when possible; strides are honoured
+        if u8:
+            x = x.permute(0, 2, 3, 1).unsqueeze(1)          # uint8 [n,1,h,w,3]: one "camera" per tile (contiguous again)
+        return x
+
+    def _db_inputs(self, data_dict):
+        """Validate and parse `db_map` / `db_frames` / `db_jitter`: (frames [b,ndb,nmap,H0,W0,3] or None, jitter [b,ndb,nmap,8] or
+        None, crop, db_map as a logical [b,ndb,nmap,3,h,w] view or None, whether db_map is uint8, 'cachetest' | 'train',
+        (b, ndb, nmap, c, h, w), device)."""
+        opt = self.opt
+        crop, db_map = None, None
         frames = data_dict.get('db_frames')
         jitter = data_dict.get('db_jitter')
         if jitter is not None and frames is None:
@@ -156,84 +256,7 @@ class DBVanilla2D(nn.Module):
                 b, ndb, nmap, c, h, w = db_map.shape
             else:
                 raise NotImplementedError
-        assert c == 3
-        prec = 3 if train else opt.mfma_precision
-        if (not train and torch.is_grad_enabled() and getattr(self, "_frozen_backbone", False) and prec == 4
-                and any(p.requires_grad for p in self.parameters())):
-            prec = 2          # heads trained on frozen features: the tight mode, as in MM.forward_q
-        # inference: the MLP heads, F.normalize and the mean over map types as ONE program launch (vecprog.hip) when the
-        # heads fit it (Linear(<=256, 256): a ResNet18/34 trunk; a ResNet50 head, Linear(1024, dim), runs per op)
-        fused = None
-        if not train and not torch.is_grad_enabled() and opt.fused_vector_path and nmap <= 4 and all(
-                m.seq[0].in_features <= 256 and m.seq[0].in_features % 32 == 0 and m.seq[0].out_features == 256
-                and m.seq[3].out_features == 256 for m in self.dbimage_mlps):
-            fused = VecProgram(b * ndb, dev)
-        if True:
-            vecs = []
-            for i in range(nmap):
-                j = 0 if opt.share_dbfe is True else i
-                if frames is not None:
-                    f = frames[:, :, i]
-                    x = ops.RawFrames(f.reshape(b * ndb, 1, *f.shape[2:]), h, w, crop=crop,      # one "camera" per tile
-                                      jitter=None if jitter is None else jitter[:, :, i].reshape(b * ndb, ops.JITTER_RECORD))
-                else:
-                    x = db_map[:, :, i].reshape(b * ndb, c, h, w)       # view when possible; strides are honoured
-                if u8:
-                    x = x.permute(0, 2, 3, 1).unsqueeze(1)          # uint8 [n,1,h,w,3]: one "camera" per tile (contiguous again)
-                if train:
-                    # share_dbfe: ONE trunk over every map type (reference :69-72); each application keeps its own
-                    # activations and tape (slot i), the parameter gradients of all of them accumulate
-                    fe = self.dbimage_fes[j].fe
-                    v = train_fns.TrunkFn.apply(train_fns.anchor_of(fe, self.dbimage_pools[j].p), x, fe, self.dbimage_pools[j], train_fns.MapSink(),
-                                                prec, False, i if opt.share_dbfe is True else 0)[0]
-                else:
-                    if trunk_maps is not None and i in trunk_maps:
-                        fpool = trunk_maps[i][1]
-                    else:
-                        fpool = self.final_pool_request(i)
-                        self.dbimage_fes[j].forward_maps(x, prec=prec, final_pool=fpool)
-                    # (a last map stored with an exponent: the stored map's GeM; the fused head multiplies by 2^e where it loads
-                    # the vector, the per-op head with a small launch)
-                    v, vscale = (fpool.gem, fpool.scale) if fused is not None else (fpool.true_gem(), None)
-                if fused is not None:
-                    # MLP + F.normalize of this map type; register 2 + i holds its vector
-                    mlp = self.dbimage_mlps[j]
-                    fused.linear(0, mlp._p0.get(), v, scale=vscale)
-                    fused.layernorm(0, mlp.seq[1], 0, relu=True)
-                    fused.linear(2 + i, mlp._p3.get(), 0)
-                    if opt.output_l2 is True:
-                        fused.l2norm(2 + i, 2 + i)
-                    vecs.append(v)
-                    continue
-                v = self.dbimage_mlps[j](v)
-                if opt.output_l2 is True:
-                    v = autograd_ops.l2normalize(v)
-                vecs.append(v)
-            if fused is not None:
-                if nmap > 1:
-                    wmean = torch.full((1,), 1.0 / nmap, device=dev)
-                    fused.wsum(2, [2 + i for i in range(nmap)], [wmean] * nmap)
-                if opt.final_l2 is True:
-                    fused.l2norm(2, 2)
-                out = fused.store(2, out_rows)
-                if defer_head is not None:
-                    defer_head.append(fused)
-                else:
-                    fused.run()
-                out = out.view(b, ndb, -1)
-                if mode == 'cachetest':
-                    out = out.view(b, -1)
-                return {'embedding': out}
-        if True:
-            out = vecs[0] if nmap == 1 else autograd_ops.wsum(
-                vecs, [torch.full((1,), 1.0 / nmap, device=vecs[0].device)] * nmap)
-            out = out.view(b, ndb, -1)
-            if mode == 'cachetest':
-                out = out.view(b, -1)
-            if opt.final_l2 is True:
-                shp = out.shape
-                out = autograd_ops.l2normalize(out.reshape(-1, shp[-1])).view(shp)
-        return {'embedding': out}
+        return frames, jitter, crop, db_map, u8, mode, (b, ndb, nmap, c, h, w), dev
 
     def _forward_db_convnext(self, data_dict, trunk_maps):
         """dbimage_fe='convnext_tiny' (agplace_amd/convnext.py) over fp32 `db_map`.  Per map type: the trunk's last map
@@ -241,51 +264,42 @@ class DBVanilla2D(nn.Module):
         heads may train on a frozen trunk (freeze_backbone) through the ops' own backward kernels.  Inference only unless
         Options.convnext_train enabled the trunks' training path: then .train() (stochastic depth; under torch.no_grad() nothing is
         saved) and gradients into the trunk run through ConvNeXt.forward_maps_train; with share_dbfe the one trunk is applied per
-        map type, each application with its own saved state, and its parameter gradients accumulate."""
+        map type, each application with its own saved state, and its parameter gradients accumulate.
+        uint8 `db_map`, `db_frames` and `db_jitter` are refused by name unless Options.convnext_u8 enabled the trunks' uint8
+        inputs; then they are taken as in the ResNet model (one "camera" per tile), in inference and in training."""
         opt = self.opt
         enabled = all(e.fe._train_enabled for e in self.dbimage_fes)
         what = "DBVanilla2D with dbimage_fe='convnext_tiny'" + ("" if enabled else " (inference only; Options.convnext_train opts in)")
         if self.training and not enabled:
             raise NotImplementedError(f"{what}: .train() is not enabled; call .eval()")
-        if 'db_frames' in data_dict or 'db_jitter' in data_dict:
+        u8_on = all(e.fe._u8_enabled for e in self.dbimage_fes)       # Options.convnext_u8
+        if not u8_on and ('db_frames' in data_dict or 'db_jitter' in data_dict):
             raise NotImplementedError(f"{what}: `db_frames` (decoded uint8 frames) is not built; pass fp32 `db_map`")
         if trunk_maps is not None:
             raise NotImplementedError(f"{what}: lock-step trunks (pair.embed_pair) are not built")
-        db_map = data_dict['db_map']
-        if db_map.dtype == torch.uint8:
+        if not u8_on and data_dict['db_map'].dtype == torch.uint8:
             raise NotImplementedError(f"{what}: uint8 `db_map` is not built; pass fp32 tiles")
         if not enabled and torch.is_grad_enabled() and any(p.requires_grad for e in self.dbimage_fes for p in e.fe.features.parameters()):
             raise NotImplementedError(f"{what}: gradients into the trunk are not enabled; run under torch.no_grad() or "
                                       "freeze_backbone()")
-        if db_map.dim() == 5:      # [b,nmap,3,h,w]  caching / testing
-            mode = 'cachetest'
-            b, nmap, c, h, w = db_map.shape
-            db_map = db_map.unsqueeze(1)
-            ndb = 1
-        elif db_map.dim() == 6:    # [b,ndb,nmap,3,h,w]  training layout
-            mode = 'train'
-            b, ndb, nmap, c, h, w = db_map.shape
-        else:
-            raise NotImplementedError
+        # (with Options.convnext_u8: uint8 `db_map`, `db_frames` with db_resize / db_cropsize and `db_jitter` under _forward_db's
+        # validation; the trunk resizes and jitters to uint8 tiles and its stem normalises them as it reads, ConvNeXt._input)
+        frames, jitter, crop, db_map, u8, mode, dims, _ = self._db_inputs(data_dict)
+        b, ndb, nmap, c, h, w = dims
         assert c == 3
         vecs = []
         for i in range(nmap):
             j = 0 if opt.share_dbfe is True else i
-            x = db_map[:, :, i].reshape(b * ndb, c, h, w).float()
+            x = self._db_tile_input(i, frames, jitter, crop, db_map, u8, dims)
+            if torch.is_tensor(x) and not u8:
+                x = x.float()
             last, _ = self.dbimage_fes[j](x)
             v = gem_op(last, self.dbimage_pools[j].p, self.dbimage_pools[j].eps)
             v = self.dbimage_mlps[j](v)
             if opt.output_l2 is True:
                 v = autograd_ops.l2normalize(v)
             vecs.append(v)
-        out = vecs[0] if nmap == 1 else autograd_ops.wsum(vecs, [torch.full((1,), 1.0 / nmap, device=vecs[0].device)] * nmap)
-        out = out.view(b, ndb, -1)
-        if mode == 'cachetest':
-            out = out.view(b, -1)
-        if opt.final_l2 is True:
-            shp = out.shape
-            out = autograd_ops.l2normalize(out.reshape(-1, shp[-1])).view(shp)
-        return {'embedding': out}
+        return {'embedding': self._mean_over_maps(vecs, b, ndb, mode)}
 
     def forward(self, data_dict, mode: List[str]):
         if mode == 'db':

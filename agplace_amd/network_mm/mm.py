@@ -56,8 +56,11 @@ class MM(nn.Module):
         self.image_fe = ImageFE(fe_type=opt.mm_imgfe, layers=opt.mm_imgfe_layers)
         if not self._convnext:
             self.image_fe.fe.set_image_norm(opt.image_mean, opt.image_std)       # Normalize of the uint8 routes (tiles, frames)
-        elif opt.convnext_train:            # the opt-in training path of the ConvNeXt trunk (agplace_amd/convnext.py)
-            self.image_fe.fe.enable_training()
+        else:
+            if opt.convnext_train:          # the opt-in training path of the ConvNeXt trunk (agplace_amd/convnext.py)
+                self.image_fe.fe.enable_training()
+            if opt.convnext_u8:             # its opt-in uint8 routes: tiles and frames, normalised by the stem as it reads
+                self.image_fe.fe.enable_u8_inputs().set_image_norm(opt.image_mean, opt.image_std)
         self.image_pool = GeM()
         planes = [int(x) for x in opt.mm_voxfe_planes.split('_')]
         layers = [int(x) for x in opt.mm_voxfe_layers.split('_')]
@@ -267,9 +270,12 @@ class MM(nn.Module):
             raise NotImplementedError(f"{what}: .train() is not built; call .eval()")
         if not enabled and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError(f"{what}: gradients are not built (a parameter requires one); run under torch.no_grad()")
-        if 'query_frames' in data_dict or 'query_jitter' in data_dict:
+        # Options.convnext_u8: uint8 `query_image` [b,ncam,h,w,3], `query_frames` with q_resize and `query_jitter`, validated by
+        # query_image() as in the ResNet model; the trunk resizes and jitters to uint8 tiles, its stem normalises them as it reads
+        u8_on = self.image_fe.fe._u8_enabled
+        if not u8_on and ('query_frames' in data_dict or 'query_jitter' in data_dict):
             raise NotImplementedError(f"{what}: `query_frames` (decoded uint8 frames) is not built; pass the fp32 `query_image`")
-        if data_dict['query_image'].dtype == torch.uint8:
+        if not u8_on and data_dict['query_image'].dtype == torch.uint8:
             raise NotImplementedError(f"{what}: uint8 `query_image` is not built; pass the normalised fp32 panorama")
         if image_maps is not None or out_rows:
             raise NotImplementedError(f"{what}: lock-step trunks and row-sliced outputs (pair.embed_pair, query sub-streams) are "
@@ -280,7 +286,7 @@ class MM(nn.Module):
             # (the guard, when Options.fp16_range_guard is on, covers the voxel branch's fp16 maps as in the ResNet model)
             with range_guard.guarded(self, self.opt, self.opt.mfma_precision, False):
                 return self._forward_q(data_dict, False, None, None, None)
-        if torch.is_grad_enabled() and data_dict['query_image'].requires_grad:
+        if torch.is_grad_enabled() and 'query_image' in data_dict and data_dict['query_image'].requires_grad:
             raise NotImplementedError("ConvNeXt: the gradient of the input image is not built (the stem returns none)")
         from .. import train_graph
         with train_graph.training_mode(self.opt.train_precision == 16, self.opt.train_dgrad_products == 1):

@@ -257,6 +257,24 @@ def pack_cameras_u8(img_u8, prec, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None
     return out
 
 
+def normalize_cameras_u8(tiles, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """uint8 [n, ncam, h, w, 3] camera tiles (HWC, on the GPU) -> the fp32 panorama [n, 3, h, ncam * w] they stand for (contiguous
+    NCHW): v = (u8 / 255 - mean[c]) / std[c], pack_cameras_u8's expression.  The image a uint8 route of the ConvNeXt trunk reads
+    (agplace_amd/convnext.py: its uint8 stems give the bits of the fp32 stems on this tensor); h and ncam * w at least 4."""
+    _need_cuda(tiles, "normalize_cameras_u8")
+    if tiles.dtype != torch.uint8 or tiles.dim() != 5 or tiles.shape[-1] != 3 or 0 in tiles.shape:
+        raise ValueError("normalize_cameras_u8 expects uint8 [n, ncam, h, w, 3]")
+    tiles = tiles.contiguous()
+    n, ncam, h, w, _ = tiles.shape
+    if h < 4 or ncam * w < 4:
+        raise ValueError(f"normalize_cameras_u8: a {h}x{ncam * w} panorama is smaller than 4x4")
+    out = torch.empty((n, 3, h, ncam * w), dtype=torch.float32, device=tiles.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    check(_L().agp_normalize_u8_cams(ptr(tiles), n, ncam, h, w, m, s, ptr(out), _lib.stream()), "agp_normalize_u8_cams")
+    return out
+
+
 # ---- camera front end (csrc/camera.hip, DESIGN.md 1d): the resize in front of the uint8 tiles, Pillow's arithmetic bit for bit
 def resized_size(h, w, size):
     """(h, w) after torchvision's Resize(size) with an int size: the shorter edge becomes `size`, the longer

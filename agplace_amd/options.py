@@ -125,6 +125,13 @@ class Options:
     # (default): the trunk is inference only and refuses both, as before.  A reference namespace does not carry this field:
     # from_reference_opt(args).copy(convnext_train=True).
     convnext_train: bool = False
+    # Opt-in uint8 inputs of the ConvNeXt-tiny trunk: DBVanilla2D and MM then call ConvNeXt.enable_u8_inputs() and
+    # set_image_norm(image_mean, image_std) on its trunks, which take uint8 tiles (`db_map`, `query_image`) and decoded frames
+    # (`db_frames` / `query_frames`, with db_cropsize, db_jitter / query_jitter) as the ResNet models do: the resize and the jitter
+    # write uint8 tiles, the stem normalises them as it reads (csrc/convnext.hip), bit for bit the fp32 route on
+    # ops.normalize_cameras_u8's image.  False (default): those inputs are refused by name, as before.  A reference namespace does
+    # not carry this field (from_reference_opt leaves it False): from_reference_opt(args).copy(convnext_u8=True).
+    convnext_u8: bool = False
     # inference: MM.forward embeds a batch as this many sub-batches on as many HIP streams (1 = off)
     query_substreams: int = 1
     # inference: the vector path (everything after the backbones) as two program launches (agplace_amd/vecprog.py) instead
@@ -175,6 +182,8 @@ class Options:
             raise ValueError(f"image_std {self.image_std!r}: every component must be positive")
         if not isinstance(self.convnext_train, bool):
             raise ValueError(f"convnext_train {self.convnext_train!r}: True | False")
+        if not isinstance(self.convnext_u8, bool):
+            raise ValueError(f"convnext_u8 {self.convnext_u8!r}: True | False")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
 
@@ -188,7 +197,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name):
+        if hasattr(ns, f.name) and f.name != "convnext_u8":      # (not a reference option: stays False)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

@@ -107,7 +107,8 @@ class CnxTrunkFn(torch.autograd.Function):
     own (convnext._TrunkFn, recorded here under enable_grad and run from this node's backward, so the trunk's parameter gradients
     accumulate through autograd as in DBVanilla2D's ConvNeXt training).  The sink carries the STREAM tensors; Stage2ImgFn adds
     its vector to the last one with ops.bcast_add_f32 and returns its SplitMap gradient through `sink.extra`, which
-    ops.pool_f32_bwd folds into the fp32 gradient handed to the trunk -- one pass over the last map in each direction."""
+    ops.pool_f32_bwd folds into the fp32 gradient handed to the trunk -- one pass over the last map in each direction.  `x` is handed
+    to the trunk unchanged: the fp32 image or, with Options.convnext_u8, uint8 tiles / ops.RawFrames."""
 
     @staticmethod
     def forward(ctx, anchor, x, trunk, gem, sink):

@@ -1087,6 +1087,22 @@ int agp_cnx_stem_bwd(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t
                      const float* bias, const float* ln_w, float eps, const float* gout, float* g_w, float* g_bias, float* g_ln_w,
                      float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
 
+/* ---- ConvNeXt-tiny trunk on uint8 camera tiles (csrc/convnext.hip, csrc/convnext_bwd.hip).  tiles: uint8 [n][ncam][h][w][3]
+ * (HWC, contiguous); the image they stand for is the panorama [n][3][h][ncam * w] with v = (u8 / 255 - mean3[c]) / std3[c] in fp32,
+ * the expression of agp_pack_u8_cams_to_nhwc; mean3 / std3 are HOST arrays of three floats.  No load leaves the
+ * n * ncam * h * w * 3 bytes of `tiles`.  AGP_E_BADARG for a null pointer, a non-positive size, h < 4 or ncam * w < 4. */
+/* The fp32 panorama itself, out fp32 [n][3][h][ncam * w] (contiguous NCHW). */
+int agp_normalize_u8_cams(const uint8_t* tiles, int n, int ncam, int h, int w, const float* mean3, const float* std3, float* out,
+                          void* stream);
+/* agp_cnx_stem_fwd on the panorama of `tiles`, which is never written: out fp32 [n][(h-4)/4+1][(ncam*w-4)/4+1][96], bit for bit
+ * what agp_cnx_stem_fwd gives on agp_normalize_u8_cams' output (one kernel body, templated on its loader). */
+int agp_cnx_stem_u8_fwd(const uint8_t* tiles, int n, int ncam, int h, int w, const float* mean3, const float* std3, const float* wt,
+                        const float* bias, const float* ln_w, const float* ln_b, float eps, float* out, void* stream);
+/* agp_cnx_stem_bwd on the panorama of `tiles`: the same workspace and partial order, the same bits. */
+int agp_cnx_stem_u8_bwd(const uint8_t* tiles, int n, int ncam, int h, int w, const float* mean3, const float* std3, const float* wt,
+                        const float* bias, const float* ln_w, float eps, const float* gout, float* g_w, float* g_bias, float* g_ln_w,
+                        float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
