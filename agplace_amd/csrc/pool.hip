@@ -88,13 +88,22 @@ __global__ __launch_bounds__(POOL_TPB) void pool_partial_kernel(
     }
 }
 
+// Acc: the type the partials are added in, in split order: float for one trip of up to POOL_F32_SPLITS = 8 partials, double
+// beyond.  An fp32 running sum loses up to 2^-24 of itself at every add: over a chain of L equal partials that is about
+// 1.5e-8 sqrt(L) of the mean per plane (rms), and a wide map has thousands of planes.  Measured against fp64: 2048 partials in
+// fp32 left the worst of the 8 planes of a [1, 370, 370, 8] map 1.25e-6 off, 256 partials the worst of the 2048 planes of
+// [1, 128, 128, 2048] 8.1e-7 -- both above four times the error of a float32 mean (6.6e-7 there).  Eight adds stay at 1.6e-7
+// over 8192 planes, and in double every count stays at 8e-8 (the rounding of inv_hw and of the result).  The adds hide behind
+// the loads.
+constexpr int POOL_F32_SPLITS = 8;
+template <typename Acc>
 __global__ void pool_final_kernel(const float* __restrict__ partial, int n, int c, int splits,
                                   float inv_hw, const float* __restrict__ pptr,
                                   float* __restrict__ mean_out, float* __restrict__ gem_out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * c) return;
     const int im = t / c, ch = t % c;
-    float sm = 0.f, sg = 0.f;
+    Acc sm = 0, sg = 0;
     for (int s0 = 0; s0 < splits; s0 += 8) {       // 16 independent loads per trip, summed in split order
         float a[8], g[8];
 #pragma unroll
@@ -106,12 +115,12 @@ __global__ void pool_final_kernel(const float* __restrict__ partial, int n, int 
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (s0 + u < splits) { sm += a[u]; sg += g[u]; }
+            if (s0 + u < splits) { sm += (Acc)a[u]; sg += (Acc)g[u]; }
     }
-    if (mean_out) mean_out[t] = sm * inv_hw;
+    if (mean_out) mean_out[t] = (float)sm * inv_hw;
     if (gem_out) {
         const float p = pptr[0];
-        gem_out[t] = __builtin_exp2f(__builtin_log2f(sg * inv_hw) / p);
+        gem_out[t] = __builtin_exp2f(__builtin_log2f((float)sg * inv_hw) / p);
     }
 }
 
@@ -345,8 +354,13 @@ extern "C" int agp_pool_fwd(const void* hi, const void* lo, int n, int h, int w,
                        (hipStream_t)stream, (const bf16_t*)hi, (const bf16_t*)lo, h, w, c, pad, p, eps,
                        splits, make_fastdiv((uint32_t)w), partial, gem_out ? 1 : 0);
     AGP_CHECK_LAUNCH();
-    AGP_LAUNCH(pool_final_kernel, dim3((n * c + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       partial, n, c, splits, 1.f / (float)(h * w), p, mean_out, gem_out);
+    if (splits <= POOL_F32_SPLITS) {
+        AGP_LAUNCH(pool_final_kernel<float>, dim3((n * c + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                   partial, n, c, splits, 1.f / (float)(h * w), p, mean_out, gem_out);
+    } else {
+        AGP_LAUNCH(pool_final_kernel<double>, dim3((n * c + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                   partial, n, c, splits, 1.f / (float)(h * w), p, mean_out, gem_out);
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
