@@ -139,6 +139,10 @@ SIGNATURES = {
     "agp_fcode_adaptive_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P]),
     "agp_fcode_adaptive_bwd_workspace_bytes": (_L, [_I, _I]),
     "agp_fcode_adaptive_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    "agp_fcode_adaptive_wide_ring_floats": (_L, [_I, _I, _I, _I]),
+    "agp_fcode_adaptive_wide_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _I, _P, _P]),
+    "agp_fcode_adaptive_wide_bwd_workspace_bytes": (_L, [_I, _I, _I]),
+    "agp_fcode_adaptive_wide_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
     "agp_linear_bwd_workspace_bytes": (_L, [_I, _I, _I]),
     "agp_linear_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
     "agp_layernorm_bwd": (_I, [_P, _P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P]),

@@ -1232,7 +1232,7 @@ def gem_f32_bwd(x, p, y, gy, need_gx=True, eps=GEM_EPS):
 # ------------------------------------------------------------------ MLP / ODE ops
 class LinearWeights:
     """[n][k] split planes (+ fp32 bias); n padded up to a multiple of 256 with zero rows."""
-    __slots__ = ("w_hi", "w_lo", "wt_hi", "wt_lo", "bias", "n", "k", "npad", "_frag")
+    __slots__ = ("w_hi", "w_lo", "wt_hi", "wt_lo", "bias", "n", "k", "npad", "_frag", "_frag_t")
 
     def __init__(self, weight, bias, with_transpose=False):
         w = weight.detach().float()
@@ -1243,7 +1243,7 @@ class LinearWeights:
             w = torch.cat([w, torch.zeros(self.npad - n, k, device=w.device)], 0)
         self.w_hi, self.w_lo = split_weight(w)
         self.wt_hi = self.wt_lo = None
-        self._frag = None
+        self._frag = self._frag_t = None
         if with_transpose:
             # W^T as [k padded to 256][n padded to 32] for the backward products gz W
             kp, np32 = (k + 255) // 256 * 256, (n + 31) // 32 * 32
@@ -1335,6 +1335,15 @@ FCODE_WIDE_DIM = 384       # the one width of agp_fcode_wide_fwd
 FCODE_WIDE_ROWS = 16       # batch rows per workgroup of that kernel
 
 
+def fcode_wide_fragment_order(plane, transpose=False):
+    """One plane [>= 384, 384] of a 384-wide Linear (or, with transpose, of its W^T) in the kernels' fragment order:
+    [wave][ks][tile][q][row][8] = M[48 wave + 16 tile + row][32 ks + 8 q .. + 7], M = W or W^T.  Pure indexing, any device."""
+    d = FCODE_WIDE_DIM
+    m = plane[:d].t() if transpose else plane[:d]
+    # [384, 384] -> (w, t, row, ks, q, e) -> (w, ks, t, q, row, e)
+    return m.contiguous().view(8, 3, 16, d // 32, 4, 8).permute(0, 3, 1, 4, 2, 5).contiguous()
+
+
 def fcode_wide_planes(lw: LinearWeights):
     """The planes of a [384, 384] Linear in the fragment order agp_fcode_wide_fwd reads (include/agplace_hip.h): for wave w
     (48 output features), K-step ks and tile t the 64 lanes' 16-byte MFMA A-fragments are contiguous.  Built once per
@@ -1344,14 +1353,28 @@ def fcode_wide_planes(lw: LinearWeights):
         d = FCODE_WIDE_DIM
         if lw.n != d or lw.k != d:
             raise NotImplementedError(f"fcode_wide is built for dim={d}, got a [{lw.n}, {lw.k}] Linear")
-        if torch.cuda.is_current_stream_capturing():
+        if lw.w_hi.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("fcode_wide: the weight planes are prepared on the first call: run the forward once before "
                                "capturing it (and again after a parameter update)")
 
-        def frag(t):        # [npad, 384] -> (w, t, row, ks, q, e) -> (w, ks, t, q, row, e)
-            return t[:d].view(8, 3, 16, d // 32, 4, 8).permute(0, 3, 1, 4, 2, 5).contiguous()
-        lw._frag = (frag(lw.w_hi), frag(lw.w_lo))
+        lw._frag = (fcode_wide_fragment_order(lw.w_hi), fcode_wide_fragment_order(lw.w_lo))
     return lw._frag
+
+
+def fcode_wide_planes_t(lw: LinearWeights):
+    """The planes of W^T of a [384, 384] Linear in the same fragment order (agp_fcode_adaptive_wide_bwd): what
+    fcode_wide_planes gives for the transposed weight -- the split is elementwise, so it commutes with the transpose.
+    Cached like them; wanted by a backward only."""
+    if lw._frag_t is None:
+        d = FCODE_WIDE_DIM
+        if lw.n != d or lw.k != d:
+            raise NotImplementedError(f"fcode_wide is built for dim={d}, got a [{lw.n}, {lw.k}] Linear")
+        if lw.w_hi.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fcode_wide: the weight planes are prepared on the first call: run the step once before "
+                               "capturing it (and again after a parameter update)")
+
+        lw._frag_t = (fcode_wide_fragment_order(lw.w_hi, transpose=True), fcode_wide_fragment_order(lw.w_lo, transpose=True))
+    return lw._frag_t
 
 
 def fcode_wide(x, lw: LinearWeights, act, method, dts, add1=None, add2=None):
@@ -1392,9 +1415,14 @@ def fcode_bwd(traj, gy, lw: LinearWeights, act, method, dts):
     return gx, gw, gb
 
 
+FCODE_ADAPTIVE_DIMS = (256, FCODE_WIDE_DIM)       # agp_fcode_adaptive_fwd, agp_fcode_adaptive_wide_fwd
+
+
 def _adaptive_args(x, lw, act, method, tol, max_steps):
-    if x.shape[1] != 256 or lw.k != 256 or lw.n != 256:
-        raise NotImplementedError(f"FCODE {method}: the adaptive solver is built for dim=256")
+    d = x.shape[1]
+    if d not in FCODE_ADAPTIVE_DIMS or lw.k != d or lw.n != d:
+        raise NotImplementedError(f"FCODE {method}: the adaptive solver is built for dim=256 and dim=384, got x "
+                                  f"{tuple(x.shape)} and a [{lw.n}, {lw.k}] Linear")
     if method not in _lib.ODE_ADAPTIVE:
         raise NotImplementedError(method)
     if act not in _lib.ACT:
@@ -1407,7 +1435,8 @@ def _adaptive_args(x, lw, act, method, tol, max_steps):
 
 def fcode_adaptive(x, lw: LinearWeights, act, method, tol, max_steps=64, add1=None, add2=None, want_traj=False):
     """y(1) of y' = act(y W^T + b), y(0) = x + add1 + add2, by the adaptive solver `method` ('dopri5') with rtol = atol = tol:
-    ONE launch (agp_fcode_adaptive_fwd), no host synchronisation, capturable.  Returns (y, ctrl) or, with want_traj,
+    ONE launch (agp_fcode_adaptive_fwd at 256 columns, agp_fcode_adaptive_wide_fwd at 384), no host synchronisation,
+    capturable.  Returns (y, ctrl) or, with want_traj,
     (y, ctrl, traj): ctrl is the device control block (ode_stats(ctrl) reads it), traj the record fcode_adaptive_bwd needs.
     A solve that fails (step cap, step-size underflow, NaN) returns NaN and says why in ctrl."""
     _need_cuda(x, "fcode_adaptive")
@@ -1417,6 +1446,18 @@ def fcode_adaptive(x, lw: LinearWeights, act, method, tol, max_steps=64, add1=No
     _adaptive_args(x, lw, act, method, tol, max_steps)
     y = torch.empty_like(x)
     ctrl = torch.empty(_L().agp_fcode_adaptive_ctrl_bytes(max_steps), dtype=torch.uint8, device=x.device)
+    if x.shape[1] == FCODE_WIDE_DIM:
+        d = x.shape[1]
+        f_hi, f_lo = fcode_wide_planes(lw)
+        if want_traj:
+            fcode_wide_planes_t(lw)      # a backward follows: its planes are prepared here, outside any capture of it
+        ring = torch.empty(_L().agp_fcode_adaptive_wide_ring_floats(b, d, max_steps, int(want_traj)), dtype=torch.float32,
+                           device=x.device)
+        check(_L().agp_fcode_adaptive_wide_fwd(ptr(x), ptr(add1), ptr(add2), ptr(f_hi), ptr(f_lo), ptr(lw.bias), b, d,
+                                               _lib.ACT[act], _lib.ODE_ADAPTIVE[method], float(tol), float(tol), max_steps,
+                                               ptr(y), ptr(ring), int(want_traj), ptr(ctrl), _lib.stream()),
+              "agp_fcode_adaptive_wide_fwd")
+        return (y, ctrl, ring) if want_traj else (y, ctrl)
     ring = torch.empty(_L().agp_fcode_adaptive_ring_floats(b, max_steps, int(want_traj)), dtype=torch.float32, device=x.device)
     check(_L().agp_fcode_adaptive_fwd(ptr(x), ptr(add1), ptr(add2), ptr(lw.w_hi), ptr(lw.w_lo), ptr(lw.bias), b, _lib.ACT[act],
                                       _lib.ODE_ADAPTIVE[method], float(tol), float(tol), max_steps, ptr(y), ptr(ring),
@@ -1431,6 +1472,15 @@ def fcode_adaptive_bwd(traj, ctrl, gy, lw: LinearWeights, act, method, max_steps
     gx = torch.empty_like(gy)
     gw = torch.empty((d, d), dtype=torch.float32, device=gy.device)
     gb = torch.empty(d, dtype=torch.float32, device=gy.device)
+    _adaptive_args(gy, lw, act, method, 1.0, max_steps)
+    if d == FCODE_WIDE_DIM:
+        ft_hi, ft_lo = fcode_wide_planes_t(lw)
+        nbytes = _L().agp_fcode_adaptive_wide_bwd_workspace_bytes(b, d, max_steps)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
+        check(_L().agp_fcode_adaptive_wide_bwd(ptr(traj), ptr(ctrl), ptr(gy), ptr(ft_hi), ptr(ft_lo), b, d, _lib.ACT[act],
+                                               _lib.ODE_ADAPTIVE[method], max_steps, ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes,
+                                               _lib.stream()), "agp_fcode_adaptive_wide_bwd")
+        return gx, gw, gb
     nbytes = _L().agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
     check(_L().agp_fcode_adaptive_bwd(ptr(traj), ptr(ctrl), ptr(gy), ptr(lw.wt_hi), ptr(lw.wt_lo), b, _lib.ACT[act],

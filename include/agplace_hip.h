@@ -518,7 +518,8 @@ int agp_fcode_fwd(const float* x, const float* add1, const float* add2, const vo
  * another); W's `hi` plane stays in registers, the `lo` plane is read from L2 once per f-evaluation.  wf_hi / wf_lo: the two
  * split-bf16 planes of W [384][384] in the kernel's FRAGMENT order, 16 bytes per entry:
  *   [wave 0..7][ks 0..11][tile 0..2][q 0..3][row 0..15][8] = W[48 wave + 16 tile + row][32 ks + 8 q .. + 7].
- * d != 384: AGP_E_UNSUPPORTED.  AGP_E_BADARG: a null pointer, b <= 0, nsteps outside 1..64, an unknown act or method. */
+ * d != 384: AGP_E_UNSUPPORTED.  AGP_E_BADARG: a null pointer, b <= 0, nsteps outside 1..64, an unknown act or method.
+ * Fixed grids only; the adaptive solver at this width is agp_fcode_adaptive_wide_fwd, which reads the same planes. */
 int agp_fcode_wide_fwd(const float* x, const float* add1, const float* add2, const void* wf_hi, const void* wf_lo,
                        const float* bias, int b, int d, int act, int method, const float* dt, int nsteps, float* y,
                        void* stream);
@@ -535,7 +536,7 @@ int agp_fcode_bwd(const float* traj, const float* gy, const void* wt_hi, const v
                   int act, int method, const float* dt, int nsteps, float* gx, float* gw, float* gb,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
-/* FCODE by the ADAPTIVE solver dopri5 (method = AGP_ODE_DOPRI5; D = 256 only): y(1) of dy/dt = act(y W^T + b),
+/* FCODE by the ADAPTIVE solver dopri5 (method = AGP_ODE_DOPRI5; D = 256, for D = 384 agp_fcode_adaptive_wide_fwd below): y(1) of dy/dt = act(y W^T + b),
  * y(0) = x (+ add1 + add2), with torchdiffeq's step control -- one RMS error norm over all b * 256 elements, steps not
  * clipped to the end time, the result read off the last step's quartic interpolant.  ONE launch of
  * one persistent workgroup per solve, no host round trip: capturable.  f runs on W's two split-bf16 planes and THREE bf16 planes
@@ -569,6 +570,32 @@ int64_t agp_fcode_adaptive_bwd_workspace_bytes(int b, int max_steps);
 int agp_fcode_adaptive_bwd(const float* traj, const void* ctrl, const float* gy, const void* wt_hi, const void* wt_lo,
                            int b, int act, int method, int max_steps, float* gx, float* gw, float* gb, void* workspace,
                            int64_t workspace_bytes, void* stream);
+
+/* The adaptive solver at d = 384 (dopri5 on a 384 x 384 Linear, csrc/fusion_adaptive.hip): the algorithm, the arithmetic (two planes
+ * of W, three of the state, five products), the control block (agp_fcode_adaptive_ctrl_bytes, agp_ode_stats), the three endings
+ * and the ring layout of agp_fcode_adaptive_fwd, with 384 columns: ring[n][0][b][384] = y before accepted step n,
+ * ring[n][1 + j][b][384] = its k_{j+1}; agp_fcode_adaptive_wide_ring_floats(b, d, max_steps, want_traj) =
+ * (want_traj ? max_steps + 1 : 2) * 8 * b * 384 floats (0 for b <= 0, max_steps < 1 or d != 384).  ONE launch of one persistent
+ * workgroup of 8 waves per solve, capturable; W does not fit a CU's registers at this width, so as in agp_fcode_wide_fwd the
+ * `hi` plane stays in registers and the `lo` plane is read from L2 once per f-evaluation and row tile.  wf_hi / wf_lo: the two
+ * split-bf16 planes of W [384][384] in the FRAGMENT order of agp_fcode_wide_fwd, 16 bytes per entry:
+ *   [wave 0..7][ks 0..11][tile 0..2][q 0..3][row 0..15][8] = W[48 wave + 16 tile + row][32 ks + 8 q .. + 7].
+ * d != 384: AGP_E_UNSUPPORTED.  AGP_E_BADARG: a null pointer, b <= 0, d <= 0, an unknown act, a method other than
+ * AGP_ODE_DOPRI5, max_steps outside 1 .. AGP_ODE_MAX_STEPS_LIMIT, a negative tolerance or rtol + atol <= 0 (checked before d). */
+int64_t agp_fcode_adaptive_wide_ring_floats(int b, int d, int max_steps, int want_traj);
+int agp_fcode_adaptive_wide_fwd(const float* x, const float* add1, const float* add2, const void* wf_hi, const void* wf_lo,
+                                const float* bias, int b, int d, int act, int method, double rtol, double atol,
+                                int max_steps, float* y, float* ring, int want_traj, void* ctrl, void* stream);
+
+/* Backward of agp_fcode_adaptive_wide_fwd, as agp_fcode_adaptive_bwd: one workgroup per 16 rows, the step count and the step
+ * sizes read from `ctrl` on the device, gw[384][384] and gb[384] OVERWRITTEN, NaN outputs after a failed forward.  wtf_hi /
+ * wtf_lo: the planes of W^T [384][384] in the same fragment order, i.e. [wave][ks][tile][q][row][8] =
+ * W[32 ks + 8 q .. + 7][48 wave + 16 tile + row].  workspace: agp_fcode_adaptive_wide_bwd_workspace_bytes(b, d, max_steps) =
+ * 2 * (6 * max_steps + 1) * Bp * 384 * 4 bytes, Bp = b rounded up to 16 (0 for b <= 0, max_steps < 1 or d != 384). */
+int64_t agp_fcode_adaptive_wide_bwd_workspace_bytes(int b, int d, int max_steps);
+int agp_fcode_adaptive_wide_bwd(const float* traj, const void* ctrl, const float* gy, const void* wtf_hi, const void* wtf_lo,
+                                int b, int d, int act, int method, int max_steps, float* gx, float* gw, float* gb,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Linear backward for y = act(x W^T + b): gz = gy * act'(y) (y = forward output, NULL for act id);
  * gx[b][k] = gz W (wt planes = split W^T, k % 256 == 0 after padding by the caller), and

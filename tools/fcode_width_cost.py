@@ -1,4 +1,4 @@
-"""Cost of FCODE(384) by route: python tools/fcode_width_cost.py [--steps 50] [--windows 5] [--mm-steps 10] [--no-mm].
+"""Cost of FCODE(384) by route: python tools/fcode_width_cost.py [--steps 50] [--windows 5] [--mm-steps 10] [--no-mm] [--dopri5].
 
 First timing: one FCODE(384) solve (relu, default-init weights, inference) for b = 16 and 64 and euler / 0.1, rk4 / 0.25, through
 the one-launch kernel (ops.fcode_wide, csrc/fusion_wide.hip) and through FCODE._forward_any_width -- called directly: it is
@@ -9,6 +9,11 @@ agp_linear_fwd and agp_wsum_fwd at the C ABI during the capture -- all of an FCO
 
 Second timing: the whole MM forward on the ConvNeXt-tiny trunk (layers 2_2_2, image [16, 3, 224, 1344], dense voxel stand-ins),
 captured and replayed, with FCODE(384) on the one-launch kernel and -- the same model -- on the any-width route.
+
+--dopri5 adds a third timing: one adaptive solve (odeint_method = 'dopri5', relu, tol = 1e-3, default-init weights, inference) for
+b = 16 and 64 at 256 columns (agp_fcode_adaptive_fwd) and at 384 (agp_fcode_adaptive_wide_fwd), captured and replayed, the median of
+its windows, with the attempted-step and f-evaluation counts of the solve beside the time: the kernel is latency-bound, its time
+is the step count times the cost of an attempted step.
 Prints one JSON line."""
 import argparse
 import json
@@ -19,11 +24,11 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from agplace_amd import _lib, ops  # noqa: E402
+from agplace_amd import _lib, autograd_ops, ops  # noqa: E402
 from agplace_amd.network_mm.ffns import FCODE  # noqa: E402
 from agplace_amd.options import Options  # noqa: E402
 
-COUNTED = ("agp_fcode_wide_fwd", "agp_linear_fwd", "agp_wsum_fwd")
+COUNTED = ("agp_fcode_wide_fwd", "agp_linear_fwd", "agp_wsum_fwd", "agp_fcode_adaptive_fwd", "agp_fcode_adaptive_wide_fwd")
 
 
 def window_us(fn, steps, windows):
@@ -90,6 +95,7 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--mm-steps", type=int, default=10)
     ap.add_argument("--no-mm", action="store_true")
+    ap.add_argument("--dopri5", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     d = ops.FCODE_WIDE_DIM
@@ -109,6 +115,19 @@ def main():
                 row[name] = {"one_launch": wide, "any_width": anyw,
                              "outputs_rel_l2": float((yw.double() - ya.double()).norm() / ya.double().norm())}
             res["fcode"][f"b{b}"] = row
+        if args.dopri5:
+            res["dopri5"] = {"act": "relu", "tol": 1e-3}
+            for width in (256, d):
+                for b in (16, 64):
+                    torch.manual_seed(0)
+                    x = torch.randn(b, width, device=dev)
+                    torch.manual_seed(1)
+                    m = FCODE(width, "relu", opt=Options(odeint_method="dopri5", tol=1e-3)).to(dev)
+                    fc = m.func.func.fc      # (through the autograd layer: FCODE.forward refuses dopri5 at 384 columns)
+                    t, _ = timed(lambda: autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, m, None, None), args.steps, args.windows)
+                    st = m.solver_stats()
+                    t.update(attempted=st["attempted"], rejected=st["rejected"], f_evals=st["f_evals"])
+                    res["dopri5"][f"d{width}_b{b}"] = t
         if not args.no_mm:
             from agplace_amd.network_mm.mm import MM
             from bench_inputs import synth_query
