@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .geo import Positives
 from .retrieval import IndexFlatL2, MAX_K      # MAX_K: agp_knn_search's limit on k
 
 
@@ -35,11 +36,17 @@ def _csr(lists, device):
 
 def best_positive_indexes(query_features, database_features, hard_positives_per_query, device="cuda"):
     """[Q] int64: for query i the row of `database_features` among hard_positives_per_query[i] nearest
-    in feature space (reference get_best_positive_index, :1241-1248); -1 for an empty list."""
+    in feature space (reference get_best_positive_index, :1241-1248); -1 for an empty list.
+    hard_positives_per_query: a list of Q index arrays, or a geo.Positives with Q rows, which is read where it lies."""
     dev = torch.device(device)
     xq = _dev(query_features, dev, torch.float32)
     xb = _dev(database_features, dev, torch.float32)
-    off, idx = _csr(hard_positives_per_query, dev)
+    if isinstance(hard_positives_per_query, Positives):
+        if len(hard_positives_per_query) != xq.shape[0]:
+            raise ValueError("best_positive_indexes: one list of hard positives per query is needed")
+        off, idx = hard_positives_per_query.offsets.to(dev), hard_positives_per_query.indices.to(dev)
+    else:
+        off, idx = _csr(hard_positives_per_query, dev)
     if idx.numel() == 0:
         idx = torch.zeros(1, dtype=torch.int64, device=dev)
     out = torch.empty(xq.shape[0], dtype=torch.int64, device=dev)
@@ -56,10 +63,17 @@ def hardest_negatives_indexes(query_features, database_features, sampled_databas
     equal distances resolve to the earlier SAMPLED row, as an index built over that array would.
     One batched search with k = negs + (most in-sample soft positives of any query) serves every query whose soft
     positives leave k <= MAX_K (1024); a query with more in-sample soft positives than that is searched on its own
-    over its own candidate set, like the reference does for every query."""
+    over its own candidate set, like the reference does for every query.
+    soft_positives_per_query: a list of Q index arrays, or a geo.Positives with Q rows; the latter stays on the device (no host
+    loop over the queries: agp_mine_drop_listed removes the listed rows from the search's result)."""
     dev = torch.device(device)
     xq = _dev(query_features, dev, torch.float32)
     xb = _dev(database_features, dev, torch.float32)
+    if isinstance(soft_positives_per_query, Positives):
+        if len(soft_positives_per_query) != xq.shape[0]:
+            raise ValueError("hardest_negatives_indexes: one list of soft positives per query is needed")
+        return _hardest_negatives_device(xq, xb, sampled_database_indexes, soft_positives_per_query,
+                                         torch.arange(xq.shape[0], device=dev), negs_num_per_query)
     cand = np.asarray(sampled_database_indexes, dtype=np.int64).reshape(-1)      # the sample's own order
     nq, nc = xq.shape[0], cand.shape[0]
     order = np.argsort(cand, kind="stable")
@@ -117,19 +131,106 @@ def hardest_negatives_indexes(query_features, database_features, sampled_databas
     return out
 
 
+def _hardest_negatives_device(xq, xb, sampled_database_indexes, soft, row_of_q, negs):
+    """hardest_negatives_indexes with the soft positives as a device CSR: query i's list is row row_of_q[i] of `soft` (int64
+    on the device), so the sampled queries' lists are never gathered.  Same result as the list route."""
+    dev = xq.device
+    soft = soft.sorted_unique()
+    if soft.device != dev:
+        soft = Positives(soft.offsets.to(dev), soft.indices.to(dev), True)
+    cand_t = sampled_database_indexes if torch.is_tensor(sampled_database_indexes) else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(sampled_database_indexes, dtype=np.int64).reshape(-1)))
+    cand_t = cand_t.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()            # the sample's own order
+    nq, nc, ndb = xq.shape[0], cand_t.shape[0], xb.shape[0]
+    out = torch.empty((nq, negs), dtype=torch.int64, device=dev)
+    if nq == 0:
+        return out
+    # in-sample soft positives per query: how often every database row was sampled, gathered through the CSR, summed per row
+    times = torch.bincount(cand_t, minlength=ndb) if nc else torch.zeros(max(ndb, 1), dtype=torch.int64, device=dev)
+    idx = soft.indices
+    w = torch.where((idx >= 0) & (idx < times.numel()), times[idx.clamp(0, times.numel() - 1)], torch.zeros_like(idx))
+    run = torch.zeros(idx.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(w, 0, out=run[1:])
+    counts = (run[soft.offsets[1:]] - run[soft.offsets[:-1]])[row_of_q]                   # [nq]
+    most_all = int(counts.max())                                                          # the one host read that chooses k
+    if nc - most_all < negs:
+        raise ValueError("fewer candidate negatives than negs_num_per_query for some query")
+    L = _lib.load()
+    pos_idx = idx if idx.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+    if most_all <= MAX_K - negs:
+        bt, xqb, rows_b, most = None, xq, row_of_q, most_all
+        single = []
+    else:
+        fits = counts <= MAX_K - negs
+        bt = torch.nonzero(fits).view(-1)
+        single = torch.nonzero(~fits).view(-1).tolist()
+        xqb, rows_b = xq.index_select(0, bt), row_of_q.index_select(0, bt).contiguous()
+        most = int(counts[bt].max()) if bt.numel() else 0
+    if xqb.shape[0]:
+        k = min(nc, negs + most)
+        index = IndexFlatL2(xq.shape[1], device=dev)
+        index.add(xb.index_select(0, cand_t))
+        _, I = index.search_device(xqb, k)                                                # [Qb,k] positions in cand, nearest first
+        nqb = xqb.shape[0]
+        out_b = out if bt is None else torch.empty((nqb, negs), dtype=torch.int64, device=dev)
+        filled = torch.empty(nqb, dtype=torch.int32, device=dev)
+        check(L.agp_mine_drop_listed(ptr(I), nqb, k, ptr(cand_t), nc, ptr(rows_b), ptr(soft.offsets), ptr(pos_idx), negs,
+                                     ptr(out_b), ptr(filled), _lib.stream()), "agp_mine_drop_listed")
+        if int(filled.min()) < negs:
+            raise RuntimeError("hardest_negatives_indexes: the batched search left a query short of negatives")
+        if bt is not None:
+            out[bt] = out_b
+    for q in single:                                     # today's single-query route, the query's list read on the device
+        r = int(row_of_q[q])
+        mine = idx[int(soft.offsets[r]):int(soft.offsets[r + 1])]                         # ascending, not empty
+        at = torch.searchsorted(mine, cand_t).clamp(max=mine.numel() - 1)
+        sub_t = cand_t[mine[at] != cand_t]                                                # sampled order, soft positives removed
+        index = IndexFlatL2(xq.shape[1], device=dev)
+        index.add(xb.index_select(0, sub_t))
+        _, I = index.search_device(xq[q:q + 1], negs)
+        out[q] = sub_t[I[0]]
+    return out
+
+
 def compute_triplets_partial(query_features, database_features, sampled_queries_indexes, hard_positives_per_query,
                              soft_positives_per_query, sampled_database_indexes, negs_num_per_query=10, device="cuda"):
     """The triplet table of `compute_triplets_partial_sep` (:1372-1410): int64 [Q, 2 + negs] rows
     (query_index, best_positive_index, neg_indexes...).  `query_features[i]` belongs to
     sampled_queries_indexes[i]; the two per-query lists are indexed by the GLOBAL query index, as
-    in the reference dataset object."""
+    in the reference dataset object.  Either list may be a geo.Positives over all queries: it is then read on the device
+    (the hard rows gathered by tensor indexing, the soft rows addressed in place), with the result of the same lists."""
     sq = np.asarray(sampled_queries_indexes, dtype=np.int64)
+    if isinstance(hard_positives_per_query, Positives) or isinstance(soft_positives_per_query, Positives):
+        return _compute_triplets_partial_device(query_features, database_features, sq, hard_positives_per_query,
+                                                soft_positives_per_query, sampled_database_indexes, negs_num_per_query, device)
     hard = [hard_positives_per_query[i] for i in sq]
     soft = [soft_positives_per_query[i] for i in sq]
     best = best_positive_indexes(query_features, database_features, hard, device)
     negs = hardest_negatives_indexes(query_features, database_features, sampled_database_indexes, soft,
                                      negs_num_per_query, device)
     return torch.cat([torch.from_numpy(sq).to(best.device).view(-1, 1), best.view(-1, 1), negs], 1)
+
+
+def _compute_triplets_partial_device(query_features, database_features, sq, hard_positives_per_query, soft_positives_per_query,
+                                     sampled_database_indexes, negs_num_per_query, device):
+    dev = torch.device(device)
+    xq = _dev(query_features, dev, torch.float32)
+    xb = _dev(database_features, dev, torch.float32)
+    for p in (hard_positives_per_query, soft_positives_per_query):
+        if sq.size and not (0 <= sq.min() and sq.max() < len(p)):
+            raise IndexError("compute_triplets_partial: sampled query index outside the lists of positives")
+    sq_t = torch.from_numpy(sq).to(dev)
+    if isinstance(hard_positives_per_query, Positives):
+        hard = hard_positives_per_query.select(sq_t.to(hard_positives_per_query.device))
+    else:
+        hard = [hard_positives_per_query[i] for i in sq]
+    best = best_positive_indexes(xq, xb, hard, dev)
+    if isinstance(soft_positives_per_query, Positives):
+        negs = _hardest_negatives_device(xq, xb, sampled_database_indexes, soft_positives_per_query, sq_t, negs_num_per_query)
+    else:
+        negs = hardest_negatives_indexes(xq, xb, sampled_database_indexes, [soft_positives_per_query[i] for i in sq],
+                                         negs_num_per_query, dev)
+    return torch.cat([sq_t.view(-1, 1), best.view(-1, 1), negs], 1)
 
 
 def compute_triplets_partial_sharded(query_features, database_features, sampled_queries_indexes, hard_positives_per_query,

@@ -11,7 +11,7 @@ complete candidate set), ties ordered by ascending database index.  k goes up to
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, geo
 from ._lib import ptr, check
 from .options import get_options
 
@@ -149,10 +149,14 @@ class IndexFlatL2:
 
 
 def recall_from_predictions(args, predictions, test_ds):
-    """The recall arithmetic of reference test.py:73-83: predictions int64 [Q, max(recall_values)]."""
+    """The recall arithmetic of reference test.py:73-83: predictions int64 [Q, max(recall_values)].
+    Where test_ds.get_positives() returns a geo.Positives (the device CSR of geo.radius_neighbors) the predictions are scored
+    on the device (geo.recall_at: one launch, same numbers); lists of arrays take the reference's loop below."""
+    positives_per_query = test_ds.get_positives()
+    if isinstance(positives_per_query, geo.Positives):
+        return geo.recall_at(predictions, positives_per_query, args.recall_values, test_ds.queries_num)
     if not isinstance(predictions, np.ndarray):
         predictions = predictions.cpu().numpy()
-    positives_per_query = test_ds.get_positives()
     recalls = np.zeros(len(args.recall_values))
     for query_index, pred in enumerate(predictions):
         for i, n in enumerate(args.recall_values):

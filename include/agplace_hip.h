@@ -878,6 +878,42 @@ int agp_mine_best_positive(const float* xq, int64_t nq, const float* xb, int64_t
                            const int64_t* pos_off, const int64_t* pos_idx, int64_t* out_best,
                            float* out_dist, void* stream);
 
+/* ---------------------------------------------------------------------- geo */
+
+/* Geographic positives as a device CSR (csrc/geo.hip, agplace_amd/geo.py): query q owns the database rows
+ * pos_idx[pos_off[q] .. pos_off[q+1]), int64, ASCENDING within a row.  All entries: one wave per query row, no atomics (two
+ * runs write the same bytes), caller-owned buffers, no allocation or synchronisation, launched on `stream`.  A null pointer,
+ * a negative size or a row count above 2^31 - 64 is AGP_E_BADARG before any launch.
+ *
+ * Radius search (reference datasets/datasets_ws_nuscenes.py:907-912, 1032-1037: sklearn radius_neighbors over UTM metres).
+ * q fp64 [nq][2], db fp64 [nb][2], r2 = the squared radius, rounded once by the caller as r * r.  Row b is within the radius
+ * of query q when  dx*dx + dy*dy <= r2  with dx = qx - bx, dy = qy - by, every operation an fp64 operation rounded on its own
+ * (no fused multiply-add): inclusive at the boundary, and the same bits as that expression in numpy.  A NaN coordinate is
+ * nobody's neighbour.
+ * agp_radius_count : counts[q] = the number of rows within the radius.
+ * agp_radius_fill  : idx[offsets[q] .. offsets[q+1]) = those rows in ascending order; offsets [nq + 1] is the caller's exclusive
+ *                    prefix sum of the counts.  A query never writes at or past its offsets[q+1].
+ * nq == 0 or nb == 0: AGP_OK, nothing is launched and nothing is written (the caller zeroes counts for an empty database). */
+int agp_radius_count(const double* q, int64_t nq, const double* db, int64_t nb, double r2, int64_t* counts, void* stream);
+int agp_radius_fill(const double* q, int64_t nq, const double* db, int64_t nb, double r2, const int64_t* offsets, int64_t* idx,
+                    void* stream);
+
+/* The column of the first correct prediction (reference test.py:73-83 asks np.isin(pred[:n], positives) per recall value n).
+ * pred int64 [nq][k] contiguous, 1 <= k <= AGP_KNN_MAX_K; first[q] (int32) = the smallest j with pred[q][j] in row q of the
+ * CSR, k if there is none.  Entries < 0 (faiss's -1 padding) match nothing.  The CSR rows must be ascending (binary search). */
+int agp_recall_first_hit(const int64_t* pred, int64_t nq, int k, const int64_t* pos_off, const int64_t* pos_idx, int32_t* first,
+                         void* stream);
+
+/* The miner's "candidates minus soft positives" (reference :1394-1404, np.setdiff1d before the negatives' search), applied
+ * AFTER one search over all sampled rows.  I int64 [nq][k]: positions in `cand`, nearest first (agp_knn_search's labels);
+ * cand int64 [nc]: the sampled database rows; row_of_q int64 [nq]: the CSR row that holds query q's list (so no sub-CSR is
+ * gathered); 1 <= k, negs <= AGP_KNN_MAX_K.  out[q][0 .. negs) = the first `negs` of cand[I[q][:]] that are not in that list,
+ * in I's order; membership is by database row, so a row sampled twice is dropped in every copy.  filled[q] (int32) = how many
+ * were found: < negs when k columns did not suffice, and out[q][filled[q] ..) is then not written.  Entries of I outside
+ * [0, nc) are skipped. */
+int agp_mine_drop_listed(const int64_t* I, int64_t nq, int k, const int64_t* cand, int64_t nc, const int64_t* row_of_q,
+                         const int64_t* pos_off, const int64_t* pos_idx, int negs, int64_t* out, int32_t* filled, void* stream);
+
 /* ------------------------------------------------------------------- losses */
 
 /* nn.TripletMarginLoss(margin, p=2, eps=1e-6, reduction="sum") summed over a table of triplets
