@@ -206,7 +206,8 @@ SIGNATURES = {
     "agp_pairdist_loss_workspace_floats": (_L, [_I, _I]),
     "agp_pairdist_loss": (_I, [_P, _P, _I, _I, _I, _P, _P, _F, _F, _I, _P, _P, _P, _P, _P, _P]),
     "agp_mine_best_positive": (_I, [_P, _L, _P, _L, _I, _P, _P, _P, _P, _P]),
-    "agp_radius_count": (_I, [_P, _L, _P, _L, C.c_double, _P, _P]),
+    "agp_mine_topk_listed": (_I, [_P, _L, _P, _L, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "agp_radius_count":(_I, [_P, _L, _P, _L, C.c_double, _P, _P]),
     "agp_radius_fill": (_I, [_P, _L, _P, _L, C.c_double, _P, _P, _P]),
     "agp_recall_first_hit": (_I, [_P, _L, _I, _P, _P, _P, _P]),
     "agp_mine_drop_listed": (_I, [_P, _L, _I, _P, _L, _P, _P, _P, _I, _P, _P, _P]),

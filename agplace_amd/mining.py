@@ -9,6 +9,13 @@ host-side feature cache.  Here the cache stays on the device and the whole refre
       query has inside the sample), followed by dropping each query's soft positives;
 results are identical to the per-query loop: same candidate order (np.setdiff1d(..., assume_unique=True) keeps the
 random sample's order), same tie rule (earlier candidate wins), exact distances.
+
+The other two modes of `--mining` give every query candidates of its OWN, so no shared search serves them:
+    * `full` (compute_triplets_full, :1295-1322): a private random sample minus the soft positives, merged with the negatives the
+      query kept last time (`NegCache`, the reference's self.neg_cache), searched, written back.  One `agp_mine_topk_listed`
+      launch (`nearest_listed`) over the [Q, negs + S] table of candidates;
+    * `random` (compute_triplets_random, :1264-1289): the first `negs` of a private draw that are not soft positives: tensor ops.
+The random draws stay with the caller, as `sampled_database_indexes` does for `partial`.
 """
 import numpy as np
 import torch
@@ -17,6 +24,10 @@ from . import _lib
 from ._lib import check, ptr
 from .geo import Positives
 from .retrieval import IndexFlatL2, MAX_K      # MAX_K: agp_knn_search's limit on k
+
+MINE_MAX_K = 128        # AGP_MINE_MAX_K (include/agplace_hip.h): agp_mine_topk_listed's limit on k
+MINE_MAX_COLS = 4096    # AGP_MINE_MAX_COLS: its limit on the columns of the candidate table
+_TOO_FEW = "fewer candidate negatives than negs_num_per_query for some query"
 
 
 def _dev(x, device, dtype):
@@ -261,3 +272,239 @@ def compute_triplets_partial_sharded(query_features, database_features, sampled_
     if errs:
         raise ValueError("compute_triplets_partial_sharded: " + "; ".join(errs))
     return parallel.all_gather_rows(local)
+
+
+# ---------------------------------------------------------------------------------------------- full and random mining
+
+def _exclusion_on(exclude, dev):
+    """`exclude` (a Positives or a list of index arrays) as a Positives with ascending rows on `dev`."""
+    if not isinstance(exclude, Positives):
+        exclude = Positives.from_lists(exclude, dev)
+    exclude = exclude.sorted_unique()
+    if exclude.device != dev:
+        exclude = Positives(exclude.offsets.to(dev), exclude.indices.to(dev), True)
+    return exclude
+
+
+def _topk_listed(xq, xb, cand, k, exclude, rows, exempt_cols):
+    """The launch behind nearest_listed, its arguments checked and on one device: exclude a sorted Positives or None."""
+    nq, ncols = cand.shape
+    dev = xq.device
+    idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    filled = torch.empty(nq, dtype=torch.int32, device=dev)
+    off_p = idx_p = rows_p = None
+    if exclude is not None:
+        keep = exclude.indices if exclude.indices.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+        off_p, idx_p, rows_p = ptr(exclude.offsets), ptr(keep), ptr(rows)
+    check(_lib.load().agp_mine_topk_listed(ptr(xq), nq, ptr(xb) if xb.shape[0] else None, xb.shape[0], xq.shape[1], ptr(cand),
+                                           ncols, rows_p, off_p, idx_p, exempt_cols, k, ptr(idx), None, ptr(filled),
+                                           _lib.stream()), "agp_mine_topk_listed")
+    return idx, filled
+
+
+def _check_topk_shapes(what, xq, xb, cand, k):
+    if xq.dim() != 2 or xb.dim() != 2 or xq.shape[1] != xb.shape[1] or xq.shape[1] == 0:
+        raise ValueError(f"{what}: features must be [Q, d] and [N, d] with one d > 0, got {tuple(xq.shape)} and {tuple(xb.shape)}")
+    if cand.dim() != 2 or cand.shape[0] != xq.shape[0]:
+        raise ValueError(f"{what}: one row of candidates per query is needed, got {tuple(cand.shape)} for {xq.shape[0]} queries")
+    if not 1 <= k <= MINE_MAX_K:
+        raise ValueError(f"{what}: k must lie between 1 and {MINE_MAX_K}, got {k}")
+    if not 1 <= cand.shape[1] <= MINE_MAX_COLS:
+        raise ValueError(f"{what}: between 1 and {MINE_MAX_COLS} candidate columns are supported, got {cand.shape[1]}")
+
+
+def nearest_listed(query_features, database_features, candidates, k, exclude=None, exclude_rows=None, exempt_cols=0,
+                   device="cuda"):
+    """(idx int64 [Q, k], filled int32 [Q]) on the device: per query the k nearest DISTINCT rows of `database_features` among
+    row q of `candidates` (int64 [Q, ncols], any order, padded with -1), nearest first; one agp_mine_topk_listed launch.
+    An entry counts when it lies in [0, N) and is not in the query's exclusion list: `exclude` (a geo.Positives or a list of
+    index arrays) read at row exclude_rows[q] (default q).  The first `exempt_cols` columns are never excluded.
+    Order: (exact fp64 squared distance, database row), both ascending, so equal distances resolve to the SMALLER row, whatever
+    the order of the columns; a row listed twice counts once; a candidate at a non-finite distance comes behind every finite one.
+    filled[q] = how many distinct valid candidates there were, at most k; idx[q, filled[q]:] = -1.
+    1 <= k <= 128, 1 <= ncols <= 4096; ValueError otherwise, and for shapes that do not agree."""
+    dev = torch.device(device)
+    xq = _dev(query_features, dev, torch.float32)
+    xb = _dev(database_features, dev, torch.float32)
+    cand = _dev(candidates, dev, torch.int64)
+    k, exempt_cols = int(k), int(exempt_cols)
+    _check_topk_shapes("nearest_listed", xq, xb, cand, k)
+    if exempt_cols < 0:
+        raise ValueError(f"nearest_listed: exempt_cols must be >= 0, got {exempt_cols}")
+    nq = xq.shape[0]
+    rows = None
+    if exclude is None:
+        if exclude_rows is not None:
+            raise ValueError("nearest_listed: exclude_rows without exclude")
+    else:
+        exclude = _exclusion_on(exclude, dev)
+        if exclude_rows is None:
+            if len(exclude) != nq:
+                raise ValueError(f"nearest_listed: {len(exclude)} exclusion lists for {nq} queries (give exclude_rows to address them)")
+            rows = torch.arange(nq, dtype=torch.int64, device=dev)
+        else:
+            rows = _dev(exclude_rows, dev, torch.int64).reshape(-1)
+            if rows.numel() != nq:
+                raise ValueError(f"nearest_listed: {rows.numel()} exclude_rows for {nq} queries")
+            if nq and not (0 <= int(rows.min()) and int(rows.max()) < len(exclude)):
+                raise IndexError("nearest_listed: exclude_rows outside the exclusion lists")
+    return _topk_listed(xq, xb, cand, k, exclude, rows, exempt_cols)
+
+
+class NegCache:
+    """The negatives every query kept at its last `full` refresh (the reference's self.neg_cache, :1026 and :1315-1319) as ONE
+    device table: int64 [queries_num, negs], -1 where a query has not been mined yet."""
+
+    def __init__(self, queries_num, negs=10, device="cuda"):
+        self.table = torch.full((int(queries_num), int(negs)), -1, dtype=torch.int64, device=torch.device(device))
+
+    @property
+    def negs(self):
+        return self.table.shape[1]
+
+    @property
+    def device(self):
+        return self.table.device
+
+    def __len__(self):
+        return self.table.shape[0]
+
+    def _index(self, sq):
+        if not torch.is_tensor(sq):
+            sq = torch.from_numpy(np.ascontiguousarray(np.asarray(sq, dtype=np.int64).reshape(-1)))
+        return sq.to(device=self.device, dtype=torch.int64)
+
+    def rows(self, sq):
+        """int64 [len(sq), negs]: the cached negatives of the given queries (a copy)."""
+        return self.table.index_select(0, self._index(sq))
+
+    def update(self, sq, negs):
+        """Row sq[i] = negs[i] (int64 [len(sq), negs])."""
+        self.table[self._index(sq)] = negs.to(device=self.device, dtype=torch.int64)
+
+    def to_lists(self):
+        """The reference's form: per query an int32 array, the -1 entries dropped (empty before the query's first refresh)."""
+        host = self.table.cpu().numpy()
+        return [row[row >= 0].astype(np.int32) for row in host]
+
+    @classmethod
+    def from_lists(cls, lists, negs=10, device="cuda"):
+        host = np.full((len(lists), int(negs)), -1, dtype=np.int64)
+        for i, x in enumerate(lists):
+            x = np.asarray(x, dtype=np.int64).reshape(-1)
+            if x.size > negs:
+                raise ValueError(f"NegCache.from_lists: list {i} has {x.size} entries, more than negs = {negs}")
+            host[i, :x.size] = x
+        cache = cls(0, negs, device)
+        cache.table = torch.from_numpy(host).to(torch.device(device))
+        return cache
+
+
+def _sampled_queries(what, sampled_queries_indexes, xq, *per_query):
+    sq = np.asarray(sampled_queries_indexes, dtype=np.int64).reshape(-1)
+    if xq.shape[0] != sq.size:
+        raise ValueError(f"{what}: {xq.shape[0]} rows of query features for {sq.size} sampled queries")
+    if np.unique(sq).size != sq.size:
+        raise ValueError(f"{what}: duplicate entries in sampled_queries_indexes")
+    for p in per_query:
+        if sq.size and not (0 <= sq.min() and sq.max() < len(p)):
+            raise IndexError(f"{what}: sampled query index outside the per-query lists")
+    return sq
+
+
+def _best_of_sampled(xq, xb, hard_positives_per_query, sq, sq_t, dev):
+    if isinstance(hard_positives_per_query, Positives):
+        hard = hard_positives_per_query.select(sq_t.to(hard_positives_per_query.device))
+    else:
+        hard = [hard_positives_per_query[i] for i in sq]
+    return best_positive_indexes(xq, xb, hard, dev)
+
+
+def _soft_of_sampled(soft_positives_per_query, sq, sq_t, dev):
+    """(sorted Positives on dev, the row of every sampled query in it): a Positives over all queries is read where it lies."""
+    if isinstance(soft_positives_per_query, Positives):
+        return _exclusion_on(soft_positives_per_query, dev), sq_t
+    soft = Positives.from_lists([soft_positives_per_query[i] for i in sq], dev, sort=True)
+    return soft, torch.arange(sq.size, dtype=torch.int64, device=dev)
+
+
+def compute_triplets_full(query_features, database_features, sampled_queries_indexes, hard_positives_per_query,
+                          soft_positives_per_query, sampled_negatives, neg_cache, negs_num_per_query=10, device="cuda"):
+    """The triplet table of the reference's `full` mining (compute_triplets_full, :1295-1322): int64 [Q, 2 + negs] rows
+    (query_index, best_positive_index, neg_indexes...), and `neg_cache` updated with the negatives found.
+    sampled_negatives int64 [Q, S]: row i is query i's own np.random.choice(database_num, neg_samples_num, replace=False).
+    Per query the candidates are its cached negatives (never filtered, as in the reference) and its sample minus its soft
+    positives; the `negs` nearest distinct ones are taken, the smaller row first at equal distance -- what the reference's
+    search over np.unique(...) gives.  One nearest_listed launch over cat([neg_cache.rows(sq), sampled_negatives], 1).
+    The per-query lists are indexed by the GLOBAL query index and may be lists or geo.Positives, as in
+    compute_triplets_partial; with two Positives no host loop runs over the queries.
+    ValueError: duplicate sampled queries (the reference's sequential cache update would make one depend on the other), or a
+    query with fewer than `negs` distinct candidates; neg_cache is then left as it was."""
+    dev = torch.device(device)
+    negs = int(negs_num_per_query)
+    xq = _dev(query_features, dev, torch.float32)
+    xb = _dev(database_features, dev, torch.float32)
+    sq = _sampled_queries("compute_triplets_full", sampled_queries_indexes, xq, hard_positives_per_query, soft_positives_per_query,
+                          neg_cache)
+    samp = _dev(sampled_negatives, dev, torch.int64)
+    if samp.dim() != 2 or samp.shape[0] != sq.size:
+        raise ValueError(f"compute_triplets_full: sampled_negatives must be [{sq.size}, S], got {tuple(samp.shape)}")
+    if neg_cache.negs != negs:
+        raise ValueError(f"compute_triplets_full: neg_cache holds {neg_cache.negs} negatives per query, negs_num_per_query is {negs}")
+    sq_t = torch.from_numpy(sq).to(dev)
+    cand = torch.cat([neg_cache.rows(sq_t).to(dev), samp], 1)
+    _check_topk_shapes("compute_triplets_full", xq, xb, cand, negs)
+    best = _best_of_sampled(xq, xb, hard_positives_per_query, sq, sq_t, dev)
+    soft, rows = _soft_of_sampled(soft_positives_per_query, sq, sq_t, dev)
+    found, filled = _topk_listed(xq, xb, cand, negs, soft, rows, negs)
+    if sq.size and int(filled.min()) < negs:
+        raise ValueError(_TOO_FEW)
+    neg_cache.update(sq_t, found)
+    return torch.cat([sq_t.view(-1, 1), best.view(-1, 1), found], 1)
+
+
+def compute_triplets_random(query_features, database_features, sampled_queries_indexes, hard_positives_per_query,
+                            soft_positives_per_query, drawn_negatives, negs_num_per_query=10, device="cuda"):
+    """The triplet table of the reference's `random` mining (compute_triplets_random, :1264-1289): int64 [Q, 2 + negs].
+    drawn_negatives: per sampled query its np.random.choice(database_num, negs + len(soft_positives), replace=False), as a list
+    of arrays or an int64 [Q, W] table padded with -1.  The negatives are the first `negs` entries of each row, in the row's
+    order, that are database rows and not soft positives of the query: np.setdiff1d(draw, soft, assume_unique=True)[:negs].
+    Tensor operations on [Q, W] only; lists and geo.Positives as in compute_triplets_full.  ValueError for duplicate sampled
+    queries and for a draw with fewer than `negs` such entries."""
+    dev = torch.device(device)
+    negs = int(negs_num_per_query)
+    xq = _dev(query_features, dev, torch.float32)
+    xb = _dev(database_features, dev, torch.float32)
+    sq = _sampled_queries("compute_triplets_random", sampled_queries_indexes, xq, hard_positives_per_query, soft_positives_per_query)
+    if negs < 1:
+        raise ValueError(f"compute_triplets_random: negs_num_per_query must be >= 1, got {negs}")
+    if isinstance(drawn_negatives, (list, tuple)):
+        if len(drawn_negatives) != sq.size:
+            raise ValueError(f"compute_triplets_random: {len(drawn_negatives)} draws for {sq.size} sampled queries")
+        host = np.full((sq.size, max([negs] + [len(x) for x in drawn_negatives])), -1, dtype=np.int64)
+        for i, x in enumerate(drawn_negatives):
+            host[i, :len(x)] = np.asarray(x, dtype=np.int64).reshape(-1)
+        drawn_negatives = host
+    drawn = _dev(drawn_negatives, dev, torch.int64)
+    if drawn.dim() != 2 or drawn.shape[0] != sq.size:
+        raise ValueError(f"compute_triplets_random: drawn_negatives must be [{sq.size}, W], got {tuple(drawn.shape)}")
+    sq_t = torch.from_numpy(sq).to(dev)
+    best = _best_of_sampled(xq, xb, hard_positives_per_query, sq, sq_t, dev)
+    soft, rows = _soft_of_sampled(soft_positives_per_query, sq, sq_t, dev)
+    nb = max(int(xb.shape[0]), 1)
+    # membership through ONE ascending key array: (list row) * nb + (database row) over the CSR's in-range entries
+    inside = (soft.indices >= 0) & (soft.indices < nb)
+    keys = (soft.rows() * nb + soft.indices)[inside]
+    keep = (drawn >= 0) & (drawn < xb.shape[0])
+    if keys.numel():
+        mine = rows.view(-1, 1) * nb + drawn.clamp(0, nb - 1)
+        at = torch.searchsorted(keys, mine).clamp(max=keys.numel() - 1)
+        keep &= keys[at] != mine
+    rank = torch.cumsum(keep, 1) - 1                                                # rank among kept entries, in the row's order
+    if sq.size and int(keep.sum(1).min()) < negs:
+        raise ValueError(_TOO_FEW)
+    sel = keep & (rank < negs)
+    out = torch.empty((sq.size, negs), dtype=torch.int64, device=dev)
+    at_row = torch.arange(sq.size, device=dev).view(-1, 1).expand_as(drawn)
+    out[at_row[sel], rank[sel]] = drawn[sel]
+    return torch.cat([sq_t.view(-1, 1), best.view(-1, 1), out], 1)

@@ -878,6 +878,37 @@ int agp_mine_best_positive(const float* xq, int64_t nq, const float* xb, int64_t
                            const int64_t* pos_off, const int64_t* pos_idx, int64_t* out_best,
                            float* out_dist, void* stream);
 
+/* The k nearest DISTINCT database rows out of a per-query candidate table: the search of the `full` mining mode (reference
+ * datasets/datasets_ws_nuscenes.py:1295-1322: every query draws its own sample, removes its soft positives, merges in the
+ * negatives it kept last time and searches that private set, :1250-1258).
+ *   xq fp32 [nq][d], xb fp32 [nb][d];
+ *   cand int64 [nq][ncols]: query q's candidates are the entries of row q, in any order, padded with anything outside [0, nb)
+ *     (-1 by convention);
+ *   row_of_q int64 [nq], excl_off, excl_idx: an exclusion CSR, query q's list being excl_idx[excl_off[r] .. excl_off[r + 1])
+ *     with r = row_of_q[q], ASCENDING without repeats (binary search; the form agp_mine_drop_listed reads).  All three NULL: no
+ *     exclusion; only some of them NULL: AGP_E_BADARG;
+ *   exempt_cols >= 0: columns [0, exempt_cols) of every row are never excluded (the negative cache, which the reference merges
+ *     in AFTER removing the soft positives).
+ * An entry is a VALID candidate when 0 <= r < nb and it is not excluded; every other entry is skipped.  For every query the
+ * result is the k smallest valid candidates under the order (squared L2 distance, database row), both ascending, a row listed
+ * more than once counting once: out_idx int64 [nq][k], nearest first.  The order is total over distinct rows, so the result
+ * does not depend on the order of the columns, and on equal distances the SMALLER ROW comes first -- what faiss's first-wins
+ * rule gives on the ascending array np.unique builds (:1315).
+ * Distances are exact fp64 sums of the squared fp32 differences in a fixed order (two runs give the same bits); out_dist
+ * (optional, fp32 [nq][k]) is that value rounded to fp32.  A candidate whose distance is NOT FINITE (a NaN or infinite
+ * component, or an overflow) sorts behind every finite one, and such candidates are ordered among themselves by row alone;
+ * out_dist reports their distance as it is (inf or NaN).
+ * filled int32 [nq] = the number of distinct valid candidates found, at most k; out_idx[q][filled[q] ..) = -1 and
+ * out_dist[q][filled[q] ..) = FLT_MAX, as agp_mine_best_positive reports an empty list.
+ * 1 <= k <= AGP_MINE_MAX_K, 1 <= ncols <= AGP_MINE_MAX_COLS, d > 0, nq, nb >= 0, nq <= 2^31 - 64; anything else, or a NULL
+ * xq, cand, out_idx, filled (or xb with nb > 0), is AGP_E_BADARG before a launch.  nq == 0: AGP_OK, nothing is launched.
+ * One workgroup per query, no atomics, no allocation or synchronisation, launched on `stream`. */
+#define AGP_MINE_MAX_K 128
+#define AGP_MINE_MAX_COLS 4096
+int agp_mine_topk_listed(const float* xq, int64_t nq, const float* xb, int64_t nb, int d, const int64_t* cand, int ncols,
+                         const int64_t* row_of_q, const int64_t* excl_off, const int64_t* excl_idx, int exempt_cols, int k,
+                         int64_t* out_idx, float* out_dist, int32_t* filled, void* stream);
+
 /* ---------------------------------------------------------------------- geo */
 
 /* Geographic positives as a device CSR (csrc/geo.hip, agplace_amd/geo.py): query q owns the database rows
