@@ -404,7 +404,9 @@ extern "C" int agp_split_f32(const float* x, void* hi, void* lo, int64_t n, int 
 
 extern "C" int agp_split_conv_weight(const float* w, int cout, int cin, int kh, int kw, int dgrad, void* hi, void* lo,
                                      void* stream) {
-    if (!w || !hi || !lo || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || (dgrad ? cout : cin) % 8) return AGP_E_BADARG;
+    // dgrad 2 is the kernel's both-planes mode (agp_split_conv_weight_both), whose second pair this entry does not have
+    if (!w || !hi || !lo || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || (dgrad != 0 && dgrad != 1) || (dgrad ? cout : cin) % 8)
+        return AGP_E_BADARG;
     const int64_t total = (int64_t)(dgrad ? cin : cout) * kh * kw * ((dgrad ? cout : cin) / 8);
     hipLaunchKernelGGL(split_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout,
                        cin, kh, kw, dgrad, (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)nullptr, (bf16_t*)nullptr, 0);

@@ -109,7 +109,8 @@ uint32_t* agp_range_flag_get(void);
 int agp_split_f32(const float* x, void* hi, void* lo, int64_t n, int fmt, void* stream);
 /* Training: conv weights straight from the parameter layout w[cout][cin][kh][kw] (fp32) to split-bf16 planes in the
  * kernels' layout, one launch.  dgrad = 0: [cout][kh][kw][cin] (agp_conv2d_fwd); dgrad = 1: the flipped, transposed
- * weights [cin][kh][kw][cout] of the data-gradient conv.  Channels of the output's innermost dimension % 8 == 0. */
+ * weights [cin][kh][kw][cout] of the data-gradient conv.  Channels of the output's innermost dimension % 8 == 0.
+ * Any other dgrad: AGP_E_BADARG, nothing is written. */
 int agp_split_conv_weight(const float* w, int cout, int cin, int kh, int kw, int dgrad, void* hi, void* lo, void* stream);
 /* Both plane pairs of agp_split_conv_weight -- the forward conv's (hi, lo) and its data-gradient conv's (hi_d, lo_d) -- in ONE
  * launch (cin % 8 == 0 and cout % 8 == 0): a training step needs both for every conv, once per weight version. */
