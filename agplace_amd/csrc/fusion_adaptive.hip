@@ -1,21 +1,26 @@
-// Adaptive Dormand-Prince 5(4) solver ('dopri5') for the Neural-ODE blocks FCODE(256) and FCODE(384), forward and backward
-// (the 384-column kernels, which cannot keep W in registers, follow the 256-column ones below).
+// Adaptive Dormand-Prince 5(4) solver ('dopri5') for the Neural-ODE blocks FCODE(256) and FCODE(384), forward and backward.
 // The algorithm is stated in DESIGN.md section 2 ("Adaptive solver") and restated in fp64 by tests/dopri5_ref.py.
 //
-// Forward: ONE launch of ONE persistent workgroup (16 waves) per solve.  torchdiffeq's step control couples the whole
-// batch (one error norm over all b*256 elements), so a workgroup per 16 rows would have to wait for the others at
-// every attempted step; a single workgroup needs nothing but its own barriers.  W's split-bf16 MFMA fragments stay in
-// registers as in fcode_kernel (fusion.hip; the state has a third plane here, see store_state3); the workgroup walks the ceil(b/16) row tiles for every stage.  y and the
-// seven stage derivatives live in a caller-supplied ring in global memory (L2-resident); a lane only ever re-reads the
-// addresses it wrote itself (same row, same four features), so the ring needs no fence.  Ring entry n holds
-// [y, k1 .. k7] of the attempt that starts from accepted step n; stage 7 writes y1 and k7 also to entry n + 1 as its
-// (y, k1) -- FSAL -- so accepting a step is `++n` and rejecting it leaves entry n as it was.  With a trajectory the
-// ring has max_steps + 1 entries and IS the record the backward reads; without one it has two.
+// Forward: ONE launch of ONE persistent workgroup per solve.  torchdiffeq's step control couples the whole batch (one error
+// norm over all b*D elements), so a workgroup per 16 rows would have to wait for the others at every attempted step; a
+// single workgroup needs nothing but its own barriers.  There is ONE driver, fcode_adaptive_kernel<E, ACT>: step control,
+// tableau arithmetic, ring and control block exist once.  What differs between the widths is a column engine E (below,
+// before the driver): Resident256 keeps both split-bf16 planes of W in registers as fcode_kernel does (fusion.hip), 16 waves,
+// a lane owns 4 features of a row; Streamed384 cannot (576 KiB of planes), keeps `hi`, streams `lo`, 8 waves, a lane owns
+// 3 x 4 features.  At either width the state has a third bf16 plane (see store_state3) and the workgroup walks the
+// ceil(b/16) row tiles for every stage.  y and the seven stage derivatives live in a caller-supplied ring in global memory
+// (L2-resident); a lane only ever re-reads the addresses it wrote itself (same row, same features), so the ring needs no
+// fence.  Ring entry n holds [y, k1 .. k7] of the attempt that starts from accepted step n; stage 7 writes y1 and k7 also
+// to entry n + 1 as its (y, k1) -- FSAL -- so accepting a step is `++n` and rejecting it leaves entry n as it was.  With a
+// trajectory the ring has max_steps + 1 entries and IS the record the backward reads; without one it has two.
 // Time, step size, norms, the error ratio and the step factor are fp64.  Norms are reduced in a fixed order (a lane over
-// its tiles in index order, butterfly over the wave, the 16 waves in wave order): two runs give the same bits.
+// its row tiles, feature tiles and elements in index order, butterfly over the wave, the waves in wave order): two runs
+// give the same bits.
 //
 // Backward: rows are independent once the step sizes are fixed: one workgroup per 16 rows like
-// fcode_bwd_state_kernel (fusion_bwd.hip), step count and step sizes read from the control block in DEVICE memory.
+// fcode_bwd_state_kernel (fusion_bwd.hip), step count and step sizes read from the control block in DEVICE memory.  The
+// two widths keep their own recursions (where the seven stage adjoints live differs in substance); the per-step constants,
+// the read of the solve's outcome and act' are shared, and so are the three sum kernels, templated on the width.
 #include <cstddef>
 #include <type_traits>
 #include "fusion_common.hpp"
@@ -96,8 +101,8 @@ constexpr int AD = 256, AKS = AD / 32, AYRB = AD * 2 + 16;
 // dt sum CE_j k_j is a cancelling sum of them: at a ratio of 0.1 and tol = 1e-4 it was mostly that noise (step sizes 40 %
 // off the fp64 restatement's on the device).  W keeps its two resident planes: their rounding is the same at every
 // stage, i.e. a slightly different but smooth right-hand side, which the estimate is indifferent to.
-__device__ __forceinline__ void store_state3(char* yhi, char* ymid, char* ylo, int yrb, int lane, int wave, const f32x4& v) {
-    const int off = (lane & 15) * yrb + (wave * 16 + (lane >> 4) * 4) * 2;
+// (hi = this lane's four features in the `hi` plane; `mid` and `lo` lie plane_bytes and 2 plane_bytes above it)
+__device__ __forceinline__ void store_state3(char* hi, int plane_bytes, const f32x4& v) {
     bf16_t h[4], m[4], l[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -106,9 +111,9 @@ __device__ __forceinline__ void store_state3(char* yhi, char* ymid, char* ylo, i
         m[r] = f2bf(r1);
         l[r] = f2bf(r1 - bf2f(m[r]));
     }
-    *(u32x2*)(yhi + off) = u32x2{pack2(h[0], h[1]), pack2(h[2], h[3])};
-    *(u32x2*)(ymid + off) = u32x2{pack2(m[0], m[1]), pack2(m[2], m[3])};
-    *(u32x2*)(ylo + off) = u32x2{pack2(l[0], l[1]), pack2(l[2], l[3])};
+    *(u32x2*)hi = u32x2{pack2(h[0], h[1]), pack2(h[2], h[3])};
+    *(u32x2*)(hi + plane_bytes) = u32x2{pack2(m[0], m[1]), pack2(m[2], m[3])};
+    *(u32x2*)(hi + 2 * plane_bytes) = u32x2{pack2(l[0], l[1]), pack2(l[2], l[3])};
 }
 template <int KS>
 __device__ __forceinline__ f32x4 mfma_resident5(const bf16x8 (&wh)[KS], const bf16x8 (&wl)[KS], const char* yhi,
@@ -129,6 +134,84 @@ __device__ __forceinline__ f32x4 mfma_resident5(const bf16x8 (&wh)[KS], const bf
     return (a0 + a1) + a2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The work shape at 384 columns (the forward's Streamed384 engine and fcode_adaptive_wide_bwd_kernel).  Both split-bf16 planes
+// of a 384 x 384 W are 576 KiB, more than a CU's register file, so the shape is fcode_wide_kernel's (fusion_wide.hip): a
+// workgroup of 8 waves, wave w owns the three 16-feature tiles [48 w, 48 w + 48) over the full K; the 36 `hi` fragments stay
+// in registers (144), the `lo` fragments of the same (tile, K-step) pairs are streamed from L2 through a ring of XRING
+// K-steps, in the fragment order of ops.fcode_wide_planes; no K split, hence no cross-wave sum and ONE barrier per
+// evaluation and row tile.  A lane owns twelve features of a row here (row l & 15 of a tile, features
+// 48 w + 16 t + 4 (l >> 4) + r), not four.
+constexpr int XD = 384, XT = 512, XKS = XD / 32, XTILES = 3, XRING = 3, XYRB = XD * 2 + 16, XWAVES = XT / 64;
+constexpr int XPLANES_FWD = 2 * 3 * FROWS * XYRB;      // 75264 B: [buf][plane hi, mid, lo]; more than 64 KB (agp_lds_attr)
+constexpr int XPLANES_BWD = 2 * 2 * FROWS * XYRB;      // 50176 B: [buf][plane hi, lo]
+constexpr int XLDS_FWD = XPLANES_FWD + XD * 4;         // + the bias
+
+// a lane's share of one 16-row tile: four features in each of its N feature tiles
+template <int N>
+struct Tiles {
+    f32x4 t[N];
+};
+using Tiles3 = Tiles<XTILES>;
+
+// acc[t] = sum_k W[48 w + 16 t + ..][k] * state[row][k] on the planes in LDS: NP = 3 the forward's five products
+// W_hi (y_hi + y_mid + y_lo) + W_lo (y_hi + y_mid), NP = 2 the backward's three, W_hi (g_hi + g_lo) + W_lo g_hi.  One chain
+// per tile as in fcode_wide_kernel (a second one costs scratch), the tiles interleaved, K-steps ascending -- a fixed order.
+// (The pointer is made opaque once per evaluation, in ring_prime, and once per K-step: W is loop-invariant, and a compiler
+// that knows it hoists all 36 `lo` fragments out of the step loop.)
+template <int NP>
+__device__ __forceinline__ Tiles3 mfma_streamed(const bf16x8 (&wh)[XKS][XTILES], const bf16x8* fl, const char* planes,
+                                                bf16x8 (&ring)[XRING][XTILES], int boff) {
+    const bf16x8* fp = fl;
+    const char* hi = planes;
+    const char* mid = planes + FROWS * XYRB;
+    const char* lo = planes + (NP - 1) * FROWS * XYRB;
+    f32x4 as[XTILES];
+#pragma unroll
+    for (int t = 0; t < XTILES; ++t) as[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < XKS; ++ks) {
+        const bf16x8 bh = *(const bf16x8*)(hi + boff + ks * 64);
+        const bf16x8 bl = *(const bf16x8*)(lo + boff + ks * 64);
+#pragma unroll
+        for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bl, as[t], 0, 0, 0);
+        if constexpr (NP == 3) {
+            const bf16x8 bm = *(const bf16x8*)(mid + boff + ks * 64);
+#pragma unroll
+            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bm, as[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bh, as[t], 0, 0, 0);
+            // (the streamed plane last: its loads have nine more MFMAs to arrive)
+#pragma unroll
+            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ks % XRING][t], bm, as[t], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bh, as[t], 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ks % XRING][t], bh, as[t], 0, 0, 0);
+        if (ks + XRING < XKS) {
+            asm volatile("" : "+v"(fp));
+#pragma unroll
+            for (int t = 0; t < XTILES; ++t) ring[ks % XRING][t] = fp[((ks + XRING) * XTILES + t) * 64];
+        }
+    }
+    Tiles3 o;
+#pragma unroll
+    for (int t = 0; t < XTILES; ++t) o.t[t] = as[t];
+    return o;
+}
+// the first XRING K-steps of an evaluation's `lo` fragments: issued BEFORE the barrier that publishes the new state
+__device__ __forceinline__ void ring_prime(const bf16x8* fl, bf16x8 (&ring)[XRING][XTILES]) {
+    const bf16x8* fp = fl;
+    asm volatile("" : "+v"(fp));
+#pragma unroll
+    for (int c = 0; c < XRING; ++c)
+#pragma unroll
+        for (int t = 0; t < XTILES; ++t) ring[c][t] = fp[(c * XTILES + t) * 64];
+}
+
+
 // per-attempt constants, written by thread 0 and read by every wave into scalar registers: the products of dt with the
 // tableau.  (Computed by every lane they are hoisted out of the step loop as 50 fp64 values and spilled.)
 struct StepCoef {
@@ -148,54 +231,135 @@ __device__ __forceinline__ void publish_step(StepCoef& c, double dt) {
 #pragma unroll
     for (int j = 0; j < 6; ++j) c.cs[j] = (float)(dt * DP_A[6][j]);
 }
+// ---- The forward's two column engines: what differs between the widths, i.e. where W lives, how a tile of the state gets
+// into LDS and how f is evaluated on it.  put(t, v) writes this lane's feature tile t of the state the next evaluation reads
+// (three bf16 planes, double-buffered); feval<ACT>() is act(W state + bias) on this lane's features of the 16 rows, behind
+// the one barrier that publishes the put()s.  An engine knows nothing of the solver: no tableau, no step control.
 
-template <int ACT>
-__global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restrict__ x, const float* __restrict__ add1,
-                                                            const float* __restrict__ add2,
-                                                            const bf16_t* __restrict__ w_hi,
-                                                            const bf16_t* __restrict__ w_lo,
-                                                            const float* __restrict__ bias, int b, double rtol,
-                                                            double atol, int max_steps, float* ring, int nring,
-                                                            float* __restrict__ yout, OdeCtrl* __restrict__ ctrl) {
-    __shared__ __attribute__((aligned(16))) char smem[2 * 3 * FROWS * AYRB];   // [buf][plane]
-    __shared__ double red[2][16];
-    __shared__ StepCoef coef;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nf = wave * 16 + (lane >> 4) * 4;
-    const int nt = (b + FROWS - 1) / FROWS;
-    const double count = (double)b * AD;
-    const float rtolf = (float)rtol, atolf = (float)atol;
-
+// 256 columns: both planes of W resident (64 registers), 16 waves of 16 features each, the bias in registers, static LDS
+struct Resident256 {
+    static constexpr int D = AD, THREADS = FT, TILES = 1, WAVES = FT / 64, LDS_DYNAMIC = 0;
+    static constexpr int BUF = 3 * FROWS * AYRB;      // [plane hi, mid, lo] of one buffer
+    using Plane = const bf16_t*;                      // a row-major [256][256] plane of ops.LinearWeights
     bf16x8 wh[AKS], wl[AKS];
-    {
+    f32x4 bia;
+    char* smem;
+    int lane, nf, buf;      // nf: this lane's first feature
+    __device__ __forceinline__ void init(Plane w_hi, Plane w_lo, const float* bias, int, int lane_, int wave) {
+        __shared__ __attribute__((aligned(16))) char planes[2 * BUF];
+        smem = planes;
+        lane = lane_;
+        buf = 0;
+        nf = wave * 16 + (lane >> 4) * 4;
         const size_t wo = (size_t)(wave * 16 + (lane & 15)) * AD + (lane >> 4) * 8;
 #pragma unroll
         for (int ks = 0; ks < AKS; ++ks) {
             wh[ks] = *(const bf16x8*)(w_hi + wo + ks * 32);
             wl[ks] = *(const bf16x8*)(w_lo + wo + ks * 32);
         }
-    }
-    f32x4 bia;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) bia[r] = bias ? bias[nf + r] : 0.f;
-
-    int buf = 0;
-    auto feval = [&](const f32x4& state) -> f32x4 {
-        char* hi = smem + buf * (3 * FROWS * AYRB);
-        char* mid = hi + FROWS * AYRB;
-        char* lo = mid + FROWS * AYRB;
-        store_state3(hi, mid, lo, AYRB, lane, wave, state);
+        for (int r = 0; r < 4; ++r) bia[r] = bias ? bias[nf + r] : 0.f;
+    }
+    __device__ __forceinline__ void put(int, const f32x4& v) {
+        store_state3(smem + buf * BUF + (lane & 15) * AYRB + nf * 2, FROWS * AYRB, v);
+    }
+    template <int ACT>
+    __device__ __forceinline__ Tiles<1> feval() {
+        const char* hi = smem + buf * BUF;
         __syncthreads();
-        f32x4 z = mfma_resident5<AKS>(wh, wl, hi, mid, lo, AYRB, lane);
+        const f32x4 z = mfma_resident5<AKS>(wh, wl, hi, hi + FROWS * AYRB, hi + 2 * FROWS * AYRB, AYRB, lane);
         buf ^= 1;
-        return act4<ACT>(z + bia);
-    };
-    // ring[entry][sub][row][256]: sub 0 = y, 1 + j = k_{j+1}.  A uniform base plus this lane's 32-bit offset.
-    const size_t plane = (size_t)b * AD;
-    const int loff = (lane & 15) * AD + nf;
+        return {{act4<ACT>(z + bia)}};
+    }
+};
+
+// 384 columns: `hi` resident (144 registers), `lo` streamed, 8 waves of three 16-feature tiles each, the bias in LDS (twelve
+// more registers are not to be had), dynamic LDS: the state planes exceed 64 KB (agp_lds_attr)
+struct Streamed384 {
+    static constexpr int D = XD, THREADS = XT, TILES = XTILES, WAVES = XWAVES, LDS_DYNAMIC = XLDS_FWD;
+    static constexpr int BUF = 3 * FROWS * XYRB;
+    using Plane = const bf16x8*;                      // a plane in fragment order (ops.fcode_wide_planes)
+    bf16x8 wh[XKS][XTILES];
+    const bf16x8* fl;
+    char* smem;
+    float* sbias;
+    int nf, soff, boff, buf;      // nf: this lane's first feature of tile 0; tile t at + 16 t
+    __device__ __forceinline__ void init(Plane wf_hi, Plane wf_lo, const float* bias, int tid, int lane, int wave) {
+        extern __shared__ __attribute__((aligned(16))) char planes[];      // XLDS_FWD: the state planes [buf][plane], the bias
+        smem = planes;
+        sbias = (float*)(planes + XPLANES_FWD);
+        buf = 0;
+        nf = wave * (16 * XTILES) + (lane >> 4) * 4;
+        soff = (lane & 15) * XYRB + nf * 2;                 // where this lane's 4 features of tile 0 go in a plane
+        boff = (lane & 15) * XYRB + (lane >> 4) * 16;       // this lane's B fragment of K-step 0
+        const bf16x8* fh = wf_hi + (size_t)wave * (XKS * XTILES * 64) + lane;
+        fl = wf_lo + (size_t)wave * (XKS * XTILES * 64) + lane;
+#pragma unroll
+        for (int ks = 0; ks < XKS; ++ks)
+#pragma unroll
+            for (int t = 0; t < XTILES; ++t) wh[ks][t] = fh[(ks * XTILES + t) * 64];
+        if (tid < XD) sbias[tid] = bias ? bias[tid] : 0.f;     // (published by the first evaluation's barrier)
+    }
+    __device__ __forceinline__ void put(int t, const f32x4& v) { store_state3(smem + buf * BUF + soff + 32 * t, FROWS * XYRB, v); }
+    template <int ACT>
+    __device__ __forceinline__ Tiles3 feval() {
+        bf16x8 lring[XRING][XTILES];
+        ring_prime(fl, lring);
+        __syncthreads();
+        Tiles3 z = mfma_streamed<3>(wh, fl, smem + buf * BUF, lring, boff);
+        buf ^= 1;
+#pragma unroll
+        for (int t = 0; t < XTILES; ++t) {
+            z.t[t] = act4<ACT>(z.t[t] + *(const f32x4*)(sbias + nf + 16 * t));
+            __builtin_amdgcn_sched_barrier(0);      // one tile at a time (twelve interleaved sigmoid divisions cost scratch)
+        }
+        return z;
+    }
+};
+
+// ---- The forward driver, once for both widths: first step size, stages 1 .. 5, stage 7 with the error ratio, accept / reject
+// and the step factor, the interpolant at t = 1, the NaN fill of a failed solve, the control block.  Its shape is the one a
+// lane with several feature tiles needs: the stage combinations run one feature tile at a time (put), then ONE evaluation
+// (feval), and stage 7 forms its error sum AFTER the evaluation from the ring (y1 is already in entry n + 1), so nothing
+// state-sized waits in registers across an evaluation; with TILES = 1 the same loops are the four-features-per-lane walk.
+// The sched_barrier(0) after each feature tile and the scalar (readfirstlane) coefficients are there because their removal
+// spilled at 384 columns.
+// Two places know that a lane may own a single feature tile (if constexpr, TILES == 1); both were forced by a measurement
+// of the plain form at 256 columns (MI355X, relu, tol 1e-3, captured solve; the two-kernel build 115.89 / 346.96 us at
+// b = 16 / 64, spread 0.05 / 0.30):
+//   - stage 7 HOLDS y, y1 and the error sum of stages 1 .. 6 in registers across the evaluation and stores y1 behind it.
+//     Read back from the ring -- what a lane with three tiles must do -- the solve took 116.95 / 372.36 us (+0.9 / +7.3 %:
+//     eight more 16-byte loads per lane, row tile and attempt); held, but with y1 stored ahead of the evaluation, 347.80 us
+//     at b = 64 (the store then sits right before the evaluation's barrier).  As it stands: 109.39 / 337.04 us.
+//   - the interpolant's seven weights are computed by every lane, not one per thread through LDS: sbeta would add 32 B to
+//     the 256 engine's static LDS (51168 B against 51136).  (Behind the step loop the per-lane form does not spill as it
+//     did inside it; at 384 columns the weights keep going through LDS, as they did.)
+template <class E, int ACT>
+__global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float* __restrict__ x, const float* __restrict__ add1,
+                                                                   const float* __restrict__ add2,
+                                                                   typename E::Plane __restrict__ w_hi,
+                                                                   typename E::Plane __restrict__ w_lo,
+                                                                   const float* __restrict__ bias, int b, double rtol,
+                                                                   double atol, int max_steps, float* ring, int nring,
+                                                                   float* __restrict__ yout, OdeCtrl* __restrict__ ctrl) {
+    constexpr int D = E::D, TILES = E::TILES;
+    __shared__ double red[2][E::WAVES];
+    __shared__ StepCoef coef;
+    __shared__ float sbeta[7];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nt = (b + FROWS - 1) / FROWS;
+    const double count = (double)b * D;
+    const float rtolf = (float)rtol, atolf = (float)atol;
+
+    E eng;
+    eng.init(w_hi, w_lo, bias, tid, lane, wave);
+    auto feval = [&]() -> Tiles<TILES> { return eng.template feval<ACT>(); };
+    // ring[entry][sub][row][D]: sub 0 = y, 1 + j = k_{j+1}.  A uniform base plus this lane's 32-bit offset; tile t at + 16 t.
+    const size_t plane = (size_t)b * D;
+    const int loff = (lane & 15) * D + eng.nf;
     auto at = [&](int entry, int sub, int T) -> float* {
-        return ring + ((size_t)(entry * 8 + sub) * plane + (size_t)T * (FROWS * AD)) + loff;
+        return ring + ((size_t)(entry * 8 + sub) * plane + (size_t)T * (FROWS * D)) + loff;
     };
     // sums of two per-thread values over the workgroup, the same bits in every thread
     auto block_sum2 = [&](double& u, double& v) {
@@ -205,7 +369,7 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
         if (lane == 0) { red[0][wave] = u; red[1][wave] = v; }
         __syncthreads();
         u = 0.; v = 0.;
-        for (int w = 0; w < 16; ++w) { u += red[0][w]; v += red[1][w]; }
+        for (int w = 0; w < E::WAVES; ++w) { u += red[0][w]; v += red[1][w]; }
     };
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
@@ -213,22 +377,32 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
     double sq0 = 0., sq1 = 0.;
     for (int T = 0; T < nt; ++T) {
         const bool live = T * FROWS + (lane & 15) < b;
-        f32x4 yv = zero4;
-        if (live) {
-            const size_t g = (size_t)T * (FROWS * AD) + loff;
-            yv = *(const f32x4*)(x + g);
-            if (add1) yv += *(const f32x4*)(add1 + g);
-            if (add2) yv += *(const f32x4*)(add2 + g);
-        }
-        const f32x4 f0 = feval(yv);
-        if (live) {
-            *(f32x4*)at(0, 0, T) = yv;
-            *(f32x4*)at(0, 1, T) = f0;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float sc = atolf + fabsf(yv[r]) * rtolf;
-                const double a = (double)(yv[r] / sc), c = (double)(f0[r] / sc);
-                sq0 += a * a; sq1 += c * c;
+        for (int t = 0; t < TILES; ++t) {
+            f32x4 yv = zero4;
+            if (live) {
+                const size_t g = (size_t)T * (FROWS * D) + loff + 16 * t;
+                yv = *(const f32x4*)(x + g);
+                if (add1) yv += *(const f32x4*)(add1 + g);
+                if (add2) yv += *(const f32x4*)(add2 + g);
+                *(f32x4*)(at(0, 0, T) + 16 * t) = yv;
+            }
+            eng.put(t, yv);
+            __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
+        }
+        const Tiles<TILES> f0 = feval();
+        if (live) {
+#pragma unroll
+            for (int t = 0; t < TILES; ++t) {
+                const f32x4 yv = *(const f32x4*)(at(0, 0, T) + 16 * t);
+                *(f32x4*)(at(0, 1, T) + 16 * t) = f0.t[t];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float sc = atolf + fabsf(yv[r]) * rtolf;
+                    const double a = (double)(yv[r] / sc), c = (double)(f0.t[t][r] / sc);
+                    sq0 += a * a; sq1 += c * c;
+                }
+                __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
             }
         }
     }
@@ -240,15 +414,25 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
         const float h0f = uniform_f((float)h0);
         for (int T = 0; T < nt; ++T) {
             const bool live = T * FROWS + (lane & 15) < b;
-            f32x4 yv = zero4, f0 = zero4;
-            if (live) { yv = *(const f32x4*)at(0, 0, T); f0 = *(const f32x4*)at(0, 1, T); }
-            const f32x4 f1 = feval(yv + h0f * f0);
+#pragma unroll
+            for (int t = 0; t < TILES; ++t) {
+                f32x4 s = zero4;
+                if (live) s = *(const f32x4*)(at(0, 0, T) + 16 * t) + h0f * *(const f32x4*)(at(0, 1, T) + 16 * t);
+                eng.put(t, s);
+                __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
+            }
+            const Tiles<TILES> f1 = feval();
             if (live) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float sc = atolf + fabsf(yv[r]) * rtolf;
-                    const double a = (double)((f1[r] - f0[r]) / sc);
-                    sq2 += a * a;
+                for (int t = 0; t < TILES; ++t) {
+                    const f32x4 yv = *(const f32x4*)(at(0, 0, T) + 16 * t), f0 = *(const f32x4*)(at(0, 1, T) + 16 * t);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float sc = atolf + fabsf(yv[r]) * rtolf;
+                        const double a = (double)((f1.t[t][r] - f0[r]) / sc);
+                        sq2 += a * a;
+                    }
+                    __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
                 }
             }
         }
@@ -270,17 +454,25 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
         for (int j = 0; j < I; ++j) cf[j] = uniform_f(coef.a[I - 1][j]);
         for (int T = 0; T < nt; ++T) {
             const bool live = T * FROWS + (lane & 15) < b;
-            f32x4 s = zero4;
-            if (live) {
-                f32x4 kk[I];
-                s = *(const f32x4*)at(cur, 0, T);
 #pragma unroll
-                for (int j = 0; j < I; ++j) kk[j] = *(const f32x4*)at(cur, 1 + j, T);
+            for (int t = 0; t < TILES; ++t) {
+                f32x4 s = zero4;
+                if (live) {
+                    f32x4 kk[I];
+                    s = *(const f32x4*)(at(cur, 0, T) + 16 * t);
 #pragma unroll
-                for (int j = 0; j < I; ++j) s += cf[j] * kk[j];
+                    for (int j = 0; j < I; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
+#pragma unroll
+                    for (int j = 0; j < I; ++j) s += cf[j] * kk[j];
+                }
+                eng.put(t, s);
+                __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
             }
-            const f32x4 k = feval(s);
-            if (live) *(f32x4*)at(cur, 1 + I, T) = k;
+            const Tiles<TILES> k = feval();
+            if (live) {
+#pragma unroll
+                for (int t = 0; t < TILES; ++t) *(f32x4*)(at(cur, 1 + I, T) + 16 * t) = k.t[t];
+            }
         }
     };
 
@@ -306,34 +498,68 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
             for (int j = 0; j < 6; ++j) cs[j] = uniform_f(coef.cs[j]);
 #pragma unroll
             for (int j = 0; j < 7; ++j) ce[j] = uniform_d(coef.ce[j]);
+            constexpr bool HOLD7 = TILES == 1;      // (see the kernel's head)
+            // the cancelling sum in fp64, stages 1 .. 6
+            auto err6 = [&](const f32x4 (&kk)[6], int r) -> double {
+                double e = 0.;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) e += ce[j] * (double)kk[j][r];
+                return e;
+            };
             for (int T = 0; T < nt; ++T) {
                 const bool live = T * FROWS + (lane & 15) < b;
-                f32x4 yv = zero4, y1 = zero4;
-                double e[4] = {0., 0., 0., 0.};
-                if (live) {
-                    yv = *(const f32x4*)at(cur, 0, T);
-                    f32x4 kk[6];
+                [[maybe_unused]] f32x4 yv_held = zero4, y1_held = zero4;
+                [[maybe_unused]] double e_held[4] = {0., 0., 0., 0.};
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)at(cur, 1 + j, T);
-                    y1 = yv;
+                for (int t = 0; t < TILES; ++t) {
+                    f32x4 y1 = zero4;
+                    if (live) {
+                        f32x4 kk[6];
+                        const f32x4 yv = *(const f32x4*)(at(cur, 0, T) + 16 * t);
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) y1 += cs[j] * kk[j];
+                        for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
+                        y1 = yv;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
+                        for (int j = 0; j < 6; ++j) y1 += cs[j] * kk[j];
+                        if constexpr (HOLD7) {
+                            yv_held = yv;
+                            y1_held = y1;
 #pragma unroll
-                        for (int j = 0; j < 6; ++j) e[r] += ce[j] * (double)kk[j][r];
+                            for (int r = 0; r < 4; ++r) e_held[r] = err6(kk, r);
+                        } else {
+                            *(f32x4*)(at(nxt, 0, T) + 16 * t) = y1;
+                        }
+                    }
+                    eng.put(t, y1);
+                    __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
                 }
-                const f32x4 k7 = feval(y1);
+                const Tiles<TILES> k7 = feval();
                 if (live) {
-                    *(f32x4*)at(cur, 7, T) = k7;
-                    *(f32x4*)at(nxt, 0, T) = y1;
-                    *(f32x4*)at(nxt, 1, T) = k7;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        // the cancelling sum in fp64, the quotient in fp32 (1e-7 relative: nothing next to the k's own rounding)
-                        const float ef = (float)(e[r] + ce[6] * (double)k7[r]);
-                        const double q = (double)(ef / (atolf + rtolf * fmaxf(fabsf(yv[r]), fabsf(y1[r]))));
-                        sq += q * q;
+                    for (int t = 0; t < TILES; ++t) {
+                        *(f32x4*)(at(cur, 7, T) + 16 * t) = k7.t[t];
+                        *(f32x4*)(at(nxt, 1, T) + 16 * t) = k7.t[t];
+                        f32x4 yv = yv_held, y1 = y1_held;
+                        double e[4] = {e_held[0], e_held[1], e_held[2], e_held[3]};
+                        if constexpr (HOLD7) {
+                            *(f32x4*)(at(nxt, 0, T) + 16 * t) = y1;
+                        } else {
+                            f32x4 kk[6];
+                            yv = *(const f32x4*)(at(cur, 0, T) + 16 * t);
+                            y1 = *(const f32x4*)(at(nxt, 0, T) + 16 * t);
+#pragma unroll
+                            for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) e[r] = err6(kk, r);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            // the quotient in fp32 (1e-7 relative: nothing next to the k's own rounding)
+                            const float ef = (float)(e[r] + ce[6] * (double)k7.t[t][r]);
+                            const double q = (double)(ef / (atolf + rtolf * fmaxf(fabsf(yv[r]), fabsf(y1[r]))));
+                            sq += q * q;
+                        }
+                        __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
                     }
                 }
             }
@@ -352,25 +578,7 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
             if (tid == 0) ctrl->dt[acc] = dt;
             const double t1 = t + dt;
             ++acc;
-            if (t1 >= 1.) {     // the quartic interpolant of this step at time 1
-                const double xs = (1. - t) / (t1 - t);
-                float be[7];
-#pragma unroll
-                for (int j = 0; j < 7; ++j) be[j] = uniform_f((float)(dt * dp_beta(j, xs)));
-                for (int T = 0; T < nt; ++T) {
-                    if (T * FROWS + (lane & 15) < b) {
-                        f32x4 o = *(const f32x4*)at(cur, 0, T);
-                        f32x4 kk[7];
-#pragma unroll
-                        for (int j = 0; j < 7; ++j) kk[j] = *(const f32x4*)at(cur, 1 + j, T);
-#pragma unroll
-                        for (int j = 0; j < 7; ++j) o += be[j] * kk[j];
-                        *(f32x4*)(yout + (size_t)T * (FROWS * AD) + loff) = o;
-                    }
-                }
-                t_end = t1;
-                break;
-            }
+            if (t1 >= 1.) { t_end = t1; break; }
             t = t1;
         } else {
             ++rej;
@@ -383,14 +591,49 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
         }
         __syncthreads();
     }
+    if (status == 0) {     // the quartic interpolant of the last step at time 1 (behind the loop: inside it the quartic's fp64
+                           // constants are hoisted out of the loop and spilled)
+        const double dt = uniform_d(coef.dt);
+        const int cur = __builtin_amdgcn_readfirstlane((acc - 1) % nring);
+        const double xs = (1. - t) / (t_end - t);
+        float be[7];
+        if constexpr (TILES == 1) {      // (see the kernel's head)
+#pragma unroll
+            for (int j = 0; j < 7; ++j) be[j] = uniform_f((float)(dt * dp_beta(j, xs)));
+        } else {     // one weight per thread
+            if (tid < 7) sbeta[tid] = (float)(dt * dp_beta(tid, xs));
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 7; ++j) be[j] = uniform_f(sbeta[j]);
+        }
+        for (int T = 0; T < nt; ++T) {
+            if (T * FROWS + (lane & 15) < b) {
+#pragma unroll
+                for (int tt = 0; tt < TILES; ++tt) {
+                    f32x4 o = *(const f32x4*)(at(cur, 0, T) + 16 * tt);
+                    f32x4 kk[7];
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * tt);
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) o += be[j] * kk[j];
+                    *(f32x4*)(yout + (size_t)T * (FROWS * D) + loff + 16 * tt) = o;
+                    __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
+                }
+            }
+        }
+    }
     if (status != 0) {     // a failed solve must not pass for a result
         const float qnan = __builtin_nanf("");
         for (int T = 0; T < nt; ++T)
-            if (T * FROWS + (lane & 15) < b) *(f32x4*)(yout + (size_t)T * (FROWS * AD) + loff) = f32x4{qnan, qnan, qnan, qnan};
+            if (T * FROWS + (lane & 15) < b) {
+#pragma unroll
+                for (int tt = 0; tt < TILES; ++tt)
+                    *(f32x4*)(yout + (size_t)T * (FROWS * D) + loff + 16 * tt) = f32x4{qnan, qnan, qnan, qnan};
+            }
         t_end = t;
     }
     // the unused tail of the control block is zero: two equal solves leave equal blocks
-    for (int i = tid; i < 3 * max_steps; i += FT)
+    for (int i = tid; i < 3 * max_steps; i += E::THREADS)
         if (i < max_steps ? i >= acc : i - max_steps >= 2 * attempts) ctrl->dt[i] = 0.;
     if (tid == 0) {
         ctrl->status = status;
@@ -400,6 +643,43 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_kernel(const float* __restr
         ctrl->t0 = t;
         ctrl->t1 = t_end;
     }
+}
+
+// ---- Backward.  The two state kernels keep their own recursions (seven stage adjoints in registers at 256 columns, in the
+// workspace at 384); what they and the three sum kernels share is below.
+
+// the outcome of the solve a control block records, as uniform values: its status and its accepted steps, clamped to the cap
+struct Solved {
+    int status, N;
+};
+__device__ __forceinline__ Solved read_solved(const OdeCtrl* ctrl, int max_steps) {
+    const int status = __builtin_amdgcn_readfirstlane(ctrl->status);
+    const int N = __builtin_amdgcn_readfirstlane(ctrl->accepted);
+    return {status, N < 0 ? 0 : (N > max_steps ? max_steps : N)};
+}
+
+// the constants of accepted step n of N into bc[28]: dt A[i][j] at i (i - 1) / 2 + j (i = 1 .. 6, j < i), dt w_j at 21 + j.
+// One constant per thread (computed by every lane they are hoisted as fp64 and spilled), between two barriers: the step
+// before has read its constants, this step's are published.
+__device__ __forceinline__ void publish_bwd_step(float (&bc)[28], const OdeCtrl* ctrl, int n, int N, int tid) {
+    __syncthreads();
+    if (tid < 28) {
+        const double dt = ctrl->dt[n];
+        double c;
+        if (tid < 21) {
+            int i = 1;
+            while ((i + 1) * i / 2 <= tid) ++i;
+            c = DP_A[i][tid - i * (i - 1) / 2];
+        } else {
+            c = DP_CS[tid - 21];
+            if (n == N - 1) {       // the last step ends at its interpolant
+                const double t0 = ctrl->t0, t1 = ctrl->t1;
+                c = dp_beta(tid - 21, (1. - t0) / (t1 - t0));
+            }
+        }
+        bc[tid] = (float)(dt * c);
+    }
+    __syncthreads();
 }
 
 template <int ACT>
@@ -437,9 +717,8 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_bwd_kernel(const float* __r
     const int brow = blockIdx.x * FROWS + (lane & 15);
     const int nf = wave * 16 + (lane >> 4) * 4;
     const bool live = brow < b;
-    const int status = __builtin_amdgcn_readfirstlane(ctrl->status);
-    int N = __builtin_amdgcn_readfirstlane(ctrl->accepted);
-    N = N < 0 ? 0 : (N > max_steps ? max_steps : N);
+    const Solved solved = read_solved(ctrl, max_steps);
+    const int status = solved.status, N = solved.N;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     if (status != 0) {      // the forward returned NaN: so does the backward (row block 0 is the only one the sums read)
         const float qnan = __builtin_nanf("");
@@ -476,23 +755,8 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_bwd_kernel(const float* __r
 
     f32x4 a = live ? *(const f32x4*)(gy + (size_t)brow * AD + nf) : zero4;
     f32x4 g7 = zero4;
-    const double t0 = ctrl->t0, t1 = ctrl->t1;
-    const double xs = (1. - t0) / (t1 - t0);
     for (int n = N - 1; n >= 0; --n) {
-        __syncthreads();          // the step before has read its constants
-        if (tid < 28) {           // one constant per thread (computed by every lane they are hoisted as fp64 and spilled)
-            const double dt = ctrl->dt[n];
-            double c;
-            if (tid < 21) {
-                int i = 1;
-                while ((i + 1) * i / 2 <= tid) ++i;
-                c = DP_A[i][tid - i * (i - 1) / 2];
-            } else {
-                c = n == N - 1 ? dp_beta(tid - 21, xs) : DP_CS[tid - 21];
-            }
-            bc[tid] = (float)(dt * c);
-        }
-        __syncthreads();
+        publish_bwd_step(bc, ctrl, n, N, tid);
         f32x4 gk[7];
 #pragma unroll
         for (int j = 0; j < 7; ++j) gk[j] = uniform_f(bc[21 + j]) * a;
@@ -610,405 +874,6 @@ __global__ __launch_bounds__(256) void adaptive_gb_kernel(const float* __restric
     if (w == 0) out[c] = ((redf[0][lane] + redf[1][lane]) + redf[2][lane]) + redf[3][lane];
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The same solver at 384 columns (agp_fcode_adaptive_wide_fwd / _bwd).  Both split-bf16 planes of a 384 x 384 W are 576 KiB,
-// more than a CU's register file, so the work shape is fcode_wide_kernel's (fusion_wide.hip): ONE workgroup of 8 waves, wave w
-// owns the three 16-feature tiles [48 w, 48 w + 48) over the full K; the 36 `hi` fragments stay in registers (144), the `lo`
-// fragments of the same (tile, K-step) pairs are streamed from L2 through a ring of XRING K-steps, in the fragment order of
-// ops.fcode_wide_planes; no K split, hence no cross-wave sum and ONE barrier per evaluation and row tile.  Everything else is
-// fcode_adaptive_kernel: the row-tile walk, the three-plane state and the five products, the FSAL ring in global memory (a
-// lane re-reads only what it wrote: row l & 15 of a tile, features 48 w + 16 t + 4 (l >> 4) + r), the norms reduced in a fixed
-// order (a lane over its row tiles, feature tiles and elements in index order, butterfly over the wave, the 8 waves in wave
-// order), fp64 step control by thread 0.  A lane owns twelve features of a row here, not four: the stage combinations run one
-// feature tile at a time, and stage 7 forms its error sum AFTER the evaluation from the ring (y1 is already in entry n + 1),
-// so nothing state-sized waits in registers across an evaluation.
-constexpr int XD = 384, XT = 512, XKS = XD / 32, XTILES = 3, XRING = 3, XYRB = XD * 2 + 16, XWAVES = XT / 64;
-constexpr int XPLANES_FWD = 2 * 3 * FROWS * XYRB;      // 75264 B: [buf][plane hi, mid, lo]; more than 64 KB (agp_lds_attr)
-constexpr int XPLANES_BWD = 2 * 2 * FROWS * XYRB;      // 50176 B: [buf][plane hi, lo]
-constexpr int XLDS_FWD = XPLANES_FWD + XD * 4;         // + the bias
-
-struct Tiles3 {
-    f32x4 t[XTILES];
-};
-
-// acc[t] = sum_k W[48 w + 16 t + ..][k] * state[row][k] on the planes in LDS: NP = 3 the forward's five products
-// W_hi (y_hi + y_mid + y_lo) + W_lo (y_hi + y_mid), NP = 2 the backward's three, W_hi (g_hi + g_lo) + W_lo g_hi.  One chain
-// per tile as in fcode_wide_kernel (a second one costs scratch), the tiles interleaved, K-steps ascending -- a fixed order.
-// (The pointer is made opaque once per evaluation, in ring_prime, and once per K-step: W is loop-invariant, and a compiler
-// that knows it hoists all 36 `lo` fragments out of the step loop.)
-template <int NP>
-__device__ __forceinline__ Tiles3 mfma_streamed(const bf16x8 (&wh)[XKS][XTILES], const bf16x8* fl, const char* planes,
-                                                bf16x8 (&ring)[XRING][XTILES], int boff) {
-    const bf16x8* fp = fl;
-    const char* hi = planes;
-    const char* mid = planes + FROWS * XYRB;
-    const char* lo = planes + (NP - 1) * FROWS * XYRB;
-    f32x4 as[XTILES];
-#pragma unroll
-    for (int t = 0; t < XTILES; ++t) as[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks) {
-        const bf16x8 bh = *(const bf16x8*)(hi + boff + ks * 64);
-        const bf16x8 bl = *(const bf16x8*)(lo + boff + ks * 64);
-#pragma unroll
-        for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bl, as[t], 0, 0, 0);
-        if constexpr (NP == 3) {
-            const bf16x8 bm = *(const bf16x8*)(mid + boff + ks * 64);
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bm, as[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bh, as[t], 0, 0, 0);
-            // (the streamed plane last: its loads have nine more MFMAs to arrive)
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ks % XRING][t], bm, as[t], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[ks][t], bh, as[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < XTILES; ++t) as[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring[ks % XRING][t], bh, as[t], 0, 0, 0);
-        if (ks + XRING < XKS) {
-            asm volatile("" : "+v"(fp));
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) ring[ks % XRING][t] = fp[((ks + XRING) * XTILES + t) * 64];
-        }
-    }
-    Tiles3 o;
-#pragma unroll
-    for (int t = 0; t < XTILES; ++t) o.t[t] = as[t];
-    return o;
-}
-// the first XRING K-steps of an evaluation's `lo` fragments: issued BEFORE the barrier that publishes the new state
-__device__ __forceinline__ void ring_prime(const bf16x8* fl, bf16x8 (&ring)[XRING][XTILES]) {
-    const bf16x8* fp = fl;
-    asm volatile("" : "+v"(fp));
-#pragma unroll
-    for (int c = 0; c < XRING; ++c)
-#pragma unroll
-        for (int t = 0; t < XTILES; ++t) ring[c][t] = fp[(c * XTILES + t) * 64];
-}
-
-template <int ACT>
-__global__ __launch_bounds__(XT) void fcode_adaptive_wide_kernel(const float* __restrict__ x, const float* __restrict__ add1,
-                                                                 const float* __restrict__ add2,
-                                                                 const bf16x8* __restrict__ wf_hi,
-                                                                 const bf16x8* __restrict__ wf_lo,
-                                                                 const float* __restrict__ bias, int b, double rtol,
-                                                                 double atol, int max_steps, float* ring, int nring,
-                                                                 float* __restrict__ yout, OdeCtrl* __restrict__ ctrl) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // XLDS_FWD: the state planes [buf][plane], the bias
-    __shared__ double red[2][XWAVES];
-    __shared__ StepCoef coef;
-    __shared__ float sbeta[7];
-    float* const sbias = (float*)(smem + XPLANES_FWD);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nf = wave * (16 * XTILES) + (lane >> 4) * 4;      // this lane's first feature of tile 0
-    const int nt = (b + FROWS - 1) / FROWS;
-    const double count = (double)b * XD;
-    const float rtolf = (float)rtol, atolf = (float)atol;
-
-    const bf16x8* fh = wf_hi + (size_t)wave * (XKS * XTILES * 64) + lane;
-    const bf16x8* fl = wf_lo + (size_t)wave * (XKS * XTILES * 64) + lane;
-    bf16x8 wh[XKS][XTILES];
-#pragma unroll
-    for (int ks = 0; ks < XKS; ++ks)
-#pragma unroll
-        for (int t = 0; t < XTILES; ++t) wh[ks][t] = fh[(ks * XTILES + t) * 64];
-    if (tid < XD) sbias[tid] = bias ? bias[tid] : 0.f;     // (published by the first evaluation's barrier)
-
-    int buf = 0;
-    const int soff = (lane & 15) * XYRB + nf * 2;                 // where this lane's 4 features of tile 0 go in a plane
-    const int boff = (lane & 15) * XYRB + (lane >> 4) * 16;       // this lane's B fragment of K-step 0
-    // one feature tile of the state an evaluation is about to read, as three bf16 planes
-    auto put = [&](int t, const f32x4& v) {
-        char* hi = smem + buf * (3 * FROWS * XYRB) + soff + 32 * t;
-        bf16_t h[4], m[4], l[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            h[r] = f2bf(v[r]);
-            const float r1 = v[r] - bf2f(h[r]);
-            m[r] = f2bf(r1);
-            l[r] = f2bf(r1 - bf2f(m[r]));
-        }
-        *(u32x2*)hi = u32x2{pack2(h[0], h[1]), pack2(h[2], h[3])};
-        *(u32x2*)(hi + FROWS * XYRB) = u32x2{pack2(m[0], m[1]), pack2(m[2], m[3])};
-        *(u32x2*)(hi + 2 * FROWS * XYRB) = u32x2{pack2(l[0], l[1]), pack2(l[2], l[3])};
-    };
-    // f of the state the three put()s wrote
-    auto feval = [&]() -> Tiles3 {
-        bf16x8 lring[XRING][XTILES];
-        ring_prime(fl, lring);
-        __syncthreads();
-        Tiles3 z = mfma_streamed<3>(wh, fl, smem + buf * (3 * FROWS * XYRB), lring, boff);
-        buf ^= 1;
-#pragma unroll
-        for (int t = 0; t < XTILES; ++t) {
-            z.t[t] = act4<ACT>(z.t[t] + *(const f32x4*)(sbias + nf + 16 * t));
-            __builtin_amdgcn_sched_barrier(0);      // one tile at a time (twelve interleaved sigmoid divisions cost scratch)
-        }
-        return z;
-    };
-    // ring[entry][sub][row][384]: sub 0 = y, 1 + j = k_{j+1}.  A uniform base plus this lane's 32-bit offset; tile t at + 16 t.
-    const size_t plane = (size_t)b * XD;
-    const int loff = (lane & 15) * XD + nf;
-    auto at = [&](int entry, int sub, int T) -> float* {
-        return ring + ((size_t)(entry * 8 + sub) * plane + (size_t)T * (FROWS * XD)) + loff;
-    };
-    auto block_sum2 = [&](double& u, double& v) {
-        u = wave_sum_f64(u);
-        v = wave_sum_f64(v);
-        __syncthreads();                      // the previous sums have been read
-        if (lane == 0) { red[0][wave] = u; red[1][wave] = v; }
-        __syncthreads();
-        u = 0.; v = 0.;
-        for (int w = 0; w < XWAVES; ++w) { u += red[0][w]; v += red[1][w]; }
-    };
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-    // ---- first step size (torchdiffeq _select_initial_step, order 4 -> exponent 1/5)
-    double sq0 = 0., sq1 = 0.;
-    for (int T = 0; T < nt; ++T) {
-        const bool live = T * FROWS + (lane & 15) < b;
-#pragma unroll
-        for (int t = 0; t < XTILES; ++t) {
-            f32x4 yv = zero4;
-            if (live) {
-                const size_t g = (size_t)T * (FROWS * XD) + loff + 16 * t;
-                yv = *(const f32x4*)(x + g);
-                if (add1) yv += *(const f32x4*)(add1 + g);
-                if (add2) yv += *(const f32x4*)(add2 + g);
-                *(f32x4*)(at(0, 0, T) + 16 * t) = yv;
-            }
-            put(t, yv);
-            __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-        }
-        const Tiles3 f0 = feval();
-        if (live) {
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) {
-                const f32x4 yv = *(const f32x4*)(at(0, 0, T) + 16 * t);
-                *(f32x4*)(at(0, 1, T) + 16 * t) = f0.t[t];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float sc = atolf + fabsf(yv[r]) * rtolf;
-                    const double a = (double)(yv[r] / sc), c = (double)(f0.t[t][r] / sc);
-                    sq0 += a * a; sq1 += c * c;
-                }
-                __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-            }
-        }
-    }
-    block_sum2(sq0, sq1);
-    const double d0 = sqrt(sq0 / count), d1 = sqrt(sq1 / count);
-    const double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-    double sq2 = 0., unused = 0.;
-    {
-        const float h0f = uniform_f((float)h0);
-        for (int T = 0; T < nt; ++T) {
-            const bool live = T * FROWS + (lane & 15) < b;
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) {
-                f32x4 s = zero4;
-                if (live) s = *(const f32x4*)(at(0, 0, T) + 16 * t) + h0f * *(const f32x4*)(at(0, 1, T) + 16 * t);
-                put(t, s);
-                __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-            }
-            const Tiles3 f1 = feval();
-            if (live) {
-#pragma unroll
-                for (int t = 0; t < XTILES; ++t) {
-                    const f32x4 yv = *(const f32x4*)(at(0, 0, T) + 16 * t), f0 = *(const f32x4*)(at(0, 1, T) + 16 * t);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float sc = atolf + fabsf(yv[r]) * rtolf;
-                        const double a = (double)((f1.t[t][r] - f0[r]) / sc);
-                        sq2 += a * a;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-                }
-            }
-        }
-    }
-    block_sum2(sq2, unused);
-    if (tid == 0) {
-        const double d2 = sqrt(sq2 / count) / h0;
-        const double dm = fmax(d1, d2);
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : (dm < 1e298 ? inv_fifth_root(dm * 100.) : 0.);
-        publish_step(coef, fmin(100. * h0, h1));
-    }
-    __syncthreads();
-
-    // stage I (0-based, 1 .. 5): k_{I+1} = f(y + dt sum_{j < I} A[I][j] k_{j+1})
-    auto stage = [&](auto Ic, int cur) {
-        constexpr int I = decltype(Ic)::value;
-        float cf[I];
-#pragma unroll
-        for (int j = 0; j < I; ++j) cf[j] = uniform_f(coef.a[I - 1][j]);
-        for (int T = 0; T < nt; ++T) {
-            const bool live = T * FROWS + (lane & 15) < b;
-#pragma unroll
-            for (int t = 0; t < XTILES; ++t) {
-                f32x4 s = zero4;
-                if (live) {
-                    f32x4 kk[I];
-                    s = *(const f32x4*)(at(cur, 0, T) + 16 * t);
-#pragma unroll
-                    for (int j = 0; j < I; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
-#pragma unroll
-                    for (int j = 0; j < I; ++j) s += cf[j] * kk[j];
-                }
-                put(t, s);
-                __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-            }
-            const Tiles3 k = feval();
-            if (live) {
-#pragma unroll
-                for (int t = 0; t < XTILES; ++t) *(f32x4*)(at(cur, 1 + I, T) + 16 * t) = k.t[t];
-            }
-        }
-    };
-
-    double t = 0., t_end = 0.;
-    int status = 0, attempts = 0, acc = 0, rej = 0, nfe = 2;
-    for (;;) {
-        const double dt = uniform_d(coef.dt);
-        if (attempts >= max_steps) { status = AGP_ODE_E_MAXSTEPS; break; }
-        if (t + dt == t) { status = AGP_ODE_E_UNDERFLOW; break; }
-        ++attempts;
-        const int cur = __builtin_amdgcn_readfirstlane(acc % nring), nxt = __builtin_amdgcn_readfirstlane((acc + 1) % nring);
-        stage(std::integral_constant<int, 1>{}, cur);
-        stage(std::integral_constant<int, 2>{}, cur);
-        stage(std::integral_constant<int, 3>{}, cur);
-        stage(std::integral_constant<int, 4>{}, cur);
-        stage(std::integral_constant<int, 5>{}, cur);
-        // stage 7: y1, k7 = f(y1) and the error ratio
-        double sq = 0., sqx = 0.;
-        {
-            float cs[6];
-            double ce[7];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) cs[j] = uniform_f(coef.cs[j]);
-#pragma unroll
-            for (int j = 0; j < 7; ++j) ce[j] = uniform_d(coef.ce[j]);
-            for (int T = 0; T < nt; ++T) {
-                const bool live = T * FROWS + (lane & 15) < b;
-#pragma unroll
-                for (int t = 0; t < XTILES; ++t) {
-                    f32x4 y1 = zero4;
-                    if (live) {
-                        f32x4 kk[6];
-                        y1 = *(const f32x4*)(at(cur, 0, T) + 16 * t);
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) y1 += cs[j] * kk[j];
-                        *(f32x4*)(at(nxt, 0, T) + 16 * t) = y1;
-                    }
-                    put(t, y1);
-                    __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-                }
-                const Tiles3 k7 = feval();
-                if (live) {
-#pragma unroll
-                    for (int t = 0; t < XTILES; ++t) {
-                        *(f32x4*)(at(cur, 7, T) + 16 * t) = k7.t[t];
-                        *(f32x4*)(at(nxt, 1, T) + 16 * t) = k7.t[t];
-                        const f32x4 yv = *(const f32x4*)(at(cur, 0, T) + 16 * t), y1 = *(const f32x4*)(at(nxt, 0, T) + 16 * t);
-                        f32x4 kk[6];
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            // the cancelling sum in fp64, the quotient in fp32 (1e-7 relative: nothing next to the k's own rounding)
-                            double e = 0.;
-#pragma unroll
-                            for (int j = 0; j < 6; ++j) e += ce[j] * (double)kk[j][r];
-                            const float ef = (float)(e + ce[6] * (double)k7.t[t][r]);
-                            const double q = (double)(ef / (atolf + rtolf * fmaxf(fabsf(yv[r]), fabsf(y1[r]))));
-                            sq += q * q;
-                        }
-                        __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-                    }
-                }
-            }
-        }
-        nfe += 6;
-        block_sum2(sq, sqx);
-        const double ratio = sqrt(sq / count);
-        if (tid == 0) {
-            double* att = ctrl->dt + max_steps + 2 * (attempts - 1);
-            att[0] = dt;
-            att[1] = ratio;
-        }
-        if (!(ratio == ratio)) { status = AGP_ODE_E_NAN; break; }
-        const bool accept = __builtin_amdgcn_readfirstlane(ratio <= 1. ? 1 : 0) != 0;
-        if (accept) {
-            if (tid == 0) ctrl->dt[acc] = dt;
-            const double t1 = t + dt;
-            ++acc;
-            if (t1 >= 1.) { t_end = t1; break; }
-            t = t1;
-        } else {
-            ++rej;
-        }
-        // every wave has read this attempt's constants (the barriers of stage 7 lie behind their last read)
-        if (tid == 0) {
-            double fac = 10.;
-            if (ratio != 0.) fac = fmin(10., fmax(ratio < 1e300 ? 0.9 * inv_fifth_root(ratio) : 0., ratio < 1. ? 1. : 0.2));
-            publish_step(coef, dt * fac);
-        }
-        __syncthreads();
-    }
-    if (status == 0) {     // the quartic interpolant of the last step at time 1, one weight per thread (behind the loop and not
-                           // in every lane: the quartic's fp64 constants are otherwise hoisted out of the loop and spilled)
-        const double dt = uniform_d(coef.dt);
-        const int cur = __builtin_amdgcn_readfirstlane((acc - 1) % nring);
-        const double xs = (1. - t) / (t_end - t);
-        if (tid < 7) sbeta[tid] = (float)(dt * dp_beta(tid, xs));
-        __syncthreads();
-        float be[7];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) be[j] = uniform_f(sbeta[j]);
-        for (int T = 0; T < nt; ++T) {
-            if (T * FROWS + (lane & 15) < b) {
-#pragma unroll
-                for (int tt = 0; tt < XTILES; ++tt) {
-                    f32x4 o = *(const f32x4*)(at(cur, 0, T) + 16 * tt);
-                    f32x4 kk[7];
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * tt);
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) o += be[j] * kk[j];
-                    *(f32x4*)(yout + (size_t)T * (FROWS * XD) + loff + 16 * tt) = o;
-                    __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
-                }
-            }
-        }
-    }
-    if (status != 0) {     // a failed solve must not pass for a result
-        const float qnan = __builtin_nanf("");
-        for (int T = 0; T < nt; ++T)
-            if (T * FROWS + (lane & 15) < b) {
-#pragma unroll
-                for (int tt = 0; tt < XTILES; ++tt)
-                    *(f32x4*)(yout + (size_t)T * (FROWS * XD) + loff + 16 * tt) = f32x4{qnan, qnan, qnan, qnan};
-            }
-        t_end = t;
-    }
-    // the unused tail of the control block is zero: two equal solves leave equal blocks
-    for (int i = tid; i < 3 * max_steps; i += XT)
-        if (i < max_steps ? i >= acc : i - max_steps >= 2 * attempts) ctrl->dt[i] = 0.;
-    if (tid == 0) {
-        ctrl->status = status;
-        ctrl->accepted = acc;
-        ctrl->rejected = rej;
-        ctrl->f_evals = nfe;
-        ctrl->t0 = t;
-        ctrl->t1 = t_end;
-    }
-}
-
 // The backward at 384 columns: the recursion of fcode_adaptive_bwd_kernel, one workgroup (8 waves) per 16 rows, W^T's `hi`
 // fragments resident and its `lo` fragments streamed, the adjoint product on two planes and three products as there.  A lane
 // owns twelve features of its row, so the seven stage adjoints gk_j (84 registers beside W's 144) do not stay in registers:
@@ -1030,9 +895,8 @@ __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float
     const int brow = blockIdx.x * FROWS + (lane & 15);
     const int nf = wave * (16 * XTILES) + (lane >> 4) * 4;
     const bool live = brow < b;
-    const int status = __builtin_amdgcn_readfirstlane(ctrl->status);
-    int N = __builtin_amdgcn_readfirstlane(ctrl->accepted);
-    N = N < 0 ? 0 : (N > max_steps ? max_steps : N);
+    const Solved solved = read_solved(ctrl, max_steps);
+    const int status = solved.status, N = solved.N;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // this lane's tile 0 within a [rows][384] block: a uniform base plus a 32-bit offset
     const size_t rbase = (size_t)blockIdx.x * (FROWS * XD);
@@ -1092,24 +956,7 @@ __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float
 #pragma unroll
     for (int t = 0; t < XTILES; ++t) a.t[t] = live ? *(const f32x4*)(gy + rbase + loff + 16 * t) : zero4;
     for (int n = N - 1; n >= 0; --n) {
-        __syncthreads();          // the step before has read its constants
-        if (tid < 28) {           // one constant per thread (computed by every lane they are hoisted as fp64 and spilled)
-            const double dt = ctrl->dt[n];
-            double c;
-            if (tid < 21) {
-                int i = 1;
-                while ((i + 1) * i / 2 <= tid) ++i;
-                c = DP_A[i][tid - i * (i - 1) / 2];
-            } else {
-                c = DP_CS[tid - 21];
-                if (n == N - 1) {       // the last step ends at its interpolant
-                    const double t0 = ctrl->t0, t1 = ctrl->t1;
-                    c = dp_beta(tid - 21, (1. - t0) / (t1 - t0));
-                }
-            }
-            bc[tid] = (float)(dt * c);
-        }
-        __syncthreads();
+        publish_bwd_step(bc, ctrl, n, N, tid);
 #pragma unroll
         for (int i = 6; i >= 1; --i) {
             asm volatile("" : "+v"(lo), "+v"(lk));
@@ -1167,9 +1014,103 @@ __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float
 }  // namespace agp_fusion
 using namespace agp_fusion;
 
-static bool adaptive_args_ok(int b, int act, int method, int max_steps) {
-    return b > 0 && method == AGP_ODE_DOPRI5 && act >= AGP_ACT_ID && act <= AGP_ACT_SIGMOID && max_steps >= 1 &&
-           max_steps <= AGP_ODE_MAX_STEPS_LIMIT;
+// ---- host side: the entries without a width argument are the 256-column ones, the _wide entries take d and serve 384
+
+static int64_t ring_floats(int b, int d, int max_steps, int want_traj) {
+    if (b <= 0 || max_steps < 1) return 0;
+    return (int64_t)(want_traj ? max_steps + 1 : 2) * 8 * b * d;
+}
+static int64_t bwd_workspace_bytes(int b, int d, int max_steps) {
+    if (b <= 0 || max_steps < 1) return 0;
+    const int64_t Bp = (b + FROWS - 1) / FROWS * FROWS;
+    return 2 * (6 * (int64_t)max_steps + 1) * Bp * d * sizeof(float);
+}
+
+// the refusals of the four launch entries, in their order: a bad argument (have: every required pointer is there;
+// tols_ok: the forward's tolerances), then a width d the entry is not built for
+static int adaptive_refusal(bool have, int b, int d, int built_for, int act, int method, int max_steps, bool tols_ok) {
+    if (!have || d <= 0 || b <= 0 || method != AGP_ODE_DOPRI5 || act < AGP_ACT_ID || act > AGP_ACT_SIGMOID || max_steps < 1 ||
+        max_steps > AGP_ODE_MAX_STEPS_LIMIT)
+        return AGP_E_BADARG;
+    if (!tols_ok) return AGP_E_BADARG;
+    return d != built_for ? AGP_E_UNSUPPORTED : AGP_OK;
+}
+
+// fn(std::integral_constant<int, ACT>{}) for a checked activation: one kernel instantiation each
+template <class F>
+static int by_act(int act, F&& fn) {
+    switch (act) {
+        case AGP_ACT_ID: return fn(std::integral_constant<int, AGP_ACT_ID>{});
+        case AGP_ACT_RELU: return fn(std::integral_constant<int, AGP_ACT_RELU>{});
+        case AGP_ACT_TANH: return fn(std::integral_constant<int, AGP_ACT_TANH>{});
+        default: return fn(std::integral_constant<int, AGP_ACT_SIGMOID>{});
+    }
+}
+
+template <class E>
+static int adaptive_fwd(const float* x, const float* add1, const float* add2, const void* w_hi, const void* w_lo,
+                        const float* bias, int b, int d, int act, int method, double rtol, double atol, int max_steps, float* y,
+                        float* ring, int want_traj, void* ctrl, void* stream) {
+    const bool tols_ok = rtol >= 0. && atol >= 0. && rtol + atol > 0.;
+    if (const int rc = adaptive_refusal(x && w_hi && w_lo && y && ring && ctrl, b, d, E::D, act, method, max_steps, tols_ok)) return rc;
+    static_assert(sizeof(agp_ode_stats) == 32 && offsetof(OdeCtrl, dt) == 32, "control block layout");
+    const int nring = want_traj ? max_steps + 1 : 2;
+    return by_act(act, [&](auto A) -> int {
+        const auto kernel = fcode_adaptive_kernel<E, decltype(A)::value>;
+        if constexpr (E::LDS_DYNAMIC != 0) {
+            static std::atomic<uint64_t> attr_done;
+            if (!agp_lds_attr((const void*)kernel, E::LDS_DYNAMIC, attr_done)) return AGP_E_LAUNCH;
+        }
+        AGP_LAUNCH(kernel, dim3(1), dim3(E::THREADS), E::LDS_DYNAMIC, (hipStream_t)stream, x, add1, add2,
+                   (typename E::Plane)w_hi, (typename E::Plane)w_lo, bias, b, rtol, atol, max_steps, ring, nring, y, (OdeCtrl*)ctrl);
+        AGP_CHECK_LAUNCH();
+        return AGP_OK;
+    });
+}
+
+// the weight and bias gradients from the gz rows the state kernel left in GZ and the stage inputs rebuilt into S
+template <int D>
+static int adaptive_sums(const float* traj, const OdeCtrl* c, int b, int max_steps, float* gw, float* gb, float* GZ, float* S,
+                         int Bp, hipStream_t s) {
+    if (gw) {
+        AGP_LAUNCH(adaptive_stage_inputs_kernel<D>, dim3(Bp * (D / 4) / 256, max_steps), dim3(256), 0, s, traj, c, b, max_steps, S, Bp);
+        AGP_CHECK_LAUNCH();
+        AGP_LAUNCH(adaptive_gw_kernel<D>, dim3(D / 64, D / 64), dim3(256), 0, s, GZ, S, gw, c, max_steps, Bp);
+        AGP_CHECK_LAUNCH();
+    }
+    if (gb) {
+        AGP_LAUNCH(adaptive_gb_kernel<D>, dim3(D / 64), dim3(256), 0, s, GZ, gb, c, max_steps, Bp);
+        AGP_CHECK_LAUNCH();
+    }
+    return AGP_OK;
+}
+
+template <int D>
+static int adaptive_bwd(const float* traj, const void* ctrl, const float* gy, const void* wt_hi, const void* wt_lo, int b, int d,
+                        int act, int method, int max_steps, float* gx, float* gw, float* gb, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
+    if (const int rc = adaptive_refusal(traj && ctrl && gy && wt_hi && wt_lo && gx && workspace, b, d, D, act, method, max_steps, true))
+        return rc;
+    if (workspace_bytes < bwd_workspace_bytes(b, D, max_steps)) return AGP_E_BADARG;
+    const int Bp = (b + FROWS - 1) / FROWS * FROWS;
+    float* GZ = (float*)workspace;
+    float* S = GZ + (6 * (size_t)max_steps + 1) * Bp * D;      // (the state kernel's scratch first, then the stage inputs)
+    hipStream_t s = (hipStream_t)stream;
+    const OdeCtrl* c = (const OdeCtrl*)ctrl;
+    const dim3 grid(Bp / FROWS);
+    const int rc = by_act(act, [&](auto A) -> int {
+        constexpr int ACT = decltype(A)::value;
+        if constexpr (D == AD) {
+            AGP_LAUNCH(fcode_adaptive_bwd_kernel<ACT>, grid, dim3(FT), 0, s, traj, c, gy, (const bf16_t*)wt_hi, (const bf16_t*)wt_lo, b,
+                       max_steps, gx, GZ, Bp);
+        } else {
+            AGP_LAUNCH(fcode_adaptive_wide_bwd_kernel<ACT>, grid, dim3(XT), 0, s, traj, c, gy, (const bf16x8*)wt_hi,
+                       (const bf16x8*)wt_lo, b, max_steps, gx, GZ, S, Bp);
+        }
+        AGP_CHECK_LAUNCH();
+        return AGP_OK;
+    });
+    return rc != AGP_OK ? rc : adaptive_sums<D>(traj, c, b, max_steps, gw, gb, GZ, S, Bp, s);
 }
 
 extern "C" int64_t agp_fcode_adaptive_ctrl_bytes(int max_steps) {
@@ -1177,148 +1118,44 @@ extern "C" int64_t agp_fcode_adaptive_ctrl_bytes(int max_steps) {
 }
 
 extern "C" int64_t agp_fcode_adaptive_ring_floats(int b, int max_steps, int want_traj) {
-    if (b <= 0 || max_steps < 1) return 0;
-    return (int64_t)(want_traj ? max_steps + 1 : 2) * 8 * b * 256;
+    return ring_floats(b, AD, max_steps, want_traj);
 }
 
 extern "C" int agp_fcode_adaptive_fwd(const float* x, const float* add1, const float* add2, const void* w_hi,
                                       const void* w_lo, const float* bias, int b, int act, int method, double rtol,
                                       double atol, int max_steps, float* y, float* ring, int want_traj, void* ctrl,
                                       void* stream) {
-    if (!x || !w_hi || !w_lo || !y || !ring || !ctrl || !adaptive_args_ok(b, act, method, max_steps)) return AGP_E_BADARG;
-    if (!(rtol >= 0.) || !(atol >= 0.) || !(rtol + atol > 0.)) return AGP_E_BADARG;
-    static_assert(sizeof(agp_ode_stats) == 32 && offsetof(OdeCtrl, dt) == 32, "control block layout");
-    const int nring = want_traj ? max_steps + 1 : 2;
-    hipStream_t s = (hipStream_t)stream;
-    const bf16_t* wh = (const bf16_t*)w_hi;
-    const bf16_t* wl = (const bf16_t*)w_lo;
-    OdeCtrl* c = (OdeCtrl*)ctrl;
-    const dim3 grid(1), blk(FT);
-    switch (act) {
-        case AGP_ACT_ID: AGP_LAUNCH(fcode_adaptive_kernel<AGP_ACT_ID>, grid, blk, 0, s, x, add1, add2, wh, wl, bias, b, rtol, atol, max_steps, ring, nring, y, c); break;
-        case AGP_ACT_RELU: AGP_LAUNCH(fcode_adaptive_kernel<AGP_ACT_RELU>, grid, blk, 0, s, x, add1, add2, wh, wl, bias, b, rtol, atol, max_steps, ring, nring, y, c); break;
-        case AGP_ACT_TANH: AGP_LAUNCH(fcode_adaptive_kernel<AGP_ACT_TANH>, grid, blk, 0, s, x, add1, add2, wh, wl, bias, b, rtol, atol, max_steps, ring, nring, y, c); break;
-        default: AGP_LAUNCH(fcode_adaptive_kernel<AGP_ACT_SIGMOID>, grid, blk, 0, s, x, add1, add2, wh, wl, bias, b, rtol, atol, max_steps, ring, nring, y, c); break;
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return adaptive_fwd<Resident256>(x, add1, add2, w_hi, w_lo, bias, b, AD, act, method, rtol, atol, max_steps, y, ring, want_traj,
+                                     ctrl, stream);
 }
 
-extern "C" int64_t agp_fcode_adaptive_bwd_workspace_bytes(int b, int max_steps) {
-    if (b <= 0 || max_steps < 1) return 0;
-    const int64_t Bp = (b + FROWS - 1) / FROWS * FROWS;
-    return 2 * (6 * (int64_t)max_steps + 1) * Bp * 256 * sizeof(float);
-}
+extern "C" int64_t agp_fcode_adaptive_bwd_workspace_bytes(int b, int max_steps) { return bwd_workspace_bytes(b, AD, max_steps); }
 
 extern "C" int agp_fcode_adaptive_bwd(const float* traj, const void* ctrl, const float* gy, const void* wt_hi,
                                       const void* wt_lo, int b, int act, int method, int max_steps, float* gx, float* gw,
                                       float* gb, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!traj || !ctrl || !gy || !wt_hi || !wt_lo || !gx || !workspace || !adaptive_args_ok(b, act, method, max_steps))
-        return AGP_E_BADARG;
-    if (workspace_bytes < agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps)) return AGP_E_BADARG;
-    const int Bp = (b + FROWS - 1) / FROWS * FROWS;
-    float* GZ = (float*)workspace;
-    float* S = GZ + (6 * (size_t)max_steps + 1) * Bp * 256;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(Bp / FROWS), blk(FT);
-    const bf16_t* wh = (const bf16_t*)wt_hi;
-    const bf16_t* wl = (const bf16_t*)wt_lo;
-    const OdeCtrl* c = (const OdeCtrl*)ctrl;
-    switch (act) {
-        case AGP_ACT_ID: AGP_LAUNCH(fcode_adaptive_bwd_kernel<AGP_ACT_ID>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, Bp); break;
-        case AGP_ACT_RELU: AGP_LAUNCH(fcode_adaptive_bwd_kernel<AGP_ACT_RELU>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, Bp); break;
-        case AGP_ACT_TANH: AGP_LAUNCH(fcode_adaptive_bwd_kernel<AGP_ACT_TANH>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, Bp); break;
-        default: AGP_LAUNCH(fcode_adaptive_bwd_kernel<AGP_ACT_SIGMOID>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, Bp); break;
-    }
-    AGP_CHECK_LAUNCH();
-    if (gw) {
-        AGP_LAUNCH(adaptive_stage_inputs_kernel<AD>, dim3(Bp * 64 / 256, max_steps), dim3(256), 0, s, traj, c, b, max_steps, S, Bp);
-        AGP_CHECK_LAUNCH();
-        AGP_LAUNCH(adaptive_gw_kernel<AD>, dim3(4, 4), dim3(256), 0, s, GZ, S, gw, c, max_steps, Bp);
-        AGP_CHECK_LAUNCH();
-    }
-    if (gb) {
-        AGP_LAUNCH(adaptive_gb_kernel<AD>, dim3(4), dim3(256), 0, s, GZ, gb, c, max_steps, Bp);
-        AGP_CHECK_LAUNCH();
-    }
-    return AGP_OK;
+    return adaptive_bwd<AD>(traj, ctrl, gy, wt_hi, wt_lo, b, AD, act, method, max_steps, gx, gw, gb, workspace, workspace_bytes, stream);
 }
 
-// ---- 384 columns
 extern "C" int64_t agp_fcode_adaptive_wide_ring_floats(int b, int d, int max_steps, int want_traj) {
-    if (b <= 0 || d != XD || max_steps < 1) return 0;
-    return (int64_t)(want_traj ? max_steps + 1 : 2) * 8 * b * XD;
+    return d != XD ? 0 : ring_floats(b, d, max_steps, want_traj);
 }
 
 extern "C" int agp_fcode_adaptive_wide_fwd(const float* x, const float* add1, const float* add2, const void* wf_hi,
                                            const void* wf_lo, const float* bias, int b, int d, int act, int method,
                                            double rtol, double atol, int max_steps, float* y, float* ring, int want_traj,
                                            void* ctrl, void* stream) {
-    if (!x || !wf_hi || !wf_lo || !y || !ring || !ctrl || d <= 0 || !adaptive_args_ok(b, act, method, max_steps))
-        return AGP_E_BADARG;
-    if (!(rtol >= 0.) || !(atol >= 0.) || !(rtol + atol > 0.)) return AGP_E_BADARG;
-    if (d != XD) return AGP_E_UNSUPPORTED;
-    const int nring = want_traj ? max_steps + 1 : 2;
-    hipStream_t s = (hipStream_t)stream;
-    const bf16x8* wh = (const bf16x8*)wf_hi;
-    const bf16x8* wl = (const bf16x8*)wf_lo;
-    OdeCtrl* c = (OdeCtrl*)ctrl;
-    const dim3 grid(1), blk(XT);
-    static std::atomic<uint64_t> attr_done[4];
-#define AGP_ADAPTIVE_WIDE_CASE(A)                                                                                          \
-    case A:                                                                                                                \
-        if (!agp_lds_attr((const void*)fcode_adaptive_wide_kernel<A>, XLDS_FWD, attr_done[A])) return AGP_E_LAUNCH;        \
-        AGP_LAUNCH(fcode_adaptive_wide_kernel<A>, grid, blk, XLDS_FWD, s, x, add1, add2, wh, wl, bias, b, rtol, atol,      \
-                   max_steps, ring, nring, y, c);                                                                          \
-        break;
-    switch (act) {
-        AGP_ADAPTIVE_WIDE_CASE(AGP_ACT_ID) AGP_ADAPTIVE_WIDE_CASE(AGP_ACT_RELU) AGP_ADAPTIVE_WIDE_CASE(AGP_ACT_TANH)
-        AGP_ADAPTIVE_WIDE_CASE(AGP_ACT_SIGMOID)
-        default: return AGP_E_BADARG;
-    }
-#undef AGP_ADAPTIVE_WIDE_CASE
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return adaptive_fwd<Streamed384>(x, add1, add2, wf_hi, wf_lo, bias, b, d, act, method, rtol, atol, max_steps, y, ring, want_traj,
+                                     ctrl, stream);
 }
 
 extern "C" int64_t agp_fcode_adaptive_wide_bwd_workspace_bytes(int b, int d, int max_steps) {
-    if (b <= 0 || d != XD || max_steps < 1) return 0;
-    const int64_t Bp = (b + FROWS - 1) / FROWS * FROWS;
-    return 2 * (6 * (int64_t)max_steps + 1) * Bp * XD * sizeof(float);
+    return d != XD ? 0 : bwd_workspace_bytes(b, d, max_steps);
 }
 
 extern "C" int agp_fcode_adaptive_wide_bwd(const float* traj, const void* ctrl, const float* gy, const void* wtf_hi,
                                            const void* wtf_lo, int b, int d, int act, int method, int max_steps, float* gx,
                                            float* gw, float* gb, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!traj || !ctrl || !gy || !wtf_hi || !wtf_lo || !gx || !workspace || d <= 0 ||
-        !adaptive_args_ok(b, act, method, max_steps))
-        return AGP_E_BADARG;
-    if (d != XD) return AGP_E_UNSUPPORTED;
-    if (workspace_bytes < agp_fcode_adaptive_wide_bwd_workspace_bytes(b, d, max_steps)) return AGP_E_BADARG;
-    const int Bp = (b + FROWS - 1) / FROWS * FROWS;
-    float* GZ = (float*)workspace;
-    float* S = GZ + (6 * (size_t)max_steps + 1) * Bp * XD;      // (the state kernel's scratch first, then the stage inputs)
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(Bp / FROWS), blk(XT);
-    const bf16x8* wh = (const bf16x8*)wtf_hi;
-    const bf16x8* wl = (const bf16x8*)wtf_lo;
-    const OdeCtrl* c = (const OdeCtrl*)ctrl;
-    switch (act) {
-        case AGP_ACT_ID: AGP_LAUNCH(fcode_adaptive_wide_bwd_kernel<AGP_ACT_ID>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, S, Bp); break;
-        case AGP_ACT_RELU: AGP_LAUNCH(fcode_adaptive_wide_bwd_kernel<AGP_ACT_RELU>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, S, Bp); break;
-        case AGP_ACT_TANH: AGP_LAUNCH(fcode_adaptive_wide_bwd_kernel<AGP_ACT_TANH>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, S, Bp); break;
-        default: AGP_LAUNCH(fcode_adaptive_wide_bwd_kernel<AGP_ACT_SIGMOID>, grid, blk, 0, s, traj, c, gy, wh, wl, b, max_steps, gx, GZ, S, Bp); break;
-    }
-    AGP_CHECK_LAUNCH();
-    if (gw) {
-        AGP_LAUNCH(adaptive_stage_inputs_kernel<XD>, dim3(Bp * (XD / 4) / 256, max_steps), dim3(256), 0, s, traj, c, b, max_steps, S, Bp);
-        AGP_CHECK_LAUNCH();
-        AGP_LAUNCH(adaptive_gw_kernel<XD>, dim3(XD / 64, XD / 64), dim3(256), 0, s, GZ, S, gw, c, max_steps, Bp);
-        AGP_CHECK_LAUNCH();
-    }
-    if (gb) {
-        AGP_LAUNCH(adaptive_gb_kernel<XD>, dim3(XD / 64), dim3(256), 0, s, GZ, gb, c, max_steps, Bp);
-        AGP_CHECK_LAUNCH();
-    }
-    return AGP_OK;
+    return adaptive_bwd<XD>(traj, ctrl, gy, wtf_hi, wtf_lo, b, d, act, method, max_steps, gx, gw, gb, workspace, workspace_bytes,
+                            stream);
 }

@@ -1415,7 +1415,17 @@ def fcode_bwd(traj, gy, lw: LinearWeights, act, method, dts):
     return gx, gw, gb
 
 
-FCODE_ADAPTIVE_DIMS = (256, FCODE_WIDE_DIM)       # agp_fcode_adaptive_fwd, agp_fcode_adaptive_wide_fwd
+FCODE_ADAPTIVE_DIMS = (256, FCODE_WIDE_DIM)
+# per width: the forward's planes of a LinearWeights, the backward's, the entries (ring size, forward, workspace size, backward)
+# and whether those entries take the width as an argument
+_ADAPTIVE = {
+    256: (lambda lw: (lw.w_hi, lw.w_lo), lambda lw: (lw.wt_hi, lw.wt_lo),
+          ("agp_fcode_adaptive_ring_floats", "agp_fcode_adaptive_fwd", "agp_fcode_adaptive_bwd_workspace_bytes",
+           "agp_fcode_adaptive_bwd"), False),
+    FCODE_WIDE_DIM: (fcode_wide_planes, fcode_wide_planes_t,
+                     ("agp_fcode_adaptive_wide_ring_floats", "agp_fcode_adaptive_wide_fwd",
+                      "agp_fcode_adaptive_wide_bwd_workspace_bytes", "agp_fcode_adaptive_wide_bwd"), True),
+}
 
 
 def _adaptive_args(x, lw, act, method, tol, max_steps):
@@ -1441,27 +1451,20 @@ def fcode_adaptive(x, lw: LinearWeights, act, method, tol, max_steps=64, add1=No
     A solve that fails (step cap, step-size underflow, NaN) returns NaN and says why in ctrl."""
     _need_cuda(x, "fcode_adaptive")
     x = x.contiguous().float()
-    b = x.shape[0]
+    b, d = x.shape
     add1, add2 = _vec_operand(add1, x, "fcode add1"), _vec_operand(add2, x, "fcode add2")
     _adaptive_args(x, lw, act, method, tol, max_steps)
     y = torch.empty_like(x)
     ctrl = torch.empty(_L().agp_fcode_adaptive_ctrl_bytes(max_steps), dtype=torch.uint8, device=x.device)
-    if x.shape[1] == FCODE_WIDE_DIM:
-        d = x.shape[1]
-        f_hi, f_lo = fcode_wide_planes(lw)
-        if want_traj:
-            fcode_wide_planes_t(lw)      # a backward follows: its planes are prepared here, outside any capture of it
-        ring = torch.empty(_L().agp_fcode_adaptive_wide_ring_floats(b, d, max_steps, int(want_traj)), dtype=torch.float32,
-                           device=x.device)
-        check(_L().agp_fcode_adaptive_wide_fwd(ptr(x), ptr(add1), ptr(add2), ptr(f_hi), ptr(f_lo), ptr(lw.bias), b, d,
-                                               _lib.ACT[act], _lib.ODE_ADAPTIVE[method], float(tol), float(tol), max_steps,
-                                               ptr(y), ptr(ring), int(want_traj), ptr(ctrl), _lib.stream()),
-              "agp_fcode_adaptive_wide_fwd")
-        return (y, ctrl, ring) if want_traj else (y, ctrl)
-    ring = torch.empty(_L().agp_fcode_adaptive_ring_floats(b, max_steps, int(want_traj)), dtype=torch.float32, device=x.device)
-    check(_L().agp_fcode_adaptive_fwd(ptr(x), ptr(add1), ptr(add2), ptr(lw.w_hi), ptr(lw.w_lo), ptr(lw.bias), b, _lib.ACT[act],
-                                      _lib.ODE_ADAPTIVE[method], float(tol), float(tol), max_steps, ptr(y), ptr(ring),
-                                      int(want_traj), ptr(ctrl), _lib.stream()), "agp_fcode_adaptive_fwd")
+    planes, planes_t, (ring_floats, fwd, _, _), takes_d = _ADAPTIVE[d]
+    width = (d,) if takes_d else ()
+    p_hi, p_lo = planes(lw)
+    if want_traj:
+        planes_t(lw)      # a backward follows: fragment-order planes are prepared here, outside any capture of it
+    ring = torch.empty(getattr(_L(), ring_floats)(b, *width, max_steps, int(want_traj)), dtype=torch.float32, device=x.device)
+    check(getattr(_L(), fwd)(ptr(x), ptr(add1), ptr(add2), ptr(p_hi), ptr(p_lo), ptr(lw.bias), b, *width, _lib.ACT[act],
+                             _lib.ODE_ADAPTIVE[method], float(tol), float(tol), max_steps, ptr(y), ptr(ring), int(want_traj),
+                             ptr(ctrl), _lib.stream()), fwd)
     return (y, ctrl, ring) if want_traj else (y, ctrl)
 
 
@@ -1473,19 +1476,13 @@ def fcode_adaptive_bwd(traj, ctrl, gy, lw: LinearWeights, act, method, max_steps
     gw = torch.empty((d, d), dtype=torch.float32, device=gy.device)
     gb = torch.empty(d, dtype=torch.float32, device=gy.device)
     _adaptive_args(gy, lw, act, method, 1.0, max_steps)
-    if d == FCODE_WIDE_DIM:
-        ft_hi, ft_lo = fcode_wide_planes_t(lw)
-        nbytes = _L().agp_fcode_adaptive_wide_bwd_workspace_bytes(b, d, max_steps)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
-        check(_L().agp_fcode_adaptive_wide_bwd(ptr(traj), ptr(ctrl), ptr(gy), ptr(ft_hi), ptr(ft_lo), b, d, _lib.ACT[act],
-                                               _lib.ODE_ADAPTIVE[method], max_steps, ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes,
-                                               _lib.stream()), "agp_fcode_adaptive_wide_bwd")
-        return gx, gw, gb
-    nbytes = _L().agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps)
+    _, planes_t, (_, _, workspace_bytes, bwd), takes_d = _ADAPTIVE[d]
+    width = (d,) if takes_d else ()
+    pt_hi, pt_lo = planes_t(lw)
+    nbytes = getattr(_L(), workspace_bytes)(b, *width, max_steps)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
-    check(_L().agp_fcode_adaptive_bwd(ptr(traj), ptr(ctrl), ptr(gy), ptr(lw.wt_hi), ptr(lw.wt_lo), b, _lib.ACT[act],
-                                      _lib.ODE_ADAPTIVE[method], max_steps, ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes,
-                                      _lib.stream()), "agp_fcode_adaptive_bwd")
+    check(getattr(_L(), bwd)(ptr(traj), ptr(ctrl), ptr(gy), ptr(pt_hi), ptr(pt_lo), b, *width, _lib.ACT[act],
+                             _lib.ODE_ADAPTIVE[method], max_steps, ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes, _lib.stream()), bwd)
     return gx, gw, gb
 
 

@@ -576,7 +576,9 @@ int agp_fcode_adaptive_bwd(const float* traj, const void* ctrl, const float* gy,
  * of W, three of the state, five products), the control block (agp_fcode_adaptive_ctrl_bytes, agp_ode_stats), the three endings
  * and the ring layout of agp_fcode_adaptive_fwd, with 384 columns: ring[n][0][b][384] = y before accepted step n,
  * ring[n][1 + j][b][384] = its k_{j+1}; agp_fcode_adaptive_wide_ring_floats(b, d, max_steps, want_traj) =
- * (want_traj ? max_steps + 1 : 2) * 8 * b * 384 floats (0 for b <= 0, max_steps < 1 or d != 384).  ONE launch of one persistent
+ * (want_traj ? max_steps + 1 : 2) * 8 * b * 384 floats (0 for b <= 0, max_steps < 1 or d != 384).  The forward is the kernel of
+ * agp_fcode_adaptive_fwd (one driver: step control, tableau arithmetic, ring, control block) over another column engine: ONE
+ * launch of one persistent
  * workgroup of 8 waves per solve, capturable; W does not fit a CU's registers at this width, so as in agp_fcode_wide_fwd the
  * `hi` plane stays in registers and the `lo` plane is read from L2 once per f-evaluation and row tile.  wf_hi / wf_lo: the two
  * split-bf16 planes of W [384][384] in the FRAGMENT order of agp_fcode_wide_fwd, 16 bytes per entry:
