@@ -191,6 +191,8 @@ SIGNATURES = {
     "agp_sparse_coarsen": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _P, _L, _P]),
     "agp_sparse_points_workspace_bytes": (_L, [_L, _I]),
     "agp_sparse_build_points": (_I, [_P, _P, _L, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "agp_sparse_points_cap_workspace_bytes": (_L, [_L, _L, _I]),
+    "agp_sparse_build_points_cap": (_I, [_P, _P, _L, _L, _I, _F, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     "agp_seg_pool_fwd": (_I, [_P, _P, _P, _I, _I, _P, _F, _P, _P, _P]),
     "agp_eca_scale_fwd": (_I, [_P, _I, _I, _P, _I, _P, _P]),
     "agp_seg_affine_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),

@@ -34,6 +34,7 @@ constexpr int BITS = 16, OFF = 1 << 15;
 constexpr int ST = 1024;                                 // threads of a segment workgroup
 constexpr int LDS_KEYS = 16384;                          // keys a workgroup sorts in LDS
 constexpr int MAX_SLOT = 65536;                          // input points of one sample (16-bit bucket slot beside the 48-bit voxel)
+constexpr int CUR_STRIDE = 32;                           // (builds from points) int32 words between two samples' bucket cursors: one 128-byte line each
 
 // coords [n][4] (batch, x, y, z) as int64 (kind 0), float32 (kind 1) or float64 (kind 2; floored like ME does for floating
 // coordinates) -> key (input order) + the per-sample histogram.  Out-of-range coordinates (|c| >= 32512: kernel offsets need
@@ -363,28 +364,42 @@ __global__ void __launch_bounds__(ST) seg_sort_kernel(const int64_t* __restrict_
 }
 
 // placement: sample b's unique keys go to rows [off_b, off_b + cnt[b]) with off = exclusive scan of cnt; batch indices, segment
-// offsets (seg_off[B] = n), padding of rows >= n; optional feature rows
-__global__ void __launch_bounds__(256) place_kernel(const int64_t* __restrict__ uniq_tmp, const float* __restrict__ f_tmp, int cf,
-                                                    const int64_t* __restrict__ seg_in, const int32_t* __restrict__ cnt, int nbatch,
-                                                    int64_t cap, int64_t* __restrict__ keys_out, float* __restrict__ f_out,
-                                                    int64_t* __restrict__ seg_off, int32_t* __restrict__ bidx) {
-    __shared__ int64_t red[2][256];
+// offsets (seg_off[B] = n), padding of rows >= n; optional feature rows.  CHK = false (agp_sparse_build, agp_sparse_coarsen,
+// agp_sparse_build_points): sum(cnt) <= cap holds by construction and rows are written unchecked.  CHK = true (the level-capacity
+// build from points): `cap` is the caller's bound, so the total is compared with it BEFORE any row is written -- a build whose
+// overflow word is set, or whose total exceeds cap, places nothing: every sample empty, all cap rows padding, bit 2 of the flag.
+template <bool CHK>
+__device__ __forceinline__ void place_body(const int64_t* __restrict__ uniq_tmp, const float* __restrict__ f_tmp, int cf,
+                                           const int64_t* __restrict__ seg_in, const int32_t* __restrict__ cnt, int nbatch,
+                                           int64_t cap, int64_t* __restrict__ keys_out, float* __restrict__ f_out,
+                                           int64_t* __restrict__ seg_off, int32_t* __restrict__ bidx, const int32_t* __restrict__ ovf,
+                                           const int32_t* __restrict__ inserts, int32_t* __restrict__ flag) {
+    __shared__ int64_t red[CHK ? 3 : 2][256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    int64_t pre = 0, all = 0;
+    int64_t pre = 0, all = 0, ins = 0;
     for (int a = tid; a < nbatch; a += 256) {
         const int c = cnt[a];
         all += c;
         if (a < b) pre += c;
+        if (CHK) ins += inserts[(size_t)a * CUR_STRIDE];     // (the counter beside sample a's bucket cursor)
     }
     red[0][tid] = pre; red[1][tid] = all;
+    if (CHK) red[2][tid] = ins;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+        if (tid < o) {
+            red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o];
+            if (CHK) red[2][tid] += red[2][tid + o];
+        }
         __syncthreads();
     }
-    const int64_t off = red[0][0], tot = red[1][0];
+    int64_t off = red[0][0], tot = red[1][0];
     const int64_t r0 = seg_in[b];
-    const int c = cnt[b];
+    int c = cnt[b];
+    if (CHK && (*ovf != 0 || red[2][0] > cap || tot > cap)) {                  // (uniform over the grid: every workgroup reads the same words)
+        if (b == 0 && tid == 0) atomicOr(flag, 4);
+        off = 0; tot = 0; c = 0;
+    }
     for (int j = tid; j < c; j += 256) {
         keys_out[off + j] = uniq_tmp[r0 + j];
         bidx[off + j] = b;
@@ -397,6 +412,13 @@ __global__ void __launch_bounds__(256) place_kernel(const int64_t* __restrict__ 
     }
     const int64_t lo = cap * b / nbatch, hi = cap * (b + 1) / nbatch;
     for (int64_t i = (lo > tot ? lo : tot) + tid; i < hi; i += 256) { keys_out[i] = SENT; bidx[i] = 0; }
+}
+
+__global__ void __launch_bounds__(256) place_kernel(const int64_t* __restrict__ uniq_tmp, const float* __restrict__ f_tmp, int cf,
+                                                    const int64_t* __restrict__ seg_in, const int32_t* __restrict__ cnt, int nbatch,
+                                                    int64_t cap, int64_t* __restrict__ keys_out, float* __restrict__ f_out,
+                                                    int64_t* __restrict__ seg_off, int32_t* __restrict__ bidx) {
+    place_body<false>(uniq_tmp, f_tmp, cf, seg_in, cnt, nbatch, cap, keys_out, f_out, seg_off, bidx, nullptr, nullptr, nullptr);
 }
 
 // Row order for the gather-GEMM: inside every batch sample, rows grouped by z-plane (stable: (x, y) order inside a plane).  Rows
@@ -583,7 +605,6 @@ extern "C" int agp_sparse_zplane_perm(const int64_t* keys, const int64_t* seg_of
 namespace agp_coords {
 
 constexpr uint64_t HEMPTY = ~0ull;                       // an empty table slot: no key (sample < 0x7fff) equals it
-constexpr int CUR_STRIDE = 32;                           // int32 words between two samples' bucket cursors: one 128-byte line each
 
 __device__ __forceinline__ uint64_t hash_mix64(uint64_t k) {          // the 64-bit finaliser of MurmurHash3
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
@@ -598,26 +619,63 @@ __device__ __forceinline__ uint64_t table_slots(int64_t nvalid, uint64_t tsize_m
     return t;
 }
 
+// The level-capacity build (agp_sparse_build_points_cap): the level has `lcap` rows, an upper bound the CALLER gives for the
+// number of voxels of the whole batch, independent of the `cap` point rows.  Two words of the workspace carry its state:
+//   total  a LOWER bound of the keys that entered the table so far: every sample counts its inserts beside its bucket cursor
+//          (cursor[b * CUR_STRIDE + 1], one atomic per workgroup) and passes them on in quanta of lcap / (2 nbatch), so total
+//          lags the truth by less than lcap / 2
+//   ovf    != 0 once the build is KNOWN to overflow: an insert found no slot, or total passed lcap
+// The table in use has table_slots(min(rows inside the offsets, lcap)) slots.  If no insert fails, total ends at A = the number of
+// If no insert fails and no thread saw ovf, the per-sample counters sum to A = the number of distinct (sample, quantised voxel)
+// cells; A <= lcap keeps the load <= 1/2, so no insert fails, total <= A never passes lcap and ovf stays 0.  ovf is only ever set
+// when more than lcap keys exist (total is a lower bound; a failed insert means a full table).  The placement therefore decides
+// "ovf != 0 or sum of the counters > lcap", which is A > lcap: a function of the input alone.  ovf rises by 1.5 lcap inserts at
+// the latest (load 3/4: probes still short); what threads do once they SEE it (drop their row unprobed) only saves work.
+__device__ __forceinline__ int64_t level_rows(int64_t nvalid, int64_t lcap) { return nvalid < lcap ? nvalid : lcap; }
+
 // table (the slots in use) <- empty, cursors <- 0, flag <- 0, features of the rows inside the offsets <- 1, poff <- the caller's
-// offsets clamped into [0, cap]
-__global__ void __launch_bounds__(256) points_init_kernel(const int64_t* __restrict__ off, int nbatch, int64_t cap, uint64_t tsize,
-                                                          uint64_t* __restrict__ table, int64_t* __restrict__ poff,
-                                                          int32_t* __restrict__ cursor, int32_t* __restrict__ flag,
-                                                          float* __restrict__ feats_out) {
+// offsets clamped into [0, cap].  CAP: the table and the features follow the level capacity lcap, total and ovf <- 0.
+template <bool CAP>
+__device__ __forceinline__ void points_init_body(const int64_t* __restrict__ off, int nbatch, int64_t cap, int64_t lcap, uint64_t tsize,
+                                                 uint64_t* __restrict__ table, int64_t* __restrict__ poff, int32_t* __restrict__ cursor,
+                                                 int32_t* __restrict__ flag, float* __restrict__ feats_out, int32_t* __restrict__ total,
+                                                 int32_t* __restrict__ ovf) {
     const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x, gsz = (uint64_t)gridDim.x * 256;
     typedef __attribute__((ext_vector_type(2))) unsigned long long u64x2;
     const u64x2 e2 = {HEMPTY, HEMPTY};
     const int64_t o_end = off[nbatch];
     const int64_t nvalid = o_end < 0 ? 0 : (o_end > cap ? cap : o_end);        // = poff[nbatch]; valid rows of the level <= nvalid
-    const uint64_t tuse = table_slots(nvalid, tsize);
+    const int64_t nrows = CAP ? level_rows(nvalid, lcap) : nvalid;
+    const uint64_t tuse = table_slots(nrows, tsize);
     for (uint64_t i = gid; i < tuse / 2; i += gsz) ((u64x2*)table)[i] = e2;
-    for (uint64_t i = gid; i < (uint64_t)nvalid; i += gsz) feats_out[i] = 1.f;
+    for (uint64_t i = gid; i < (uint64_t)nrows; i += gsz) feats_out[i] = 1.f;
     for (uint64_t i = gid; i <= (uint64_t)nbatch; i += gsz) {
         const int64_t o = off[i];
         poff[i] = o < 0 ? 0 : (o > cap ? cap : o);
-        if (i < (uint64_t)nbatch) cursor[i * CUR_STRIDE] = 0;
+        if (i < (uint64_t)nbatch) {
+            cursor[i * CUR_STRIDE] = 0;
+            if (CAP) cursor[i * CUR_STRIDE + 1] = 0;
+        }
     }
-    if (gid == 0) *flag = 0;
+    if (gid == 0) {
+        *flag = 0;
+        if (CAP) { *total = 0; *ovf = 0; }
+    }
+}
+
+__global__ void __launch_bounds__(256) points_init_kernel(const int64_t* __restrict__ off, int nbatch, int64_t cap, uint64_t tsize,
+                                                          uint64_t* __restrict__ table, int64_t* __restrict__ poff,
+                                                          int32_t* __restrict__ cursor, int32_t* __restrict__ flag,
+                                                          float* __restrict__ feats_out) {
+    points_init_body<false>(off, nbatch, cap, 0, tsize, table, poff, cursor, flag, feats_out, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(256) points_init_cap_kernel(const int64_t* __restrict__ off, int nbatch, int64_t cap, int64_t lcap,
+                                                              uint64_t tsize, uint64_t* __restrict__ table, int64_t* __restrict__ poff,
+                                                              int32_t* __restrict__ cursor, int32_t* __restrict__ flag,
+                                                              float* __restrict__ feats_out, int32_t* __restrict__ total,
+                                                              int32_t* __restrict__ ovf) {
+    points_init_body<true>(off, nbatch, cap, lcap, tsize, table, poff, cursor, flag, feats_out, total, ovf);
 }
 
 // One thread per input row.  Row i belongs to the sample b with poff[b] <= i < poff[b+1]; rows outside [poff[0], poff[nbatch]) are
@@ -628,16 +686,22 @@ __global__ void __launch_bounds__(256) points_init_kernel(const int64_t* __restr
 // x matrix in fp64, (qx R0j + qy R1j) + qz R2j: |q| < 2^15 times an fp32 value is exact in fp64, so the floored result is
 // defined bit for bit.  The hash table in use has table_slots(poff[nbatch]) slots: a short scan in a large buffer clears and
 // probes a table of its own size.
-__global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __restrict__ pts, const int64_t* __restrict__ poff, int nbatch,
-                                                             float quant, const float* __restrict__ rot, int rot_per_sample,
-                                                             uint64_t* __restrict__ table, uint64_t tsize, int32_t* __restrict__ cursor,
-                                                             int64_t* __restrict__ bkeys, int32_t* __restrict__ flag) {
+// CAP (level capacity lcap, words total / ovf: see above): the table has table_slots(min(poff[nbatch], lcap)) slots, so a probe
+// sequence may find NO slot -- the loop is bounded by the table size either way, and a thread that runs it out sets ovf.  A thread
+// that sees ovf set (before its first probe, and every 64 probes) drops its row; its finite / range test still raises bit 0.
+template <bool CAP>
+__device__ __forceinline__ void points_voxelize_body(const float* __restrict__ pts, const int64_t* __restrict__ poff, int nbatch,
+                                                     float quant, const float* __restrict__ rot, int rot_per_sample,
+                                                     uint64_t* __restrict__ table, uint64_t tsize, int32_t* __restrict__ cursor,
+                                                     int64_t* __restrict__ bkeys, int32_t* __restrict__ flag, int64_t lcap,
+                                                     int64_t quantum, int32_t* __restrict__ total, int32_t* __restrict__ ovf) {
     __shared__ int s_base;
     const int tid = threadIdx.x, lane = tid & 63;
     const int64_t base = (int64_t)blockIdx.x * ST, i = base + tid;
     const int64_t n_end = poff[nbatch];
     if (base >= n_end) return;                              // (uniform) a block of tail rows
-    const uint64_t tmask = table_slots(n_end, tsize) - 1;
+    const uint64_t tmask = table_slots(CAP ? level_rows(n_end, lcap) : n_end, tsize) - 1;
+    auto overflowed = [&] { return CAP && __hip_atomic_load(ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; };
     auto sample_of = [&](int64_t r) {                       // the last b in [0, nbatch) with poff[b] <= r (0 if there is none)
         int lo = 0, hi = nbatch;
         while (hi - lo > 1) {
@@ -648,7 +712,7 @@ __global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __rest
     };
     const int b_first = sample_of(base);
     int b = -1;
-    bool win = false, bad = false;
+    bool win = false, bad = false, ins = false;
     uint64_t key = 0;
     if (i < n_end) {
         const int bb = i < poff[b_first + 1] ? b_first : sample_of(i);
@@ -665,23 +729,27 @@ __global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __rest
         }
         if (!ok) {
             bad = true;
-        } else {
+        } else if (!overflowed()) {
             const int q0 = (int)qf[0], q1 = (int)qf[1], q2 = (int)qf[2];
             const uint64_t hk = ((uint64_t)b << (3 * BITS)) | ((uint64_t)(q0 + OFF) << (2 * BITS)) | ((uint64_t)(q1 + OFF) << BITS) |
                                 (uint64_t)(q2 + OFF);
             uint64_t h = hash_mix64(hk) & tmask;
             // a voxel already in the table costs a load, not an atomic: 70 000 points of one voxel do one CAS per wave that sees
             // the slot empty, then read.  The table holds at most tsize / 2 keys, so a probe sequence always meets an empty slot.
+            bool settled = false;                           // (CAP) the key is in the table, or the row was dropped on seeing ovf
             for (uint64_t step = 0; step <= tmask; ++step) {
+                if (CAP && (step & 63) == 63 && overflowed()) { settled = true; break; }
                 const uint64_t cur = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == hk) break;
+                if (cur == hk) { settled = true; break; }
                 if (cur == HEMPTY) {
                     const uint64_t prev = atomicCAS((unsigned long long*)&table[h], (unsigned long long)HEMPTY, (unsigned long long)hk);
-                    if (prev == HEMPTY) { win = true; break; }
-                    if (prev == hk) break;
+                    if (prev == HEMPTY) { win = true; settled = true; break; }
+                    if (prev == hk) { settled = true; break; }
                 }
                 h = (h + 1) & tmask;
             }
+            if (CAP && !settled) atomicOr(ovf, 1);           // every slot holds another key: more than lcap keys
+            ins = win;
             key = hk;
             if (win && rot) {
                 const float* R = rot + (rot_per_sample ? (size_t)b * 9 : 0);
@@ -700,6 +768,21 @@ __global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __rest
     {
         const uint64_t anybad = __builtin_amdgcn_ballot_w64(bad);
         if (anybad && lane == __builtin_ctzll(anybad)) atomicOr(flag, 1);
+    }
+    if (CAP) {
+        // the keys this workgroup put into the table (counted before the rotation drops any) join the insert counter beside its
+        // first sample's cursor (same 128-byte line; only the SUM over the samples is used, so a workgroup that straddles samples
+        // may book all of them there).  One counter for the whole batch would serialise a returning atomic per workgroup in L2 --
+        // measured: +0.06 ms at 7500 workgroups -- so only the whole quanta a counter crosses go on to the global total.
+        const int nins = __syncthreads_count(ins ? 1 : 0);
+        if (tid == 0 && nins) {
+            const int before = atomicAdd(&cursor[(size_t)b_first * CUR_STRIDE + 1], nins);
+            const int64_t crossed = ((int64_t)before + nins) / quantum - (int64_t)before / quantum;
+            if (crossed) {
+                const int g = atomicAdd(total, (int)(crossed * quantum));
+                if ((int64_t)g + crossed * quantum > lcap) atomicOr(ovf, 1);
+            }
+        }
     }
     // append to the sample's bucket bkeys[poff[b] + slot]: a block inside ONE sample claims its slots with one atomic
     const bool uniform = !win || b == b_first;
@@ -725,14 +808,31 @@ __global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __rest
     }
 }
 
+__global__ void __launch_bounds__(ST) points_voxelize_kernel(const float* __restrict__ pts, const int64_t* __restrict__ poff, int nbatch,
+                                                             float quant, const float* __restrict__ rot, int rot_per_sample,
+                                                             uint64_t* __restrict__ table, uint64_t tsize, int32_t* __restrict__ cursor,
+                                                             int64_t* __restrict__ bkeys, int32_t* __restrict__ flag) {
+    points_voxelize_body<false>(pts, poff, nbatch, quant, rot, rot_per_sample, table, tsize, cursor, bkeys, flag, 0, 1, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(ST) points_voxelize_cap_kernel(const float* __restrict__ pts, const int64_t* __restrict__ poff, int nbatch,
+                                                                 float quant, const float* __restrict__ rot, int rot_per_sample,
+                                                                 uint64_t* __restrict__ table, uint64_t tsize,
+                                                                 int32_t* __restrict__ cursor, int64_t* __restrict__ bkeys,
+                                                                 int32_t* __restrict__ flag, int64_t lcap, int64_t quantum,
+                                                                 int32_t* __restrict__ total, int32_t* __restrict__ ovf) {
+    points_voxelize_body<true>(pts, poff, nbatch, quant, rot, rot_per_sample, table, tsize, cursor, bkeys, flag, lcap, quantum, total, ovf);
+}
+
 // seg_sort_kernel<false> for buckets given as (first row, count): sample b's keys are bkeys[poff[b] .. + cursor[b]), sorted whole
 // (mask = all ones).  More than 65536 VOXELS in one sample: empty sample, flagged (bit 1) like the input-point limit of
-// agp_sparse_build -- the rows a sample may own downstream are the same.
-__global__ void __launch_bounds__(ST) seg_sort_points_kernel(const int64_t* __restrict__ bkeys, const int64_t* __restrict__ poff,
-                                                             const int32_t* __restrict__ cursor, int64_t* __restrict__ uniq_tmp,
-                                                             int32_t* __restrict__ cnt, uint64_t* __restrict__ gscr,
-                                                             int32_t* __restrict__ flag) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
+// agp_sparse_build -- the rows a sample may own downstream are the same.  CAP: a build that overflowed sorts nothing (the placement
+// empties it); bit 1 is still reported for the buckets as they stand.
+template <bool CAP>
+__device__ __forceinline__ void seg_sort_points_body(uint64_t* sk, const int64_t* __restrict__ bkeys, const int64_t* __restrict__ poff,
+                                                     const int32_t* __restrict__ cursor, int64_t* __restrict__ uniq_tmp,
+                                                     int32_t* __restrict__ cnt, uint64_t* __restrict__ gscr, int32_t* __restrict__ flag,
+                                                     const int32_t* __restrict__ ovf) {
     const int b = blockIdx.x;
     const int64_t r0 = poff[b];
     const int n = cursor[(size_t)b * CUR_STRIDE];
@@ -741,17 +841,47 @@ __global__ void __launch_bounds__(ST) seg_sort_points_kernel(const int64_t* __re
         if (threadIdx.x == 0) { cnt[b] = 0; atomicOr(flag, 2); }
         return;
     }
+    if (CAP && *ovf != 0) { if (threadIdx.x == 0) cnt[b] = 0; return; }          // (uniform)
     int P = 2;
     while (P < n) P <<= 1;
     if (n <= LDS_KEYS) seg_sort_body<false>(KeyArr<true>{sk}, bkeys, r0, n, P, (int64_t)-1, b, nullptr, nullptr, 0, uniq_tmp, nullptr, cnt);
     else seg_sort_body<false>(KeyArr<false>{gscr + 2 * r0}, bkeys, r0, n, P, (int64_t)-1, b, nullptr, nullptr, 0, uniq_tmp, nullptr, cnt);
 }
 
-struct PWs { int64_t table, bkeys, uniq, gscr, poff, cursor, cnt, total; uint64_t tsize; };
-inline PWs points_layout(int64_t cap, int nbatch) {
+__global__ void __launch_bounds__(ST) seg_sort_points_kernel(const int64_t* __restrict__ bkeys, const int64_t* __restrict__ poff,
+                                                             const int32_t* __restrict__ cursor, int64_t* __restrict__ uniq_tmp,
+                                                             int32_t* __restrict__ cnt, uint64_t* __restrict__ gscr,
+                                                             int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
+    seg_sort_points_body<false>(sk, bkeys, poff, cursor, uniq_tmp, cnt, gscr, flag, nullptr);
+}
+
+__global__ void __launch_bounds__(ST) seg_sort_points_cap_kernel(const int64_t* __restrict__ bkeys, const int64_t* __restrict__ poff,
+                                                                 const int32_t* __restrict__ cursor, int64_t* __restrict__ uniq_tmp,
+                                                                 int32_t* __restrict__ cnt, uint64_t* __restrict__ gscr,
+                                                                 int32_t* __restrict__ flag, const int32_t* __restrict__ ovf) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t sk[];
+    seg_sort_points_body<true>(sk, bkeys, poff, cursor, uniq_tmp, cnt, gscr, flag, ovf);
+}
+
+__global__ void __launch_bounds__(256) place_cap_kernel(const int64_t* __restrict__ uniq_tmp, const int64_t* __restrict__ seg_in,
+                                                        const int32_t* __restrict__ cnt, int nbatch, int64_t lcap,
+                                                        int64_t* __restrict__ keys_out, int64_t* __restrict__ seg_off,
+                                                        int32_t* __restrict__ bidx, const int32_t* __restrict__ ovf,
+                                                        const int32_t* __restrict__ inserts, int32_t* __restrict__ flag) {
+    place_body<true>(uniq_tmp, nullptr, 0, seg_in, cnt, nbatch, lcap, keys_out, nullptr, seg_off, bidx, ovf, inserts, flag);
+}
+
+// Workspace of the builds from points.  `cap` = point rows, `lcap` = rows of the level (the uncapped build: lcap = cap).  The TABLE
+// follows lcap (a power of two >= 2 lcap, >= 64 slots): it is the part that is cleared and probed on every call.  The per-sample
+// buckets (bkeys), the unique keys (uniq) and the scratch of the global-memory sort (gscr) stay addressed by POINT rows -- a sample's
+// bucket is the row range its points occupy, which is what makes the append need no scan; they are written for winners only, so
+// their size costs address space, not traffic.  total / ovf: the two state words of the capped build, a 128-byte line each.
+struct PWs { int64_t table, bkeys, uniq, gscr, poff, cursor, cnt, count, ovf, total; uint64_t tsize; };
+inline PWs points_layout(int64_t cap, int64_t lcap, int nbatch, bool capped) {
     PWs w;
     w.tsize = 64;
-    while (w.tsize < 2 * (uint64_t)cap) w.tsize <<= 1;
+    while (w.tsize < 2 * (uint64_t)lcap) w.tsize <<= 1;
     w.table = 0;
     w.bkeys = al(w.table + (int64_t)w.tsize * 8);
     w.uniq = al(w.bkeys + cap * 8);
@@ -759,8 +889,14 @@ inline PWs points_layout(int64_t cap, int nbatch) {
     w.poff = al(w.gscr + 2 * cap * 8);
     w.cursor = al(w.poff + (int64_t)(nbatch + 1) * 8);
     w.cnt = al(w.cursor + (int64_t)nbatch * CUR_STRIDE * 4);
-    w.total = al(w.cnt + (int64_t)nbatch * 4);
+    w.count = al(w.cnt + (int64_t)nbatch * 4);
+    w.ovf = capped ? al(w.count + 4) : w.count;
+    w.total = capped ? al(w.ovf + 4) : w.count;          // (the uncapped build has no state words: its size is what it was)
     return w;
+}
+inline unsigned points_init_blocks(uint64_t tsize) {
+    const uint64_t blocks = (tsize / 2 + 256 * 8 - 1) / (256 * 8);
+    return (unsigned)(blocks < 1 ? 1 : (blocks > 65536 ? 65536 : blocks));
 }
 
 }  // namespace agp_coords
@@ -769,7 +905,7 @@ extern "C" int64_t agp_sparse_points_workspace_bytes(int64_t cap, int nbatch) {
     if (cap < 1) cap = 1;
     if (cap >= (1ll << 30)) cap = (1ll << 30) - 1;
     if (nbatch < 1) nbatch = 1;
-    return points_layout(cap, nbatch).total;
+    return points_layout(cap, cap, nbatch, false).total;
 }
 
 extern "C" int agp_sparse_build_points(const float* points, const int64_t* point_offsets, int64_t cap, int nbatch, float quant_size,
@@ -779,16 +915,15 @@ extern "C" int agp_sparse_build_points(const float* points, const int64_t* point
         cap >= (1ll << 30) || nbatch <= 0 || nbatch >= 0x7fff || !(quant_size > 0.f) || !(quant_size <= 3.4e38f) ||
         rot_per_sample < 0 || rot_per_sample > 1)
         return AGP_E_BADARG;
-    const PWs w = points_layout(cap, nbatch);
+    const PWs w = points_layout(cap, cap, nbatch, false);
     if (workspace_bytes < w.total) return AGP_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     uint64_t* table = (uint64_t*)(ws + w.table);
     int64_t* poff = (int64_t*)(ws + w.poff);
     int32_t* cursor = (int32_t*)(ws + w.cursor);
-    const uint64_t init_blocks = (w.tsize / 2 + 256 * 8 - 1) / (256 * 8);
-    AGP_LAUNCH(points_init_kernel, dim3((unsigned)(init_blocks < 1 ? 1 : (init_blocks > 65536 ? 65536 : init_blocks))), dim3(256), 0, s,
-               point_offsets, nbatch, cap, w.tsize, table, poff, cursor, range_flag, feats_out);
+    AGP_LAUNCH(points_init_kernel, dim3(points_init_blocks(w.tsize)), dim3(256), 0, s, point_offsets, nbatch, cap, w.tsize, table, poff,
+               cursor, range_flag, feats_out);
     AGP_CHECK_LAUNCH();
     AGP_LAUNCH(points_voxelize_kernel, dim3((unsigned)((cap + ST - 1) / ST)), dim3(ST), 0, s, points, (const int64_t*)poff, nbatch,
                quant_size, rotation, rot_per_sample, table, w.tsize, cursor, (int64_t*)(ws + w.bkeys), range_flag);
@@ -803,6 +938,56 @@ extern "C" int agp_sparse_build_points(const float* points, const int64_t* point
     }
     AGP_LAUNCH(place_kernel, dim3(nbatch), dim3(256), 0, s, (const int64_t*)(ws + w.uniq), (const float*)nullptr, 0, (const int64_t*)poff,
                (const int32_t*)(ws + w.cnt), nbatch, cap, keys, (float*)nullptr, seg_off, bidx);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+extern "C" int64_t agp_sparse_points_cap_workspace_bytes(int64_t npoints, int64_t level_cap, int nbatch) {
+    if (npoints < 1) npoints = 1;
+    if (npoints >= (1ll << 30)) npoints = (1ll << 30) - 1;
+    if (level_cap < 1) level_cap = 1;
+    if (level_cap >= (1ll << 30)) level_cap = (1ll << 30) - 1;
+    if (nbatch < 1) nbatch = 1;
+    return points_layout(npoints, level_cap, nbatch, true).total;
+}
+
+// agp_sparse_build_points with a level of `level_cap` rows: the same four launches on the capped instantiations.  The init grid is
+// sized by the table of level_cap (its loops stride over the features and the offsets), the voxelise grid by the point rows.
+extern "C" int agp_sparse_build_points_cap(const float* points, const int64_t* point_offsets, int64_t npoints, int64_t level_cap,
+                                           int nbatch, float quant_size, const float* rotation, int rot_per_sample, int64_t* keys,
+                                           float* feats_out, int64_t* seg_off, int32_t* bidx, int32_t* range_flag, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    if (!points || !point_offsets || !keys || !feats_out || !seg_off || !bidx || !range_flag || !workspace || npoints <= 0 ||
+        npoints >= (1ll << 30) || level_cap < 1 || level_cap >= (1ll << 30) || nbatch <= 0 || nbatch >= 0x7fff ||
+        !(quant_size > 0.f) || !(quant_size <= 3.4e38f) || rot_per_sample < 0 || rot_per_sample > 1)
+        return AGP_E_BADARG;
+    const PWs w = points_layout(npoints, level_cap, nbatch, true);
+    if (workspace_bytes < w.total) return AGP_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    uint64_t* table = (uint64_t*)(ws + w.table);
+    int64_t* poff = (int64_t*)(ws + w.poff);
+    int32_t* cursor = (int32_t*)(ws + w.cursor);
+    int32_t* total = (int32_t*)(ws + w.count);
+    int32_t* ovf = (int32_t*)(ws + w.ovf);
+    const int64_t quantum = level_cap / (2 * (int64_t)nbatch) > 0 ? level_cap / (2 * (int64_t)nbatch) : 1;
+    AGP_LAUNCH(points_init_cap_kernel, dim3(points_init_blocks(w.tsize)), dim3(256), 0, s, point_offsets, nbatch, npoints, level_cap,
+               w.tsize, table, poff, cursor, range_flag, feats_out, total, ovf);
+    AGP_CHECK_LAUNCH();
+    AGP_LAUNCH(points_voxelize_cap_kernel, dim3((unsigned)((npoints + ST - 1) / ST)), dim3(ST), 0, s, points, (const int64_t*)poff, nbatch,
+               quant_size, rotation, rot_per_sample, table, w.tsize, cursor, (int64_t*)(ws + w.bkeys), range_flag, level_cap, quantum, total, ovf);
+    AGP_CHECK_LAUNCH();
+    {
+        constexpr int lds = (LDS_KEYS + LDS_KEYS / 32) * 8;
+        static std::atomic<uint64_t> attr_done{0};
+        if (!agp_lds_attr((const void*)seg_sort_points_cap_kernel, lds, attr_done)) return AGP_E_LAUNCH;
+        AGP_LAUNCH(seg_sort_points_cap_kernel, dim3(nbatch), dim3(ST), lds, s, (const int64_t*)(ws + w.bkeys), (const int64_t*)poff,
+                   (const int32_t*)cursor, (int64_t*)(ws + w.uniq), (int32_t*)(ws + w.cnt), (uint64_t*)(ws + w.gscr), range_flag,
+                   (const int32_t*)ovf);
+        AGP_CHECK_LAUNCH();
+    }
+    AGP_LAUNCH(place_cap_kernel, dim3(nbatch), dim3(256), 0, s, (const int64_t*)(ws + w.uniq), (const int64_t*)poff,
+               (const int32_t*)(ws + w.cnt), nbatch, level_cap, keys, seg_off, bidx, (const int32_t*)ovf, (const int32_t*)cursor + 1, range_flag);
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }

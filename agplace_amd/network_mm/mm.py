@@ -109,7 +109,8 @@ class MM(nn.Module):
     # ---- the voxel-range flag.  agp_sparse_build zeroes a device word at the start of every build and sets it when it had to clamp
     # a voxel coordinate into the +-32511 range of the 16-bit key fields, met a batch index outside [0, batch size) or a sample of
     # more than 65536 points (from raw `points`, agp_sparse_build_points: when it had to DROP a point -- non-finite, or its voxel outside that
-    # range -- or a sample holds more than 65536 voxels): the voxel branch's outputs of that batch are then wrong.  Every inference
+    # range -- or a sample holds more than 65536 voxels; with Options.voxel_capacity, bit 2: more distinct voxels than the capacity,
+    # the build is empty): the voxel branch's outputs of that batch are then wrong.  Every inference
     # forward from `coords` or `points` ORs
     # that word into a STICKY device word and copies the sticky word to pinned host memory, both enqueued behind the build on the
     # calling stream -- captured into a hipGraph they are nodes of the graph, so every REPLAY publishes its own flag and the host
@@ -122,11 +123,21 @@ class MM(nn.Module):
                           'host': torch.zeros(1, dtype=torch.int32).pin_memory(), 'event': None, 'calls': 0}
         return slots[key]
 
-    def _raise_voxel_range(self, which):
+    def _raise_voxel_range(self, which, word=None):
+        if word is None:                   # (a caller that has synchronised, pair.CapturedPair.finish: the sticky words say which bits)
+            word = 0
+            for sl in self.__dict__.get('_vox_flag_slots', {}).values():
+                word |= int(sl['sticky'].item())
         for sl in self.__dict__.get('_vox_flag_slots', {}).values():       # the error is reported once: start again from zero
             sl['sticky'].mul_(0)       # (an elementwise kernel, not zero_(): no eager memset beside replayed graphs, csrc/coords.hip)
             sl['host'].zero_()
             sl['event'] = None
+        if word & 4:
+            # bit 2 (agp_sparse_build_points_cap): the batch held more distinct voxels than Options.voxel_capacity rows
+            also = " (a dropped point or an oversized sample was flagged as well)" if word & 3 else ""
+            raise ValueError(f"MM.forward_q: in {which} batch the raw scans held more distinct voxels than the voxel capacity "
+                             f"(Options.voxel_capacity = {self.opt.voxel_capacity}): the build came out empty and the voxel "
+                             f"branch's outputs of that batch are those of an empty cloud; raise the capacity{also}")
         raise ValueError(f"MM.forward_q: in {which} batch a voxel coordinate lies outside the supported range (|c| <= 32511 after "
                          "flooring; from `coords` the point was clamped into the origin voxel, from raw `points` it was dropped, as "
                          "was a point with a non-finite component), a batch index outside [0, batch size), or one sample holds more "
@@ -139,7 +150,7 @@ class MM(nn.Module):
         replays of a captured forward (agplace_amd.pair.CapturedPair.replay does)."""
         for sl in self.__dict__.get('_vox_flag_slots', {}).values():
             if int(sl['host'][0]) != 0:
-                self._raise_voxel_range("an earlier")
+                self._raise_voxel_range("an earlier", int(sl['host'][0]))
 
     def voxel_coords_in_range(self):
         """False if ANY inference forward from `coords` or raw `points` since the last report (eager or replayed) had to clamp a voxel
@@ -174,7 +185,7 @@ class MM(nn.Module):
             if sl['event'] is not None:
                 sl['event'].synchronize()
                 if int(sl['host'][0]) != 0:
-                    self._raise_voxel_range("the previous")
+                    self._raise_voxel_range("the previous", int(sl['host'][0]))
         sl['sticky'].bitwise_or_(flag)
         sl['host'].copy_(sl['sticky'], non_blocking=True)
         if capturing:
@@ -185,7 +196,7 @@ class MM(nn.Module):
         if sl['calls'] == 1:
             sl['event'].synchronize()
             if int(sl['host'][0]) != 0:
-                self._raise_voxel_range("this")
+                self._raise_voxel_range("this", int(sl['host'][0]))
 
     def load_reference_state_dict(self, sd):
         """Load a reference checkpoint's `modelq_state_dict` (the voxel branch uses MinkowskiEngine's
@@ -332,7 +343,8 @@ class MM(nn.Module):
                 if train:
                     if from_points:
                         sp = sparse.SparseTensor.from_points_levels(data_dict['points'], data_dict['point_offsets'], image.shape[0],
-                                                                    len(self.vox_fe.convs), opt.quant_size, data_dict.get('pc_rotation'))
+                                                                    len(self.vox_fe.convs), opt.quant_size, data_dict.get('pc_rotation'),
+                                                                    level_capacity=opt.voxel_capacity)
                     else:
                         sp = sparse.SparseTensor.from_coords_levels(data_dict['features'], data_dict['coords'], image.shape[0], len(self.vox_fe.convs))
                     vsink = train_fns.VoxSink()
@@ -394,7 +406,8 @@ class MM(nn.Module):
                     # from the module's workspace -- the branch is hipGraph-capturable (agplace_amd/sparse/coords.py)
                     if from_points:
                         sp = sparse.SparseTensor.from_points_capacity(data_dict['points'], data_dict['point_offsets'], image.shape[0],
-                                                                      opt.quant_size, vox_ws, data_dict.get('pc_rotation'))
+                                                                      opt.quant_size, vox_ws, data_dict.get('pc_rotation'),
+                                                                      level_capacity=opt.voxel_capacity)
                     else:
                         sp = sparse.SparseTensor.from_coords_capacity(data_dict['features'], data_dict['coords'], image.shape[0], vox_ws)
                     vox_flag = sp.range_flag

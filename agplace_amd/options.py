@@ -132,6 +132,12 @@ class Options:
     # ops.normalize_cameras_u8's image.  False (default): those inputs are refused by name, as before.  A reference namespace does
     # not carry this field (from_reference_opt leaves it False): from_reference_opt(args).copy(convnext_u8=True).
     convnext_u8: bool = False
+    # Opt-in level capacity of the raw-points route (MM.forward_q from `points` / `point_offsets`, inference and training): an upper
+    # bound on the voxels of a whole batch, None or an int in 1 .. 2^30 - 1.  With a value every level of the voxel branch has that
+    # many rows instead of one per raw point (SparseTensor.from_points_capacity / from_points_levels, level_capacity);
+    # a batch of more distinct voxels is reported as a "voxel capacity" ValueError (bit 2 of the voxel flag) and its voxel branch
+    # sees an empty cloud.  The `coords` route ignores it.  Not a reference option: from_reference_opt leaves it None.
+    voxel_capacity: Optional[int] = None
     # inference: MM.forward embeds a batch as this many sub-batches on as many HIP streams (1 = off)
     query_substreams: int = 1
     # inference: the vector path (everything after the backbones) as two program launches (agplace_amd/vecprog.py) instead
@@ -186,6 +192,9 @@ class Options:
             raise ValueError(f"convnext_u8 {self.convnext_u8!r}: True | False")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
+        v = self.voxel_capacity
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < (1 << 30)):
+            raise ValueError(f"voxel_capacity {v!r}: None or an integer in 1 .. 2^30 - 1 (rows of every level from raw points)")
 
     def copy(self, **kw):
         d = {f.name: getattr(self, f.name) for f in fields(self)}
@@ -197,7 +206,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name != "convnext_u8":      # (not a reference option: stays False)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "voxel_capacity"):      # (not reference options: stay False / None)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

@@ -23,7 +23,8 @@ Ways to build the levels:
   * `SparseTensor.from_coords_levels` (training, what MM uses): the same device-side kernels for ALL levels back to back, then ONE
     read-back of the row counts -> exact-size tensors (the counts size the activation tapes of the backward pass);
   * `SparseTensor.from_points_capacity` / `from_points_levels`: the same two from RAW lidar points -- quantisation, per-sample
-    deduplication and the optional rotation run on the device too (agp_sparse_build_points; specification: DESIGN.md 1c);
+    deduplication and the optional rotation run on the device too (agp_sparse_build_points; specification: DESIGN.md 1c); with
+    `level_capacity` the levels have that many rows instead of one per raw point (agp_sparse_build_points_cap);
   * `SparseTensor.from_coords` (+ `strided()` on its result): exact-size levels from torch.unique on the keys, one host
     synchronisation per level -- the plain restatement the other two are tested against.
 """
@@ -171,59 +172,92 @@ class SparseTensor:
         return p, off, r, per
 
     @staticmethod
-    def from_points_capacity(points, point_offsets, nbatch, quant_size, ws, rotation=None):
+    def _level_capacity(level_capacity):
+        """None, or the rows of every level as an int in 1 .. 2^30 - 1 (the bound agp_sparse_build_points_cap accepts)"""
+        if level_capacity is None:
+            return None
+        if isinstance(level_capacity, bool) or not isinstance(level_capacity, int) or not 1 <= level_capacity < (1 << 30):
+            raise ValueError(f"level_capacity {level_capacity!r}: None or an int in 1 .. 2^30 - 1")
+        return level_capacity
+
+    @staticmethod
+    def _build_points(L, p, off, n, rows, capped, nbatch, quant_size, r, per, keys, f_out, seg_off, bidx, flag, tmp, nbytes):
+        """One launch sequence of the front end into buffers of `rows` rows: the capped entry point if a level capacity was given."""
+        if capped:
+            check(L.agp_sparse_build_points_cap(ptr(p), ptr(off), n, rows, nbatch, float(quant_size), ptr(r), per, ptr(keys), ptr(f_out),
+                                                ptr(seg_off), ptr(bidx), ptr(flag), ptr(tmp), nbytes, _lib.stream()),
+                  "agp_sparse_build_points_cap")
+        else:
+            check(L.agp_sparse_build_points(ptr(p), ptr(off), n, nbatch, float(quant_size), ptr(r), per, ptr(keys), ptr(f_out),
+                                            ptr(seg_off), ptr(bidx), ptr(flag), ptr(tmp), nbytes, _lib.stream()), "agp_sparse_build_points")
+
+    @staticmethod
+    def from_points_capacity(points, point_offsets, nbatch, quant_size, ws, rotation=None, level_capacity=None):
         """Level 0 from RAW scans (inference; the counterpart of `from_coords_capacity`): points fp32 [N, 3] in metres, sample b owns
         rows [point_offsets[b], point_offsets[b+1]) (int64 [nbatch + 1] on the device; rows from point_offsets[nbatch] on are
         ignored, so one buffer of N rows serves scans of any length under a captured graph), quantised with `quant_size`,
         deduplicated per sample and -- with `rotation`, fp32 [3, 3] or [nbatch, 3, 3] -- rotated as `coords @ R`.
         The capacity of every level is N.  Features are the reference's all-ones column.  One call of agp_sparse_build_points: no
-        host synchronisation; pass device tensors (a host `rotation` or `point_offsets` is copied on the calling stream)."""
+        host synchronisation; pass device tensors (a host `rotation` or `point_offsets` is copied on the calling stream).
+        `level_capacity` (int, 1 .. 2^30 - 1): the capacity of every level is that number instead of N -- an upper bound the caller
+        knows for the voxels of the whole batch (a sweep deduplicates 7-16 times, so N rows are mostly padding).  Every buffer of the
+        level, and through `self.n` every coarser level, kernel map and feature map, then has `level_capacity` rows; a build that
+        fits is bit-equal to the one without the argument.  More distinct voxels than that: bit 2 (value 4) of `range_flag`, every
+        sample empty (agp_sparse_build_points_cap)."""
         p, off, r, per = SparseTensor._points_args(points, point_offsets, nbatch, quant_size, rotation)
+        lcap = SparseTensor._level_capacity(level_capacity)
         dev, n = p.device, p.shape[0]
+        rows = n if lcap is None else lcap
         L = _lib.load()
-        keys = ws.tensor("sp.keys0", (n,), torch.int64, dev)
-        f_out = ws.tensor("sp.f0", (n, 1), torch.float32, dev)
+        keys = ws.tensor("sp.keys0", (rows,), torch.int64, dev)
+        f_out = ws.tensor("sp.f0", (rows, 1), torch.float32, dev)
         seg_off = ws.tensor("sp.seg0", (nbatch + 1,), torch.int64, dev)
-        bidx = ws.tensor("sp.bidx0", (n,), torch.int32, dev)
+        bidx = ws.tensor("sp.bidx0", (rows,), torch.int32, dev)
         flag = ws.tensor("sp.flag", (1,), torch.int32, dev, zero=True)
-        nbytes = L.agp_sparse_points_workspace_bytes(n, nbatch)
+        nbytes = L.agp_sparse_points_workspace_bytes(n, nbatch) if lcap is None else L.agp_sparse_points_cap_workspace_bytes(n, lcap, nbatch)
         tmp = ws.tensor("sp.ptmp0", (nbytes,), torch.uint8, dev)
-        check(L.agp_sparse_build_points(ptr(p), ptr(off), n, nbatch, float(quant_size), ptr(r), per, ptr(keys), ptr(f_out), ptr(seg_off),
-                                        ptr(bidx), ptr(flag), ptr(tmp), nbytes, _lib.stream()), "agp_sparse_build_points")
+        SparseTensor._build_points(L, p, off, n, rows, lcap is not None, nbatch, quant_size, r, per, keys, f_out, seg_off, bidx, flag,
+                                   tmp, nbytes)
         t = SparseTensor(None, keys, nbatch, 1, f32=f_out, n_dev=seg_off[nbatch:], ws=ws)
         t._seg = (seg_off, bidx)
         t.range_flag = flag
         return t
 
     @staticmethod
-    def from_points_levels(points, point_offsets, nbatch, nlevels, quant_size, rotation=None):
+    def from_points_levels(points, point_offsets, nbatch, nlevels, quant_size, rotation=None, level_capacity=None):
         """The exact-size levels of the training path from RAW scans (the counterpart of `from_coords_levels`, same inputs as
         `from_points_capacity`): agp_sparse_build_points + `nlevels` x agp_sparse_coarsen back to back, then ONE read-back of the
         row counts and the flag.  Raises ValueError on a flagged build (a non-finite or out-of-range point, more than 65536
-        voxels in one sample)."""
+        voxels in one sample).  `level_capacity`: the level buffers (and the coarsening's workspace) are allocated with that many
+        rows instead of N; more distinct voxels than that raise a ValueError that names the capacity (the same read-back)."""
         p, off, r, per = SparseTensor._points_args(points, point_offsets, nbatch, quant_size, rotation)
+        lcap = SparseTensor._level_capacity(level_capacity)
         dev, n = p.device, p.shape[0]
+        rows = n if lcap is None else lcap
         L = _lib.load()
-        nbytes = L.agp_sparse_points_workspace_bytes(n, nbatch)
+        nbytes = L.agp_sparse_points_workspace_bytes(n, nbatch) if lcap is None else L.agp_sparse_points_cap_workspace_bytes(n, lcap, nbatch)
         tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        cbytes = L.agp_sparse_coords_workspace_bytes(n, nbatch, 0)
+        cbytes = L.agp_sparse_coords_workspace_bytes(rows, nbatch, 0)
         ctmp = torch.empty((cbytes,), dtype=torch.uint8, device=dev)
         flag = torch.zeros((1,), dtype=torch.int32, device=dev)
 
         def level_buffers():
-            return (torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((nbatch + 1,), dtype=torch.int64, device=dev),
-                    torch.empty((n,), dtype=torch.int32, device=dev))
+            return (torch.empty((rows,), dtype=torch.int64, device=dev), torch.empty((nbatch + 1,), dtype=torch.int64, device=dev),
+                    torch.empty((rows,), dtype=torch.int32, device=dev))
         keys, seg, bidx = level_buffers()
-        f_out = torch.empty((n, 1), dtype=torch.float32, device=dev)
-        check(L.agp_sparse_build_points(ptr(p), ptr(off), n, nbatch, float(quant_size), ptr(r), per, ptr(keys), ptr(f_out), ptr(seg),
-                                        ptr(bidx), ptr(flag), ptr(tmp), nbytes, _lib.stream()), "agp_sparse_build_points")
+        f_out = torch.empty((rows, 1), dtype=torch.float32, device=dev)
+        SparseTensor._build_points(L, p, off, n, rows, lcap is not None, nbatch, quant_size, r, per, keys, f_out, seg, bidx, flag, tmp,
+                                   nbytes)
         levels = [(keys, seg, bidx)]
         for l in range(nlevels):
             k2, s2, b2 = level_buffers()
-            check(L.agp_sparse_coarsen(ptr(levels[-1][0]), ptr(levels[-1][1]), n, 1 << l, nbatch, ptr(k2), ptr(s2), ptr(b2), ptr(ctmp),
+            check(L.agp_sparse_coarsen(ptr(levels[-1][0]), ptr(levels[-1][1]), rows, 1 << l, nbatch, ptr(k2), ptr(s2), ptr(b2), ptr(ctmp),
                                        cbytes, _lib.stream()), "agp_sparse_coarsen")
             levels.append((k2, s2, b2))
         counts = torch.cat([s_[nbatch:] for _, s_, _ in levels] + [flag.to(torch.int64)]).tolist()      # the one synchronisation
+        if counts[-1] & 4:
+            raise ValueError(f"voxel capacity {rows} exceeded: the scans hold more distinct voxels than level_capacity={rows} rows "
+                             "(agp_sparse_build_points_cap emptied the build); pass a larger level_capacity / Options.voxel_capacity")
         if counts[-1]:
             raise ValueError("a lidar point with a non-finite component or a voxel coordinate out of the +-32511 range (16-bit key "
                              "fields, kernel offsets need headroom), or more than 65536 voxels in one sample")

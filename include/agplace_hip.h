@@ -1079,6 +1079,26 @@ int64_t agp_sparse_points_workspace_bytes(int64_t cap, int nbatch);
 int agp_sparse_build_points(const float* points, const int64_t* point_offsets, int64_t cap, int nbatch, float quant_size,
                             const float* rotation, int rot_per_sample, int64_t* keys, float* feats_out, int64_t* seg_off,
                             int32_t* bidx, int32_t* range_flag, void* workspace, int64_t workspace_bytes, void* stream);
+/* agp_sparse_build_points with a LEVEL CAPACITY: `points` has npoints rows (point_offsets are clamped into [0, npoints]), while
+ * keys [level_cap], feats_out [level_cap] and bidx [level_cap] have level_cap rows -- the caller's upper bound on the number of
+ * voxels of the whole batch, smaller or larger than npoints.  Arithmetic, drop rules, flag bits 0 and 1, key format and row order
+ * are those of agp_sparse_build_points: for a build that fits, the valid rows, seg_off, bidx, the features and the flag are
+ * bit-equal to it; rows from the valid count up to level_cap are padding (INT64_MAX, batch index 0).  The hash table (a power of
+ * two >= 2 level_cap, >= 64 slots, smaller still for fewer rows inside the offsets), its clear, the feature fill and the padding
+ * stores follow level_cap, not npoints.
+ *   Overflow: let A = the number of distinct (sample, quantised voxel) cells among the rows that pass the finite / range test,
+ * counted before the rotation.  *range_flag |= 4 if and only if A > level_cap; such a build comes out EMPTY for every sample
+ * (seg_off all zero, all level_cap rows padding).  Bits 0 and 1 are still raised for the rows the build looked at before it knew.
+ * The probe loop is bounded by the table size and rows are dropped unprobed once the overflow is known: a grossly wrong bound
+ * costs about what a build costs.  workspace: 256-byte aligned, agp_sparse_points_cap_workspace_bytes(npoints, level_cap, nbatch)
+ * bytes (table by level_cap; per-sample buckets and sort scratch by npoints).  4 kernel launches on `stream`, no memset node, no
+ * host read-back.  AGP_E_BADARG, before any launch: as agp_sparse_build_points (npoints in the place of cap), and level_cap
+ * outside [1, 2^30). */
+int64_t agp_sparse_points_cap_workspace_bytes(int64_t npoints, int64_t level_cap, int nbatch);
+int agp_sparse_build_points_cap(const float* points, const int64_t* point_offsets, int64_t npoints, int64_t level_cap, int nbatch,
+                                float quant_size, const float* rotation, int rot_per_sample, int64_t* keys, float* feats_out,
+                                int64_t* seg_off, int32_t* bidx, int32_t* range_flag, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 /* Per-sample mean (ME.MinkowskiGlobalPooling / GlobalAvgPooling) and GeM (layers/pooling.py:70-87)
  * of a feature matrix: mean_out / gem_out fp32 [nseg][c] (either may be NULL). */
 int agp_seg_pool_fwd(const void* hi, const void* lo, const int64_t* seg_off, int nseg, int c, const float* p,
