@@ -132,6 +132,10 @@ SIGNATURES = {
     "agp_fcode_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, _P, _P, _P]),
     "agp_fcode_traj_floats": (_L, [_I, _I, _I]),
     "agp_fcode_wide_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _I, _P, _P]),
+    "agp_fcode_wide_traj_floats": (_L, [_I, _I, _I, _I]),
+    "agp_fcode_wide_fwd_traj": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _I, _P, _P, _P]),
+    "agp_fcode_wide_bwd_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "agp_fcode_wide_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(_F), _I, _P, _P, _P, _P, _L, _P]),
     "agp_fcode_bwd_workspace_bytes": (_L, [_I, _I, _I]),
     "agp_fcode_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), _I, _P, _P, _P, _P, _L, _P]),
     "agp_fcode_adaptive_ctrl_bytes": (_L, [_I]),

@@ -43,8 +43,8 @@ def linear(x, module, prep, act=None, add1=None, add2=None):
 
 
 class FCODEFn(torch.autograd.Function):
-    """Neural-ODE block; backward is discretise-then-optimise (agp_fcode_bwd; agp_fcode_adaptive_bwd for an adaptive method,
-    through the accepted steps, with the step control a constant)."""
+    """Neural-ODE block; backward is discretise-then-optimise (agp_fcode_bwd, at 384 columns agp_fcode_wide_bwd;
+    agp_fcode_adaptive_bwd for an adaptive method, through the accepted steps, with the step control a constant)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, mod, add1, add2):
@@ -59,7 +59,8 @@ class FCODEFn(torch.autograd.Function):
                 ctx.mod = mod
                 ctx.has = (add1 is not None, add2 is not None)
             return out[0]
-        out = ops.fcode(x, lw, mod.act_name, mod.method, mod.dts, add1=add1, add2=add2, want_traj=need)
+        fwd = ops.fcode_wide if lw.n == ops.FCODE_WIDE_DIM else ops.fcode
+        out = fwd(x, lw, mod.act_name, mod.method, mod.dts, add1=add1, add2=add2, want_traj=need)
         if not need:
             return out
         y, traj = out
@@ -77,7 +78,11 @@ class FCODEFn(torch.autograd.Function):
             gx, gw, gb = ops.fcode_adaptive_bwd(traj, ctrl, gy, lw, mod.act_name, mod.method, mod.max_steps)
         else:
             (traj,) = ctx.saved_tensors
-            gx, gw, gb = ops.fcode_bwd(traj, gy, lw, mod.act_name, mod.method, mod.dts)
+            if lw.n == ops.FCODE_WIDE_DIM:      # (frozen weights: no weight-gradient GEMM, no column sum)
+                gx, gw, gb = ops.fcode_wide_bwd(traj, gy, lw, mod.act_name, mod.method, mod.dts,
+                                                need_w=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+            else:
+                gx, gw, gb = ops.fcode_bwd(traj, gy, lw, mod.act_name, mod.method, mod.dts)
         return (gx if ctx.needs_input_grad[0] else None, gw if ctx.needs_input_grad[1] else None,
                 gb if ctx.needs_input_grad[2] else None, None,
                 gx if ctx.has[0] and ctx.needs_input_grad[4] else None,

@@ -14,19 +14,6 @@
 
 namespace agp_fusion {
 
-template <int ACT>
-__device__ __forceinline__ f32x4 dact_from_output(const f32x4& k) {
-    f32x4 o;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (ACT == AGP_ACT_RELU) o[r] = k[r] > 0.f ? 1.f : 0.f;
-        else if (ACT == AGP_ACT_TANH) o[r] = 1.f - k[r] * k[r];
-        else if (ACT == AGP_ACT_SIGMOID) o[r] = k[r] * (1.f - k[r]);
-        else o[r] = 1.f;
-    }
-    return o;
-}
-
 // One workgroup (16 waves) per 16 batch rows; lane owns (batch row l&15, features 16w+4(l>>4)+r).
 template <int ACT>
 __global__ __launch_bounds__(FT) void fcode_bwd_state_kernel(const float* __restrict__ traj,
@@ -288,7 +275,18 @@ __global__ __launch_bounds__(256) void l2normalize_bwd_kernel(const float* __res
     }
 }
 
-inline int stages_of(int method) { return method == AGP_ODE_EULER ? 1 : (method == AGP_ODE_MIDPOINT ? 2 : 4); }
+// (declared in fusion_common.hpp: the fixed-grid backward at 384 columns, fusion_wide.hip, ends in the same two sums)
+int gemm_tn(const float* A, const float* B, float* C, int M, int N, int R, int lda, int ldb, int ldc, hipStream_t s) {
+    AGP_LAUNCH(gemm_tn_f32_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, s, A, B, C, M, N, R, lda, ldb, ldc);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int colsum(const float* A, int R, int cols, int lda, float* out, hipStream_t s) {
+    AGP_LAUNCH(colsum_kernel, dim3((cols + 63) / 64), dim3(256), 0, s, A, R, cols, lda, out);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
 
 }  // namespace agp_fusion
 using namespace agp_fusion;
@@ -297,13 +295,6 @@ using namespace agp_fusion;
 extern "C" int agp_linear_fwd(const float* x, const float* add1, const float* add2, const void* w_hi,
                               const void* w_lo, const float* bias, int b, int k, int n, int act, float* y,
                               void* stream);
-
-static int gemm_tn(const float* A, const float* B, float* C, int M, int N, int R, int lda, int ldb, int ldc,
-                   hipStream_t s) {
-    AGP_LAUNCH(gemm_tn_f32_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, s, A, B, C, M, N, R, lda, ldb, ldc);
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
-}
 
 extern "C" int64_t agp_fcode_bwd_workspace_bytes(int b, int method, int nsteps) {
     const int64_t Bp = (b + FROWS - 1) / FROWS * FROWS;
@@ -340,8 +331,8 @@ extern "C" int agp_fcode_bwd(const float* traj, const float* gy, const void* wt_
         if (rc != AGP_OK) return rc;
     }
     if (gb) {
-        AGP_LAUNCH(colsum_kernel, dim3(4), dim3(256), 0, s, GZ, R, 256, 256, gb);
-        AGP_CHECK_LAUNCH();
+        const int rc = colsum(GZ, R, 256, 256, gb, s);
+        if (rc != AGP_OK) return rc;
     }
     return AGP_OK;
 }
@@ -376,8 +367,8 @@ extern "C" int agp_linear_bwd(const float* x, const float* y, const float* gy, c
         if (rc != AGP_OK) return rc;
     }
     if (gb) {
-        AGP_LAUNCH(colsum_kernel, dim3((n + 63) / 64), dim3(256), 0, s, gz, b, n, np, gb);
-        AGP_CHECK_LAUNCH();
+        const int rc = colsum(gz, b, n, np, gb, s);
+        if (rc != AGP_OK) return rc;
     }
     return AGP_OK;
 }

@@ -52,5 +52,25 @@ __device__ __forceinline__ f32x4 act4(const f32x4& z) {
     return o;
 }
 
+// act'(z) from the recorded OUTPUT k = act(z)
+template <int ACT>
+__device__ __forceinline__ f32x4 dact_from_output(const f32x4& k) {
+    f32x4 o;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (ACT == AGP_ACT_RELU) o[r] = k[r] > 0.f ? 1.f : 0.f;
+        else if (ACT == AGP_ACT_TANH) o[r] = 1.f - k[r] * k[r];
+        else if (ACT == AGP_ACT_SIGMOID) o[r] = k[r] * (1.f - k[r]);
+        else o[r] = 1.f;
+    }
+    return o;
+}
+
+inline int stages_of(int method) { return method == AGP_ODE_EULER ? 1 : (method == AGP_ODE_MIDPOINT ? 2 : 4); }
+
+// The fixed-order fp32 sums behind the fixed-grid backward kernels (defined in fusion_bwd.hip; general M, N, R):
+// C[M][N] = sum_r A[r][M] * B[r][N] (gemm_tn_f32_kernel) and out[c] = sum_r A[r][c], c < cols (colsum_kernel).  Both OVERWRITE.
+int gemm_tn(const float* A, const float* B, float* C, int M, int N, int R, int lda, int ldb, int ldc, hipStream_t s);
+int colsum(const float* A, int R, int cols, int lda, float* out, hipStream_t s);
 
 }  // namespace agp_fusion

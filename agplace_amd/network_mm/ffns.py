@@ -5,8 +5,10 @@ options={'step_size': opt.odeint_size})[-1] with f(t, y) = act(Linear(y)).  torc
 used: the whole fixed-grid solve (all steps, all stages) is ONE persistent HIP kernel
 (agp_fcode_fwd) that keeps W's MFMA fragments in registers.  dim = 384 in inference (no gradient wanted) is one launch as well
 (agp_fcode_wide_fwd: W's `hi` plane in registers, the `lo` plane streamed from L2); every other width, and
-384 with a gradient wanted, runs the same steps as a sequence of differentiable launches (_forward_any_width).  The time grid follows
-torchdiffeq's constructor exactly (niters = ceil(1/step + 1), arange * step, last point forced
+384 with a gradient wanted, runs the same steps as a sequence of differentiable launches (_forward_any_width) -- unless
+Options.fcode_wide opted in: FCODE(384) then trains on the one-launch kernel recording its trajectory and its one-launch backward
+(agp_fcode_wide_fwd_traj / agp_fcode_wide_bwd) and takes odeint_method = 'dopri5' (agp_fcode_adaptive_wide_fwd / _bwd).
+The time grid follows torchdiffeq's constructor exactly (niters = ceil(1/step + 1), arange * step, last point forced
 to 1) and is kept in fp32 (the reference builds t with .float().type_as(x)).
 'rk4' is torchdiffeq's 3/8-rule variant.  rtol/atol (opt.tol) are ignored by fixed-grid solvers.
 odeint_method = 'dopri5' (torchdiffeq's default, adaptive) reads them: rtol = atol = opt.tol, one launch per solve as well
@@ -101,11 +103,17 @@ class FCODE(nn.Module):
             raise ValueError(f"tol {opt.tol!r}: dopri5 needs rtol = atol > 0")
         self.dts = None if self.adaptive else ops.ode_grid_dts(self.step_size)
         self._ctrl = None                 # device control block of the last adaptive solve (solver_stats)
+        self.wide_routes = bool(opt.fcode_wide) and dim == ops.FCODE_WIDE_DIM       # Options.fcode_wide, at its one width
         self._prep = _PreparedLinear(self.func.func.fc)
 
     def forward(self, x, add1=None, add2=None):
         fc = self.func.func.fc
         if fc.in_features == 256:
+            return autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, self, add1, add2)
+        if self.wide_routes and (self.adaptive or (torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad for t in (x, add1, add2, fc.weight, fc.bias)))):
+            # opted in at 384 columns: a fixed grid with a gradient wanted records its trajectory in the one-launch kernel, dopri5
+            # runs on the adaptive kernels; a fixed grid without a gradient is the inference launch below either way
             return autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, self, add1, add2)
         if fc.in_features == ops.FCODE_WIDE_DIM and not self.adaptive and not (torch.is_grad_enabled() and any(
                 t is not None and t.requires_grad for t in (x, add1, add2, fc.weight, fc.bias))):

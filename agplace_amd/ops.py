@@ -1377,9 +1377,10 @@ def fcode_wide_planes_t(lw: LinearWeights):
     return lw._frag_t
 
 
-def fcode_wide(x, lw: LinearWeights, act, method, dts, add1=None, add2=None):
+def fcode_wide(x, lw: LinearWeights, act, method, dts, add1=None, add2=None, want_traj=False):
     """y(1) of y' = act(y W^T + b), y(0) = x + add1 + add2 at 384 columns on the fixed grid `dts`: ONE launch
-    (agp_fcode_wide_fwd), no host synchronisation, capturable; no trajectory -- the inference kernel of FCODE(384)."""
+    (agp_fcode_wide_fwd), no host synchronisation, capturable; no trajectory -- the inference kernel of FCODE(384).
+    want_traj: (y, traj) from the same kernel recording what fcode_wide_bwd reads (agp_fcode_wide_fwd_traj); y's bits are the same."""
     _need_cuda(x, "fcode_wide")
     x = x.contiguous().float()
     b, d = x.shape
@@ -1394,9 +1395,40 @@ def fcode_wide(x, lw: LinearWeights, act, method, dts, add1=None, add2=None):
     n = len(dts)
     arr = (C.c_float * n)(*dts)
     y = torch.empty_like(x)
+    if want_traj:
+        fcode_wide_planes_t(lw)      # a backward follows: fragment-order planes are prepared here, outside any capture of it
+        traj = torch.empty(_L().agp_fcode_wide_traj_floats(b, d, _lib.ODE[method], n), dtype=torch.float32, device=x.device)
+        check(_L().agp_fcode_wide_fwd_traj(ptr(x), ptr(add1), ptr(add2), ptr(f_hi), ptr(f_lo), ptr(lw.bias), b, d, _lib.ACT[act],
+                                           _lib.ODE[method], arr, n, ptr(y), ptr(traj), _lib.stream()), "agp_fcode_wide_fwd_traj")
+        return y, traj
     check(_L().agp_fcode_wide_fwd(ptr(x), ptr(add1), ptr(add2), ptr(f_hi), ptr(f_lo), ptr(lw.bias), b, d, _lib.ACT[act],
                                   _lib.ODE[method], arr, n, ptr(y), _lib.stream()), "agp_fcode_wide_fwd")
     return y
+
+
+def fcode_wide_bwd(traj, gy, lw: LinearWeights, act, method, dts, need_w=True):
+    """(gx, gw, gb) of fcode_wide(..., want_traj=True) (agp_fcode_wide_bwd: one state launch, then the weight gradient's GEMM and
+    the bias gradient's column sum); need_w=False (frozen weights): (gx, None, None), the same gx bits from the one launch."""
+    _need_cuda(gy, "fcode_wide_bwd")
+    gy = gy.contiguous().float()
+    b, d = gy.shape
+    if d != FCODE_WIDE_DIM:
+        raise NotImplementedError(f"fcode_wide is built for dim={FCODE_WIDE_DIM}, got {d}")
+    if method not in _lib.ODE:
+        raise NotImplementedError(method)
+    if act not in _lib.ACT:
+        raise NotImplementedError(act)
+    n = len(dts)
+    arr = (C.c_float * n)(*dts)
+    pt_hi, pt_lo = fcode_wide_planes_t(lw)
+    gx = torch.empty_like(gy)
+    gw = torch.empty((d, d), dtype=torch.float32, device=gy.device) if need_w else None
+    gb = torch.empty(d, dtype=torch.float32, device=gy.device) if need_w else None
+    nbytes = _L().agp_fcode_wide_bwd_workspace_bytes(b, d, _lib.ODE[method], n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
+    check(_L().agp_fcode_wide_bwd(ptr(traj), ptr(gy), ptr(pt_hi), ptr(pt_lo), b, d, _lib.ACT[act], _lib.ODE[method], arr, n,
+                                  ptr(gx), ptr(gw), ptr(gb), ptr(ws), nbytes, _lib.stream()), "agp_fcode_wide_bwd")
+    return gx, gw, gb
 
 
 def fcode_bwd(traj, gy, lw: LinearWeights, act, method, dts):

@@ -132,6 +132,13 @@ class Options:
     # ops.normalize_cameras_u8's image.  False (default): those inputs are refused by name, as before.  A reference namespace does
     # not carry this field (from_reference_opt leaves it False): from_reference_opt(args).copy(convnext_u8=True).
     convnext_u8: bool = False
+    # Opt-in one-launch routes of FCODE(384) (the Neural-ODE blocks of MM on the ConvNeXt-tiny trunk): with a gradient wanted a
+    # fixed-grid solve records its trajectory in the one-launch kernel and differentiates through agp_fcode_wide_bwd instead of
+    # the any-width sequence of launches, and odeint_method = "dopri5" runs on the adaptive kernels at 384 columns instead of
+    # being refused (csrc/fusion_wide.hip, csrc/fusion_adaptive.hip).  False (default): FCODE(384) routes
+    # as before, launch for launch.  Other widths ignore it.  A reference namespace does not carry this field
+    # (from_reference_opt leaves it False): from_reference_opt(args).copy(fcode_wide=True).
+    fcode_wide: bool = False
     # Opt-in level capacity of the raw-points route (MM.forward_q from `points` / `point_offsets`, inference and training): an upper
     # bound on the voxels of a whole batch, None or an int in 1 .. 2^30 - 1.  With a value every level of the voxel branch has that
     # many rows instead of one per raw point (SparseTensor.from_points_capacity / from_points_levels, level_capacity);
@@ -190,6 +197,8 @@ class Options:
             raise ValueError(f"convnext_train {self.convnext_train!r}: True | False")
         if not isinstance(self.convnext_u8, bool):
             raise ValueError(f"convnext_u8 {self.convnext_u8!r}: True | False")
+        if not isinstance(self.fcode_wide, bool):
+            raise ValueError(f"fcode_wide {self.fcode_wide!r}: True | False")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
         v = self.voxel_capacity
@@ -206,7 +215,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "voxel_capacity"):      # (not reference options: stay False / None)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "fcode_wide", "voxel_capacity"):      # (not reference options: stay False / None)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

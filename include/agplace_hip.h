@@ -525,6 +525,32 @@ int agp_fcode_wide_fwd(const float* x, const float* add1, const float* add2, con
                        const float* bias, int b, int d, int act, int method, const float* dt, int nsteps, float* y,
                        void* stream);
 
+/* agp_fcode_wide_fwd recording its trajectory for agp_fcode_wide_bwd: the same kernel with the stores compiled in, so y has the
+ * bits agp_fcode_wide_fwd gives.  traj (required): agp_fcode_wide_traj_floats(b, d, method, nsteps) =
+ * nsteps * (1 + stages) * b * 384 floats, laid out as agp_fcode_fwd's: traj[s][0][b][384] = y before step s,
+ * traj[s][1 + i][b][384] = k_i of step s (i < stages: euler 1, midpoint 2, rk4 4); only rows < b are written.  The size is 0
+ * for b <= 0, nsteps outside 1..64, an unknown method or d != 384.  Refusals as agp_fcode_wide_fwd, a null traj among them. */
+int64_t agp_fcode_wide_traj_floats(int b, int d, int method, int nsteps);
+int agp_fcode_wide_fwd_traj(const float* x, const float* add1, const float* add2, const void* wf_hi, const void* wf_lo,
+                            const float* bias, int b, int d, int act, int method, const float* dt, int nsteps, float* y,
+                            float* traj, void* stream);
+
+/* Backward of agp_fcode_wide_fwd_traj, as agp_fcode_bwd (discretise-then-optimise through the recorded stages) at d = 384: gx =
+ * dL/dx (also the gradient of add1 / add2); gw[384][384] = dL/dW and gb[384] = dL/db are OVERWRITTEN, and either may be NULL
+ * (frozen weights: the same gx bits, its sum is not launched).  One workgroup of 8 waves per 16 batch rows; wtf_hi / wtf_lo: the
+ * split-bf16 planes of W^T in the fragment order of agp_fcode_wide_fwd, i.e. [wave][ks][tile][q][row][8] =
+ * W[32 ks + 8 q .. + 7][48 wave + 16 tile + row]; the adjoint products gz W on two planes and three products, K-steps ascending.
+ * Every (gz_i, stage input s_i) pair goes to workspace row (s * stages + i) * Bp + row (Bp = b rounded up to 16, rows >= b
+ * zero); gw is ONE fixed-order fp32 GEMM over those R = nsteps * stages * Bp rows, gb a column sum: no atomics, two runs give
+ * the same bits.  No allocation, no synchronisation, capturable.  workspace: agp_fcode_wide_bwd_workspace_bytes(b, d, method,
+ * nsteps) = 2 * R * 384 * 4 bytes (0 for the arguments agp_fcode_wide_traj_floats gives 0 for).
+ * Checked before any launch: AGP_E_BADARG for a null required pointer, b <= 0, nsteps outside 1..64, an unknown act or
+ * method, a short workspace; AGP_E_UNSUPPORTED for d != 384. */
+int64_t agp_fcode_wide_bwd_workspace_bytes(int b, int d, int method, int nsteps);
+int agp_fcode_wide_bwd(const float* traj, const float* gy, const void* wtf_hi, const void* wtf_lo, int b, int d, int act,
+                       int method, const float* dt, int nsteps, float* gx, float* gw, float* gb, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* FCODE backward (discretise-then-optimise, like autograd through odeint at ffns.py:84): given
  * gy = dL/dy(1) and the recorded trajectory, produce gx = dL/dx (also the gradient of add1/add2)
  * and OVERWRITE gw[256][256] = dL/dW, gb[256] = dL/db.  wt_hi/wt_lo are the split planes of W^T.

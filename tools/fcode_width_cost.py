@@ -1,4 +1,4 @@
-"""Cost of FCODE(384) by route: python tools/fcode_width_cost.py [--steps 50] [--windows 5] [--mm-steps 10] [--no-mm] [--dopri5].
+"""Cost of FCODE(384) by route: python tools/fcode_width_cost.py [--steps 50] [--windows 5] [--mm-steps 10] [--no-mm] [--dopri5] [--train].
 
 First timing: one FCODE(384) solve (relu, default-init weights, inference) for b = 16 and 64 and euler / 0.1, rk4 / 0.25, through
 the one-launch kernel (ops.fcode_wide, csrc/fusion_wide.hip) and through FCODE._forward_any_width -- called directly: it is
@@ -14,6 +14,13 @@ captured and replayed, with FCODE(384) on the one-launch kernel and -- the same 
 b = 16 and 64 at 256 columns (agp_fcode_adaptive_fwd) and at 384 (agp_fcode_adaptive_wide_fwd), captured and replayed, the median of
 its windows, with the attempted-step and f-evaluation counts of the solve beside the time: the kernel is latency-bound, its time
 is the step count times the cost of an attempted step.
+
+--train adds a fourth timing: forward + backward of one FCODE(384) block (relu, default-init weights) with the gradients of x,
+weight and bias wanted, for b = 16 and 64 and euler / 0.1, rk4 / 0.25, captured and replayed like the others: with
+Options.fcode_wide (agp_fcode_wide_fwd_traj, then agp_fcode_wide_bwd: the state kernel, the weight gradient's GEMM and the column
+sum) and without it (the any-width route: agp_linear_fwd / agp_wsum_fwd forward, autograd's agp_linear_bwd and weighted sums
+behind them).  Both blocks hold the same weights; `entry_calls` counts calls at the C ABI, and an entry of a backward is more than
+one kernel.  `new_not_slower` is the condition the switch was built under, per cell.
 Prints one JSON line."""
 import argparse
 import json
@@ -28,7 +35,8 @@ from agplace_amd import _lib, autograd_ops, ops  # noqa: E402
 from agplace_amd.network_mm.ffns import FCODE  # noqa: E402
 from agplace_amd.options import Options  # noqa: E402
 
-COUNTED = ("agp_fcode_wide_fwd", "agp_linear_fwd", "agp_wsum_fwd", "agp_fcode_adaptive_fwd", "agp_fcode_adaptive_wide_fwd")
+COUNTED = ("agp_fcode_wide_fwd", "agp_linear_fwd", "agp_wsum_fwd", "agp_fcode_adaptive_fwd", "agp_fcode_adaptive_wide_fwd",
+           "agp_fcode_wide_fwd_traj", "agp_fcode_wide_bwd", "agp_linear_bwd")
 
 
 def window_us(fn, steps, windows):
@@ -96,6 +104,7 @@ def main():
     ap.add_argument("--mm-steps", type=int, default=10)
     ap.add_argument("--no-mm", action="store_true")
     ap.add_argument("--dopri5", action="store_true")
+    ap.add_argument("--train", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     d = ops.FCODE_WIDE_DIM
@@ -145,6 +154,30 @@ def main():
                 FCODE.forward = plain
             res["mm_forward"] = {"layers": "2_2_2", "image": [16, 3, 224, 1344], "voxel": "dense stand-ins",
                                  "fcode_one_launch": one, "fcode_any_width": anyw}
+    if args.train:
+        res["train"] = {"act": "relu", "gradients": ["x", "weight", "bias"]}
+        for b in (16, 64):
+            torch.manual_seed(0)
+            x = torch.randn(b, d, device=dev, requires_grad=True)
+            gy = torch.randn(b, d, device=dev)
+            row = {}
+            for name, kw in (("euler/0.1", dict(odeint_method="euler", odeint_size=0.1)),
+                             ("rk4/0.25", dict(odeint_method="rk4", odeint_size=0.25))):
+                cell, grads = {}, {}
+                for route, switch in (("fcode_wide", True), ("any_width", False)):
+                    torch.manual_seed(1)
+                    m = FCODE(d, "relu", opt=Options(fcode_wide=switch, **kw)).to(dev)
+                    fc = m.func.func.fc
+                    t, grads[route] = timed(lambda: torch.autograd.grad(m(x), (x, fc.weight, fc.bias), gy), args.steps, args.windows)
+                    t["entry_calls"] = t.pop("counted_launches")
+                    t["calls_by_entry"] = t.pop("launches_by_entry")
+                    cell[route] = t
+                assert set(cell["fcode_wide"]["calls_by_entry"]) == {"agp_fcode_wide_fwd_traj", "agp_fcode_wide_bwd"}, cell
+                cell["gradients_rel_l2"] = [float((p.double() - q.double()).norm() / q.double().norm())
+                                            for p, q in zip(grads["fcode_wide"], grads["any_width"])]
+                cell["new_not_slower"] = cell["fcode_wide"]["us"] <= cell["any_width"]["us"]
+                row[name] = cell
+            res["train"][f"b{b}"] = row
     print(json.dumps(res))
 
 

@@ -7,7 +7,8 @@ At the bench's last-map shape [16, 14, 84, 384] (HIP events, a warm-up, the medi
 The comparison sequences are existing ops of this tree.  Beside each time: the bytes the route must move, computed from the shape
 (reads + writes of every pass), and the rate that gives.
   3. one whole training step (forward, loss, backward) of MM(mm_imgfe='convnext_tiny', layers 2_2_2, convnext_train=True) in
-     .train() on 16 x [3, 224, 1344] with the dense voxel stand-ins.
+     .train() on 16 x [3, 224, 1344] with the dense voxel stand-ins, with Options.fcode_wide off (its three FCODE(384) blocks on
+     the any-width route) and on (on agp_fcode_wide_fwd_traj / agp_fcode_wide_bwd); the same seed, so the same weights.
 Prints one JSON line."""
 import argparse
 import json
@@ -101,20 +102,25 @@ def main():
     if not args.no_mm:
         from agplace_amd.network_mm.mm import MM
         from bench_inputs import synth_query
-        opt = Options(mm_imgfe="convnext_tiny", mm_imgfe_layers="2_2_2", mm_imgfe_planes="96_192_384", mm_imgfe_dim=384,
-                      mm_stg2fuse_dim=384, mm_voxfe_planes="64_128_384", mm_voxfe_dim=384, convnext_train=True)
-        torch.manual_seed(2)
-        model = MM(opt=opt).to(dev).train()
-        data = {k: ([t.to(dev) for t in v] if isinstance(v, list) else v.to(dev)) for k, v in synth_query(16, 224, 1344, opt, seed=1).items()}
-        G = torch.randn(16, 384, device=dev)
+        data, G = None, torch.randn(16, 384, device=dev)
+        res["mm_train_step"] = {"layers": "2_2_2", "image": [16, 3, 224, 1344], "voxel": "dense stand-ins"}
+        for name, switch in (("fcode_wide_off", False), ("fcode_wide_on", True)):
+            opt = Options(mm_imgfe="convnext_tiny", mm_imgfe_layers="2_2_2", mm_imgfe_planes="96_192_384", mm_imgfe_dim=384,
+                          mm_stg2fuse_dim=384, mm_voxfe_planes="64_128_384", mm_voxfe_dim=384, convnext_train=True, fcode_wide=switch)
+            torch.manual_seed(2)
+            model = MM(opt=opt).to(dev).train()
+            if data is None:
+                data = {k: ([t.to(dev) for t in v] if isinstance(v, list) else v.to(dev))
+                        for k, v in synth_query(16, 224, 1344, opt, seed=1).items()}
 
-        def step():
-            for q in model.parameters():
-                q.grad = None
-            (model(data, mode="q")["embedding"] * G).sum().backward()
-        row = timed(step, args.mm_steps, args.windows)
-        res["mm_train_step"] = {"layers": "2_2_2", "image": [16, 3, 224, 1344], "voxel": "dense stand-ins",
-                                "ms": round(row["us"] / 1e3, 2), "min_ms": round(row["min_us"] / 1e3, 2), "max_ms": round(row["max_us"] / 1e3, 2)}
+            def step():
+                for q in model.parameters():
+                    q.grad = None
+                (model(data, mode="q")["embedding"] * G).sum().backward()
+            row = timed(step, args.mm_steps, args.windows)
+            res["mm_train_step"][name] = {"ms": round(row["us"] / 1e3, 2), "min_ms": round(row["min_us"] / 1e3, 2),
+                                          "max_ms": round(row["max_us"] / 1e3, 2)}
+            del model
     print(json.dumps(res))
 
 
