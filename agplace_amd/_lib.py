@@ -18,7 +18,7 @@ PREC_F16 = 4
 FMT_BF16, FMT_F16 = 0, 1
 ACT = {None: 0, "id": 0, "relu": 1, "tanh": 2, "sigmoid": 3}
 ODE = {"euler": 0, "midpoint": 1, "rk4": 2}      # fixed-grid methods (agp_fcode_fwd, the vector programs)
-ODE_ADAPTIVE = {"dopri5": 3}                     # adaptive methods (agp_fcode_adaptive_fwd)
+ODE_ADAPTIVE = {"dopri5": 3, "bosh3": 4}         # adaptive methods (agp_fcode_adaptive_fwd): AGP_ODE_DOPRI5, AGP_ODE_BOSH3
 ODE_STATUS = {0: "ok", 1: "odeint_max_steps attempted steps did not reach t = 1", 2: "step size underflow (t + dt == t)",
               3: "the error ratio is NaN"}
 ODE_MAX_STEPS_LIMIT = 4096

@@ -1,16 +1,21 @@
-// Adaptive Dormand-Prince 5(4) solver ('dopri5') for the Neural-ODE blocks FCODE(256) and FCODE(384), forward and backward.
-// The algorithm is stated in DESIGN.md section 2 ("Adaptive solver") and restated in fp64 by tests/dopri5_ref.py.
+// Adaptive embedded Runge-Kutta solvers for the Neural-ODE blocks FCODE(256) and FCODE(384), forward and backward: 'dopri5'
+// (Dormand-Prince 5(4)) and 'bosh3' (Bogacki-Shampine 3(2)).  A method is a Tableau (below): a type the forward driver and
+// the backward kernels take as a template parameter; step control, ring, control block, interpolant and both backward
+// recursions are written once for every FSAL table of at most seven stages.
+// The algorithm is stated in DESIGN.md section 2 ("Adaptive solver") and restated in fp64 by tests/dopri5_ref.py (dopri5)
+// and tests/rk_adaptive_ref.py (any table).
 //
 // Forward: ONE launch of ONE persistent workgroup per solve.  torchdiffeq's step control couples the whole batch (one error
 // norm over all b*D elements), so a workgroup per 16 rows would have to wait for the others at every attempted step; a
-// single workgroup needs nothing but its own barriers.  There is ONE driver, fcode_adaptive_kernel<E, ACT>: step control,
+// single workgroup needs nothing but its own barriers.  There is ONE driver, fcode_adaptive_kernel<E, TB, ACT>: step control,
 // tableau arithmetic, ring and control block exist once.  What differs between the widths is a column engine E (below,
 // before the driver): Resident256 keeps both split-bf16 planes of W in registers as fcode_kernel does (fusion.hip), 16 waves,
 // a lane owns 4 features of a row; Streamed384 cannot (576 KiB of planes), keeps `hi`, streams `lo`, 8 waves, a lane owns
 // 3 x 4 features.  At either width the state has a third bf16 plane (see store_state3) and the workgroup walks the
-// ceil(b/16) row tiles for every stage.  y and the seven stage derivatives live in a caller-supplied ring in global memory
+// ceil(b/16) row tiles for every stage.  y and the S stage derivatives live in a caller-supplied ring in global memory
 // (L2-resident); a lane only ever re-reads the addresses it wrote itself (same row, same features), so the ring needs no
-// fence.  Ring entry n holds [y, k1 .. k7] of the attempt that starts from accepted step n; stage 7 writes y1 and k7 also
+// fence.  Ring entry n holds [y, k1 .. kS] of the attempt that starts from accepted step n (eight sub-planes whatever S is:
+// a table with fewer than seven stages leaves the last ones unused); stage S writes y1 and kS also
 // to entry n + 1 as its (y, k1) -- FSAL -- so accepting a step is `++n` and rejecting it leaves entry n as it was.  With a
 // trajectory the ring has max_steps + 1 entries and IS the record the backward reads; without one it has two.
 // Time, step size, norms, the error ratio and the step factor are fp64.  Norms are reduced in a fixed order (a lane over
@@ -19,7 +24,7 @@
 //
 // Backward: rows are independent once the step sizes are fixed: one workgroup per 16 rows like
 // fcode_bwd_state_kernel (fusion_bwd.hip), step count and step sizes read from the control block in DEVICE memory.  The
-// two widths keep their own recursions (where the seven stage adjoints live differs in substance); the per-step constants,
+// two widths keep their own recursions (where the S stage adjoints live differs in substance); the per-step constants,
 // the read of the solve's outcome and act' are shared, and so are the three sum kernels, templated on the width.
 #include <cstddef>
 #include <type_traits>
@@ -43,12 +48,39 @@ __device__ const double DP_MID[7] = {0.5 * 6025192743. / 30085553152., 0., 0.5 *
                                      0.5 * -2691868925. / 45128329728., 0.5 * 187940372067. / 1594534317056.,
                                      0.5 * -1776094331. / 19743644256., 0.5 * 11237099. / 235043384.};
 
-// out = y + dt sum_j beta_j(x) k_j is the quartic interpolant of a step at x in [0, 1]; beta(1) = DP_CS
-__device__ __forceinline__ double dp_beta(int j, double x) {
-    const double d1 = j == 0 ? 1. : 0., d7 = j == 6 ? 1. : 0.;
-    const double c4 = 16. * DP_MID[j] - 8. * DP_CS[j] + 2. * (d7 - d1);
-    const double c3 = 14. * DP_CS[j] - 32. * DP_MID[j] + 5. * d1 - 3. * d7;
-    const double c2 = 16. * DP_MID[j] - 5. * DP_CS[j] + d7 - 4. * d1;
+// Bogacki-Shampine 3(2), FSAL as well.  MID is torchdiffeq's: y_mid = y + dt k2 / 2, the midpoint rule's value.
+__device__ const double BS_A[4][3] = {{0., 0., 0.}, {1. / 2, 0., 0.}, {0., 3. / 4, 0.}, {2. / 9, 1. / 3, 4. / 9}};
+__device__ const double BS_CS[4] = {2. / 9, 1. / 3, 4. / 9, 0.};
+__device__ const double BS_CE[4] = {2. / 9 - 7. / 24, 1. / 3 - 1. / 4, 4. / 9 - 1. / 3, -1. / 8};
+__device__ const double BS_MID[4] = {0., 0.5, 0., 0.};
+
+// A Tableau is an embedded explicit FSAL method of S <= 7 stages: k_1 = f(y) (the step before's k_S),
+// k_i = f(y + dt sum_{j < i} A[i-1][j] k_j) for i = 2 .. S, row S - 1 of A being the solution weights CS (so k_S = f(y1)),
+// the error estimate dt sum_j CE[j] k_j of a method of order ORDER (the step factor is ratio^(-1/ORDER)), and the
+// mid-point weights MID of the quartic interpolant.  METHOD is its AGP_ODE_* number.
+struct Dopri5 {
+    static constexpr int S = 7, ORDER = 5, METHOD = AGP_ODE_DOPRI5;
+    static __device__ __forceinline__ double A(int i, int j) { return DP_A[i][j]; }
+    static __device__ __forceinline__ double CS(int j) { return DP_CS[j]; }
+    static __device__ __forceinline__ double CE(int j) { return DP_CE[j]; }
+    static __device__ __forceinline__ double MID(int j) { return DP_MID[j]; }
+};
+struct Bosh3 {
+    static constexpr int S = 4, ORDER = 3, METHOD = AGP_ODE_BOSH3;
+    static __device__ __forceinline__ double A(int i, int j) { return BS_A[i][j]; }
+    static __device__ __forceinline__ double CS(int j) { return BS_CS[j]; }
+    static __device__ __forceinline__ double CE(int j) { return BS_CE[j]; }
+    static __device__ __forceinline__ double MID(int j) { return BS_MID[j]; }
+};
+
+// out = y + dt sum_j beta_j(x) k_j is the quartic interpolant of a step at x in [0, 1]: the quartic through y, y_mid and y1
+// with the end slopes k_1 and k_S; beta(1) = CS
+template <class T>
+__device__ __forceinline__ double rk_beta(int j, double x) {
+    const double d1 = j == 0 ? 1. : 0., dS = j == T::S - 1 ? 1. : 0.;
+    const double c4 = 16. * T::MID(j) - 8. * T::CS(j) + 2. * (dS - d1);
+    const double c3 = 14. * T::CS(j) - 32. * T::MID(j) + 5. * d1 - 3. * dS;
+    const double c2 = 16. * T::MID(j) - 5. * T::CS(j) + dS - 4. * d1;
     return (((c4 * x + c3) * x + c2) * x + d1) * x;
 }
 
@@ -76,21 +108,39 @@ __device__ __forceinline__ double uniform_d(double v) {
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
-// r^(-1/5) for finite r > 0, to fp64 accuracy: r = a 32^q with a in [1/2, 16), a single-precision power of a, two Newton
-// steps z <- z (6 - a z^5) / 5 (quadratic: 1e-7 -> 1e-14 -> rounding).  A double-precision pow() next to W's 64 resident
-// registers spills; this does not.
-__device__ __forceinline__ double inv_fifth_root(double r) {
+// z^P by squaring (P = 5: (z^2 z^2) z)
+template <int P>
+__device__ __forceinline__ double ipow(double z) {
+    if constexpr (P == 1) {
+        return z;
+    } else if constexpr (P % 2 == 1) {
+        return ipow<P - 1>(z) * z;
+    } else {
+        const double h = ipow<P / 2>(z);
+        return h * h;
+    }
+}
+// r^(-1/P) for finite r > 0, to fp64 accuracy: r = a (2^P)^q with a in [1/2, 2^(P-1)), a single-precision power of a, two
+// Newton steps z <- z (P + 1 - a z^P) / P (quadratic: 1e-7 -> 1e-14 -> rounding).  A double-precision pow() next to W's 64
+// resident registers spills; this does not.
+template <int P>
+__device__ __forceinline__ double inv_root(double r) {
     int e;
     const double m = frexp(r, &e);
-    const int q = e >= 0 ? e / 5 : -((4 - e) / 5);
-    const double a = ldexp(m, e - 5 * q);
-    double z = (double)powf((float)a, -0.2f);
+    const int q = e >= 0 ? e / P : -((P - 1 - e) / P);
+    const double a = ldexp(m, e - P * q);
+    double z = (double)powf((float)a, -1.f / P);
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const double z2 = z * z;
-        z = z * (6. - a * (z2 * z2 * z)) * 0.2;
-    }
+    for (int it = 0; it < 2; ++it) z = z * ((P + 1.) - a * ipow<P>(z)) * (1. / P);
     return ldexp(z, -q);
+}
+// fn(integral_constant<int, I>) for I = FROM .. TO, unrolled
+template <int FROM, int TO, class F>
+__device__ __forceinline__ void static_for(F&& fn) {
+    if constexpr (FROM <= TO) {
+        fn(std::integral_constant<int, FROM>{});
+        static_for<FROM + 1, TO>(fn);
+    }
 }
 
 constexpr int AD = 256, AKS = AD / 32, AYRB = AD * 2 + 16;
@@ -214,22 +264,24 @@ __device__ __forceinline__ void ring_prime(const bf16x8* fl, bf16x8 (&ring)[XRIN
 
 // per-attempt constants, written by thread 0 and read by every wave into scalar registers: the products of dt with the
 // tableau.  (Computed by every lane they are hoisted out of the step loop as 50 fp64 values and spilled.)
+template <class T>
 struct StepCoef {
     double dt;
-    double ce[7];      // dt * CE
-    float a[5][5];     // dt * A rows 1 .. 5
-    float cs[6];       // dt * CS
+    double ce[T::S];               // dt * CE
+    float a[T::S - 2][T::S - 2];   // dt * A rows 1 .. S - 2
+    float cs[T::S - 1];            // dt * CS
 };
-__device__ __forceinline__ void publish_step(StepCoef& c, double dt) {
+template <class T>
+__device__ __forceinline__ void publish_step(StepCoef<T>& c, double dt) {
     c.dt = dt;
 #pragma unroll
-    for (int j = 0; j < 7; ++j) c.ce[j] = dt * DP_CE[j];
+    for (int j = 0; j < T::S; ++j) c.ce[j] = dt * T::CE(j);
 #pragma unroll
-    for (int i = 1; i <= 5; ++i)
+    for (int i = 1; i <= T::S - 2; ++i)
 #pragma unroll
-        for (int j = 0; j < i; ++j) c.a[i - 1][j] = (float)(dt * DP_A[i][j]);
+        for (int j = 0; j < i; ++j) c.a[i - 1][j] = (float)(dt * T::A(i, j));
 #pragma unroll
-    for (int j = 0; j < 6; ++j) c.cs[j] = (float)(dt * DP_A[6][j]);
+    for (int j = 0; j < T::S - 1; ++j) c.cs[j] = (float)(dt * T::A(T::S - 1, j));
 }
 // ---- The forward's two column engines: what differs between the widths, i.e. where W lives, how a tile of the state gets
 // into LDS and how f is evaluated on it.  put(t, v) writes this lane's feature tile t of the state the next evaluation reads
@@ -317,24 +369,25 @@ struct Streamed384 {
     }
 };
 
-// ---- The forward driver, once for both widths: first step size, stages 1 .. 5, stage 7 with the error ratio, accept / reject
+// ---- The forward driver, once for both widths and every Tableau TB: first step size, stages 2 .. S - 1, stage S (the FSAL
+// stage) with the error ratio, accept / reject
 // and the step factor, the interpolant at t = 1, the NaN fill of a failed solve, the control block.  Its shape is the one a
 // lane with several feature tiles needs: the stage combinations run one feature tile at a time (put), then ONE evaluation
-// (feval), and stage 7 forms its error sum AFTER the evaluation from the ring (y1 is already in entry n + 1), so nothing
+// (feval), and stage S forms its error sum AFTER the evaluation from the ring (y1 is already in entry n + 1), so nothing
 // state-sized waits in registers across an evaluation; with TILES = 1 the same loops are the four-features-per-lane walk.
 // The sched_barrier(0) after each feature tile and the scalar (readfirstlane) coefficients are there because their removal
 // spilled at 384 columns.
 // Two places know that a lane may own a single feature tile (if constexpr, TILES == 1); both were forced by a measurement
-// of the plain form at 256 columns (MI355X, relu, tol 1e-3, captured solve; the two-kernel build 115.89 / 346.96 us at
+// of the plain form at 256 columns (MI355X, dopri5, relu, tol 1e-3, captured solve; the two-kernel build 115.89 / 346.96 us at
 // b = 16 / 64, spread 0.05 / 0.30):
-//   - stage 7 HOLDS y, y1 and the error sum of stages 1 .. 6 in registers across the evaluation and stores y1 behind it.
+//   - stage S HOLDS y, y1 and the error sum of stages 1 .. S - 1 in registers across the evaluation and stores y1 behind it.
 //     Read back from the ring -- what a lane with three tiles must do -- the solve took 116.95 / 372.36 us (+0.9 / +7.3 %:
 //     eight more 16-byte loads per lane, row tile and attempt); held, but with y1 stored ahead of the evaluation, 347.80 us
 //     at b = 64 (the store then sits right before the evaluation's barrier).  As it stands: 109.39 / 337.04 us.
-//   - the interpolant's seven weights are computed by every lane, not one per thread through LDS: sbeta would add 32 B to
+//   - the interpolant's S weights are computed by every lane, not one per thread through LDS: sbeta would add 32 B to
 //     the 256 engine's static LDS (51168 B against 51136).  (Behind the step loop the per-lane form does not spill as it
 //     did inside it; at 384 columns the weights keep going through LDS, as they did.)
-template <class E, int ACT>
+template <class E, class TB, int ACT>
 __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float* __restrict__ x, const float* __restrict__ add1,
                                                                    const float* __restrict__ add2,
                                                                    typename E::Plane __restrict__ w_hi,
@@ -342,10 +395,11 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
                                                                    const float* __restrict__ bias, int b, double rtol,
                                                                    double atol, int max_steps, float* ring, int nring,
                                                                    float* __restrict__ yout, OdeCtrl* __restrict__ ctrl) {
-    constexpr int D = E::D, TILES = E::TILES;
+    constexpr int D = E::D, TILES = E::TILES, S = TB::S;
+    static_assert(S >= 3 && S <= 7, "a ring entry has eight sub-planes: y and at most seven stages");
     __shared__ double red[2][E::WAVES];
-    __shared__ StepCoef coef;
-    __shared__ float sbeta[7];
+    __shared__ StepCoef<TB> coef;
+    __shared__ float sbeta[S];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nt = (b + FROWS - 1) / FROWS;
@@ -373,7 +427,7 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
     };
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-    // ---- first step size (torchdiffeq _select_initial_step, order 4 -> exponent 1/5)
+    // ---- first step size (torchdiffeq _select_initial_step; the exponent is 1 / ORDER)
     double sq0 = 0., sq1 = 0.;
     for (int T = 0; T < nt; ++T) {
         const bool live = T * FROWS + (lane & 15) < b;
@@ -441,12 +495,12 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
     if (tid == 0) {
         const double d2 = sqrt(sq2 / count) / h0;
         const double dm = fmax(d1, d2);
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : (dm < 1e298 ? inv_fifth_root(dm * 100.) : 0.);
+        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : (dm < 1e298 ? inv_root<TB::ORDER>(dm * 100.) : 0.);
         publish_step(coef, fmin(100. * h0, h1));
     }
     __syncthreads();
 
-    // stage I (0-based, 1 .. 5): k_{I+1} = f(y + dt sum_{j < I} A[I][j] k_{j+1})
+    // stage I (0-based, 1 .. S - 2): k_{I+1} = f(y + dt sum_{j < I} A[I][j] k_{j+1})
     auto stage = [&](auto Ic, int cur) {
         constexpr int I = decltype(Ic)::value;
         float cf[I];
@@ -484,26 +538,22 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
         if (t + dt == t) { status = AGP_ODE_E_UNDERFLOW; break; }
         ++attempts;
         const int cur = __builtin_amdgcn_readfirstlane(acc % nring), nxt = __builtin_amdgcn_readfirstlane((acc + 1) % nring);
-        stage(std::integral_constant<int, 1>{}, cur);
-        stage(std::integral_constant<int, 2>{}, cur);
-        stage(std::integral_constant<int, 3>{}, cur);
-        stage(std::integral_constant<int, 4>{}, cur);
-        stage(std::integral_constant<int, 5>{}, cur);
-        // stage 7: y1, k7 = f(y1) and the error ratio
+        static_for<1, S - 2>([&](auto Ic) { stage(Ic, cur); });
+        // stage S: y1, kS = f(y1) and the error ratio
         double sq = 0., sqx = 0.;
         {
-            float cs[6];
-            double ce[7];
+            float cs[S - 1];
+            double ce[S];
 #pragma unroll
-            for (int j = 0; j < 6; ++j) cs[j] = uniform_f(coef.cs[j]);
+            for (int j = 0; j < S - 1; ++j) cs[j] = uniform_f(coef.cs[j]);
 #pragma unroll
-            for (int j = 0; j < 7; ++j) ce[j] = uniform_d(coef.ce[j]);
-            constexpr bool HOLD7 = TILES == 1;      // (see the kernel's head)
-            // the cancelling sum in fp64, stages 1 .. 6
-            auto err6 = [&](const f32x4 (&kk)[6], int r) -> double {
+            for (int j = 0; j < S; ++j) ce[j] = uniform_d(coef.ce[j]);
+            constexpr bool HOLD = TILES == 1;      // (see the kernel's head)
+            // the cancelling sum in fp64, stages 1 .. S - 1
+            auto err_head = [&](const f32x4 (&kk)[S - 1], int r) -> double {
                 double e = 0.;
 #pragma unroll
-                for (int j = 0; j < 6; ++j) e += ce[j] * (double)kk[j][r];
+                for (int j = 0; j < S - 1; ++j) e += ce[j] * (double)kk[j][r];
                 return e;
             };
             for (int T = 0; T < nt; ++T) {
@@ -514,18 +564,18 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
                 for (int t = 0; t < TILES; ++t) {
                     f32x4 y1 = zero4;
                     if (live) {
-                        f32x4 kk[6];
+                        f32x4 kk[S - 1];
                         const f32x4 yv = *(const f32x4*)(at(cur, 0, T) + 16 * t);
 #pragma unroll
-                        for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
+                        for (int j = 0; j < S - 1; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
                         y1 = yv;
 #pragma unroll
-                        for (int j = 0; j < 6; ++j) y1 += cs[j] * kk[j];
-                        if constexpr (HOLD7) {
+                        for (int j = 0; j < S - 1; ++j) y1 += cs[j] * kk[j];
+                        if constexpr (HOLD) {
                             yv_held = yv;
                             y1_held = y1;
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) e_held[r] = err6(kk, r);
+                            for (int r = 0; r < 4; ++r) e_held[r] = err_head(kk, r);
                         } else {
                             *(f32x4*)(at(nxt, 0, T) + 16 * t) = y1;
                         }
@@ -533,29 +583,29 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
                     eng.put(t, y1);
                     __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
                 }
-                const Tiles<TILES> k7 = feval();
+                const Tiles<TILES> kS = feval();
                 if (live) {
 #pragma unroll
                     for (int t = 0; t < TILES; ++t) {
-                        *(f32x4*)(at(cur, 7, T) + 16 * t) = k7.t[t];
-                        *(f32x4*)(at(nxt, 1, T) + 16 * t) = k7.t[t];
+                        *(f32x4*)(at(cur, S, T) + 16 * t) = kS.t[t];
+                        *(f32x4*)(at(nxt, 1, T) + 16 * t) = kS.t[t];
                         f32x4 yv = yv_held, y1 = y1_held;
                         double e[4] = {e_held[0], e_held[1], e_held[2], e_held[3]};
-                        if constexpr (HOLD7) {
+                        if constexpr (HOLD) {
                             *(f32x4*)(at(nxt, 0, T) + 16 * t) = y1;
                         } else {
-                            f32x4 kk[6];
+                            f32x4 kk[S - 1];
                             yv = *(const f32x4*)(at(cur, 0, T) + 16 * t);
                             y1 = *(const f32x4*)(at(nxt, 0, T) + 16 * t);
 #pragma unroll
-                            for (int j = 0; j < 6; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
+                            for (int j = 0; j < S - 1; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * t);
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) e[r] = err6(kk, r);
+                            for (int r = 0; r < 4; ++r) e[r] = err_head(kk, r);
                         }
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             // the quotient in fp32 (1e-7 relative: nothing next to the k's own rounding)
-                            const float ef = (float)(e[r] + ce[6] * (double)k7.t[t][r]);
+                            const float ef = (float)(e[r] + ce[S - 1] * (double)kS.t[t][r]);
                             const double q = (double)(ef / (atolf + rtolf * fmaxf(fabsf(yv[r]), fabsf(y1[r]))));
                             sq += q * q;
                         }
@@ -564,7 +614,7 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
                 }
             }
         }
-        nfe += 6;
+        nfe += S - 1;
         block_sum2(sq, sqx);
         const double ratio = sqrt(sq / count);
         if (tid == 0) {
@@ -583,10 +633,10 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
         } else {
             ++rej;
         }
-        // every wave has read this attempt's constants (the barriers of stage 7 lie behind their last read)
+        // every wave has read this attempt's constants (the barriers of stage S lie behind their last read)
         if (tid == 0) {
             double fac = 10.;
-            if (ratio != 0.) fac = fmin(10., fmax(ratio < 1e300 ? 0.9 * inv_fifth_root(ratio) : 0., ratio < 1. ? 1. : 0.2));
+            if (ratio != 0.) fac = fmin(10., fmax(ratio < 1e300 ? 0.9 * inv_root<TB::ORDER>(ratio) : 0., ratio < 1. ? 1. : 0.2));
             publish_step(coef, dt * fac);
         }
         __syncthreads();
@@ -596,26 +646,26 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
         const double dt = uniform_d(coef.dt);
         const int cur = __builtin_amdgcn_readfirstlane((acc - 1) % nring);
         const double xs = (1. - t) / (t_end - t);
-        float be[7];
+        float be[S];
         if constexpr (TILES == 1) {      // (see the kernel's head)
 #pragma unroll
-            for (int j = 0; j < 7; ++j) be[j] = uniform_f((float)(dt * dp_beta(j, xs)));
+            for (int j = 0; j < S; ++j) be[j] = uniform_f((float)(dt * rk_beta<TB>(j, xs)));
         } else {     // one weight per thread
-            if (tid < 7) sbeta[tid] = (float)(dt * dp_beta(tid, xs));
+            if (tid < S) sbeta[tid] = (float)(dt * rk_beta<TB>(tid, xs));
             __syncthreads();
 #pragma unroll
-            for (int j = 0; j < 7; ++j) be[j] = uniform_f(sbeta[j]);
+            for (int j = 0; j < S; ++j) be[j] = uniform_f(sbeta[j]);
         }
         for (int T = 0; T < nt; ++T) {
             if (T * FROWS + (lane & 15) < b) {
 #pragma unroll
                 for (int tt = 0; tt < TILES; ++tt) {
                     f32x4 o = *(const f32x4*)(at(cur, 0, T) + 16 * tt);
-                    f32x4 kk[7];
+                    f32x4 kk[S];
 #pragma unroll
-                    for (int j = 0; j < 7; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * tt);
+                    for (int j = 0; j < S; ++j) kk[j] = *(const f32x4*)(at(cur, 1 + j, T) + 16 * tt);
 #pragma unroll
-                    for (int j = 0; j < 7; ++j) o += be[j] * kk[j];
+                    for (int j = 0; j < S; ++j) o += be[j] * kk[j];
                     *(f32x4*)(yout + (size_t)T * (FROWS * D) + loff + 16 * tt) = o;
                     __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
                 }
@@ -645,7 +695,7 @@ __global__ __launch_bounds__(E::THREADS) void fcode_adaptive_kernel(const float*
     }
 }
 
-// ---- Backward.  The two state kernels keep their own recursions (seven stage adjoints in registers at 256 columns, in the
+// ---- Backward.  The two state kernels keep their own recursions (the S stage adjoints in registers at 256 columns, in the
 // workspace at 384); what they and the three sum kernels share is below.
 
 // the outcome of the solve a control block records, as uniform values: its status and its accepted steps, clamped to the cap
@@ -658,23 +708,30 @@ __device__ __forceinline__ Solved read_solved(const OdeCtrl* ctrl, int max_steps
     return {status, N < 0 ? 0 : (N > max_steps ? max_steps : N)};
 }
 
-// the constants of accepted step n of N into bc[28]: dt A[i][j] at i (i - 1) / 2 + j (i = 1 .. 6, j < i), dt w_j at 21 + j.
+// the constants of accepted step n of N into bc[NA + S], NA = S (S - 1) / 2: dt A[i][j] at i (i - 1) / 2 + j (i = 1 .. S - 1,
+// j < i), dt w_j at NA + j (dopri5: 21 + 7, bosh3: 6 + 4).
 // One constant per thread (computed by every lane they are hoisted as fp64 and spilled), between two barriers: the step
 // before has read its constants, this step's are published.
-__device__ __forceinline__ void publish_bwd_step(float (&bc)[28], const OdeCtrl* ctrl, int n, int N, int tid) {
+template <class TB>
+struct BwdCoef {
+    static constexpr int NA = TB::S * (TB::S - 1) / 2, COUNT = NA + TB::S;
+};
+template <class TB>
+__device__ __forceinline__ void publish_bwd_step(float (&bc)[BwdCoef<TB>::COUNT], const OdeCtrl* ctrl, int n, int N, int tid) {
+    constexpr int NA = BwdCoef<TB>::NA;
     __syncthreads();
-    if (tid < 28) {
+    if (tid < NA + TB::S) {
         const double dt = ctrl->dt[n];
         double c;
-        if (tid < 21) {
+        if (tid < NA) {
             int i = 1;
             while ((i + 1) * i / 2 <= tid) ++i;
-            c = DP_A[i][tid - i * (i - 1) / 2];
+            c = TB::A(i, tid - i * (i - 1) / 2);
         } else {
-            c = DP_CS[tid - 21];
+            c = TB::CS(tid - NA);
             if (n == N - 1) {       // the last step ends at its interpolant
                 const double t0 = ctrl->t0, t1 = ctrl->t1;
-                c = dp_beta(tid - 21, (1. - t0) / (t1 - t0));
+                c = rk_beta<TB>(tid - NA, (1. - t0) / (t1 - t0));
             }
         }
         bc[tid] = (float)(dt * c);
@@ -696,13 +753,14 @@ __device__ __forceinline__ f32x4 dact_out(const f32x4& k) {
 }
 
 // Discretise-then-optimise through the accepted steps.  Step n: s_1 = y, s_i = y + dt sum_{j<i} A_ij k_j, k_i = f(s_i)
-// (i = 2 .. 7, A_7 = CS), out = y + dt sum_j w_j k_j with w = CS (out = s_7) or, for the last step, w = beta(x).
-// k_1 of step n + 1 IS k_7 of step n (FSAL), so the adjoint of k_1 is carried into the step before (g7).  With a = dL/d out:
-//     gk_j = dt w_j a (+ g7 for j = 7);  for i = 7 .. 2: gz_i = gk_i act'(k_i), gs_i = gz_i W, a += gs_i,
-//     gk_j += dt A_ij gs_i (j < i);  g7 <- gk_1;  at step 0: gz_1 = gk_1 act'(k_1), a += gz_1 W.
-// Every gz_i goes to the workspace, row block 6 n + (i - 2), the one of step 0's k_1 to block 6 N; the stage inputs s_i the
-// weight gradient pairs them with are rebuilt by adaptive_stage_inputs_kernel (the recursion itself does not need them).
-template <int ACT>
+// (i = 2 .. S, A_S = CS), out = y + dt sum_j w_j k_j with w = CS (out = s_S) or, for the last step, w = beta(x).
+// k_1 of step n + 1 IS k_S of step n (FSAL), so the adjoint of k_1 is carried into the step before (gfsal).  With a = dL/d out:
+//     gk_j = dt w_j a (+ gfsal for j = S);  for i = S .. 2: gz_i = gk_i act'(k_i), gs_i = gz_i W, a += gs_i,
+//     gk_j += dt A_ij gs_i (j < i);  gfsal <- gk_1;  at step 0: gz_1 = gk_1 act'(k_1), a += gz_1 W.
+// Every gz_i goes to the workspace, row block (S - 1) n + (i - 2), the one of step 0's k_1 to block (S - 1) N; the stage
+// inputs s_i the weight gradient pairs them with are rebuilt by adaptive_stage_inputs_kernel (the recursion itself does
+// not need them).
+template <class TB, int ACT>
 __global__ __launch_bounds__(FT) void fcode_adaptive_bwd_kernel(const float* __restrict__ traj,
                                                                 const OdeCtrl* __restrict__ ctrl,
                                                                 const float* __restrict__ gy,
@@ -710,8 +768,9 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_bwd_kernel(const float* __r
                                                                 const bf16_t* __restrict__ wt_lo, int b, int max_steps,
                                                                 float* __restrict__ gx, float* __restrict__ GZ,
                                                                 int Bp) {
+    constexpr int S = TB::S, NA = BwdCoef<TB>::NA;
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * FROWS * AYRB];
-    __shared__ float bc[28];      // this step's dt A[i][j] at i (i - 1) / 2 + j (i = 1 .. 6, j < i), dt w_j at 21 + j
+    __shared__ float bc[BwdCoef<TB>::COUNT];      // this step's constants (publish_bwd_step)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int brow = blockIdx.x * FROWS + (lane & 15);
@@ -754,26 +813,26 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_bwd_kernel(const float* __r
     auto emit = [&](int blk, const f32x4& gz) { *(f32x4*)(GZ + ((size_t)blk * Bp + brow) * AD + nf) = gz; };
 
     f32x4 a = live ? *(const f32x4*)(gy + (size_t)brow * AD + nf) : zero4;
-    f32x4 g7 = zero4;
+    f32x4 gfsal = zero4;
     for (int n = N - 1; n >= 0; --n) {
-        publish_bwd_step(bc, ctrl, n, N, tid);
-        f32x4 gk[7];
+        publish_bwd_step<TB>(bc, ctrl, n, N, tid);
+        f32x4 gk[S];
 #pragma unroll
-        for (int j = 0; j < 7; ++j) gk[j] = uniform_f(bc[21 + j]) * a;
-        gk[6] += g7;
+        for (int j = 0; j < S; ++j) gk[j] = uniform_f(bc[NA + j]) * a;
+        gk[S - 1] += gfsal;
 #pragma unroll
-        for (int i = 6; i >= 1; --i) {
+        for (int i = S - 1; i >= 1; --i) {
             const f32x4 gz = gk[i] * dact_out<ACT>(ld(n, 1 + i));
-            emit(6 * n + (i - 1), gz);
+            emit((S - 1) * n + (i - 1), gz);
             const f32x4 gs = times_w(gz);
             a += gs;
 #pragma unroll
             for (int j = 0; j < i; ++j) gk[j] += uniform_f(bc[i * (i - 1) / 2 + j]) * gs;
         }
-        g7 = gk[0];
+        gfsal = gk[0];
         if (n == 0) {
-            const f32x4 gz = g7 * dact_out<ACT>(ld(0, 1));
-            emit(6 * N, gz);
+            const f32x4 gz = gfsal * dact_out<ACT>(ld(0, 1));
+            emit((S - 1) * N, gz);
             a += times_w(gz);
         }
     }
@@ -781,13 +840,14 @@ __global__ __launch_bounds__(FT) void fcode_adaptive_bwd_kernel(const float* __r
     if (live) *(f32x4*)(gx + (size_t)brow * AD + nf) = a;
 }
 
-// S[6 n + i - 1] = y_n + dt_n sum_{j < i} A[i][j] k_{j+1} (i = 1 .. 6: the inputs of stages 2 .. 7 of accepted step n),
-// S[6 N] = y_0.  blockIdx.y = n; one thread per (row, four features); rows beyond b are zero like their gz.
-// D = the width (256 or 384): the three kernels below are the same code at either, in the same fixed order.
-template <int D>
+// SI[(S - 1) n + i - 1] = y_n + dt_n sum_{j < i} A[i][j] k_{j+1} (i = 1 .. S - 1: the inputs of stages 2 .. S of accepted
+// step n), SI[(S - 1) N] = y_0.  blockIdx.y = n; one thread per (row, four features); rows beyond b are zero like their gz.
+// D = the width (256 or 384): the three kernels below are the same code at either, in the same fixed order; they walk
+// the (S - 1) N + 1 row blocks of the Tableau TB's S stages.
+template <int D, class TB>
 __global__ __launch_bounds__(256) void adaptive_stage_inputs_kernel(const float* __restrict__ traj,
                                                                     const OdeCtrl* __restrict__ ctrl, int b, int max_steps,
-                                                                    float* __restrict__ S, int Bp) {
+                                                                    float* __restrict__ SI, int Bp) {
     const int idx = blockIdx.x * 256 + threadIdx.x;      // < Bp * D / 4
     const int brow = idx / (D / 4), nf = (idx % (D / 4)) * 4;
     const int n = blockIdx.y;
@@ -799,29 +859,30 @@ __global__ __launch_bounds__(256) void adaptive_stage_inputs_kernel(const float*
     auto ld = [&](int sub) -> f32x4 {
         return live ? *(const f32x4*)(traj + (((size_t)n * 8 + sub) * b + brow) * D + nf) : zero4;
     };
-    auto st = [&](int blk, const f32x4& v) { *(f32x4*)(S + ((size_t)blk * Bp + brow) * D + nf) = v; };
+    auto st = [&](int blk, const f32x4& v) { *(f32x4*)(SI + ((size_t)blk * Bp + brow) * D + nf) = v; };
+    constexpr int S = TB::S;
     if (n == 0) {
         const float qnan = __builtin_nanf("");
-        st(6 * N, status != 0 && live ? f32x4{qnan, qnan, qnan, qnan} : ld(0));
+        st((S - 1) * N, status != 0 && live ? f32x4{qnan, qnan, qnan, qnan} : ld(0));
     }
     if (n >= N) return;
     const double dt = ctrl->dt[n];
     const f32x4 y = ld(0);
-    f32x4 k[6];
+    f32x4 k[S - 1];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) k[j] = ld(1 + j);
+    for (int j = 0; j < S - 1; ++j) k[j] = ld(1 + j);
 #pragma unroll
-    for (int i = 1; i <= 6; ++i) {
+    for (int i = 1; i <= S - 1; ++i) {
         f32x4 s = y;
 #pragma unroll
-        for (int j = 0; j < i; ++j) s += (float)(dt * DP_A[i][j]) * k[j];
-        st(6 * n + i - 1, s);
+        for (int j = 0; j < i; ++j) s += (float)(dt * TB::A(i, j)) * k[j];
+        st((S - 1) * n + i - 1, s);
     }
 }
 
-// C[D][D] = sum_r A[r][m] * B[r][n] over the R = (6 N + 1) Bp rows the state kernel wrote, N read from the control
+// C[D][D] = sum_r A[r][m] * B[r][n] over the R = ((S - 1) N + 1) Bp rows the state kernel wrote, N read from the control
 // block (gemm_tn_f32_kernel of fusion_bwd.hip with a device-side row count; same tile shape, same fixed order).
-template <int D>
+template <int D, class TB>
 __global__ __launch_bounds__(256) void adaptive_gw_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                           float* __restrict__ C, const OdeCtrl* __restrict__ ctrl,
                                                           int max_steps, int Bp) {
@@ -830,7 +891,7 @@ __global__ __launch_bounds__(256) void adaptive_gw_kernel(const float* __restric
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
     int N = ctrl->status != 0 ? 0 : ctrl->accepted;
     N = N < 0 ? 0 : (N > max_steps ? max_steps : N);
-    const int R = (6 * N + 1) * Bp;      // a multiple of 16
+    const int R = ((TB::S - 1) * N + 1) * Bp;      // a multiple of 16
     float acc[4][4] = {};
     for (int r0 = 0; r0 < R; r0 += 16) {
         for (int i = tid; i < 16 * 64; i += 256) {
@@ -858,7 +919,7 @@ __global__ __launch_bounds__(256) void adaptive_gw_kernel(const float* __restric
 }
 
 // gb[c] = sum_r GZ[r][c]: wave w adds the rows w, w + 4, ..., the four wave sums are added in wave order
-template <int D>
+template <int D, class TB>
 __global__ __launch_bounds__(256) void adaptive_gb_kernel(const float* __restrict__ A, float* __restrict__ out,
                                                           const OdeCtrl* __restrict__ ctrl, int max_steps, int Bp) {
     __shared__ float redf[4][64];
@@ -866,7 +927,7 @@ __global__ __launch_bounds__(256) void adaptive_gb_kernel(const float* __restric
     const int c = blockIdx.x * 64 + lane;
     int N = ctrl->status != 0 ? 0 : ctrl->accepted;
     N = N < 0 ? 0 : (N > max_steps ? max_steps : N);
-    const int R = (6 * N + 1) * Bp;
+    const int R = ((TB::S - 1) * N + 1) * Bp;
     float s = 0.f;
     for (int r = w; r < R; r += 4) s += A[(size_t)r * D + c];
     redf[w][lane] = s;
@@ -876,20 +937,21 @@ __global__ __launch_bounds__(256) void adaptive_gb_kernel(const float* __restric
 
 // The backward at 384 columns: the recursion of fcode_adaptive_bwd_kernel, one workgroup (8 waves) per 16 rows, W^T's `hi`
 // fragments resident and its `lo` fragments streamed, the adjoint product on two planes and three products as there.  A lane
-// owns twelve features of its row, so the seven stage adjoints gk_j (84 registers beside W's 144) do not stay in registers:
-// they wait in the first seven row blocks of S, the half of the workspace adaptive_stage_inputs_kernel fills AFTER this
+// owns twelve features of its row, so the S stage adjoints gk_j (dopri5: 84 registers beside W's 144) do not stay in registers:
+// they wait in the first S row blocks of SI, the half of the workspace adaptive_stage_inputs_kernel fills AFTER this
 // kernel -- this workgroup's rows only, every lane re-reading only what it wrote itself, so no fence.  gk_1 of a step (the
-// FSAL adjoint the step before adds to its gk_7) is read from its block before that step overwrites it.
-template <int ACT>
+// FSAL adjoint the step before adds to its gk_S) is read from its block before that step overwrites it.
+template <class TB, int ACT>
 __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float* __restrict__ traj,
                                                                      const OdeCtrl* __restrict__ ctrl,
                                                                      const float* __restrict__ gy,
                                                                      const bf16x8* __restrict__ wtf_hi,
                                                                      const bf16x8* __restrict__ wtf_lo, int b, int max_steps,
                                                                      float* __restrict__ gx, float* __restrict__ GZ,
-                                                                     float* S, int Bp) {
+                                                                     float* SI, int Bp) {
+    constexpr int S = TB::S, NA = BwdCoef<TB>::NA;
     __shared__ __attribute__((aligned(16))) char smem[XPLANES_BWD];
-    __shared__ float bc[28];      // this step's dt A[i][j] at i (i - 1) / 2 + j (i = 1 .. 6, j < i), dt w_j at 21 + j
+    __shared__ float bc[BwdCoef<TB>::COUNT];      // this step's constants (publish_bwd_step)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int brow = blockIdx.x * FROWS + (lane & 15);
@@ -950,28 +1012,28 @@ __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float
     };
     auto sel = [&](const f32x4& v) -> f32x4 { return live ? v : zero4; };
     auto emit = [&](int blk, int t, const f32x4& gz) { *(f32x4*)(GZ + ((size_t)blk * Bp * XD + rbase) + lo + 16 * t) = gz; };
-    auto gkp = [&](int j, int t) -> float* { return S + ((size_t)j * Bp * XD + rbase) + lo + 16 * t; };
+    auto gkp = [&](int j, int t) -> float* { return SI + ((size_t)j * Bp * XD + rbase) + lo + 16 * t; };
 
     Tiles3 a;
 #pragma unroll
     for (int t = 0; t < XTILES; ++t) a.t[t] = live ? *(const f32x4*)(gy + rbase + loff + 16 * t) : zero4;
     for (int n = N - 1; n >= 0; --n) {
-        publish_bwd_step(bc, ctrl, n, N, tid);
+        publish_bwd_step<TB>(bc, ctrl, n, N, tid);
 #pragma unroll
-        for (int i = 6; i >= 1; --i) {
+        for (int i = S - 1; i >= 1; --i) {
             asm volatile("" : "+v"(lo), "+v"(lk));
-            // gz_{i+1} = gk_{i+1} act'(k_{i+1}); stage 7's gk is dt w_7 a plus the FSAL adjoint of the step after
+            // gz_{i+1} = gk_{i+1} act'(k_{i+1}); stage S's gk is dt w_S a plus the FSAL adjoint of the step after
 #pragma unroll
             for (int t = 0; t < XTILES; ++t) {
                 f32x4 gk;
-                if (i == 6) {
-                    gk = uniform_f(bc[27]) * a.t[t];
+                if (i == S - 1) {
+                    gk = uniform_f(bc[NA + S - 1]) * a.t[t];
                     if (n != N - 1) gk += *(const f32x4*)gkp(0, t);
                 } else {
                     gk = *(const f32x4*)gkp(i, t);
                 }
                 const f32x4 gz = sel(gk * dact_out<ACT>(ld(n, 1 + i, t)));
-                emit(6 * n + (i - 1), t, gz);
+                emit((S - 1) * n + (i - 1), t, gz);
                 put(t, gz);
                 __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
             }
@@ -980,7 +1042,7 @@ __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float
             for (int t = 0; t < XTILES; ++t) {
 #pragma unroll
                 for (int j = 0; j < i; ++j) {
-                    const f32x4 base = i == 6 ? uniform_f(bc[21 + j]) * a.t[t] : *(const f32x4*)gkp(j, t);
+                    const f32x4 base = i == S - 1 ? uniform_f(bc[NA + j]) * a.t[t] : *(const f32x4*)gkp(j, t);
                     *(f32x4*)gkp(j, t) = base + uniform_f(bc[i * (i - 1) / 2 + j]) * gs.t[t];
                 }
                 a.t[t] += gs.t[t];
@@ -992,7 +1054,7 @@ __global__ __launch_bounds__(XT) void fcode_adaptive_wide_bwd_kernel(const float
 #pragma unroll
             for (int t = 0; t < XTILES; ++t) {
                 const f32x4 gz = sel(*(const f32x4*)gkp(0, t) * dact_out<ACT>(ld(0, 1, t)));
-                emit(6 * N, t, gz);
+                emit((S - 1) * N, t, gz);
                 put(t, gz);
                 __builtin_amdgcn_sched_barrier(0);      // one feature tile at a time
             }
@@ -1029,7 +1091,7 @@ static int64_t bwd_workspace_bytes(int b, int d, int max_steps) {
 // the refusals of the four launch entries, in their order: a bad argument (have: every required pointer is there;
 // tols_ok: the forward's tolerances), then a width d the entry is not built for
 static int adaptive_refusal(bool have, int b, int d, int built_for, int act, int method, int max_steps, bool tols_ok) {
-    if (!have || d <= 0 || b <= 0 || method != AGP_ODE_DOPRI5 || act < AGP_ACT_ID || act > AGP_ACT_SIGMOID || max_steps < 1 ||
+    if (!have || d <= 0 || b <= 0 || (method != Dopri5::METHOD && method != Bosh3::METHOD) || act < AGP_ACT_ID || act > AGP_ACT_SIGMOID || max_steps < 1 ||
         max_steps > AGP_ODE_MAX_STEPS_LIMIT)
         return AGP_E_BADARG;
     if (!tols_ok) return AGP_E_BADARG;
@@ -1047,6 +1109,12 @@ static int by_act(int act, F&& fn) {
     }
 }
 
+// fn(TB{}) for a checked adaptive method's Tableau
+template <class F>
+static int by_method(int method, F&& fn) {
+    return method == Bosh3::METHOD ? fn(Bosh3{}) : fn(Dopri5{});
+}
+
 template <class E>
 static int adaptive_fwd(const float* x, const float* add1, const float* add2, const void* w_hi, const void* w_lo,
                         const float* bias, int b, int d, int act, int method, double rtol, double atol, int max_steps, float* y,
@@ -1055,31 +1123,34 @@ static int adaptive_fwd(const float* x, const float* add1, const float* add2, co
     if (const int rc = adaptive_refusal(x && w_hi && w_lo && y && ring && ctrl, b, d, E::D, act, method, max_steps, tols_ok)) return rc;
     static_assert(sizeof(agp_ode_stats) == 32 && offsetof(OdeCtrl, dt) == 32, "control block layout");
     const int nring = want_traj ? max_steps + 1 : 2;
-    return by_act(act, [&](auto A) -> int {
-        const auto kernel = fcode_adaptive_kernel<E, decltype(A)::value>;
-        if constexpr (E::LDS_DYNAMIC != 0) {
-            static std::atomic<uint64_t> attr_done;
-            if (!agp_lds_attr((const void*)kernel, E::LDS_DYNAMIC, attr_done)) return AGP_E_LAUNCH;
-        }
-        AGP_LAUNCH(kernel, dim3(1), dim3(E::THREADS), E::LDS_DYNAMIC, (hipStream_t)stream, x, add1, add2,
-                   (typename E::Plane)w_hi, (typename E::Plane)w_lo, bias, b, rtol, atol, max_steps, ring, nring, y, (OdeCtrl*)ctrl);
-        AGP_CHECK_LAUNCH();
-        return AGP_OK;
+    return by_method(method, [&](auto M) -> int {
+        return by_act(act, [&](auto A) -> int {
+            const auto kernel = fcode_adaptive_kernel<E, decltype(M), decltype(A)::value>;
+            if constexpr (E::LDS_DYNAMIC != 0) {
+                static std::atomic<uint64_t> attr_done;      // (one per instantiation of this lambda: per method and activation)
+                if (!agp_lds_attr((const void*)kernel, E::LDS_DYNAMIC, attr_done)) return AGP_E_LAUNCH;
+            }
+            AGP_LAUNCH(kernel, dim3(1), dim3(E::THREADS), E::LDS_DYNAMIC, (hipStream_t)stream, x, add1, add2,
+                       (typename E::Plane)w_hi, (typename E::Plane)w_lo, bias, b, rtol, atol, max_steps, ring, nring, y,
+                       (OdeCtrl*)ctrl);
+            AGP_CHECK_LAUNCH();
+            return AGP_OK;
+        });
     });
 }
 
 // the weight and bias gradients from the gz rows the state kernel left in GZ and the stage inputs rebuilt into S
-template <int D>
+template <int D, class TB>
 static int adaptive_sums(const float* traj, const OdeCtrl* c, int b, int max_steps, float* gw, float* gb, float* GZ, float* S,
                          int Bp, hipStream_t s) {
     if (gw) {
-        AGP_LAUNCH(adaptive_stage_inputs_kernel<D>, dim3(Bp * (D / 4) / 256, max_steps), dim3(256), 0, s, traj, c, b, max_steps, S, Bp);
+        AGP_LAUNCH((adaptive_stage_inputs_kernel<D, TB>), dim3(Bp * (D / 4) / 256, max_steps), dim3(256), 0, s, traj, c, b, max_steps, S, Bp);
         AGP_CHECK_LAUNCH();
-        AGP_LAUNCH(adaptive_gw_kernel<D>, dim3(D / 64, D / 64), dim3(256), 0, s, GZ, S, gw, c, max_steps, Bp);
+        AGP_LAUNCH((adaptive_gw_kernel<D, TB>), dim3(D / 64, D / 64), dim3(256), 0, s, GZ, S, gw, c, max_steps, Bp);
         AGP_CHECK_LAUNCH();
     }
     if (gb) {
-        AGP_LAUNCH(adaptive_gb_kernel<D>, dim3(D / 64), dim3(256), 0, s, GZ, gb, c, max_steps, Bp);
+        AGP_LAUNCH((adaptive_gb_kernel<D, TB>), dim3(D / 64), dim3(256), 0, s, GZ, gb, c, max_steps, Bp);
         AGP_CHECK_LAUNCH();
     }
     return AGP_OK;
@@ -1094,23 +1165,27 @@ static int adaptive_bwd(const float* traj, const void* ctrl, const float* gy, co
     if (workspace_bytes < bwd_workspace_bytes(b, D, max_steps)) return AGP_E_BADARG;
     const int Bp = (b + FROWS - 1) / FROWS * FROWS;
     float* GZ = (float*)workspace;
-    float* S = GZ + (6 * (size_t)max_steps + 1) * Bp * D;      // (the state kernel's scratch first, then the stage inputs)
+    // (the state kernel's scratch first, then the stage inputs; the halves are sized for seven stages, the most a Tableau has)
+    float* S = GZ + (6 * (size_t)max_steps + 1) * Bp * D;
     hipStream_t s = (hipStream_t)stream;
     const OdeCtrl* c = (const OdeCtrl*)ctrl;
     const dim3 grid(Bp / FROWS);
-    const int rc = by_act(act, [&](auto A) -> int {
-        constexpr int ACT = decltype(A)::value;
-        if constexpr (D == AD) {
-            AGP_LAUNCH(fcode_adaptive_bwd_kernel<ACT>, grid, dim3(FT), 0, s, traj, c, gy, (const bf16_t*)wt_hi, (const bf16_t*)wt_lo, b,
-                       max_steps, gx, GZ, Bp);
-        } else {
-            AGP_LAUNCH(fcode_adaptive_wide_bwd_kernel<ACT>, grid, dim3(XT), 0, s, traj, c, gy, (const bf16x8*)wt_hi,
-                       (const bf16x8*)wt_lo, b, max_steps, gx, GZ, S, Bp);
-        }
-        AGP_CHECK_LAUNCH();
-        return AGP_OK;
+    return by_method(method, [&](auto M) -> int {
+        using TB = decltype(M);
+        const int rc = by_act(act, [&](auto A) -> int {
+            constexpr int ACT = decltype(A)::value;
+            if constexpr (D == AD) {
+                AGP_LAUNCH((fcode_adaptive_bwd_kernel<TB, ACT>), grid, dim3(FT), 0, s, traj, c, gy, (const bf16_t*)wt_hi,
+                           (const bf16_t*)wt_lo, b, max_steps, gx, GZ, Bp);
+            } else {
+                AGP_LAUNCH((fcode_adaptive_wide_bwd_kernel<TB, ACT>), grid, dim3(XT), 0, s, traj, c, gy, (const bf16x8*)wt_hi,
+                           (const bf16x8*)wt_lo, b, max_steps, gx, GZ, S, Bp);
+            }
+            AGP_CHECK_LAUNCH();
+            return AGP_OK;
+        });
+        return rc != AGP_OK ? rc : adaptive_sums<D, TB>(traj, c, b, max_steps, gw, gb, GZ, S, Bp, s);
     });
-    return rc != AGP_OK ? rc : adaptive_sums<D>(traj, c, b, max_steps, gw, gb, GZ, S, Bp, s);
 }
 
 extern "C" int64_t agp_fcode_adaptive_ctrl_bytes(int max_steps) {

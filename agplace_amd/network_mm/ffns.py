@@ -7,18 +7,20 @@ used: the whole fixed-grid solve (all steps, all stages) is ONE persistent HIP k
 (agp_fcode_wide_fwd: W's `hi` plane in registers, the `lo` plane streamed from L2); every other width, and
 384 with a gradient wanted, runs the same steps as a sequence of differentiable launches (_forward_any_width) -- unless
 Options.fcode_wide opted in: FCODE(384) then trains on the one-launch kernel recording its trajectory and its one-launch backward
-(agp_fcode_wide_fwd_traj / agp_fcode_wide_bwd) and takes odeint_method = 'dopri5' (agp_fcode_adaptive_wide_fwd / _bwd).
+(agp_fcode_wide_fwd_traj / agp_fcode_wide_bwd) and takes the adaptive methods (agp_fcode_adaptive_wide_fwd / _bwd).
 The time grid follows torchdiffeq's constructor exactly (niters = ceil(1/step + 1), arange * step, last point forced
 to 1) and is kept in fp32 (the reference builds t with .float().type_as(x)).
 'rk4' is torchdiffeq's 3/8-rule variant.  rtol/atol (opt.tol) are ignored by fixed-grid solvers.
 odeint_method = 'dopri5' (torchdiffeq's default, adaptive) reads them: rtol = atol = opt.tol, one launch per solve as well
 (agp_fcode_adaptive_fwd), at most opt.odeint_max_steps attempted steps; odeint_size is ignored.
+odeint_method = 'bosh3' (Bogacki-Shampine 3(2), four stages) is the same controller and the same kernels over another table;
+it is taken only with Options.odeint_adaptive_family set and refused otherwise.
 state_dict keys: func.func.fc.{weight,bias} (via ODEFunc -> FC -> nn.Linear).
 """
 import torch
 import torch.nn as nn
 
-from .. import autograd_ops, ops
+from .. import _lib, autograd_ops, ops
 from ..options import get_options
 
 _ACTS = (None, 'id', 'relu', 'tanh', 'sigmoid')
@@ -94,13 +96,14 @@ class FCODE(nn.Module):
         self.act_name = act
         self.method = opt.odeint_method
         self.step_size = opt.odeint_size
-        if self.method not in ('euler', 'midpoint', 'rk4', 'dopri5'):
+        family = tuple(_lib.ODE_ADAPTIVE) if opt.odeint_adaptive_family else ('dopri5',)
+        if self.method not in ('euler', 'midpoint', 'rk4') + family:
             raise NotImplementedError(self.method)
-        self.adaptive = self.method == 'dopri5'
+        self.adaptive = self.method in _lib.ODE_ADAPTIVE
         self.tol = float(opt.tol)
         self.max_steps = int(opt.odeint_max_steps)
         if self.adaptive and not self.tol > 0.0:
-            raise ValueError(f"tol {opt.tol!r}: dopri5 needs rtol = atol > 0")
+            raise ValueError(f"tol {opt.tol!r}: {self.method} needs rtol = atol > 0")
         self.dts = None if self.adaptive else ops.ode_grid_dts(self.step_size)
         self._ctrl = None                 # device control block of the last adaptive solve (solver_stats)
         self.wide_routes = bool(opt.fcode_wide) and dim == ops.FCODE_WIDE_DIM       # Options.fcode_wide, at its one width
@@ -112,8 +115,8 @@ class FCODE(nn.Module):
             return autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, self, add1, add2)
         if self.wide_routes and (self.adaptive or (torch.is_grad_enabled() and any(
                 t is not None and t.requires_grad for t in (x, add1, add2, fc.weight, fc.bias)))):
-            # opted in at 384 columns: a fixed grid with a gradient wanted records its trajectory in the one-launch kernel, dopri5
-            # runs on the adaptive kernels; a fixed grid without a gradient is the inference launch below either way
+            # opted in at 384 columns: a fixed grid with a gradient wanted records its trajectory in the one-launch kernel, an
+            # adaptive method runs on the adaptive kernels; a fixed grid without a gradient is the inference launch below either way
             return autograd_ops.FCODEFn.apply(x, fc.weight, fc.bias, self, add1, add2)
         if fc.in_features == ops.FCODE_WIDE_DIM and not self.adaptive and not (torch.is_grad_enabled() and any(
                 t is not None and t.requires_grad for t in (x, add1, add2, fc.weight, fc.bias))):
@@ -129,7 +132,6 @@ class FCODE(nn.Module):
             raise RuntimeError("solver_stats: no adaptive solve has run on this block")
         st = ops.ode_stats(self._ctrl)
         if st["status"] != 0:
-            from .. import _lib
             raise RuntimeError(f"FCODE {self.method}: {_lib.ODE_STATUS.get(st['status'], st['status'])} after "
                                f"{st['attempted']} attempted steps (t = {st['t0']:.6g}); the output is NaN")
         return st

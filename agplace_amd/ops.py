@@ -1476,7 +1476,7 @@ def _adaptive_args(x, lw, act, method, tol, max_steps):
 
 
 def fcode_adaptive(x, lw: LinearWeights, act, method, tol, max_steps=64, add1=None, add2=None, want_traj=False):
-    """y(1) of y' = act(y W^T + b), y(0) = x + add1 + add2, by the adaptive solver `method` ('dopri5') with rtol = atol = tol:
+    """y(1) of y' = act(y W^T + b), y(0) = x + add1 + add2, by the adaptive solver `method` ('dopri5' | 'bosh3') with rtol = atol = tol:
     ONE launch (agp_fcode_adaptive_fwd at 256 columns, agp_fcode_adaptive_wide_fwd at 384), no host synchronisation,
     capturable.  Returns (y, ctrl) or, with want_traj,
     (y, ctrl, traj): ctrl is the device control block (ode_stats(ctrl) reads it), traj the record fcode_adaptive_bwd needs.
@@ -1501,7 +1501,8 @@ def fcode_adaptive(x, lw: LinearWeights, act, method, tol, max_steps=64, add1=No
 
 
 def fcode_adaptive_bwd(traj, ctrl, gy, lw: LinearWeights, act, method, max_steps=64):
-    """(gx, gw, gb) of fcode_adaptive(..., want_traj=True); the step count and the step sizes stay on the device."""
+    """(gx, gw, gb) of fcode_adaptive(..., want_traj=True) with the same `method` ('dopri5' | 'bosh3'); the step count and
+    the step sizes stay on the device."""
     gy = gy.contiguous().float()
     b, d = gy.shape
     gx = torch.empty_like(gy)

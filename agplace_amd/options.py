@@ -73,7 +73,7 @@ class Options:
     diff_direction: str = "backward"
     odeint_method: str = "euler"
     odeint_size: float = 0.1
-    tol: float = 1e-3                 # rtol = atol of the adaptive solver (odeint_method = "dopri5"); fixed grids ignore it
+    tol: float = 1e-3                 # rtol = atol of an adaptive solver (odeint_method = "dopri5" | "bosh3"); fixed grids ignore it
     odeint_max_steps: int = 64        # attempted steps after which an adaptive solve gives up and returns NaN (torchdiffeq: 2^31 - 1)
     imagevoxorg_weight: float = 0.0
     imagevoxorg_learnweight: bool = False
@@ -139,6 +139,12 @@ class Options:
     # as before, launch for launch.  Other widths ignore it.  A reference namespace does not carry this field
     # (from_reference_opt leaves it False): from_reference_opt(args).copy(fcode_wide=True).
     fcode_wide: bool = False
+    # Opt-in further members of torchdiffeq's adaptive Runge-Kutta family: odeint_method = "bosh3" (Bogacki-Shampine 3(2)) then
+    # runs on the adaptive kernels (csrc/fusion_adaptive.hip, the Tableau Bosh3) at 256 columns, and at 384
+    # columns together with fcode_wide, exactly as "dopri5" does.  False (default): FCODE refuses "bosh3" with
+    # NotImplementedError, as before.  "dopri5" does not need it.  A reference namespace does not carry this field
+    # (from_reference_opt leaves it False): from_reference_opt(args).copy(odeint_adaptive_family=True).
+    odeint_adaptive_family: bool = False
     # Opt-in level capacity of the raw-points route (MM.forward_q from `points` / `point_offsets`, inference and training): an upper
     # bound on the voxels of a whole batch, None or an int in 1 .. 2^30 - 1.  With a value every level of the voxel branch has that
     # many rows instead of one per raw point (SparseTensor.from_points_capacity / from_points_levels, level_capacity);
@@ -199,6 +205,8 @@ class Options:
             raise ValueError(f"convnext_u8 {self.convnext_u8!r}: True | False")
         if not isinstance(self.fcode_wide, bool):
             raise ValueError(f"fcode_wide {self.fcode_wide!r}: True | False")
+        if not isinstance(self.odeint_adaptive_family, bool):
+            raise ValueError(f"odeint_adaptive_family {self.odeint_adaptive_family!r}: True | False")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
         v = self.voxel_capacity
@@ -215,7 +223,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "fcode_wide", "voxel_capacity"):      # (not reference options: stay False / None)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "fcode_wide", "odeint_adaptive_family", "voxel_capacity"):      # (not reference options: stay False / None)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

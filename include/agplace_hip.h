@@ -70,8 +70,9 @@ extern "C" {
 #define AGP_ODE_EULER 0
 #define AGP_ODE_MIDPOINT 1
 #define AGP_ODE_RK4 2 /* torchdiffeq 'rk4' = 3/8 rule */
-/* adaptive solver (agp_fcode_adaptive_fwd / _bwd only): Dormand-Prince 5(4), torchdiffeq's default method */
-#define AGP_ODE_DOPRI5 3
+/* adaptive solvers (agp_fcode_adaptive_fwd / _bwd and their _wide forms only), torchdiffeq's embedded Runge-Kutta family */
+#define AGP_ODE_DOPRI5 3 /* Dormand-Prince 5(4), seven stages: torchdiffeq's default method */
+#define AGP_ODE_BOSH3 4  /* Bogacki-Shampine 3(2), four stages */
 /* agp_ode_stats.status of an adaptive solve; non-zero = the output is NaN */
 #define AGP_ODE_OK 0
 #define AGP_ODE_E_MAXSTEPS 1  /* max_steps attempted steps did not reach t = 1 */
@@ -563,7 +564,7 @@ int agp_fcode_bwd(const float* traj, const float* gy, const void* wt_hi, const v
                   int act, int method, const float* dt, int nsteps, float* gx, float* gw, float* gb,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
-/* FCODE by the ADAPTIVE solver dopri5 (method = AGP_ODE_DOPRI5; D = 256, for D = 384 agp_fcode_adaptive_wide_fwd below): y(1) of dy/dt = act(y W^T + b),
+/* FCODE by an ADAPTIVE solver (method = AGP_ODE_DOPRI5 or AGP_ODE_BOSH3, a method of S = 7 or 4 stages; D = 256, for D = 384 agp_fcode_adaptive_wide_fwd below): y(1) of dy/dt = act(y W^T + b),
  * y(0) = x (+ add1 + add2), with torchdiffeq's step control -- one RMS error norm over all b * 256 elements, steps not
  * clipped to the end time, the result read off the last step's quartic interpolant.  ONE launch of
  * one persistent workgroup per solve, no host round trip: capturable.  f runs on W's two split-bf16 planes and THREE bf16 planes
@@ -573,8 +574,8 @@ int agp_fcode_bwd(const float* traj, const float* gy, const void* wt_hi, const v
  *         double dt[max_steps], the step size of every ACCEPTED step, and double attempt[max_steps][2], the step size and
  *         the error ratio of every ATTEMPTED step (accepted iff ratio <= 1).
  *   ring: agp_fcode_adaptive_ring_floats(b, max_steps, want_traj) floats of DEVICE scratch.  want_traj != 0: on return
- *         ring[n][0][b][256] = y before accepted step n, ring[n][1 + j][b][256] = its k_{j+1} (j < 7) -- the trajectory
- *         agp_fcode_adaptive_bwd reads. */
+ *         ring[n][0][b][256] = y before accepted step n, ring[n][1 + j][b][256] = its k_{j+1} (j < S; an entry is eight
+ *         planes for every method) -- the trajectory agp_fcode_adaptive_bwd reads. */
 typedef struct agp_ode_stats {
     int32_t status;   /* AGP_ODE_OK or AGP_ODE_E_* */
     int32_t accepted; /* accepted steps */
@@ -591,14 +592,15 @@ int agp_fcode_adaptive_fwd(const float* x, const float* add1, const float* add2,
 /* Backward of agp_fcode_adaptive_fwd: discretise-then-optimise through the ACCEPTED steps with their recorded step sizes
  * (step control is a constant, as in torchdiffeq), the last step through its interpolation weights; the adjoint of a step's
  * first stage flows into the step before (FSAL).  The step count and the step sizes are read from `ctrl` on the device.
- * traj = the forward's ring (want_traj != 0, same max_steps).  Outputs as agp_fcode_bwd; after a failed forward they are
- * NaN.  workspace: agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps) bytes. */
+ * traj = the forward's ring (want_traj != 0, same max_steps, same method).  Outputs as agp_fcode_bwd; after a failed forward
+ * they are NaN.  workspace: agp_fcode_adaptive_bwd_workspace_bytes(b, max_steps) bytes (sized for seven stages: enough for
+ * every method). */
 int64_t agp_fcode_adaptive_bwd_workspace_bytes(int b, int max_steps);
 int agp_fcode_adaptive_bwd(const float* traj, const void* ctrl, const float* gy, const void* wt_hi, const void* wt_lo,
                            int b, int act, int method, int max_steps, float* gx, float* gw, float* gb, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
-/* The adaptive solver at d = 384 (dopri5 on a 384 x 384 Linear, csrc/fusion_adaptive.hip): the algorithm, the arithmetic (two planes
+/* The adaptive solver at d = 384 (the same methods on a 384 x 384 Linear, csrc/fusion_adaptive.hip): the algorithm, the arithmetic (two planes
  * of W, three of the state, five products), the control block (agp_fcode_adaptive_ctrl_bytes, agp_ode_stats), the three endings
  * and the ring layout of agp_fcode_adaptive_fwd, with 384 columns: ring[n][0][b][384] = y before accepted step n,
  * ring[n][1 + j][b][384] = its k_{j+1}; agp_fcode_adaptive_wide_ring_floats(b, d, max_steps, want_traj) =
@@ -610,7 +612,7 @@ int agp_fcode_adaptive_bwd(const float* traj, const void* ctrl, const float* gy,
  * split-bf16 planes of W [384][384] in the FRAGMENT order of agp_fcode_wide_fwd, 16 bytes per entry:
  *   [wave 0..7][ks 0..11][tile 0..2][q 0..3][row 0..15][8] = W[48 wave + 16 tile + row][32 ks + 8 q .. + 7].
  * d != 384: AGP_E_UNSUPPORTED.  AGP_E_BADARG: a null pointer, b <= 0, d <= 0, an unknown act, a method other than
- * AGP_ODE_DOPRI5, max_steps outside 1 .. AGP_ODE_MAX_STEPS_LIMIT, a negative tolerance or rtol + atol <= 0 (checked before d). */
+ * AGP_ODE_DOPRI5 and AGP_ODE_BOSH3, max_steps outside 1 .. AGP_ODE_MAX_STEPS_LIMIT, a negative tolerance or rtol + atol <= 0 (checked before d). */
 int64_t agp_fcode_adaptive_wide_ring_floats(int b, int d, int max_steps, int want_traj);
 int agp_fcode_adaptive_wide_fwd(const float* x, const float* add1, const float* add2, const void* wf_hi, const void* wf_lo,
                                 const float* bias, int b, int d, int act, int method, double rtol, double atol,
@@ -620,7 +622,8 @@ int agp_fcode_adaptive_wide_fwd(const float* x, const float* add1, const float* 
  * sizes read from `ctrl` on the device, gw[384][384] and gb[384] OVERWRITTEN, NaN outputs after a failed forward.  wtf_hi /
  * wtf_lo: the planes of W^T [384][384] in the same fragment order, i.e. [wave][ks][tile][q][row][8] =
  * W[32 ks + 8 q .. + 7][48 wave + 16 tile + row].  workspace: agp_fcode_adaptive_wide_bwd_workspace_bytes(b, d, max_steps) =
- * 2 * (6 * max_steps + 1) * Bp * 384 * 4 bytes, Bp = b rounded up to 16 (0 for b <= 0, max_steps < 1 or d != 384). */
+ * 2 * (6 * max_steps + 1) * Bp * 384 * 4 bytes for every method, Bp = b rounded up to 16 (0 for b <= 0, max_steps < 1 or
+ * d != 384). */
 int64_t agp_fcode_adaptive_wide_bwd_workspace_bytes(int b, int d, int max_steps);
 int agp_fcode_adaptive_wide_bwd(const float* traj, const void* ctrl, const float* gy, const void* wtf_hi, const void* wtf_lo,
                                 int b, int d, int act, int method, int max_steps, float* gx, float* gw, float* gb,
