@@ -227,6 +227,9 @@ SIGNATURES = {
     "agp_cnx_dwconv_ln_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _L, _P]),
     "agp_cnx_mlp_fwd": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "agp_cnx_downsample_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P]),
+    "agp_cnx_dwconv_ln_f16_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _L, _P]),
+    "agp_cnx_mlp_f16_fwd": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "agp_cnx_downsample_f16_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P]),
     "agp_cnx_bwd_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "agp_cnx_bwd_slice_pixels": (_L, []),
     "agp_cnx_mlp_fwd_rows": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),

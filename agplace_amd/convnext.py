@@ -26,6 +26,14 @@ panorama [n,3,h,ncam*w] with v = (u8 / 255 - mean[c]) / std[c] (`set_image_norm`
 loader of the same kernel body, so the maps and gradients are, bit for bit, those of the fp32 route on
 ops.normalize_cameras_u8(tiles, mean, std), and the training node saves the uint8 tiles instead of an fp32 image.
 
+Precision 4 is OPT-IN as well (`ConvNeXt.set_precision(4)`, Options.convnext_precision) and covers the inference path
+(`forward_maps`) only: the three matrix kernels run their PREC = 4 instantiations (agp_cnx_*_f16_fwd), in which the block's LayerNorm
+output (one fp16 operand plane instead of two bf16 ones), W1, the GELU output, W2, the downsample's LayerNorm output and its weight
+are rounded to fp16 (nearest even, saturating at +-65504, NaN kept) and every product is ONE fp16 MFMA with fp32 accumulation.  The
+stream, the stem, the depthwise conv, LayerNorm statistics, biases, GELU, layer_scale and the residual add stay fp32, so the maps
+are still fp32 tensors and there is still no fp16 map to guard; the fp32 and uint8 stems are the same kernels.  `forward_maps_train`
+and the backward stay in mode 3 whatever is set (the ResNets' rule for Options.mfma_precision).  With 3 nothing changes.
+
 Stochastic depth restates torchvision's StochasticDepth(p, "row") (torchvision is not a dependency): block k of the FULL
 18-block network has p_k = stochastic_depth_prob * k / 17 (the truncation happens after construction, so a kept block keeps its
 k); in .train() each image draws scale = bernoulli(1 - p_k) / (1 - p_k) and out = x + scale[n] * layer_scale * branch(x);
@@ -44,6 +52,15 @@ DEPTHS = (3, 3, 9, 3)
 LN_EPS = 1e-6
 STAGE_FIRST_BLOCK = (0, 3, 6)          # index k of a stage's first block in the full network
 TRAIN_SWITCH = "opt in with ConvNeXt.enable_training() / Options.convnext_train"
+
+
+def precision_from_options(opt):
+    """Options.convnext_precision for a trunk that `opt` configures; precision 4 together with the fp16 range guard is refused:
+    the guard's sticky word is not wired into the precision-4 kernels, and a guard that silently skips the trunk would be worse."""
+    if opt.convnext_precision == 4 and opt.fp16_range_guard:
+        raise NotImplementedError("ConvNeXt: convnext_precision=4 together with fp16_range_guard=True is not built (the guard's word "
+                                  "is not wired into the fp16 ConvNeXt kernels); use convnext_precision=3 or turn the guard off")
+    return opt.convnext_precision
 
 
 class LayerNorm2d(nn.LayerNorm):
@@ -65,6 +82,20 @@ def _split(w):
     """fp32 -> (hi, lo) bf16 planes: hi = rn(w), lo = rn(w - hi), as csrc/common.hpp split_bf16."""
     hi = w.to(torch.bfloat16)
     return hi.contiguous(), (w - hi.float()).to(torch.bfloat16).contiguous()
+
+
+def _half(w):
+    """fp32 -> ONE fp16 plane (precision 4): round to nearest even, saturating at +-65504, NaN kept."""
+    return w.clamp(-65504.0, 65504.0).to(torch.float16).contiguous()
+
+
+def _planes(w, prec):
+    """The kernel-side planes of a fragment-ordered fp32 tensor: (hi, lo) bf16 for precision 3, (fp16,) for precision 4."""
+    if prec == 3:
+        return _split(w)
+    if prec == 4:
+        return (_half(w),)
+    raise ValueError(f"ConvNeXt: precision {prec!r}: 3 (three bf16 products) | 4 (one fp16 product)")
 
 
 def _frag_rows(w):
@@ -91,19 +122,20 @@ def prep_stem(conv, ln):
     return dict(w=_f32(conv.weight).reshape(DIMS[0], 48).t().contiguous(), bias=_f32(conv.bias), g=_f32(ln.weight), b=_f32(ln.bias))
 
 
-def prep_block(blk):
-    """Kernel-side weights of one CNBlock: the depthwise taps as [49][C], the two Linear layers as fragment-ordered planes."""
+def prep_block(blk, prec=3):
+    """Kernel-side weights of one CNBlock: the depthwise taps as [49][C], the two Linear layers as fragment-ordered planes
+    (prec 3: (hi, lo) bf16; prec 4: one fp16 plane of the same tensors)."""
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     c = dw.weight.shape[0]
     return dict(c=c, dw=_f32(dw.weight).reshape(c, 49).t().contiguous(), dwb=_f32(dw.bias), g=_f32(ln.weight), b=_f32(ln.bias),
-                w1=_split(_frag_rows(_f32(l1.weight))), b1=_f32(l1.bias), w2=_split(_frag_acc(_f32(l2.weight))), b2=_f32(l2.bias),
-                ls=_f32(blk.layer_scale).reshape(c))
+                w1=_planes(_frag_rows(_f32(l1.weight)), prec), b1=_f32(l1.bias), w2=_planes(_frag_acc(_f32(l2.weight)), prec),
+                b2=_f32(l2.bias), ls=_f32(blk.layer_scale).reshape(c))
 
 
-def prep_down(ln, conv):
+def prep_down(ln, conv, prec=3):
     c = conv.weight.shape[1]
     wk = _f32(conv.weight).permute(0, 2, 3, 1).reshape(2 * c, 4 * c)      # k = (ky * 2 + kx) * C + c
-    return dict(c=c, g=_f32(ln.weight), b=_f32(ln.bias), w=_split(_frag_rows(wk)), bias=_f32(conv.bias))
+    return dict(c=c, g=_f32(ln.weight), b=_f32(ln.bias), w=_planes(_frag_rows(wk), prec), bias=_f32(conv.bias))
 
 
 def prep_block_bwd(blk):
@@ -150,21 +182,40 @@ def stem_fwd(x, p):
     return out
 
 
-def dwconv_ln_fwd(x, p, ws):
-    """Depthwise 7x7 + LayerNorm of the stream x into the workspace `ws` (uint8, >= workspace_bytes(*x.shape))."""
+def _planes_ok(planes, prec, what):
+    """`prec` must be the precision the weights were prepared for (prep_block / prep_down): the kernels cannot tell."""
+    if prec not in (3, 4) or len(planes) != (2 if prec == 3 else 1):
+        raise ValueError(f"ConvNeXt.{what}: prec={prec!r} does not match the prepared weights ({len(planes)} plane(s)); "
+                         "prec is 3 or 4 and the same as in prep_block / prep_down")
+
+
+def dwconv_ln_fwd(x, p, ws, prec=3):
+    """Depthwise 7x7 + LayerNorm of the stream x into the workspace `ws` (uint8, >= workspace_bytes(*x.shape)): two bf16 planes
+    (prec 3) or one fp16 plane at its start (prec 4)."""
     _stream_ok(x, p["c"])
     n, h, w, c = x.shape
+    if prec == 4:
+        check(_lib.load().agp_cnx_dwconv_ln_f16_fwd(ptr(x), n, h, w, c, ptr(p["dw"]), ptr(p["dwb"]), ptr(p["g"]), ptr(p["b"]), LN_EPS,
+                                                    ptr(ws), ws.numel(), _lib.stream()), "agp_cnx_dwconv_ln_f16_fwd")
+        return
+    if prec != 3:
+        raise ValueError(f"ConvNeXt.dwconv_ln_fwd: prec {prec!r}: 3 | 4")
     check(_lib.load().agp_cnx_dwconv_ln_fwd(ptr(x), n, h, w, c, ptr(p["dw"]), ptr(p["dwb"]), ptr(p["g"]), ptr(p["b"]), LN_EPS,
                                             ptr(ws), ws.numel(), _lib.stream()), "agp_cnx_dwconv_ln_fwd")
 
 
-def mlp_fwd(ws, p, resid, out):
-    """out = resid + layer_scale * MLP(the operand in `ws`); `out` may be `resid`."""
+def mlp_fwd(ws, p, resid, out, prec=3):
+    """out = resid + layer_scale * MLP(the operand in `ws`); `out` may be `resid`.  prec: that of dwconv_ln_fwd and prep_block."""
     _stream_ok(resid, p["c"])
     _stream_ok(out, p["c"])
     if out.shape != resid.shape:
         raise ValueError("ConvNeXt.mlp_fwd: out and resid differ in shape")
+    _planes_ok(p["w1"], prec, "mlp_fwd")
     n, h, w, c = resid.shape
+    if prec == 4:
+        check(_lib.load().agp_cnx_mlp_f16_fwd(ptr(ws), ws.numel(), n * h * w, c, ptr(p["w1"][0]), ptr(p["b1"]), ptr(p["w2"][0]),
+                                              ptr(p["b2"]), ptr(p["ls"]), ptr(resid), ptr(out), _lib.stream()), "agp_cnx_mlp_f16_fwd")
+        return out
     check(_lib.load().agp_cnx_mlp_fwd(ptr(ws), ws.numel(), n * h * w, c, ptr(p["w1"][0]), ptr(p["w1"][1]), ptr(p["b1"]),
                                       ptr(p["w2"][0]), ptr(p["w2"][1]), ptr(p["b2"]), ptr(p["ls"]), ptr(resid), ptr(out),
                                       _lib.stream()), "agp_cnx_mlp_fwd")
@@ -177,6 +228,7 @@ def mlp_fwd_rows(ws, p, resid, out, row_scale=None):
     _stream_ok(out, p["c"])
     if out.shape != resid.shape:
         raise ValueError("ConvNeXt.mlp_fwd_rows: out and resid differ in shape")
+    _planes_ok(p["w1"], 3, "mlp_fwd_rows")
     n, h, w, c = resid.shape
     _rows_ok(row_scale, n, resid.device)
     check(_lib.load().agp_cnx_mlp_fwd_rows(ptr(ws), ws.numel(), n * h * w, c, ptr(p["w1"][0]), ptr(p["w1"][1]), ptr(p["b1"]),
@@ -274,11 +326,16 @@ def stem_u8_bwd(tiles, mean, std, gout, p, grads, bws):
           "agp_cnx_stem_u8_bwd")
 
 
-def downsample_fwd(x, p):
-    """LayerNorm + 2x2 / stride-2 conv of the stream x -> a new stream [n, h//2, w//2, 2C]."""
+def downsample_fwd(x, p, prec=3):
+    """LayerNorm + 2x2 / stride-2 conv of the stream x -> a new stream [n, h//2, w//2, 2C].  prec: that of prep_down."""
     _stream_ok(x, p["c"])
+    _planes_ok(p["w"], prec, "downsample_fwd")
     n, h, w, c = x.shape
     out = torch.empty((n, h // 2, w // 2, 2 * c), dtype=torch.float32, device=x.device)
+    if prec == 4:
+        check(_lib.load().agp_cnx_downsample_f16_fwd(ptr(x), n, h, w, c, ptr(p["g"]), ptr(p["b"]), LN_EPS, ptr(p["w"][0]),
+                                                     ptr(p["bias"]), ptr(out), _lib.stream()), "agp_cnx_downsample_f16_fwd")
+        return out
     check(_lib.load().agp_cnx_downsample_fwd(ptr(x), n, h, w, c, ptr(p["g"]), ptr(p["b"]), LN_EPS, ptr(p["w"][0]), ptr(p["w"][1]),
                                              ptr(p["bias"]), ptr(out), _lib.stream()), "agp_cnx_downsample_fwd")
     return out
@@ -330,8 +387,9 @@ class ConvNeXt(nn.Module):
                 nn.init.zeros_(m.bias)
         # registered and unused, as in the reference (never part of a forward: frozen like ResNet.fc)
         self.classifier.requires_grad_(False)
-        self._prep, self._prep_key = None, None
+        self._prep, self._prep_key = {}, None          # {precision: kernel-side weights} of the parameter versions in _prep_key
         self._prep_bwd, self._prep_bwd_key = None, None
+        self.precision = 3
         self._train_enabled = False
         self._u8_enabled = False
         # ToTensor + Normalize of uint8 inputs (tiles, frames); the owning model sets them from its Options (set_image_norm)
@@ -344,6 +402,17 @@ class ConvNeXt(nn.Module):
         """Opt in to (or out of) the training path: .train() and gradients into the trunk.  Off by default; while off both are
         refused and nothing changes for inference."""
         self._train_enabled = bool(flag)
+        return self
+
+    # ------------------------------------------------------------------ precision of the inference path
+    def set_precision(self, p):
+        """MFMA operand precision of `forward_maps` (Options.convnext_precision): 3 (default) = bf16 (hi, lo) pairs and three
+        products; 4 = the operands rounded to fp16 and ONE product (module docstring).  `forward_maps_train` and the backward stay
+        in 3 whatever is set here.  A captured graph holds the kernels and weight planes of the precision it was captured with:
+        after a change run one eager forward (it prepares the planes), then capture again, as after a weight reload."""
+        if isinstance(p, bool) or p not in (3, 4):
+            raise ValueError(f"ConvNeXt.set_precision({p!r}): 3 (three bf16 products) | 4 (one fp16 product, inference only)")
+        self.precision = int(p)
         return self
 
     # ------------------------------------------------------------------ uint8 inputs
@@ -397,18 +466,21 @@ class ConvNeXt(nn.Module):
     def _version_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def _prepared(self):
-        """Kernel-side weights, rebuilt when a parameter changes (ResNet._version_key's rule)."""
+    def _prepared(self, prec=3):
+        """Kernel-side weights for precision `prec`, cached per (parameter version, precision): rebuilt when a parameter changes
+        (ResNet._version_key's rule).  The training forward and the backward always ask for 3."""
         key = self._version_key()
         if key != self._prep_key:
+            self._prep, self._prep_key = {}, key
+        if prec not in self._prep:
             with torch.no_grad():
                 prep = {"stem": prep_stem(*self.features[0])}
                 for s in range(3):
-                    prep[("blocks", s)] = [prep_block(blk) for blk in self.features[1 + 2 * s]]
+                    prep[("blocks", s)] = [prep_block(blk, prec) for blk in self.features[1 + 2 * s]]
                     if s < 2:
-                        prep[("down", s)] = prep_down(*self.features[2 + 2 * s])
-            self._prep, self._prep_key = prep, key
-        return self._prep
+                        prep[("down", s)] = prep_down(*self.features[2 + 2 * s], prec)
+            self._prep[prec] = prep
+        return self._prep[prec]
 
     def _prepared_bwd(self):
         key = self._version_key()
@@ -454,15 +526,16 @@ class ConvNeXt(nn.Module):
         x = self._input(x, "forward_maps")
         n, H, W = self._geometry(x)
         sizes = self.map_sizes(H, W)
-        prep = self._prepared()
+        prec = self.precision
+        prep = self._prepared(prec)
         ws = self._ws.tensor("cnx_ws", (max(workspace_bytes(n, h, w, DIMS[s]) for s, (h, w) in enumerate(sizes)),), torch.uint8,
                              x.device)
         maps, cur = [], None
         for s in range(3):
-            cur = self._stem(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)])
+            cur = self._stem(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)], prec)
             for p in prep[("blocks", s)]:
-                dwconv_ln_fwd(cur, p, ws)
-                mlp_fwd(ws, p, cur, cur)
+                dwconv_ln_fwd(cur, p, ws, prec)
+                mlp_fwd(ws, p, cur, cur, prec)
             maps.append(cur.permute(0, 3, 1, 2))
         return maps
 

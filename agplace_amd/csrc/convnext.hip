@@ -5,6 +5,10 @@
 // The residual stream is a plain fp32 [n][h][w][C] tensor (C = 96, 192 or 384).  Arithmetic follows the project's mode 3
 // (AGP_PREC_BF16X3): every MFMA operand is a bf16 (hi, lo) pair and a product is hi*hi + hi*lo + lo*hi accumulated in fp32;
 // LayerNorm statistics, GELU and the residual add are fp32; nothing is stored in fp16.
+// The opt-in precision 4 of the inference path (template parameter PREC = 4 of the three matrix kernels, agp_cnx_*_f16_fwd) rounds
+// the MFMA operands -- normalised operand, W1, GELU output, W2, downsample operand and weight -- to fp16 (cnx_h2: nearest even,
+// saturating, NaN kept) and spends ONE mfma_f32_32x32x16_f16 per product; everything else, the fp32 stream included, is shared, and
+// every difference sits behind `if constexpr`, so the PREC = 3 instantiations are the code they were.
 //
 // The matrix kernels compute TRANSPOSED products with mfma_f32_32x32x16_bf16: the weights are the A operand (output feature on
 // the row), 32 pixels are the B operand (pixel on the column = on the lane).  A 32x32 result then has its pixel on the lane and
@@ -100,7 +104,8 @@ __global__ void cnx_normalize_u8_kernel(const CnxLoadU8 ld, int W, long long tot
 // pixel index, so it cannot reach into a neighbouring image) and its 49 x 32 weights go to LDS; thread (cl = t & 31,
 // col = t >> 5) computes the 4 outputs of its column for channel cl of the chunk.  Its C / 32 x 4 conv results stay in
 // registers; the 32 lanes of a half wave then hold one pixel's C channels for the LayerNorm.  wt: [49][C].
-template <int C>
+// PREC: 3 = the operand as bf16 (hi, lo) planes; 4 = as ONE fp16 plane in o_hi (cnx_h1: nearest even, saturating), o_lo unused.
+template <int C, int PREC = 3>
 __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restrict__ x, int h, int w, int tiles_y, int tiles_x,
                                                             const float* __restrict__ wt, const float* __restrict__ bias,
                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
@@ -166,10 +171,14 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
                 const int c = k * 32 + cl;
-                bf16_t hi, lo;
-                split_bf16(fmaf(conv[i][k] * rstd, g[c], b[c]), hi, lo);
-                o_hi[p * C + c] = hi;
-                o_lo[p * C + c] = lo;
+                if constexpr (PREC == 4) {
+                    o_hi[p * C + c] = cnx_h1(fmaf(conv[i][k] * rstd, g[c], b[c]));
+                } else {
+                    bf16_t hi, lo;
+                    split_bf16(fmaf(conv[i][k] * rstd, g[c], b[c]), hi, lo);
+                    o_hi[p * C + c] = hi;
+                    o_lo[p * C + c] = lo;
+                }
             }
         }
     }
@@ -187,7 +196,9 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
 // arithmetic does not change.
 //   w1 planes: [4C / 32][C / 16][64 lanes][8]     lane (r, h) of block jb, step kk: W1[jb * 32 + r][kk * 16 + 8 h + e]
 //   w2 planes: [4C / 32][2][C / 32][64 lanes][8]  lane (r, h) of block jb, half t, tile ct: W2[ct * 32 + r][jb * 32 + acc_row(8 t + e, h)]
-template <int C, bool ROWS>
+// PREC = 4 (agp_cnx_mlp_f16_fwd): the operand, W1, the GELU output and W2 are fp16 and a product is ONE MFMA (mfma1h); one operand
+// plane in LDS, one plane per weight (the *_hi arguments; the *_lo ones are unused), the same layouts, loop order and epilogue.
+template <int C, bool ROWS, int PREC = 3>
 __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo, long long P,
                                                       const bf16x8* __restrict__ w1_hi, const bf16x8* __restrict__ w1_lo,
                                                       const float* __restrict__ b1, const bf16x8* __restrict__ w2_hi,
@@ -195,7 +206,7 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
                                                       const float* __restrict__ ls, const float* resid, float* out,
                                                       const float* __restrict__ row_scale, long long ppi) {
     constexpr int LD = C + CNX_KPAD, KK = C / 16, CT = C / 32, JB = C / 8, VR = C / 8;
-    constexpr int XBYTES = 2 * CNX_TP * LD * 2, RBYTES = 4 * 32 * 36 * 4;
+    constexpr int XBYTES = (PREC == 4 ? 1 : 2) * CNX_TP * LD * 2, RBYTES = 4 * 32 * 36 * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem[XBYTES > RBYTES ? XBYTES : RBYTES];
     bf16_t* const sx_hi = (bf16_t*)smem;
     bf16_t* const sx_lo = sx_hi + CNX_TP * LD;
@@ -206,10 +217,10 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
         u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
         if (p0 + row < P) {
             vh = *(const u32x4*)(x_hi + (size_t)(p0 + row) * C + v * 8);
-            vl = *(const u32x4*)(x_lo + (size_t)(p0 + row) * C + v * 8);
+            if constexpr (PREC != 4) vl = *(const u32x4*)(x_lo + (size_t)(p0 + row) * C + v * 8);
         }
         *(u32x4*)(sx_hi + row * LD + v * 8) = vh;
-        *(u32x4*)(sx_lo + row * LD + v * 8) = vl;
+        if constexpr (PREC != 4) *(u32x4*)(sx_lo + row * LD + v * 8) = vl;
     }
     __syncthreads();
     f32x16 y[CT];
@@ -230,23 +241,38 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
         }
         const bf16x8* const a_hi = w1_hi + (size_t)jb * KK * 64 + lane;
         const bf16x8* const a_lo = w1_lo + (size_t)jb * KK * 64 + lane;
+        if constexpr (PREC == 4) {
 #pragma unroll 4
-        for (int kk = 0; kk < KK; ++kk)
-            mfma3(hacc, a_hi[kk * 64], a_lo[kk * 64], *(const bf16x8*)(bx_hi + kk * 16), *(const bf16x8*)(bx_lo + kk * 16));
-        bf16x8 g_hi[2], g_lo[2];
+            for (int kk = 0; kk < KK; ++kk) mfma1h(hacc, a_hi[kk * 64], *(const bf16x8*)(bx_hi + kk * 16));
+            u32x4 gp[2];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            bf16_t hi, lo;
-            split_bf16(gelu_exact(hacc[i]), hi, lo);
-            g_hi[i >> 3][i & 7] = (short)hi;
-            g_lo[i >> 3][i & 7] = (short)lo;
-        }
+            for (int i = 0; i < 16; i += 2) gp[i >> 3][(i & 7) >> 1] = cnx_h2(gelu_exact(hacc[i]), gelu_exact(hacc[i + 1]));
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const bf16x8* const c_hi = w2_hi + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
-            const bf16x8* const c_lo = w2_lo + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
+            for (int tt = 0; tt < 2; ++tt) {
+                const bf16x8* const c_hi = w2_hi + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
+                const bf16x8 gv = __builtin_bit_cast(bf16x8, gp[tt]);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) mfma3(y[ct], c_hi[ct * 64], c_lo[ct * 64], g_hi[tt], g_lo[tt]);
+                for (int ct = 0; ct < CT; ++ct) mfma1h(y[ct], c_hi[ct * 64], gv);
+            }
+        } else {
+#pragma unroll 4
+            for (int kk = 0; kk < KK; ++kk)
+                mfma3(hacc, a_hi[kk * 64], a_lo[kk * 64], *(const bf16x8*)(bx_hi + kk * 16), *(const bf16x8*)(bx_lo + kk * 16));
+            bf16x8 g_hi[2], g_lo[2];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                bf16_t hi, lo;
+                split_bf16(gelu_exact(hacc[i]), hi, lo);
+                g_hi[i >> 3][i & 7] = (short)hi;
+                g_lo[i >> 3][i & 7] = (short)lo;
+            }
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+                const bf16x8* const c_hi = w2_hi + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
+                const bf16x8* const c_lo = w2_lo + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) mfma3(y[ct], c_hi[ct * 64], c_lo[ct * 64], g_hi[tt], g_lo[tt]);
+            }
         }
     }
     float* const red = (float*)smem;       // [4 waves][32 pixels][36]: 32 channels + 4 floats of padding
@@ -284,7 +310,8 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
 // the MLP kernel's MFMA core.  K is walked in chunks of 384 = 384 / C whole input pixels: eight lanes normalise one input
 // pixel (fp32 statistics, two passes in registers) and write its operand planes to LDS, then wave v accumulates the output
 // feature blocks v, v + 4, ... over the chunk.  w planes: [2C / 32][4C / 16][64 lanes][8] as w1 above.
-template <int C>
+// PREC = 4 (agp_cnx_downsample_f16_fwd): the normalised operand and the weight are fp16, one plane each (w_hi; w_lo unused), ONE MFMA.
+template <int C, int PREC = 3>
 __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __restrict__ x, int h, int w, int ho, int wo, long long P,
                                                              const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                              const bf16x8* __restrict__ w_hi, const bf16x8* __restrict__ w_lo,
@@ -292,7 +319,7 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
     constexpr int KC = 384, LD = KC + CNX_KPAD, IPP = KC / C, NCH = 4 * C / KC, NT = 2 * C / 32, NTW = (NT + 3) / 4, KKT = 4 * C / 16;
     constexpr int NV = C / 32;             // float4 per lane of a pixel's eight
     __shared__ __attribute__((aligned(16))) bf16_t sx_hi[CNX_TP * LD];
-    __shared__ __attribute__((aligned(16))) bf16_t sx_lo[CNX_TP * LD];
+    __shared__ __attribute__((aligned(16))) bf16_t sx_lo[PREC == 4 ? 8 : CNX_TP * LD];     // (precision 4: one plane, unused)
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, r = lane & 31, hh = lane >> 5;
     const long long p0 = (long long)blockIdx.x * CNX_TP;
     const int lpx = t >> 3, sl = t & 7;
@@ -345,11 +372,18 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
             for (int m = 0; m < NV; ++m) {
                 const int c = (sl + 8 * m) * 4;
                 const f32x4 gv = *(const f32x4*)(g + c), bv = *(const f32x4*)(b + c);
-                bf16_t hi[4], lo[4];
+                if constexpr (PREC == 4) {
+                    float xn[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) split_bf16(lp < P ? fmaf(v[m][i] * rstd, gv[i], bv[i]) : 0.f, hi[i], lo[i]);
-                *(u32x2*)(sx_hi + lpx * LD + sub * C + c) = u32x2{pack2(hi[0], hi[1]), pack2(hi[2], hi[3])};
-                *(u32x2*)(sx_lo + lpx * LD + sub * C + c) = u32x2{pack2(lo[0], lo[1]), pack2(lo[2], lo[3])};
+                    for (int i = 0; i < 4; ++i) xn[i] = lp < P ? fmaf(v[m][i] * rstd, gv[i], bv[i]) : 0.f;
+                    *(u32x2*)(sx_hi + lpx * LD + sub * C + c) = u32x2{cnx_h2(xn[0], xn[1]), cnx_h2(xn[2], xn[3])};
+                } else {
+                    bf16_t hi[4], lo[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) split_bf16(lp < P ? fmaf(v[m][i] * rstd, gv[i], bv[i]) : 0.f, hi[i], lo[i]);
+                    *(u32x2*)(sx_hi + lpx * LD + sub * C + c) = u32x2{pack2(hi[0], hi[1]), pack2(hi[2], hi[3])};
+                    *(u32x2*)(sx_lo + lpx * LD + sub * C + c) = u32x2{pack2(lo[0], lo[1]), pack2(lo[2], lo[3])};
+                }
             }
         }
         __syncthreads();
@@ -360,8 +394,10 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
                 const bf16x8* const a_hi = w_hi + ((size_t)nt * KKT + ch * (KC / 16)) * 64 + lane;
                 const bf16x8* const a_lo = w_lo + ((size_t)nt * KKT + ch * (KC / 16)) * 64 + lane;
 #pragma unroll 4
-                for (int kk = 0; kk < KC / 16; ++kk)
-                    mfma3(y[n], a_hi[kk * 64], a_lo[kk * 64], *(const bf16x8*)(bx_hi + kk * 16), *(const bf16x8*)(bx_lo + kk * 16));
+                for (int kk = 0; kk < KC / 16; ++kk) {
+                    if constexpr (PREC == 4) mfma1h(y[n], a_hi[kk * 64], *(const bf16x8*)(bx_hi + kk * 16));
+                    else mfma3(y[n], a_hi[kk * 64], a_lo[kk * 64], *(const bf16x8*)(bx_hi + kk * 16), *(const bf16x8*)(bx_lo + kk * 16));
+                }
             }
         }
     }
@@ -493,6 +529,58 @@ int agp_cnx_downsample_fwd(const float* x, int n, int h, int w, int C, const flo
     if (C == 96) { AGP_LAUNCH(cnx_downsample_kernel<96>, grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, b, bias, out); }
     else if (C == 192) { AGP_LAUNCH(cnx_downsample_kernel<192>, grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, b, bias, out); }
     else { AGP_LAUNCH(cnx_downsample_kernel<384>, grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, b, bias, out); }
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+// ---- precision 4 (Options.convnext_precision = 4): the PREC = 4 instantiations.  One fp16 operand plane [P_pad][C] at the start of
+// the workspace, one fp16 plane per weight; the kernels' unused second-plane arguments are null.
+int agp_cnx_dwconv_ln_f16_fwd(const float* x, int n, int h, int w, int C, const float* wt, const float* bias, const float* ln_w,
+                              const float* ln_b, float eps, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!x || !wt || !bias || !ln_w || !ln_b || !workspace || !cnx_map_ok(n, h, w) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    if (workspace_bytes < cnx_pad((long long)n * h * w) * C * 2 || ((uintptr_t)workspace & 15)) return AGP_E_BADARG;
+    bf16_t* const xp = (bf16_t*)workspace;
+    bf16_t* const none = nullptr;
+    const int ty = (h + 3) / 4, tx = (w + 7) / 8;
+    const dim3 grid((unsigned)((long long)n * ty * tx));
+    hipStream_t s = (hipStream_t)stream;
+    if (C == 96) { AGP_LAUNCH((cnx_dwconv_ln_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
+    else if (C == 192) { AGP_LAUNCH((cnx_dwconv_ln_kernel<192, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
+    else { AGP_LAUNCH((cnx_dwconv_ln_kernel<384, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_mlp_f16_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1, const float* b1,
+                        const void* w2, const float* b2, const float* layer_scale, const float* resid, float* out, void* stream) {
+    if (!workspace || !w1 || !b1 || !w2 || !b2 || !layer_scale || !resid || !out) return AGP_E_BADARG;
+    if (P <= 0 || P >= (1ll << 31) / 32 || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    if (workspace_bytes < cnx_pad(P) * C * 2 || ((uintptr_t)workspace & 15)) return AGP_E_BADARG;
+    const bf16_t* const xp = (const bf16_t*)workspace;
+    const bf16_t* const nox = nullptr;
+    const bf16x8 *a = (const bf16x8*)w1, *c = (const bf16x8*)w2, *now = nullptr;
+    const float* const norows = nullptr;
+    const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
+    hipStream_t s = (hipStream_t)stream;
+#define CNX_MLP_H(CC) AGP_LAUNCH((cnx_mlp_kernel<CC, false, 4>), grid, dim3(256), 0, s, xp, nox, (long long)P, a, now, b1, c, now, b2, layer_scale, resid, out, norows, 0ll)
+    if (C == 96) { CNX_MLP_H(96); } else if (C == 192) { CNX_MLP_H(192); } else { CNX_MLP_H(384); }
+#undef CNX_MLP_H
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_downsample_f16_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
+                               const void* wt, const float* bias, float* out, void* stream) {
+    if (!x || !ln_w || !ln_b || !wt || !bias || !out || !cnx_map_ok(n, h, w) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    const int ho = h / 2, wo = w / 2;
+    if (ho < 1 || wo < 1) return AGP_E_BADARG;
+    const long long P = (long long)n * ho * wo;
+    const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
+    hipStream_t s = (hipStream_t)stream;
+    const bf16x8 *a = (const bf16x8*)wt, *none = nullptr;
+    if (C == 96) { AGP_LAUNCH((cnx_downsample_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
+    else if (C == 192) { AGP_LAUNCH((cnx_downsample_kernel<192, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
+    else { AGP_LAUNCH((cnx_downsample_kernel<384, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }

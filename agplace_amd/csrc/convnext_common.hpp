@@ -1,4 +1,5 @@
-// Shared by convnext.hip (forward) and convnext_bwd.hip (backward): tile constants, wave reductions, the three-product MFMA.
+// Shared by convnext.hip (forward) and convnext_bwd.hip (backward): tile constants, wave reductions, the three-product MFMA, and the
+// one-product fp16 MFMA with its conversion (the forward's precision 4).
 #pragma once
 #include "common.hpp"
 
@@ -27,6 +28,20 @@ __device__ __forceinline__ void mfma3(f32x16& acc, const bf16x8& wh, const bf16x
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc, 0, 0, 0);
 }
+
+// ---- precision 4 of the inference kernels (convnext.hip, PREC = 4): fp16 operands, ONE product per MFMA.  The fragments travel
+// in the bf16 fragment type (8 x 16 bits) so that both precisions share loads, stores and signatures.
+__device__ __forceinline__ void mfma1h(f32x16& acc, const bf16x8& w, const bf16x8& x) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), acc, 0, 0, 0);
+}
+// two fp32 -> one packed fp16 pair (a in the low half): round to nearest even, saturating at +-65504, NaN kept (the clamp alone
+// would turn a NaN into -65504: v_med3_f32 returns the minimum of its operands when one is NaN)
+__device__ __forceinline__ uint32_t cnx_h2(float a, float b) {
+    const float ca = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f), cb = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
+    const f32x2v v = {a != a ? a : ca, b != b ? b : cb};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+}
+__device__ __forceinline__ bf16_t cnx_h1(float a) { return (bf16_t)(cnx_h2(a, 0.f) & 0xffffu); }
 
 // feature row (inside a 32-row block) of accumulator register `reg` of a lane in half `h`
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }

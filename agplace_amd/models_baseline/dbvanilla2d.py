@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import autograd_ops, ops, range_guard, train_fns
+from ..convnext import precision_from_options
 from ..network.image_fe import ImageFE
 from ..network.image_pooling import GeM
 from ..network_mm.image_pooling import gem_op
@@ -56,6 +57,7 @@ class DBVanilla2D(nn.Module):
                         e.fe.enable_training()
                     if opt.convnext_u8:     # its opt-in uint8 routes: tiles and frames, normalised by the stem as it reads
                         e.fe.enable_u8_inputs().set_image_norm(opt.image_mean, opt.image_std)
+                    e.fe.set_precision(precision_from_options(opt))     # 3, or the opt-in one-product fp16 inference mode (4)
             self.dbimage_fes = nn.ModuleList(fes)
             self.dbimage_pools = nn.ModuleList([GeM() for _ in maptype])
             self.dbimage_mlps = nn.ModuleList([MLP(e.last_dim, dim) for e in fes])

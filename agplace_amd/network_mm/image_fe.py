@@ -9,7 +9,8 @@ stages as ops.SplitMap without the fp32 export (the fused MM / DBVanilla2D paths
 'convnext_tiny' (agplace_amd/convnext.py) is inference only unless `fe.enable_training()` opted in (then .train() and gradients
 into the trunk run through ConvNeXt.forward_maps_train); it takes exactly three `layers` entries, which are BLOCK COUNTS
 there: features[6:] are dropped and stage i keeps its first layers[i] blocks, last_dim = 384, the list holds the outputs of
-features[1], [3], [5].  It runs in the mode-3 arithmetic only (prec None or 3) and has no ops.SplitMap form: `forward_maps`
+features[1], [3], [5].  It runs in the mode-3 arithmetic (prec None or 3) unless Options.convnext_precision = 4 of `opt` (or
+`fe.set_precision(4)`) selected the one-product fp16 inference mode, and has no ops.SplitMap form: `forward_maps`
 with pool requests raises NotImplementedError.  The SqueezeNet branch of the reference is not built.
 """
 import torch.nn as nn
@@ -41,7 +42,8 @@ class ImageFE(nn.Module):
                                           "features[1], [3], [5] under last_dim = 768, which breaks its own head (the last map has "
                                           "384 channels); use three entries")
             self.last_dim = 384
-            self.fe = ConvNeXt(layers)
+            # Options.convnext_precision of `opt` (None: the process-wide options now); MM / DBVanilla2D set their own afterwards
+            self.fe = ConvNeXt(layers).set_precision((opt or get_options()).convnext_precision)
             return
         self.last_dim = self._LAST_DIM[fe_type][len(layers)]
         self.fe = ResNet(fe_type, nstages=len(layers))
@@ -69,6 +71,12 @@ class ImageFE(nn.Module):
         if self.fe_type == "convnext_tiny":
             if prec not in (None, 3):
                 raise ValueError(f"ImageFE('convnext_tiny'): prec must be None or 3 (three bf16 products, fp32 maps), got {prec}")
+            if self.fe.precision == 4:
+                if prec == 3:
+                    raise ValueError("ImageFE('convnext_tiny'): prec=3 on a trunk set to precision 4; call fe.set_precision(3)")
+                if (self.opt or get_options()).fp16_range_guard:
+                    raise NotImplementedError("ImageFE('convnext_tiny'): precision 4 together with fp16_range_guard=True is not "
+                                              "built (the guard's word is not wired into the fp16 ConvNeXt kernels)")
             x_list = self.fe.forward_maps(x)
             return x_list[-1], x_list
         prec = self.export_precision() if prec is None else prec

@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from .. import autograd_ops, ops, range_guard, sparse, train_fns
+from ..convnext import precision_from_options
 from ..options import get_options
 from .ffns import _PreparedLinear
 from .fuse_block_toshallow import FuseBlockToShallow
@@ -61,6 +62,7 @@ class MM(nn.Module):
                 self.image_fe.fe.enable_training()
             if opt.convnext_u8:             # its opt-in uint8 routes: tiles and frames, normalised by the stem as it reads
                 self.image_fe.fe.enable_u8_inputs().set_image_norm(opt.image_mean, opt.image_std)
+            self.image_fe.fe.set_precision(precision_from_options(opt))      # 3, or the opt-in one-product fp16 inference mode (4)
         self.image_pool = GeM()
         planes = [int(x) for x in opt.mm_voxfe_planes.split('_')]
         layers = [int(x) for x in opt.mm_voxfe_layers.split('_')]

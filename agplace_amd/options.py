@@ -100,7 +100,8 @@ class Options:
     # saturated map elements and warns (resnet.SATURATION_CHECK).  Such a checkpoint stays in modes 2 / 4 with calibrated map
     # exponents (agplace_amd/map_exponents.py: the image path's maps stored times 2^-e, folded into host-prepared constants --
     # same kernels, same speed); mode 3 remains the remedy for what they do not cover (the sparse-voxel branch's maps).  Training
-    # (.train()) always runs on split-bf16 maps (3); kNN has its own setting.
+    # (.train()) always runs on split-bf16 maps (3); kNN has its own setting.  The ConvNeXt-tiny trunk (dbimage_fe / mm_imgfe =
+    # "convnext_tiny") does not read this field: it follows convnext_precision below.
     mfma_precision: int = 4
     # Opt-in fp16 range guard (agplace_amd/range_guard.py): inference forwards in modes 2 / 4 bind a sticky device word that
     # every kernel storing an inference fp16 map (the table in DESIGN.md section 2) sets when it had to clamp a value to +-65504
@@ -132,6 +133,15 @@ class Options:
     # ops.normalize_cameras_u8's image.  False (default): those inputs are refused by name, as before.  A reference namespace does
     # not carry this field (from_reference_opt leaves it False): from_reference_opt(args).copy(convnext_u8=True).
     convnext_u8: bool = False
+    # MFMA operand precision of the ConvNeXt-tiny trunk's INFERENCE path (ConvNeXt.forward_maps; ConvNeXt.set_precision is the
+    # op-level form): 3 (default) = bf16 (hi, lo) pairs, three products, as before, launch for launch and bit for bit.  4 = opt-in:
+    # the block's LayerNorm output, W1, the GELU output, W2, the downsample's LayerNorm output and its weight are rounded to fp16
+    # (nearest even, saturating at +-65504) and every product is ONE fp16 MFMA with fp32 accumulation; the stream, the stem, the
+    # depthwise conv, LayerNorm statistics, biases, GELU, layer_scale and the residual add stay fp32 (maps
+    # within 1e-3 of fp64).  The training forward and the backward stay in mode 3 whatever this says, the rule mfma_precision has
+    # for the ResNets.  4 together with fp16_range_guard is refused (NotImplementedError): the guard's word is not wired into these
+    # kernels.  Not a reference option: from_reference_opt leaves it 3.
+    convnext_precision: int = 3
     # Opt-in one-launch routes of FCODE(384) (the Neural-ODE blocks of MM on the ConvNeXt-tiny trunk): with a gradient wanted a
     # fixed-grid solve records its trajectory in the one-launch kernel and differentiates through agp_fcode_wide_bwd instead of
     # the any-width sequence of launches, and odeint_method = "dopri5" runs on the adaptive kernels at 384 columns instead of
@@ -203,6 +213,9 @@ class Options:
             raise ValueError(f"convnext_train {self.convnext_train!r}: True | False")
         if not isinstance(self.convnext_u8, bool):
             raise ValueError(f"convnext_u8 {self.convnext_u8!r}: True | False")
+        v = self.convnext_precision
+        if isinstance(v, bool) or not isinstance(v, int) or v not in (3, 4):
+            raise ValueError(f"convnext_precision {v!r}: 3 (three bf16 products) | 4 (one fp16 product, inference only)")
         if not isinstance(self.fcode_wide, bool):
             raise ValueError(f"fcode_wide {self.fcode_wide!r}: True | False")
         if not isinstance(self.odeint_adaptive_family, bool):
@@ -223,7 +236,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "fcode_wide", "odeint_adaptive_family", "voxel_capacity"):      # (not reference options: stay False / None)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity"):      # (not reference options: stay at their defaults)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

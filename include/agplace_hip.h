@@ -1194,6 +1194,18 @@ int agp_cnx_mlp_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, i
  * order. */
 int agp_cnx_downsample_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
                            const void* w_hi, const void* w_lo, const float* bias, float* out, void* stream);
+/* The opt-in precision 4 of the three matrix kernels above (Options.convnext_precision = 4, inference only): same stream, same
+ * fp32 depthwise conv, LayerNorm statistics, biases, GELU, layer_scale and residual add, but every MFMA operand is ONE fp16 value
+ * (round to nearest even, saturating at +-65504, NaN kept) and a product is ONE MFMA with fp32 accumulation.  The workspace holds
+ * the normalised operand as ONE fp16 plane [P_pad][C], the first half of agp_cnx_workspace_bytes (which is unchanged: an upper
+ * bound); w1 / w2 / wt: the fp16 rounding of the same fragment-ordered weights, one plane each.  Arguments are validated as by
+ * the entries above.  Weights below 2^-14 in magnitude are fp16 subnormals: there is no per-row weight scale. */
+int agp_cnx_dwconv_ln_f16_fwd(const float* x, int n, int h, int w, int C, const float* wt, const float* bias, const float* ln_w,
+                              const float* ln_b, float eps, void* workspace, int64_t workspace_bytes, void* stream);
+int agp_cnx_mlp_f16_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1, const float* b1,
+                        const void* w2, const float* b2, const float* layer_scale, const float* resid, float* out, void* stream);
+int agp_cnx_downsample_f16_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
+                               const void* wt, const float* bias, float* out, void* stream);
 
 /* ---- ConvNeXt-tiny trunk, training (csrc/convnext.hip: the scaled forward; csrc/convnext_bwd.hip: the backward).  Same
  * arithmetic; no atomics: every sum over pixels or workgroups has a fixed order, two runs give the same bits.  Nothing allocates

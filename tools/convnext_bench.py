@@ -4,6 +4,9 @@ the same batch for context; then one training forward + backward of '2_2_2' (the
 no stochastic depth) and each backward entry alone.
 
 python tools/convnext_bench.py [--batch 64] [--size 256] [--reps 10] [--windows 5] [--json out.json] [--train-only]
+                               [--precision {3,4}] [--infer-only]
+--precision 4 times the inference legs in the opt-in one-product fp16 mode (Options.convnext_precision = 4); the training leg runs
+in mode 3 whatever the precision and is skipped then.
 Events on the launch stream around `reps` back-to-back calls, the median of `windows` such windows after a warm-up.  GMAC are
 algorithmic (one multiply-accumulate per weight use, whatever the three bf16 products cost); the fraction of peak is
 2 * MAC / time over the 2.5 PFLOP/s dense bf16 peak.  Weights are seeded random values (zeros would flatter the clock)."""
@@ -126,7 +129,11 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--train-only", action="store_true", help="skip the inference legs")
+    ap.add_argument("--infer-only", action="store_true", help="skip the training leg")
+    ap.add_argument("--precision", type=int, choices=(3, 4), default=3, help="ConvNeXt inference precision (Options.convnext_precision)")
     a = ap.parse_args()
+    prec = a.precision
+    tag = "" if prec == 3 else ", prec 4"
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
     n, hw = a.batch, a.size
@@ -144,7 +151,7 @@ def main():
         fe = randomize(ImageFE("convnext_tiny", "3_3_9"), 0).to(dev).eval()
         sizes = cnx.ConvNeXt.map_sizes(hw, hw)
         _, per = convnext_macs([3, 3, 9], hw, hw)
-        prep = fe.fe._prepared()
+        prep = fe.fe._prepared(prec)
         report("stem", n * per["stem"], timed(lambda: cnx.stem_fwd(x, prep["stem"]), a.reps, a.windows))
         for s, (h, w) in enumerate(sizes):
             c = cnx.DIMS[s]
@@ -152,26 +159,28 @@ def main():
             ws = torch.empty(cnx.workspace_bytes(n, h, w, c), dtype=torch.uint8, device=dev)
             p = prep[("blocks", s)][0]
             out = torch.empty_like(cur)
-            report(f"dwconv+ln C={c} {h}x{w}", n * per[("dwconv", c)], timed(lambda: cnx.dwconv_ln_fwd(cur, p, ws), a.reps, a.windows))
-            report(f"fused mlp C={c} {h}x{w}", n * per[("mlp", c)], timed(lambda: cnx.mlp_fwd(ws, p, cur, out), a.reps, a.windows))
+            report(f"dwconv+ln C={c} {h}x{w}", n * per[("dwconv", c)], timed(lambda: cnx.dwconv_ln_fwd(cur, p, ws, prec), a.reps, a.windows))
+            report(f"fused mlp C={c} {h}x{w}", n * per[("mlp", c)], timed(lambda: cnx.mlp_fwd(ws, p, cur, out, prec), a.reps, a.windows))
             if s < 2:
                 d = prep[("down", s)]
-                report(f"ln+downsample C={c} {h}x{w}", n * per[("down", c)], timed(lambda: cnx.downsample_fwd(cur, d), a.reps, a.windows))
+                report(f"ln+downsample C={c} {h}x{w}", n * per[("down", c)], timed(lambda: cnx.downsample_fwd(cur, d, prec), a.reps, a.windows))
             del cur, ws, out
         # ---- whole trunks
         for layers in ("2_2_2", "3_3_9"):
             fe = randomize(ImageFE("convnext_tiny", layers), 0).to(dev).eval()
+            fe.fe.set_precision(prec)
             macs, _ = convnext_macs([int(v) for v in layers.split("_")], hw, hw)
-            report(f"convnext_tiny {layers} trunk", n * macs, timed(lambda: fe(x), max(2, a.reps // 2), a.windows))
+            report(f"convnext_tiny {layers} trunk{tag}", n * macs, timed(lambda: fe(x), max(2, a.reps // 2), a.windows))
             del fe
         r18 = ImageFE("resnet18", "2_2_2").to(dev).eval()
         report("resnet18 2_2_2 trunk, mode 3", n * bench_inputs.resnet_gmacs("resnet18", 3, hw, hw),
                timed(lambda: r18(x, prec=3), max(2, a.reps // 2), a.windows))
-    train_leg(a, dev, x, report, rows)
+    if not a.infer_only and (prec == 3 or a.train_only):
+        train_leg(a, dev, x, report, rows)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
-            json.dump({"batch": n, "size": hw, "reps": a.reps, "windows": a.windows, "rows": rows}, f, indent=1)
+            json.dump({"batch": n, "size": hw, "reps": a.reps, "windows": a.windows, **({} if prec == 3 else {"precision": prec}), "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":
