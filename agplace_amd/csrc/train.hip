@@ -249,8 +249,15 @@ __device__ __forceinline__ u32x4 ld_once(const bf16_t* p) { return __builtin_non
 // out = relu?(a*scale[c] + shift[c] + r)
 // o_h16 (optional): the same values once more as ONE fp16 plane -- the operand plane of the one-pass weight gradient
 // (wgrad_tr.hip: wgrad_f16_kernel), which the conv that consumes this map as its input reads instead of the bf16 pair.
+// rf (here and in affine_maxpool_kernel): the fp16 range guard's word in the guarded instantiation (common.hpp rg_word), absent
+// otherwise.  Tracked: exactly the values this kernel converts to fp16 -- the o_h16 plane, and the output itself when it is ONE
+// fp16 plane (o_lo == NULL); a bf16 pair does not clamp.  The values are tracked AFTER the ReLU: a negative one was not clamped.
+template <class... RF>
 __global__ void affine_kernel(MapGeo geo, const bf16_t* a_hi, const bf16_t* a_lo, const float* scale, const float* shift,
-                              const bf16_t* r_hi, const bf16_t* r_lo, int relu, bf16_t* o_hi, bf16_t* o_lo, bf16_t* o_h16) {
+                              const bf16_t* r_hi, const bf16_t* r_lo, int relu, bf16_t* o_hi, bf16_t* o_lo, bf16_t* o_h16,
+                              RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
+    const bool f16 = !o_lo || o_h16;               // an fp16 plane is written (the map, or the operand plane)
     // The channel group of a thread is the same in every iteration when the grid stride is a multiple of the groups
     // (256 threads, groups a power of two <= 32): its 16 coefficients are loaded once, not per element.
     const int groups0 = geo.c / 8;
@@ -308,10 +315,12 @@ __global__ void affine_kernel(MapGeo geo, const bf16_t* a_hi, const bf16_t* a_lo
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
+                rg.sym8_if(f16, v);
                 store8(o_hi, o_lo, off[u], v);
                 if (o_h16) *(u32x4*)(o_h16 + off[u]) = pack8_h(v);
             }
         }
+        rg.flush(rg_word(rf...));
         return;
     }
     AGP_FOR_MAP(geo) {
@@ -335,9 +344,11 @@ __global__ void affine_kernel(MapGeo geo, const bf16_t* a_hi, const bf16_t* a_lo
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
         }
+        rg.sym8_if(f16, v);
         store8(o_hi, o_lo, off, v);
         if (o_h16) *(u32x4*)(o_h16 + off) = pack8_h(v);
     }
+    rg.flush(rg_word(rf...));
 }
 
 // Per-channel maximum of |value| over a kernel's elements, as fp32 bit patterns (order-preserving for non-negative floats, so an
@@ -554,10 +565,14 @@ __global__ void maxpool_bwd_kernel(MapGeo gin, const uint8_t* __restrict__ idx, 
 // and the backward recomputes the ReLU mask from z with the SAME fp32 fma (agp_maxpool_bn_bwd with scale / shift).
 __device__ __forceinline__ float stem_act(float z, float sc, float sh) { return fmaxf(__builtin_fmaf(z, sc, sh), 0.f); }
 
+// (rf: see affine_kernel; the pooled values are post-ReLU, so only the upper bound can clamp)
+template <class... RF>
 __global__ void affine_maxpool_kernel(MapGeo gin, const bf16_t* __restrict__ z_hi, const bf16_t* __restrict__ z_lo,
                                       const float* __restrict__ scale, const float* __restrict__ shift, bf16_t* __restrict__ o_hi,
                                       bf16_t* __restrict__ o_lo, int ho, int wo, int opad, uint8_t* __restrict__ idx,
-                                      bf16_t* __restrict__ o_h16) {
+                                      bf16_t* __restrict__ o_h16, RF... rf) {
+    RangeTrack<sizeof...(RF) != 0> rg;
+    const bool f16 = !o_lo || o_h16;               // an fp16 plane is written (the map, or the operand plane)
     const int groups = gin.c / 8;
     const int64_t total = (int64_t)gin.n * ho * wo * groups;
     const int hip_ = gin.h + 2 * gin.pad, wip = gin.w + 2 * gin.pad;
@@ -588,12 +603,14 @@ __global__ void affine_maxpool_kernel(MapGeo gin, const bf16_t* __restrict__ z_h
                 }
             }
         const size_t ooff = (((size_t)im * hop + oy + opad) * wop + ox + opad) * gin.c + g * 8;
+        rg.sym8_if(f16, best);
         store8(o_hi, o_lo, ooff, best);
         if (o_h16) *(u32x4*)(o_h16 + ooff) = pack8_h(best);
         u32x2 pk = {(uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24),
                     (uint32_t)bi[4] | ((uint32_t)bi[5] << 8) | ((uint32_t)bi[6] << 16) | ((uint32_t)bi[7] << 24)};
         *(u32x2*)(idx + ((((size_t)im * ho + oy) * wo + ox) * gin.c + g * 8)) = pk;
     }
+    rg.flush(rg_word(rf...));
 }
 
 // ---- max-pool backward FUSED with the BatchNorm backward of the unit below it (the ResNet stem: conv -> BN -> ReLU -> max-pool):
@@ -936,8 +953,15 @@ extern "C" int agp_map_affine(const void* a_hi, const void* a_lo, const float* s
     if (!a_hi || !o_hi || c % 8 || n <= 0) return AGP_E_BADARG;
     const MapGeo g = geo_of(n, h, w, c, pad);
     if (!geo_fits(n, h, w, c)) return AGP_E_BADARG;
-    AGP_LAUNCH(affine_kernel, dim3(grid_for((int64_t)n * h * w * (c / 8))), dim3(256), 0, (hipStream_t)stream, g, CBF(a_hi),
-               CBF(a_lo), scale, shift, CBF(r_hi), CBF(r_lo), relu, BF(o_hi), BF(o_lo), BF(o_h16));
+    // the guarded form only when a word is bound AND this call stores fp16 at all (a bf16 pair without the operand plane does not)
+    uint32_t* const rf = (!o_lo || o_h16) ? agp_range_flag_get() : nullptr;
+    if (rf) {
+        AGP_LAUNCH((affine_kernel<uint32_t*>), dim3(grid_for((int64_t)n * h * w * (c / 8))), dim3(256), 0, (hipStream_t)stream, g,
+                   CBF(a_hi), CBF(a_lo), scale, shift, CBF(r_hi), CBF(r_lo), relu, BF(o_hi), BF(o_lo), BF(o_h16), rf);
+    } else {
+        AGP_LAUNCH((affine_kernel<>), dim3(grid_for((int64_t)n * h * w * (c / 8))), dim3(256), 0, (hipStream_t)stream, g, CBF(a_hi),
+                   CBF(a_lo), scale, shift, CBF(r_hi), CBF(r_lo), relu, BF(o_hi), BF(o_lo), BF(o_h16));
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }
@@ -1178,8 +1202,15 @@ extern "C" int agp_affine_maxpool3x3s2_fwd(const void* z_hi, const void* z_lo, c
     if (hout != (h + 2 - 3) / 2 + 1 || wout != (w + 2 - 3) / 2 + 1) return AGP_E_BADARG;
     const MapGeo g = geo_of(n, h, w, c, pad);
     if (!geo_fits(n, h, w, c)) return AGP_E_BADARG;
-    AGP_LAUNCH(affine_maxpool_kernel, dim3(grid_for((int64_t)n * hout * wout * (c / 8))), dim3(256), 0, (hipStream_t)stream, g,
-               CBF(z_hi), CBF(z_lo), scale, shift, BF(out_hi), BF(out_lo), hout, wout, pout, argmax, BF(out_h16));
+    uint32_t* const rf = (!out_lo || out_h16) ? agp_range_flag_get() : nullptr;       // (as agp_map_affine)
+    if (rf) {
+        AGP_LAUNCH((affine_maxpool_kernel<uint32_t*>), dim3(grid_for((int64_t)n * hout * wout * (c / 8))), dim3(256), 0,
+                   (hipStream_t)stream, g, CBF(z_hi), CBF(z_lo), scale, shift, BF(out_hi), BF(out_lo), hout, wout, pout, argmax,
+                   BF(out_h16), rf);
+    } else {
+        AGP_LAUNCH((affine_maxpool_kernel<>), dim3(grid_for((int64_t)n * hout * wout * (c / 8))), dim3(256), 0, (hipStream_t)stream, g,
+                   CBF(z_hi), CBF(z_lo), scale, shift, BF(out_hi), BF(out_lo), hout, wout, pout, argmax, BF(out_h16));
+    }
     AGP_CHECK_LAUNCH();
     return AGP_OK;
 }

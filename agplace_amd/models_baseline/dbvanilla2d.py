@@ -72,7 +72,8 @@ class DBVanilla2D(nn.Module):
         return self
 
     def poll_fp16_range(self):
-        """NON-BLOCKING fp16 range check of the guarded inference forwards so far (MM.poll_fp16_range)."""
+        """NON-BLOCKING fp16 range check of the guarded inference forwards -- and, with Options.train_range_guard, training
+        forwards -- so far (MM.poll_fp16_range)."""
         range_guard.poll(self)
 
     def fp16_range_ok(self):
@@ -105,7 +106,9 @@ class DBVanilla2D(nn.Module):
                 return self._forward_db(data_dict, train, trunk_maps, out_rows, defer_head)
         from .. import train_graph
         # the opt-in fast modes (train_graph.py) for THIS model's forward only, as in MM.forward_q
-        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1):
+        # (Options.train_range_guard: the guard word bound around the training FORWARD, published behind it, as in MM.forward_q)
+        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1), \
+                range_guard.guarded_train(self, opt):
             return self._forward_db(data_dict, train, trunk_maps, out_rows, defer_head)
 
     def _forward_db(self, data_dict, train, trunk_maps, out_rows, defer_head):

@@ -87,6 +87,21 @@ class ImageFE(nn.Module):
             x_list = [m.to_f32() for m in maps]
         return x_list[-1], x_list
 
+    def forward_maps_train(self, x, slot=0):
+        """The op-level forward on the TRAINING graph: the trunk's `fe.forward_maps_train(x)` (batch-statistics BatchNorm in
+        .train(), what `fe.backward_maps` needs recorded) under THIS module's Options, as MM.forward_q / DBVanilla2D.forward_db run
+        their trunks: train_precision / train_dgrad_products select the mode for this forward only (train_graph.training_mode), and
+        with train_range_guard the module's fp16 range guard is bound around the forward and published behind it, so that
+        poll_fp16_range() / fp16_range_ok() cover it.  Returns the stage outputs (ops.SplitMap; ConvNeXt: fp32 tensors).  The
+        ConvNeXt trunk stores no fp16 in training and ignores both: nothing is bound there."""
+        opt = self.opt or get_options()
+        if self.fe_type == "convnext_tiny":
+            return self.fe.forward_maps_train(x)
+        from .. import train_graph
+        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1), \
+                range_guard.guarded_train(self, opt):
+            return self.fe.forward_maps_train(x, slot=slot)
+
     def poll_fp16_range(self):
         """NON-BLOCKING fp16 range check of the guarded forwards so far (MM.poll_fp16_range)."""
         range_guard.poll(self)

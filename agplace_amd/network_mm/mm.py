@@ -166,7 +166,8 @@ class MM(nn.Module):
     # ---- the fp16 range guard (Options.fp16_range_guard, agplace_amd/range_guard.py): the same contract as the voxel-range flag
     def poll_fp16_range(self):
         """NON-BLOCKING: raises ValueError if a guarded inference forward (eager or replayed) whose state has reached the host so
-        far stored a saturated fp16 map value."""
+        far stored a saturated fp16 map value -- or, with Options.train_range_guard, a training forward a saturated fp16 plane
+        (the message then says so)."""
         range_guard.poll(self)
 
     def fp16_range_ok(self):
@@ -261,7 +262,9 @@ class MM(nn.Module):
         from .. import train_graph
         # the opt-in fast modes (train_graph.py): one-product forward convs, one-product data gradients -- for THIS model's
         # forward only, the process-wide switches restored when it returns
-        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1):
+        # (Options.train_range_guard: the model's guard word bound around the training FORWARD, published behind it)
+        with train_graph.training_mode(opt.train_precision == 16, opt.train_dgrad_products == 1), \
+                range_guard.guarded_train(self, opt):
             return self._forward_q(data_dict, train, image_maps, out_rows, rider)
 
     def _forward_q_convnext(self, data_dict, image_maps, out_rows):
@@ -302,7 +305,10 @@ class MM(nn.Module):
         if torch.is_grad_enabled() and 'query_image' in data_dict and data_dict['query_image'].requires_grad:
             raise NotImplementedError("ConvNeXt: the gradient of the input image is not built (the stem returns none)")
         from .. import train_graph
-        with train_graph.training_mode(self.opt.train_precision == 16, self.opt.train_dgrad_products == 1):
+        # (Options.train_range_guard: the trunk stores no fp16 and reads no binding; stage 2 and the voxel branch run the ResNet
+        # model's training graph, whose fp16 stores report as they do there)
+        with train_graph.training_mode(self.opt.train_precision == 16, self.opt.train_dgrad_products == 1), \
+                range_guard.guarded_train(self, self.opt):
             return self._forward_q(data_dict, True, None, None, None)
 
     def _forward_q(self, data_dict, train, image_maps, out_rows, rider):

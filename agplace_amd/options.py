@@ -107,7 +107,8 @@ class Options:
     # every kernel storing an inference fp16 map (the table in DESIGN.md section 2) sets when it had to clamp a value to +-65504
     # -- eager forwards then raise ValueError
     # (one call late; the last call by fp16_range_ok()), captured replays publish it to pinned memory for poll_fp16_range().
-    # Stored values are the same bits either way.  Mode 3 and training store no fp16 maps and never bind.  Independent of the
+    # Stored values are the same bits either way.  Mode 3 stores no fp16 maps and never binds; training forwards never bind through
+    # this option (their fp16 planes have a switch of their own, train_range_guard below).  Independent of the
     # first-forward warning above (resnet.SATURATION_CHECK).
     fp16_range_guard: bool = False
     # TRAINING (.train(), or .eval() with gradients): 32 (default) = the tight mode -- split-bf16 maps, three MFMA products in
@@ -120,6 +121,15 @@ class Options:
     # 3 (default) | 1 = opt-in: the data gradients of the 3x3 convs as ONE bf16 product of the hi planes (train_graph.DGRAD_HI_ONLY),
     # usually together with train_precision = 16; measured error: tests/test_gpu_train.py, timing: bench.py train.fast_mode
     train_dgrad_products: int = 3
+    # Opt-in fp16 range guard of the TRAINING forwards (.train(), or .eval() under autograd / frozen BatchNorm), in both
+    # train_precision modes: the training graph stores fp16 too -- the fast mode's pre-BatchNorm planes z16 and conv1 -> conv2
+    # planes y16, and in both modes the fp16 operand planes of the one-pass weight gradient (the inventory in DESIGN.md section
+    # 2) -- all saturating at +-65504.  With the option the model's guard word (agplace_amd/range_guard.py, the contract of
+    # fp16_range_guard) is bound around every training forward, not the backward (which stores no fp16 map), and published after
+    # it: poll_fp16_range() / fp16_range_ok() then cover training forwards.  The guard reports; it does not rescue.  Stored values
+    # are the same bits either way; off (default) = as before, launch for launch.  ConvNeXt trunks store no fp16 in training: the
+    # option is accepted with them and binds nothing there.  Not a reference option: from_reference_opt leaves it False.
+    train_range_guard: bool = False
     # Opt-in training of the ConvNeXt-tiny trunk (dbimage_fe / mm_imgfe = "convnext_tiny"): DBVanilla2D and MM then call
     # ConvNeXt.enable_training() on its trunks, so .train() (torchvision's stochastic depth, p_k = 0.1 k / 17) and gradients into
     # the trunk run on the kernels of csrc/convnext_bwd.hip (mode-3 products, fixed-order sums: repeatable bit for bit).  False
@@ -222,6 +232,8 @@ class Options:
             raise ValueError(f"odeint_adaptive_family {self.odeint_adaptive_family!r}: True | False")
         if not isinstance(self.fp16_range_guard, bool):
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
+        if not isinstance(self.train_range_guard, bool):
+            raise ValueError(f"train_range_guard {self.train_range_guard!r}: True | False")
         v = self.voxel_capacity
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < (1 << 30)):
             raise ValueError(f"voxel_capacity {v!r}: None or an integer in 1 .. 2^30 - 1 (rows of every level from raw points)")
@@ -236,7 +248,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity"):      # (not reference options: stay at their defaults)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity", "train_range_guard"):      # (not reference options: stay at their defaults)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

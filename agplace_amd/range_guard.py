@@ -15,6 +15,11 @@ The word and the mirrors are made OUTSIDE any capture (at the first guarded eage
 is never allocated inside a capture, and a first guarded forward inside one raises RuntimeError.  A capture stream that has no
 mirror of its own takes the spare mirror the last eager forward on the device left behind.  The word is zeroed with an
 elementwise kernel (mul_(0)) after a device synchronisation, never with a memset next to replayed graphs (mm.py, _vox_slot).
+
+Training (Options.train_range_guard, guarded_train): forwards on the training graph store fp16 too -- the fast mode's z16 / y16
+planes and, in both train_precision modes, the fp16 operand planes of the one-pass weight gradient (DESIGN.md section 2 lists
+every store).  The same Guard of the model is bound around the training FORWARD only (the backward stores no fp16 map) and
+published behind it; the report then says that a training forward saturated.  The guard reports, it does not rescue.
 """
 import contextlib
 
@@ -26,6 +31,17 @@ from . import _lib
 def active(opt, prec, train):
     """Whether a forward at MFMA precision `prec` binds the guard: inference on fp16 maps (modes 2 / 4) with the option on."""
     return bool(getattr(opt, "fp16_range_guard", False)) and not train and prec in (2, 4)
+
+
+def active_train(opt):
+    """Whether a forward on the TRAINING graph binds the guard (Options.train_range_guard), in either train_precision mode: the
+    fast mode's z16 / y16 planes and, in both modes, the fp16 operand planes of the one-pass weight gradient."""
+    return bool(getattr(opt, "train_range_guard", False))
+
+
+# what a training forward publishes as its `prec` (Guard.last_prec): "train16" = the fast mode, "train32" = the tight mode
+def train_tag(opt):
+    return f"train{getattr(opt, 'train_precision', 32)}"
 
 
 class Guard:
@@ -126,6 +142,13 @@ class Guard:
         self.reset()           # the error is reported once: start again from zero
         prec = self.last_prec
         also = "".join(f"; this report also covers {a}" for a in sorted(self.also))
+        if isinstance(prec, str) and prec.startswith("train"):
+            raise ValueError(f"{self.owner}: in {which} batch a training forward (Options.train_precision = {prec[5:]}) stored an fp16 "
+                             "value saturated (|v| > 65504 before the clamp): a pre-BatchNorm plane or a conv1 -> conv2 plane of the "
+                             "fast mode, or an fp16 operand plane of the one-pass weight gradient (DESIGN.md section 2). The step "
+                             f"trained on clamped activations or clamped weight-gradient operands{also}. The guard reports, it does "
+                             "not rescue: lower the weights' / BatchNorm gammas' scale, or train this model in the tight mode "
+                             "(train_precision = 32), whose maps are split-bf16")
         raise ValueError(f"{self.owner}: in {which} batch a feature map left fp16's range (|v| > 65504) and was stored saturated in "
                          f"precision mode {prec}: its outputs are wrong{also}. Run this model with Options.mfma_precision = 3 "
                          "(split-bf16 maps, fp32 range). For the image path agplace_amd.map_exponents.calibrate chooses per-map "
@@ -156,6 +179,19 @@ def guarded(model, opt, prec, train):
     with g.bind(dev):
         yield
     g.publish(dev, prec)
+
+
+@contextlib.contextmanager
+def guarded_train(model, opt):
+    """Around a model's forward on the TRAINING graph (not its backward, which stores no fp16 map): bind the model's one guard
+    when active_train(opt), publish behind the forward on exit -- the same word, mirrors and capture rules as guarded()."""
+    if not active_train(opt):
+        yield
+        return
+    g, dev = guard_of(model), model_device(model)
+    with g.bind(dev):
+        yield
+    g.publish(dev, train_tag(opt))
 
 
 def poll(model):

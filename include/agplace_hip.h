@@ -97,6 +97,12 @@ const char* agp_arch(void);
  * is given, and passes the pointer as a kernel argument.  Under stream capture the pointer becomes part of the captured node,
  * so every replay ORs into the same word.  Another host thread sees its own binding (NULL until it sets one).
  *
+ * Training forwards store fp16 too and may run bound (Options.train_range_guard binds around them, never around a backward):
+ * beside the kernels above, agp_map_affine and agp_affine_maxpool3x3s2_fwd are guarded for exactly the values they convert to
+ * fp16 -- the o_h16 / out_h16 operand plane, and the output itself when it is ONE fp16 plane (o_lo / out_lo NULL) -- with the
+ * semantics above; both fold their ReLU in front of the conversion, so with it a negative value is stored as 0, not clamped,
+ * and does not count.  A call that stores only a split-bf16 pair launches the unguarded kernel whatever is bound.
+ *
  * agp_range_flag_set binds `word` (a device pointer, or NULL to unbind) and returns the previous binding of this thread;
  * agp_range_flag_get returns the current one.  Neither touches the device. */
 uint32_t* agp_range_flag_set(uint32_t* word);
@@ -730,7 +736,10 @@ int agp_bn_stats_from_partial(const float* partial, int tiles, int c, int64_t co
                               const float* gamma, const float* beta, float* scale, float* shift, void* stream);
 /* out = relu?(a * scale[c] + shift[c] + r)   (BatchNorm apply with optional residual).
  * o_h16 (optional, else NULL): the output once more as ONE fp16 plane of the same geometry (halo not written) -- the
- * input operand of the one-pass weight gradient (agp_conv_desc::in_h16) of the conv that consumes this map. */
+ * input operand of the one-pass weight gradient (agp_conv_desc::in_h16) of the conv that consumes this map.
+ * fp16 range guard: while a word is bound (agp_range_flag_set) and the call stores fp16 at all (o_h16, or o_lo == NULL: the
+ * output is ONE fp16 plane), the guarded kernel runs and reports a converted value that had to be clamped (after the ReLU, if
+ * any); the stored bits are the same.  A pair-only call, or no binding: the unguarded kernel. */
 int agp_map_affine(const void* a_hi, const void* a_lo, const float* scale, const float* shift,
                    const void* r_hi, const void* r_lo, int n, int h, int w, int c, int pad, int relu,
                    void* o_hi, void* o_lo, void* o_h16, void* stream);
@@ -817,7 +826,9 @@ int agp_maxpool_bn_bwd(const uint8_t* argmax, const void* gp_hi, const void* gp_
 /* pooled = MaxPool2d(3, 2, 1)(relu(z * scale[c] + shift[c])) with the argmax of agp_maxpool3x3s2_fwd, in ONE pass over the conv
  * output z: BatchNorm apply + ReLU + max-pool of the ResNet stem in training (reference network_mm/image_fe.py:97-103) without
  * storing the full-size activation (agp_map_affine + agp_maxpool3x3s2_fwd: 13 bytes per element of the step's largest map,
- * here 5).  out_h16 (optional, else NULL): the pooled map once more as one fp16 plane (agp_map_affine's o_h16). */
+ * here 5).  out_h16 (optional, else NULL): the pooled map once more as one fp16 plane (agp_map_affine's o_h16).
+ * fp16 range guard: as agp_map_affine -- out_h16, and the pooled map when out_lo == NULL, are the tracked stores (the pooled
+ * values are post-ReLU: only a value above +65504 can clamp). */
 int agp_affine_maxpool3x3s2_fwd(const void* z_hi, const void* z_lo, const float* scale, const float* shift, int n, int h,
                                 int w, int c, int pad, void* out_hi, void* out_lo, int hout, int wout, int pout,
                                 uint8_t* argmax, void* out_h16, void* stream);

@@ -44,6 +44,10 @@ def main():
     ap.add_argument("--fuse-bn-stats", type=int, default=1, choices=[0, 1], help="A/B: BatchNorm statistics from the conv epilogues (train_graph.FUSE_BN_STATS)")
     ap.add_argument("--y16-only", type=int, default=1, choices=[0, 1], help="A/B: conv1 outputs of a block as ONE fp16 plane in the fast mode")
     ap.add_argument("--fwd16-entries", type=int, default=1, choices=[0, 1], help="A/B: the fast mode's one-product forward also on the stage entries")
+    ap.add_argument("--range-guard", action="store_true",
+                    help="Options.train_range_guard: the fp16 range guard bound around both models' training forwards (A/B of its cost)")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="timed windows of --steps steps each; ms_per_step is their median, ms_windows lists them")
     args = ap.parse_args()
     import types
     from agplace_amd import train_graph
@@ -63,7 +67,8 @@ def main():
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
     _lib.load()
-    opt = Options(mfma_precision=args.prec, train_precision=args.train_precision, train_dgrad_products=args.dgrad_products)
+    opt = Options(mfma_precision=args.prec, train_precision=args.train_precision, train_dgrad_products=args.dgrad_products,
+                  **({"train_range_guard": True} if args.range_guard else {}))
     torch.manual_seed(0)
     mq = MM(opt=opt).to(dev).train()
     mdb = DBVanilla2D("db", opt.features_dim, opt=opt).to(dev).train()
@@ -140,14 +145,20 @@ def main():
         step()
     parallel.barrier()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.steps):
-        loss = step()
-    e1.record()
-    torch.cuda.synchronize()
+    windows = []
+    for _ in range(max(1, args.windows)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.steps):
+            loss = step()
+        e1.record()
+        torch.cuda.synchronize()
+        windows.append(e0.elapsed_time(e1) / args.steps)
     parallel.barrier()
-    ms = e0.elapsed_time(e1) / args.steps
+    ms = sorted(windows)[len(windows) // 2]
+    if args.range_guard:
+        mq.poll_fp16_range()
+        assert mq.fp16_range_ok() and mdb.fp16_range_ok(), "the bench inputs must report clean"
     if world > 1:
         t = torch.tensor([ms], device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -160,6 +171,8 @@ def main():
             "images_per_s": round(nq * (1 + args.ndb) / ms * 1e3, 1),
             "pairs_equiv_per_s": round(nq * args.ndb / ms * 1e3, 1),
             "n_gpus": world, "batch_per_gpu": b, "ndb": args.ndb, "tile": args.tile, "prec": args.prec,
+            "train_precision": args.train_precision, "range_guard": bool(args.range_guard),
+            "ms_windows": [round(w, 3) for w in windows],
             "loss": float(loss.detach()), "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 2)}))
     if world > 1:
         torch.distributed.destroy_process_group()
