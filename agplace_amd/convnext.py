@@ -31,8 +31,13 @@ Precision 4 is OPT-IN as well (`ConvNeXt.set_precision(4)`, Options.convnext_pre
 output (one fp16 operand plane instead of two bf16 ones), W1, the GELU output, W2, the downsample's LayerNorm output and its weight
 are rounded to fp16 (nearest even, saturating at +-65504, NaN kept) and every product is ONE fp16 MFMA with fp32 accumulation.  The
 stream, the stem, the depthwise conv, LayerNorm statistics, biases, GELU, layer_scale and the residual add stay fp32, so the maps
-are still fp32 tensors and there is still no fp16 map to guard; the fp32 and uint8 stems are the same kernels.  `forward_maps_train`
+are still fp32 tensors and there is still no fp16 MAP to guard; the fp32 and uint8 stems are the same kernels.  `forward_maps_train`
 and the backward stay in mode 3 whatever is set (the ResNets' rule for Options.mfma_precision).  With 3 nothing changes.
+The six fp16 OPERANDS do saturate, and a clamped forward returns finite, wrong maps: while the caller has bound an fp16 range guard
+(range_guard.Guard.bind -- Options.convnext_range_guard makes ImageFE, DBVanilla2D and MM do it) the three kernels run guarded
+twins that report a LayerNorm or GELU output beyond +-65504 into the bound word (real pixels only, NaN kept and not reported, the
+same stored bits), and `forward_maps` hands the weight planes' clamp flag (prep_block / prep_down "sat", _half_clamped) to the
+bound guard on every forward.  The ops know nothing of Options: no binding, no twin, no flag.
 
 Stochastic depth restates torchvision's StochasticDepth(p, "row") (torchvision is not a dependency): block k of the FULL
 18-block network has p_k = stochastic_depth_prob * k / 17 (the truncation happens after construction, so a kept block keeps its
@@ -44,7 +49,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, range_guard
 from ._lib import check, ptr
 
 DIMS = (96, 192, 384, 768)
@@ -55,9 +60,10 @@ TRAIN_SWITCH = "opt in with ConvNeXt.enable_training() / Options.convnext_train"
 
 
 def precision_from_options(opt):
-    """Options.convnext_precision for a trunk that `opt` configures; precision 4 together with the fp16 range guard is refused:
-    the guard's sticky word is not wired into the precision-4 kernels, and a guard that silently skips the trunk would be worse."""
-    if opt.convnext_precision == 4 and opt.fp16_range_guard:
+    """Options.convnext_precision for a trunk that `opt` configures; precision 4 together with the fp16 range guard is refused
+    unless Options.convnext_range_guard wires the guard's sticky word into the precision-4 kernels: a guard that silently skips the
+    trunk would be worse."""
+    if opt.convnext_precision == 4 and opt.fp16_range_guard and not getattr(opt, "convnext_range_guard", False):
         raise NotImplementedError("ConvNeXt: convnext_precision=4 together with fp16_range_guard=True is not built (the guard's word "
                                   "is not wired into the fp16 ConvNeXt kernels); use convnext_precision=3 or turn the guard off")
     return opt.convnext_precision
@@ -87,6 +93,15 @@ def _split(w):
 def _half(w):
     """fp32 -> ONE fp16 plane (precision 4): round to nearest even, saturating at +-65504, NaN kept."""
     return w.clamp(-65504.0, 65504.0).to(torch.float16).contiguous()
+
+
+def _half_clamped(*ws):
+    """int32 [1] on the tensors' device: 1 if _half clamps an element of any of them (|w| > 65504; NaN is kept, not clamped), else
+    0.  Tensor ops only -- no read-back, no synchronisation: the fp16 range guard ORs it into its word (range_guard.note_planes)."""
+    flag = (ws[0].abs() > 65504.0).any()
+    for w in ws[1:]:
+        flag = flag | (w.abs() > 65504.0).any()
+    return flag.to(torch.int32).reshape(1)
 
 
 def _planes(w, prec):
@@ -127,7 +142,9 @@ def prep_block(blk, prec=3):
     (prec 3: (hi, lo) bf16; prec 4: one fp16 plane of the same tensors)."""
     dw, ln, l1, l2 = blk.block[0], blk.block[2], blk.block[3], blk.block[5]
     c = dw.weight.shape[0]
-    return dict(c=c, dw=_f32(dw.weight).reshape(c, 49).t().contiguous(), dwb=_f32(dw.bias), g=_f32(ln.weight), b=_f32(ln.bias),
+    # "sat" (precision 4): whether the W1 / W2 plane holds a clamped element, for the fp16 range guard
+    sat = _half_clamped(_f32(l1.weight), _f32(l2.weight)) if prec == 4 else None
+    return dict(c=c, sat=sat, dw=_f32(dw.weight).reshape(c, 49).t().contiguous(), dwb=_f32(dw.bias), g=_f32(ln.weight), b=_f32(ln.bias),
                 w1=_planes(_frag_rows(_f32(l1.weight)), prec), b1=_f32(l1.bias), w2=_planes(_frag_acc(_f32(l2.weight)), prec),
                 b2=_f32(l2.bias), ls=_f32(blk.layer_scale).reshape(c))
 
@@ -135,7 +152,8 @@ def prep_block(blk, prec=3):
 def prep_down(ln, conv, prec=3):
     c = conv.weight.shape[1]
     wk = _f32(conv.weight).permute(0, 2, 3, 1).reshape(2 * c, 4 * c)      # k = (ky * 2 + kx) * C + c
-    return dict(c=c, g=_f32(ln.weight), b=_f32(ln.bias), w=_planes(_frag_rows(wk), prec), bias=_f32(conv.bias))
+    return dict(c=c, sat=_half_clamped(wk) if prec == 4 else None, g=_f32(ln.weight), b=_f32(ln.bias), w=_planes(_frag_rows(wk), prec),
+                bias=_f32(conv.bias))
 
 
 def prep_block_bwd(blk):
@@ -479,6 +497,9 @@ class ConvNeXt(nn.Module):
                     prep[("blocks", s)] = [prep_block(blk, prec) for blk in self.features[1 + 2 * s]]
                     if s < 2:
                         prep[("down", s)] = prep_down(*self.features[2 + 2 * s], prec)
+                if prec == 4:       # one clamp flag over every fp16 weight plane of this parameter version (prep_block, prep_down)
+                    flags = [p["sat"] for k, v in prep.items() if k != "stem" for p in (v if isinstance(v, list) else [v])]
+                    prep["sat"] = torch.stack(flags).amax(0) if flags else None
             self._prep[prec] = prep
         return self._prep[prec]
 
@@ -507,13 +528,21 @@ class ConvNeXt(nn.Module):
             raise ValueError(f"ConvNeXt: a {h}x{w} input is too small for three stages (map sizes {sizes})")
         return sizes
 
+    def takes_training_path(self):
+        """Whether `forward_maps` would hand this call to `forward_maps_train` (mode 3, no fp16: nothing for the range guard)."""
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters())
+        return self._train_enabled and (self.training or wants_grad)
+
     def forward_maps(self, x):
         """fp32 [n,3,H,W] on the GPU (any strides) -> the outputs of features[1], [3], [5] as fp32 tensors of logical shape
         [n,C,h,w] in channels_last memory.  The inference path: allocates the three maps, launches on the current stream and never
         synchronises (capturable after one eager call has prepared the weights).  With the training switch on, .train() or
         trainable trunk parameters under enabled gradients go through `forward_maps_train` instead.  With uint8 inputs enabled
         (enable_u8_inputs) x may also be uint8 tiles [n,ncam,h,w,3] or an ops.RawFrames: H, W are then the panorama's (h, ncam*w);
-        frames need their resize tables on the device before a capture (one eager call, or ops.prepare_resize)."""
+        frames need their resize tables on the device before a capture (one eager call, or ops.prepare_resize).
+        At precision 4, while the caller has bound an fp16 range guard (range_guard.Guard.bind; Options.convnext_range_guard does
+        it in ImageFE / DBVanilla2D / MM), the three matrix kernels run their guarded twins and the weight planes' clamp flag is
+        handed to that guard; the maps are the same bits."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters())
         if self._train_enabled and (self.training or wants_grad):
             return self.forward_maps_train(x)
@@ -530,6 +559,10 @@ class ConvNeXt(nn.Module):
         prep = self._prepared(prec)
         ws = self._ws.tensor("cnx_ws", (max(workspace_bytes(n, h, w, DIMS[s]) for s, (h, w) in enumerate(sizes)),), torch.uint8,
                              x.device)
+        if prec == 4:
+            # under a bound fp16 range guard (range_guard.Guard.bind; the kernels below then run their guarded twins): the clamp
+            # flag of the fp16 weight planes, on EVERY forward that uses them; without a binding nothing happens
+            range_guard.note_planes(prep["sat"])
         maps, cur = [], None
         for s in range(3):
             cur = self._stem(x, prep["stem"]) if s == 0 else downsample_fwd(cur, prep[("down", s - 1)], prec)

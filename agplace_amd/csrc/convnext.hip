@@ -105,12 +105,16 @@ __global__ void cnx_normalize_u8_kernel(const CnxLoadU8 ld, int W, long long tot
 // col = t >> 5) computes the 4 outputs of its column for channel cl of the chunk.  Its C / 32 x 4 conv results stay in
 // registers; the 32 lanes of a half wave then hold one pixel's C channels for the LayerNorm.  wt: [49][C].
 // PREC: 3 = the operand as bf16 (hi, lo) planes; 4 = as ONE fp16 plane in o_hi (cnx_h1: nearest even, saturating), o_lo unused.
-template <int C, int PREC = 3>
+// rf (here, in cnx_mlp_kernel and in cnx_downsample_kernel; PREC = 4 only): the fp16 range guard's word in the guarded instantiation
+// (common.hpp rg_word), absent otherwise.  Tracked: the fp32 values handed to cnx_h1 / cnx_h2, before the clamp, of REAL pixels only.
+template <int C, int PREC = 3, class... RF>
 __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restrict__ x, int h, int w, int tiles_y, int tiles_x,
                                                             const float* __restrict__ wt, const float* __restrict__ bias,
                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
-                                                            bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo) {
+                                                            bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, RF... rf) {
+    static_assert(sizeof...(RF) == 0 || PREC == 4, "the range guard covers the fp16 instantiations only");
     constexpr int NK = C / 32;
+    RangeTrack<sizeof...(RF) != 0> rg;
     __shared__ __attribute__((aligned(16))) float tile[10][14][32];
     __shared__ float wl[49][32];
     const int t = threadIdx.x, cl = t & 31, col = t >> 5;
@@ -172,7 +176,12 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
             for (int k = 0; k < NK; ++k) {
                 const int c = k * 32 + cl;
                 if constexpr (PREC == 4) {
-                    o_hi[p * C + c] = cnx_h1(fmaf(conv[i][k] * rstd, g[c], b[c]));
+                    const float xn = fmaf(conv[i][k] * rstd, g[c], b[c]);
+                    rg.sym2(xn, 0.f);          // inside the image test: the out-of-image positions of a partial tile do not report
+                    o_hi[p * C + c] = cnx_h1(xn);
+                    // (the twin only: without it the scheduler hoists every channel's gamma / beta load above the running maximum
+                    // and C = 384 needs 100 VGPRs instead of 86 -- 4 waves per SIMD instead of the unguarded form's 5)
+                    if constexpr (sizeof...(RF) != 0) __builtin_amdgcn_sched_barrier(0);
                 } else {
                     bf16_t hi, lo;
                     split_bf16(fmaf(conv[i][k] * rstd, g[c], b[c]), hi, lo);
@@ -182,6 +191,7 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
             }
         }
     }
+    rg.flush(rg_word(rf...));
 }
 
 // --------------------------------------------------------------------------------------- Linear -> GELU -> Linear, fused
@@ -198,14 +208,18 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
 //   w2 planes: [4C / 32][2][C / 32][64 lanes][8]  lane (r, h) of block jb, half t, tile ct: W2[ct * 32 + r][jb * 32 + acc_row(8 t + e, h)]
 // PREC = 4 (agp_cnx_mlp_f16_fwd): the operand, W1, the GELU output and W2 are fp16 and a product is ONE MFMA (mfma1h); one operand
 // plane in LDS, one plane per weight (the *_hi arguments; the *_lo ones are unused), the same layouts, loop order and epilogue.
-template <int C, bool ROWS, int PREC = 3>
+// Guarded (rf): a lane's hidden values belong to pixel p0 + r; rows p0 + r >= P are tile padding (a zero operand, hidden = GELU(b1))
+// and do not report.
+template <int C, bool ROWS, int PREC = 3, class... RF>
 __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo, long long P,
                                                       const bf16x8* __restrict__ w1_hi, const bf16x8* __restrict__ w1_lo,
                                                       const float* __restrict__ b1, const bf16x8* __restrict__ w2_hi,
                                                       const bf16x8* __restrict__ w2_lo, const float* __restrict__ b2,
                                                       const float* __restrict__ ls, const float* resid, float* out,
-                                                      const float* __restrict__ row_scale, long long ppi) {
+                                                      const float* __restrict__ row_scale, long long ppi, RF... rf) {
+    static_assert(sizeof...(RF) == 0 || (PREC == 4 && !ROWS), "the range guard covers the fp16 instantiations only");
     constexpr int LD = C + CNX_KPAD, KK = C / 16, CT = C / 32, JB = C / 8, VR = C / 8;
+    RangeTrack<sizeof...(RF) != 0> rg;
     constexpr int XBYTES = (PREC == 4 ? 1 : 2) * CNX_TP * LD * 2, RBYTES = 4 * 32 * 36 * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem[XBYTES > RBYTES ? XBYTES : RBYTES];
     bf16_t* const sx_hi = (bf16_t*)smem;
@@ -246,7 +260,11 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
             for (int kk = 0; kk < KK; ++kk) mfma1h(hacc, a_hi[kk * 64], *(const bf16x8*)(bx_hi + kk * 16));
             u32x4 gp[2];
 #pragma unroll
-            for (int i = 0; i < 16; i += 2) gp[i >> 3][(i & 7) >> 1] = cnx_h2(gelu_exact(hacc[i]), gelu_exact(hacc[i + 1]));
+            for (int i = 0; i < 16; i += 2) {
+                const float ga = gelu_exact(hacc[i]), gb = gelu_exact(hacc[i + 1]);
+                rg.sym2_if(p0 + r < P, ga, gb);
+                gp[i >> 3][(i & 7) >> 1] = cnx_h2(ga, gb);
+            }
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) {
                 const bf16x8* const c_hi = w2_hi + ((size_t)(jb * 2 + tt) * CT) * 64 + lane;
@@ -275,6 +293,7 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
             }
         }
     }
+    rg.flush(rg_word(rf...));
     float* const red = (float*)smem;       // [4 waves][32 pixels][36]: 32 channels + 4 floats of padding
     const int epx = t >> 3, ec = (t & 7) * 4;
     const long long ep = p0 + epx;
@@ -311,11 +330,13 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
 // pixel (fp32 statistics, two passes in registers) and write its operand planes to LDS, then wave v accumulates the output
 // feature blocks v, v + 4, ... over the chunk.  w planes: [2C / 32][4C / 16][64 lanes][8] as w1 above.
 // PREC = 4 (agp_cnx_downsample_f16_fwd): the normalised operand and the weight are fp16, one plane each (w_hi; w_lo unused), ONE MFMA.
-template <int C, int PREC = 3>
+template <int C, int PREC = 3, class... RF>
 __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __restrict__ x, int h, int w, int ho, int wo, long long P,
                                                              const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                              const bf16x8* __restrict__ w_hi, const bf16x8* __restrict__ w_lo,
-                                                             const float* __restrict__ bias, float* __restrict__ out) {
+                                                             const float* __restrict__ bias, float* __restrict__ out, RF... rf) {
+    static_assert(sizeof...(RF) == 0 || PREC == 4, "the range guard covers the fp16 instantiations only");
+    RangeTrack<sizeof...(RF) != 0> rg;
     constexpr int KC = 384, LD = KC + CNX_KPAD, IPP = KC / C, NCH = 4 * C / KC, NT = 2 * C / 32, NTW = (NT + 3) / 4, KKT = 4 * C / 16;
     constexpr int NV = C / 32;             // float4 per lane of a pixel's eight
     __shared__ __attribute__((aligned(16))) bf16_t sx_hi[CNX_TP * LD];
@@ -376,6 +397,8 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
                     float xn[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) xn[i] = lp < P ? fmaf(v[m][i] * rstd, gv[i], bv[i]) : 0.f;
+                    rg.sym2(xn[0], xn[1]);     // (a padding row lp >= P holds zeros)
+                    rg.sym2(xn[2], xn[3]);
                     *(u32x2*)(sx_hi + lpx * LD + sub * C + c) = u32x2{cnx_h2(xn[0], xn[1]), cnx_h2(xn[2], xn[3])};
                 } else {
                     bf16_t hi[4], lo[4];
@@ -401,6 +424,7 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
             }
         }
     }
+    rg.flush(rg_word(rf...));
     const long long op = p0 + r;
     if (op < P) {
 #pragma unroll
@@ -544,7 +568,13 @@ int agp_cnx_dwconv_ln_f16_fwd(const float* x, int n, int h, int w, int C, const 
     const int ty = (h + 3) / 4, tx = (w + 7) / 8;
     const dim3 grid((unsigned)((long long)n * ty * tx));
     hipStream_t s = (hipStream_t)stream;
-    if (C == 96) { AGP_LAUNCH((cnx_dwconv_ln_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
+    // the guarded twin while a range-guard word is bound (common.hpp RangeTrack); here and in the two launchers below
+    if (uint32_t* const rf = agp_range_flag_get()) {
+#define CNX_DW_G(CC) AGP_LAUNCH((cnx_dwconv_ln_kernel<CC, 4, uint32_t*>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none, rf)
+        if (C == 96) { CNX_DW_G(96); } else if (C == 192) { CNX_DW_G(192); } else { CNX_DW_G(384); }
+#undef CNX_DW_G
+    }
+    else if (C == 96) { AGP_LAUNCH((cnx_dwconv_ln_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
     else if (C == 192) { AGP_LAUNCH((cnx_dwconv_ln_kernel<192, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
     else { AGP_LAUNCH((cnx_dwconv_ln_kernel<384, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
     AGP_CHECK_LAUNCH();
@@ -563,7 +593,12 @@ int agp_cnx_mlp_f16_fwd(const void* workspace, int64_t workspace_bytes, int64_t 
     const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
     hipStream_t s = (hipStream_t)stream;
 #define CNX_MLP_H(CC) AGP_LAUNCH((cnx_mlp_kernel<CC, false, 4>), grid, dim3(256), 0, s, xp, nox, (long long)P, a, now, b1, c, now, b2, layer_scale, resid, out, norows, 0ll)
-    if (C == 96) { CNX_MLP_H(96); } else if (C == 192) { CNX_MLP_H(192); } else { CNX_MLP_H(384); }
+#define CNX_MLP_G(CC) AGP_LAUNCH((cnx_mlp_kernel<CC, false, 4, uint32_t*>), grid, dim3(256), 0, s, xp, nox, (long long)P, a, now, b1, c, now, b2, layer_scale, resid, out, norows, 0ll, rf)
+    if (uint32_t* const rf = agp_range_flag_get()) {
+        if (C == 96) { CNX_MLP_G(96); } else if (C == 192) { CNX_MLP_G(192); } else { CNX_MLP_G(384); }
+    }
+    else if (C == 96) { CNX_MLP_H(96); } else if (C == 192) { CNX_MLP_H(192); } else { CNX_MLP_H(384); }
+#undef CNX_MLP_G
 #undef CNX_MLP_H
     AGP_CHECK_LAUNCH();
     return AGP_OK;
@@ -578,7 +613,12 @@ int agp_cnx_downsample_f16_fwd(const float* x, int n, int h, int w, int C, const
     const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
     hipStream_t s = (hipStream_t)stream;
     const bf16x8 *a = (const bf16x8*)wt, *none = nullptr;
-    if (C == 96) { AGP_LAUNCH((cnx_downsample_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
+    if (uint32_t* const rf = agp_range_flag_get()) {
+#define CNX_DS_G(CC) AGP_LAUNCH((cnx_downsample_kernel<CC, 4, uint32_t*>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out, rf)
+        if (C == 96) { CNX_DS_G(96); } else if (C == 192) { CNX_DS_G(192); } else { CNX_DS_G(384); }
+#undef CNX_DS_G
+    }
+    else if (C == 96) { AGP_LAUNCH((cnx_downsample_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
     else if (C == 192) { AGP_LAUNCH((cnx_downsample_kernel<192, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
     else { AGP_LAUNCH((cnx_downsample_kernel<384, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
     AGP_CHECK_LAUNCH();

@@ -58,6 +58,7 @@ class DBVanilla2D(nn.Module):
                     if opt.convnext_u8:     # its opt-in uint8 routes: tiles and frames, normalised by the stem as it reads
                         e.fe.enable_u8_inputs().set_image_norm(opt.image_mean, opt.image_std)
                     e.fe.set_precision(precision_from_options(opt))     # 3, or the opt-in one-product fp16 inference mode (4)
+                    e.model_opt = opt       # (Options.convnext_range_guard: the trunks report through THIS model's guard)
             self.dbimage_fes = nn.ModuleList(fes)
             self.dbimage_pools = nn.ModuleList([GeM() for _ in maptype])
             self.dbimage_mlps = nn.ModuleList([MLP(e.last_dim, dim) for e in fes])
@@ -292,19 +293,26 @@ class DBVanilla2D(nn.Module):
         frames, jitter, crop, db_map, u8, mode, dims, _ = self._db_inputs(data_dict)
         b, ndb, nmap, c, h, w = dims
         assert c == 3
-        vecs = []
-        for i in range(nmap):
-            j = 0 if opt.share_dbfe is True else i
-            x = self._db_tile_input(i, frames, jitter, crop, db_map, u8, dims)
-            if torch.is_tensor(x) and not u8:
-                x = x.float()
-            last, _ = self.dbimage_fes[j](x)
-            v = gem_op(last, self.dbimage_pools[j].p, self.dbimage_pools[j].eps)
-            v = self.dbimage_mlps[j](v)
-            if opt.output_l2 is True:
-                v = autograd_ops.l2normalize(v)
-            vecs.append(v)
-        return {'embedding': self._mean_over_maps(vecs, b, ndb, mode)}
+        # Options.convnext_range_guard: this model's guard word bound around its INFERENCE trunks at precision 4 (the guarded twins
+        # of csrc/convnext.hip, the weight planes' clamp flag) and published behind the forward; training forwards are mode 3
+        tag = None
+        if not any(e.fe.takes_training_path() for e in self.dbimage_fes):
+            tag = range_guard.cnx_tag(opt, self.dbimage_fes[0].fe.precision)
+        with range_guard.guarded_cnx(self, tag):
+            vecs = []
+            for i in range(nmap):
+                j = 0 if opt.share_dbfe is True else i
+                x = self._db_tile_input(i, frames, jitter, crop, db_map, u8, dims)
+                if torch.is_tensor(x) and not u8:
+                    x = x.float()
+                last, _ = self.dbimage_fes[j](x)
+                v = gem_op(last, self.dbimage_pools[j].p, self.dbimage_pools[j].eps)
+                v = self.dbimage_mlps[j](v)
+                if opt.output_l2 is True:
+                    v = autograd_ops.l2normalize(v)
+                vecs.append(v)
+            out = {'embedding': self._mean_over_maps(vecs, b, ndb, mode)}
+        return out
 
     def forward(self, data_dict, mode: List[str]):
         if mode == 'db':

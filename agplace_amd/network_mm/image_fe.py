@@ -10,8 +10,9 @@ stages as ops.SplitMap without the fp32 export (the fused MM / DBVanilla2D paths
 into the trunk run through ConvNeXt.forward_maps_train); it takes exactly three `layers` entries, which are BLOCK COUNTS
 there: features[6:] are dropped and stage i keeps its first layers[i] blocks, last_dim = 384, the list holds the outputs of
 features[1], [3], [5].  It runs in the mode-3 arithmetic (prec None or 3) unless Options.convnext_precision = 4 of `opt` (or
-`fe.set_precision(4)`) selected the one-product fp16 inference mode, and has no ops.SplitMap form: `forward_maps`
-with pool requests raises NotImplementedError.  The SqueezeNet branch of the reference is not built.
+`fe.set_precision(4)`) selected the one-product fp16 inference mode (with Options.convnext_range_guard its saturating operands
+report through this module's fp16 range guard, or through the model's when a model runs it), and has no ops.SplitMap form:
+`forward_maps` with pool requests raises NotImplementedError.  The SqueezeNet branch of the reference is not built.
 """
 import torch.nn as nn
 
@@ -42,6 +43,9 @@ class ImageFE(nn.Module):
                                           "features[1], [3], [5] under last_dim = 768, which breaks its own head (the last map has "
                                           "384 channels); use three entries")
             self.last_dim = 384
+            # the Options of the MODEL that runs this trunk (DBVanilla2D sets it; None: used on its own): with its
+            # convnext_range_guard the trunk's precision-4 operands report through that model's guard, not this module's
+            self.model_opt = None
             # Options.convnext_precision of `opt` (None: the process-wide options now); MM / DBVanilla2D set their own afterwards
             self.fe = ConvNeXt(layers).set_precision((opt or get_options()).convnext_precision)
             return
@@ -74,10 +78,19 @@ class ImageFE(nn.Module):
             if self.fe.precision == 4:
                 if prec == 3:
                     raise ValueError("ImageFE('convnext_tiny'): prec=3 on a trunk set to precision 4; call fe.set_precision(3)")
-                if (self.opt or get_options()).fp16_range_guard:
+                # (inside a model that turned convnext_range_guard on, the model has accepted the combination and binds its guard)
+                in_guarded_model = self.model_opt is not None and self.model_opt.convnext_range_guard
+                o = self.opt or get_options()
+                if o.fp16_range_guard and not o.convnext_range_guard and not in_guarded_model:
                     raise NotImplementedError("ImageFE('convnext_tiny'): precision 4 together with fp16_range_guard=True is not "
                                               "built (the guard's word is not wired into the fp16 ConvNeXt kernels)")
-            x_list = self.fe.forward_maps(x)
+            # Options.convnext_range_guard of the op-level drop-in: its own guard around its own INFERENCE forward at precision 4 --
+            # inside DBVanilla2D / MM it binds nothing, the report goes through the model that runs it (the ResNet path's rule below)
+            tag = None
+            if self.model_opt is None and not self.fe.takes_training_path():
+                tag = range_guard.cnx_tag(self.opt or get_options(), self.fe.precision)
+            with range_guard.guarded_cnx(self, tag):
+                x_list = self.fe.forward_maps(x)
             return x_list[-1], x_list
         prec = self.export_precision() if prec is None else prec
         # the fp16 range guard of the op-level drop-in (Options.fp16_range_guard): around its own forward only -- inside MM /

@@ -63,6 +63,7 @@ class MM(nn.Module):
             if opt.convnext_u8:             # its opt-in uint8 routes: tiles and frames, normalised by the stem as it reads
                 self.image_fe.fe.enable_u8_inputs().set_image_norm(opt.image_mean, opt.image_std)
             self.image_fe.fe.set_precision(precision_from_options(opt))      # 3, or the opt-in one-product fp16 inference mode (4)
+            self.image_fe.model_opt = opt       # (Options.convnext_range_guard: the trunk reports through THIS model's guard)
         self.image_pool = GeM()
         planes = [int(x) for x in opt.mm_voxfe_planes.split('_')]
         layers = [int(x) for x in opt.mm_voxfe_layers.split('_')]
@@ -273,7 +274,8 @@ class MM(nn.Module):
         the per-op one (the fused vector programs are 256 columns wide; FCODE(384) is one launch per solve, csrc/fusion_wide.hip),
         and stage 2 packs the last map into the 384-wide BasicBlock.  The image side runs in the mode-3 arithmetic whatever
         Options.mfma_precision says (the ConvNeXt trunk's contract: fp32 range, so neither map exponents nor the fp16 range guard
-        have work on it); the voxel branch runs at Options.mfma_precision as in the ResNet model.  No host synchronisation:
+        have work on it -- at Options.convnext_precision = 4 its fp16 operands saturate, which Options.convnext_range_guard
+        reports through this model's guard); the voxel branch runs at Options.mfma_precision as in the ResNet model.  No host synchronisation:
         capturable after one eager warm-up.
         Inference only unless Options.convnext_train opted in.  Then `train` is derived as in forward_q and the training graph of
         the ResNet model runs with train_fns.CnxTrunkFn in TrunkFn's place: the trunk trains through its own node
@@ -299,6 +301,18 @@ class MM(nn.Module):
         train = enabled and (self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
                                                and any(p.requires_grad for p in self.parameters())))
         if not train:
+            # Options.convnext_range_guard at trunk precision 4: with fp16_range_guard also binding (mfma_precision 2 / 4) the
+            # whole-forward binding below covers the trunk too -- ONE word over the trunk, stage 2 and the voxel branch, published
+            # under a tag that names both sources; alone, _forward_q binds around the trunk call only (stage 2 and the voxel branch
+            # follow fp16_range_guard as before) and the word is published behind the forward, side streams joined
+            tag = range_guard.cnx_tag(self.opt, self.image_fe.fe.precision, self.opt.mfma_precision)
+            if tag is not None:
+                if tag != "cnx4":
+                    with range_guard.guarded_cnx(self, tag):
+                        return self._forward_q(data_dict, False, None, None, None)
+                out = self._forward_q(data_dict, False, None, None, None, cnx_guard=True)
+                range_guard.publish_tag(self, tag)
+                return out
             # (the guard, when Options.fp16_range_guard is on, covers the voxel branch's fp16 maps as in the ResNet model)
             with range_guard.guarded(self, self.opt, self.opt.mfma_precision, False):
                 return self._forward_q(data_dict, False, None, None, None)
@@ -311,7 +325,8 @@ class MM(nn.Module):
                 range_guard.guarded_train(self, self.opt):
             return self._forward_q(data_dict, True, None, None, None)
 
-    def _forward_q(self, data_dict, train, image_maps, out_rows, rider):
+    def _forward_q(self, data_dict, train, image_maps, out_rows, rider, cnx_guard=False):
+        """cnx_guard: bind this model's fp16 range guard around the ConvNeXt trunk call ALONE (_forward_q_convnext)."""
         opt = self.opt
         prec = 3 if train else opt.mfma_precision       # training runs on split-bf16 maps (range + precision of gradients)
         if (not train and torch.is_grad_enabled() and getattr(self, "_frozen_backbone", False) and prec == 4
@@ -392,7 +407,8 @@ class MM(nn.Module):
                 fpool = None
                 if self._convnext:
                     # fp32 maps, no conv epilogue to pool in: one pass over each map, the last one for both of its poolings
-                    maps = self.image_fe.fe.forward_maps(image)
+                    with range_guard.bound(self, cnx_guard):
+                        maps = self.image_fe.fe.forward_maps(image)
                     levels = [_Pooled(ops.pool_f32(m, None, want_mean=True, want_gem=False)[0]) for m in maps[:-1]]
                     mean3, imagefeatvec = ops.pool_f32(maps[-1], self.image_pool.p, want_mean=True, want_gem=True, eps=self.image_pool.eps)
                     levels.append(_Pooled(mean3))

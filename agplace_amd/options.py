@@ -150,8 +150,21 @@ class Options:
     # depthwise conv, LayerNorm statistics, biases, GELU, layer_scale and the residual add stay fp32 (maps
     # within 1e-3 of fp64).  The training forward and the backward stay in mode 3 whatever this says, the rule mfma_precision has
     # for the ResNets.  4 together with fp16_range_guard is refused (NotImplementedError): the guard's word is not wired into these
-    # kernels.  Not a reference option: from_reference_opt leaves it 3.
+    # kernels -- unless convnext_range_guard below is on.  Not a reference option: from_reference_opt leaves it 3.
     convnext_precision: int = 3
+    # Opt-in fp16 range guard of the ConvNeXt-tiny trunk's precision 4: the six operands that mode rounds to fp16 saturate at
+    # +-65504 and a clamped forward returns finite, wrong maps.  With the switch every INFERENCE forward of a trunk at
+    # convnext_precision = 4 binds the model's guard word (agplace_amd/range_guard.py, the contract of fp16_range_guard: eager
+    # forwards raise ValueError one call late, fp16_range_ok() closes a loop, captured replays publish for poll_fp16_range()); the
+    # guarded twins of the three precision-4 kernels report a block's LayerNorm output, the GELU output and a downsample's LayerNorm
+    # output beyond fp16's range, and every forward reports a clamped W1 / W2 / downsample weight plane.  The
+    # guard reports; it does not rescue: convnext_precision = 3 is the remedy.  ImageFE on its own binds its own guard;
+    # DBVanilla2D and MM bind theirs (MM with fp16_range_guard too: ONE word over the trunk, stage 2 and the voxel branch; with
+    # this switch alone the trunk only).  With it, convnext_precision = 4 together with fp16_range_guard is accepted.  Stored values
+    # are the same bits either way; off (default) = as before, launch for launch and text for text.  With precision 3, on ResNet
+    # trunks and on every training forward (mode 3 whatever is set) it is accepted and binds nothing.  Not a reference option:
+    # from_reference_opt leaves it False.
+    convnext_range_guard: bool = False
     # Opt-in one-launch routes of FCODE(384) (the Neural-ODE blocks of MM on the ConvNeXt-tiny trunk): with a gradient wanted a
     # fixed-grid solve records its trajectory in the one-launch kernel and differentiates through agp_fcode_wide_bwd instead of
     # the any-width sequence of launches, and odeint_method = "dopri5" runs on the adaptive kernels at 384 columns instead of
@@ -234,6 +247,8 @@ class Options:
             raise ValueError(f"fp16_range_guard {self.fp16_range_guard!r}: True | False")
         if not isinstance(self.train_range_guard, bool):
             raise ValueError(f"train_range_guard {self.train_range_guard!r}: True | False")
+        if not isinstance(self.convnext_range_guard, bool):
+            raise ValueError(f"convnext_range_guard {self.convnext_range_guard!r}: True | False")
         v = self.voxel_capacity
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < (1 << 30)):
             raise ValueError(f"voxel_capacity {v!r}: None or an integer in 1 .. 2^30 - 1 (rows of every level from raw points)")
@@ -248,7 +263,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity", "train_range_guard"):      # (not reference options: stay at their defaults)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity", "train_range_guard", "convnext_range_guard"):      # (not reference options: stay at their defaults)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

@@ -20,8 +20,20 @@ Training (Options.train_range_guard, guarded_train): forwards on the training gr
 planes and, in both train_precision modes, the fp16 operand planes of the one-pass weight gradient (DESIGN.md section 2 lists
 every store).  The same Guard of the model is bound around the training FORWARD only (the backward stores no fp16 map) and
 published behind it; the report then says that a training forward saturated.  The guard reports, it does not rescue.
+
+The ConvNeXt trunk's precision 4 (Options.convnext_range_guard, guarded_cnx / cnx_tag): its inference kernels round six MFMA
+operands to fp16 -- a block's LayerNorm output, the GELU output and a downsample's LayerNorm output in the kernels (guarded twins of
+csrc/convnext.hip, which read the bound word like every other guarded kernel), W1, W2 and the downsample weight on the host when
+the planes are prepared (convnext._half).  A prepared plane cannot report through a kernel, so it carries a device-side int32 flag
+(computed with tensor ops when the plane is made, no read-back); a forward that uses the planes under a binding hands the flag to
+the bound guard (note_planes, through the thread-local that bind() sets) and publish() ORs it into the word with an elementwise
+kernel on the calling stream -- there, because the calling stream has joined its side streams by then, so no kernel's atomic OR
+can fall between that kernel's read and its write; captured, the OR is a node of the graph and every replay reports the planes
+again.  The report carries the tag "cnx4"; "cnx4+2" / "cnx4+4" when the same word also covers fp16 maps of mfma_precision 2 / 4
+(MM with both switches).
 """
 import contextlib
+import threading
 
 import torch
 
@@ -39,6 +51,38 @@ def active_train(opt):
     return bool(getattr(opt, "train_range_guard", False))
 
 
+def active_cnx(opt, fe_precision, train=False):
+    """Whether an INFERENCE forward of a ConvNeXt trunk at precision `fe_precision` binds the guard (Options.convnext_range_guard):
+    precision 4 only; precision 3 and every training forward (mode 3 whatever is set) store no fp16 and bind nothing."""
+    return bool(getattr(opt, "convnext_range_guard", False)) and not train and fe_precision == 4
+
+
+def cnx_tag(opt, fe_precision, maps_prec=None):
+    """What a guarded ConvNeXt inference forward publishes as its `prec` (Guard.last_prec), or None when active_cnx() is false:
+    "cnx4" = the trunk's precision-4 operands alone; "cnx4+2" / "cnx4+4" = one word over the trunk AND the fp16 maps a model stores
+    at mfma_precision `maps_prec` with fp16_range_guard on (MM: stage 2 and the voxel branch)."""
+    if not active_cnx(opt, fe_precision):
+        return None
+    return f"cnx4+{maps_prec}" if maps_prec is not None and active(opt, maps_prec, False) else "cnx4"
+
+
+_tls = threading.local()           # .bound: (Guard, word tensor) of the innermost Guard.bind of this host thread, or None
+
+
+def bound_word():
+    """The int32 [1] device word Guard.bind bound for the calling host thread (the tensor behind agp_range_flag_get), or None."""
+    b = getattr(_tls, "bound", None)
+    return None if b is None else b[1]
+
+
+def note_planes(flag):
+    """A forward uses host-prepared fp16 planes whose clamp flag is `flag` (int32 [1] on the device, non-zero: an element was
+    clamped): under a binding the bound guard ORs it into its word at its next publish(); without one nothing happens."""
+    b = getattr(_tls, "bound", None)
+    if b is not None and flag is not None and flag.device == b[1].device:
+        b[0]._pending[id(flag)] = flag
+
+
 # what a training forward publishes as its `prec` (Guard.last_prec): "train16" = the fast mode, "train32" = the tight mode
 def train_tag(opt):
     return f"train{getattr(opt, 'train_precision', 32)}"
@@ -52,6 +96,7 @@ class Guard:
         self._slots = {}            # (str(device), stream handle) -> {'host', 'event', 'calls'}
         self.last_prec = None
         self.also = set()           # other sources whose maps this word covers (pair.embed_pair: the other model's trunks)
+        self._pending = {}          # id -> clamp flag of host-prepared fp16 planes used since the last publish (note_planes)
 
     # ---- storage (eager only)
     def _word(self, dev):
@@ -87,9 +132,12 @@ class Guard:
         w = self._word(dev)
         lib = _lib.load()
         prev = lib.agp_range_flag_set(w.data_ptr())
+        prev_bound = getattr(_tls, "bound", None)
+        _tls.bound = (self, w)      # the same binding for Python callers (bound_word, note_planes)
         try:
             yield w
         finally:
+            _tls.bound = prev_bound
             lib.agp_range_flag_set(prev)
 
     def publish(self, dev, prec):
@@ -101,6 +149,10 @@ class Guard:
         w = self._word(dev)
         sl = self._slot(dev)
         capturing = torch.cuda.is_current_stream_capturing()
+        pending, self._pending = self._pending, {}
+        for flag in pending.values():
+            if flag.device == w.device:
+                w.bitwise_or_(flag)        # an elementwise kernel on the calling stream, never a memset (module docstring)
         if not capturing and sl['event'] is not None:
             sl['event'].synchronize()
             if int(sl['host'][0]) != 0:
@@ -142,6 +194,18 @@ class Guard:
         self.reset()           # the error is reported once: start again from zero
         prec = self.last_prec
         also = "".join(f"; this report also covers {a}" for a in sorted(self.also))
+        if isinstance(prec, str) and prec.startswith("cnx4"):
+            maps = prec[5:]         # "" | the mfma_precision whose fp16 maps the same word covers
+            both = (f" -- or, since this word also covers them, a feature map of precision mode {maps} (stage 2, the voxel branch) "
+                    "left fp16's range (|v| > 65504) and was stored saturated" if maps else "")
+            fix = (f"; if the saturated value was a feature map, Options.mfma_precision = 3 (split-bf16 maps, fp32 range) is the "
+                   "remedy for it" if maps else "")
+            raise ValueError(f"{self.owner}: in {which} batch an operand of the ConvNeXt trunk's precision-4 products "
+                             "(Options.convnext_precision = 4) was stored saturated (|v| > 65504 before the clamp): a block's "
+                             "LayerNorm output, the GELU output, a downsample's LayerNorm output, or an fp16 weight plane (W1, W2, "
+                             f"the downsample weight){both}. The trunk's maps and everything computed from them are wrong{also}. The "
+                             "guard reports, it does not rescue: run this trunk with Options.convnext_precision = 3 (bf16 pairs, "
+                             f"fp32 range){fix}")
         if isinstance(prec, str) and prec.startswith("train"):
             raise ValueError(f"{self.owner}: in {which} batch a training forward (Options.train_precision = {prec[5:]}) stored an fp16 "
                              "value saturated (|v| > 65504 before the clamp): a pre-BatchNorm plane or a conv1 -> conv2 plane of the "
@@ -179,6 +243,34 @@ def guarded(model, opt, prec, train):
     with g.bind(dev):
         yield
     g.publish(dev, prec)
+
+
+@contextlib.contextmanager
+def guarded_cnx(model, tag):
+    """Around inference work that runs a ConvNeXt trunk at precision 4 (`tag` from cnx_tag; None: nothing is bound): bind the model's
+    one guard, publish behind the work under `tag` -- the same word, mirrors and capture rules as guarded()."""
+    if tag is None:
+        yield
+        return
+    g, dev = guard_of(model), model_device(model)
+    with g.bind(dev):
+        yield
+    g.publish(dev, tag)
+
+
+@contextlib.contextmanager
+def bound(model, on):
+    """Bind the model's guard around a PART of its forward when `on`, publishing nothing: the caller publishes behind the whole
+    forward (publish_tag), once its side streams have joined."""
+    if not on:
+        yield
+        return
+    with guard_of(model).bind(model_device(model)):
+        yield
+
+
+def publish_tag(model, tag):
+    guard_of(model).publish(model_device(model), tag)
 
 
 @contextlib.contextmanager

@@ -103,6 +103,12 @@ const char* agp_arch(void);
  * semantics above; both fold their ReLU in front of the conversion, so with it a negative value is stored as 0, not clamped,
  * and does not count.  A call that stores only a split-bf16 pair launches the unguarded kernel whatever is bound.
  *
+ * The ConvNeXt trunk's precision-4 entries are guarded too (Options.convnext_range_guard binds around them): agp_cnx_dwconv_ln_f16_fwd
+ * (the LayerNorm output it rounds into the fp16 operand plane), agp_cnx_mlp_f16_fwd (the GELU output it rounds in registers) and
+ * agp_cnx_downsample_f16_fwd (the normalised operand it rounds into LDS) report |v| > 65504 before their symmetric clamp, for values
+ * of real pixels only (never a tile's padding rows or out-of-image positions).  Their precision-3 forms store no fp16 and read no
+ * binding.
+ *
  * agp_range_flag_set binds `word` (a device pointer, or NULL to unbind) and returns the previous binding of this thread;
  * agp_range_flag_get returns the current one.  Neither touches the device. */
 uint32_t* agp_range_flag_set(uint32_t* word);

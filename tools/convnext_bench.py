@@ -4,9 +4,11 @@ the same batch for context; then one training forward + backward of '2_2_2' (the
 no stochastic depth) and each backward entry alone.
 
 python tools/convnext_bench.py [--batch 64] [--size 256] [--reps 10] [--windows 5] [--json out.json] [--train-only]
-                               [--precision {3,4}] [--infer-only]
+                               [--precision {3,4}] [--infer-only] [--range-guard]
 --precision 4 times the inference legs in the opt-in one-product fp16 mode (Options.convnext_precision = 4); the training leg runs
-in mode 3 whatever the precision and is skipped then.
+in mode 3 whatever the precision and is skipped then.  --range-guard (with --precision 4 only) turns Options.convnext_range_guard on
+for the measured trunks -- each eager forward then binds the module's fp16 range guard and publishes behind it -- and binds a guard's
+word around the per-kernel legs, which then run the guarded twins.
 Events on the launch stream around `reps` back-to-back calls, the median of `windows` such windows after a warm-up.  GMAC are
 algorithmic (one multiply-accumulate per weight use, whatever the three bf16 products cost); the fraction of peak is
 2 * MAC / time over the 2.5 PFLOP/s dense bf16 peak.  Weights are seeded random values (zeros would flatter the clock)."""
@@ -20,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import bench_inputs  # noqa: E402
-from agplace_amd import convnext as cnx  # noqa: E402
+from agplace_amd import convnext as cnx, range_guard  # noqa: E402
+from agplace_amd.options import Options  # noqa: E402
 from agplace_amd.network.image_fe import ImageFE  # noqa: E402
 
 PEAK = 2.5e15
@@ -131,9 +134,12 @@ def main():
     ap.add_argument("--train-only", action="store_true", help="skip the inference legs")
     ap.add_argument("--infer-only", action="store_true", help="skip the training leg")
     ap.add_argument("--precision", type=int, choices=(3, 4), default=3, help="ConvNeXt inference precision (Options.convnext_precision)")
+    ap.add_argument("--range-guard", action="store_true", help="Options.convnext_range_guard on the measured model (--precision 4 only)")
     a = ap.parse_args()
     prec = a.precision
-    tag = "" if prec == 3 else ", prec 4"
+    if a.range_guard and prec != 4:
+        ap.error("--range-guard needs --precision 4 (the guard covers the fp16 operands of that mode only)")
+    tag = "" if prec == 3 else ", prec 4" + (", range guard" if a.range_guard else "")
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
     n, hw = a.batch, a.size
@@ -152,6 +158,9 @@ def main():
         sizes = cnx.ConvNeXt.map_sizes(hw, hw)
         _, per = convnext_macs([3, 3, 9], hw, hw)
         prep = fe.fe._prepared(prec)
+        if a.range_guard:       # the guarded twins: a word bound for the whole per-kernel section
+            bound = range_guard.Guard("convnext_bench").bind(dev)
+            bound.__enter__()
         report("stem", n * per["stem"], timed(lambda: cnx.stem_fwd(x, prep["stem"]), a.reps, a.windows))
         for s, (h, w) in enumerate(sizes):
             c = cnx.DIMS[s]
@@ -165,10 +174,12 @@ def main():
                 d = prep[("down", s)]
                 report(f"ln+downsample C={c} {h}x{w}", n * per[("down", c)], timed(lambda: cnx.downsample_fwd(cur, d, prec), a.reps, a.windows))
             del cur, ws, out
+        if a.range_guard:
+            bound.__exit__(None, None, None)
         # ---- whole trunks
         for layers in ("2_2_2", "3_3_9"):
-            fe = randomize(ImageFE("convnext_tiny", layers), 0).to(dev).eval()
-            fe.fe.set_precision(prec)
+            fe = randomize(ImageFE("convnext_tiny", layers, opt=Options(convnext_precision=prec, convnext_range_guard=a.range_guard)),
+                           0).to(dev).eval()
             macs, _ = convnext_macs([int(v) for v in layers.split("_")], hw, hw)
             report(f"convnext_tiny {layers} trunk{tag}", n * macs, timed(lambda: fe(x), max(2, a.reps // 2), a.windows))
             del fe
@@ -180,7 +191,8 @@ def main():
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
-            json.dump({"batch": n, "size": hw, "reps": a.reps, "windows": a.windows, **({} if prec == 3 else {"precision": prec}), "rows": rows}, f, indent=1)
+            json.dump({"batch": n, "size": hw, "reps": a.reps, "windows": a.windows, **({} if prec == 3 else {"precision": prec}),
+                       **({"range_guard": True} if a.range_guard else {}), "rows": rows}, f, indent=1)
 
 
 if __name__ == "__main__":
