@@ -154,13 +154,22 @@ template <bool RG> struct RangeTrack {
         }
     }
 };
-// The bound word reaches a guarded kernel as a TRAILING argument the unguarded instantiation does not have (a parameter pack
-// `RF... rf`, empty when unguarded): appending it to an argument struct, or appending a fixed argument, grows the kernel-argument
-// segment, and the compiler may then merge the scalar loads of the last fields differently (it did for igemm_kxr2, igemm_s2,
-// fblock64 and stem_walk) -- the unguarded code would change.
+// A guarded kernel and its unguarded twin are two instantiations of one template.  Two forms, each with one host-side switch:
+//   the `bool RG` form  the word is a field of the kernel's params struct, or an argument beside it that both instantiations
+//                       take (igemm, igemm_d16, igemm_kxrw).  The launcher is itself a template on RG and is reached through
+//                       agp_rg_dispatch.  Only for a kernel that is already written this way, or whose launcher does more
+//                       with RG than launch (fills the struct, picks among instantiations); stem_walk's launcher is of this
+//                       form around a kernel of the next one.
+//   the pack form       the word is a TRAILING argument the unguarded instantiation does not have (a parameter pack
+//                       `RF... rf`, empty when unguarded; RangeTrack<sizeof...(RF) != 0>, flush(rg_word(rf...))).  Launched
+//                       through agp_launch_rg (end of this file), which takes the pair and the argument list once.  For
+//                       every new twin: appending the word to an argument struct, or appending a fixed argument, grows the
+//                       kernel-argument segment, and the compiler may then merge the scalar loads of the last fields
+//                       differently (it did for igemm_kxr2, igemm_s2, fblock64 and stem_walk) -- the unguarded code would change.
+// Either way a launcher reads agp_range_flag_get() on every call and never keeps the word.
 __device__ __forceinline__ uint32_t* rg_word() { return nullptr; }
 __device__ __forceinline__ uint32_t* rg_word(uint32_t* w) { return w; }
-// Host: call fn(std::integral_constant<bool, RG>) with RG = (word != NULL) -- the launcher's one switch between the two forms.
+// Host, the `bool RG` form: call fn(std::integral_constant<bool, RG>) with RG = (word != NULL).
 #include <type_traits>
 template <class F> static inline int agp_rg_dispatch(const uint32_t* word, F&& fn) {
     return word ? fn(std::true_type{}) : fn(std::false_type{});
@@ -320,3 +329,21 @@ static inline bool agp_lds_attr(const void* fn, int bytes, std::atomic<uint64_t>
 // Launch wrapper: drop any stale (not ours) sticky HIP error first, so that AGP_CHECK_LAUNCH
 // reports only the status of this launch.
 #define AGP_LAUNCH (void)hipGetLastError(); hipLaunchKernelGGL
+
+// The pack form of a guarded kernel pair (see rg_word above): launch Guarded with `rf` appended when a word is bound, Plain
+// otherwise, the arguments written once.  What AGP_LAUNCH + AGP_CHECK_LAUNCH do, as a value: AGP_OK or AGP_E_LAUNCH.
+// lds_attr != 0 raises the launched twin's dynamic-LDS limit to that many bytes first (agp_lds_attr; the mask lives here, one
+// per kernel).  AGP_RG_TWINS(K, T...) names the pair of a kernel with leading template arguments; without any, write
+// `K<>, K<uint32_t*>`.
+template <auto Plain, auto Guarded, class... B>
+static inline int agp_launch_rg(uint32_t* rf, dim3 grid, dim3 block, int lds, int lds_attr, hipStream_t s, const B&... args) {
+    if (lds_attr) {
+        static std::atomic<uint64_t> attr_done[2];
+        if (!agp_lds_attr(rf ? (const void*)Guarded : (const void*)Plain, lds_attr, attr_done[rf != nullptr])) return AGP_E_LAUNCH;
+    }
+    (void)hipGetLastError();
+    if (rf) hipLaunchKernelGGL(Guarded, grid, block, lds, s, args..., rf);
+    else hipLaunchKernelGGL(Plain, grid, block, lds, s, args...);
+    return hipGetLastError() == hipSuccess ? AGP_OK : AGP_E_LAUNCH;
+}
+#define AGP_RG_TWINS(K, ...) K<__VA_ARGS__>, K<__VA_ARGS__, uint32_t*>

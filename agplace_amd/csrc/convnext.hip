@@ -568,17 +568,14 @@ int agp_cnx_dwconv_ln_f16_fwd(const float* x, int n, int h, int w, int C, const 
     const int ty = (h + 3) / 4, tx = (w + 7) / 8;
     const dim3 grid((unsigned)((long long)n * ty * tx));
     hipStream_t s = (hipStream_t)stream;
-    // the guarded twin while a range-guard word is bound (common.hpp RangeTrack); here and in the two launchers below
-    if (uint32_t* const rf = agp_range_flag_get()) {
-#define CNX_DW_G(CC) AGP_LAUNCH((cnx_dwconv_ln_kernel<CC, 4, uint32_t*>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none, rf)
-        if (C == 96) { CNX_DW_G(96); } else if (C == 192) { CNX_DW_G(192); } else { CNX_DW_G(384); }
-#undef CNX_DW_G
-    }
-    else if (C == 96) { AGP_LAUNCH((cnx_dwconv_ln_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
-    else if (C == 192) { AGP_LAUNCH((cnx_dwconv_ln_kernel<192, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
-    else { AGP_LAUNCH((cnx_dwconv_ln_kernel<384, 4>), grid, dim3(256), 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none); }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    // the guarded twin while a range-guard word is bound (common.hpp agp_launch_rg); here and in the two launchers below
+    auto launch = [&](auto cc) {
+        return agp_launch_rg<AGP_RG_TWINS(cnx_dwconv_ln_kernel, decltype(cc)::value, 4)>(
+            agp_range_flag_get(), grid, dim3(256), 0, 0, s, x, h, w, ty, tx, wt, bias, ln_w, ln_b, eps, xp, none);
+    };
+    if (C == 96) return launch(std::integral_constant<int, 96>{});
+    if (C == 192) return launch(std::integral_constant<int, 192>{});
+    return launch(std::integral_constant<int, 384>{});
 }
 
 int agp_cnx_mlp_f16_fwd(const void* workspace, int64_t workspace_bytes, int64_t P, int C, const void* w1, const float* b1,
@@ -592,16 +589,14 @@ int agp_cnx_mlp_f16_fwd(const void* workspace, int64_t workspace_bytes, int64_t 
     const float* const norows = nullptr;
     const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
     hipStream_t s = (hipStream_t)stream;
-#define CNX_MLP_H(CC) AGP_LAUNCH((cnx_mlp_kernel<CC, false, 4>), grid, dim3(256), 0, s, xp, nox, (long long)P, a, now, b1, c, now, b2, layer_scale, resid, out, norows, 0ll)
-#define CNX_MLP_G(CC) AGP_LAUNCH((cnx_mlp_kernel<CC, false, 4, uint32_t*>), grid, dim3(256), 0, s, xp, nox, (long long)P, a, now, b1, c, now, b2, layer_scale, resid, out, norows, 0ll, rf)
-    if (uint32_t* const rf = agp_range_flag_get()) {
-        if (C == 96) { CNX_MLP_G(96); } else if (C == 192) { CNX_MLP_G(192); } else { CNX_MLP_G(384); }
-    }
-    else if (C == 96) { CNX_MLP_H(96); } else if (C == 192) { CNX_MLP_H(192); } else { CNX_MLP_H(384); }
-#undef CNX_MLP_G
-#undef CNX_MLP_H
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    auto launch = [&](auto cc) {
+        return agp_launch_rg<AGP_RG_TWINS(cnx_mlp_kernel, decltype(cc)::value, false, 4)>(
+            agp_range_flag_get(), grid, dim3(256), 0, 0, s, xp, nox, (long long)P, a, now, b1, c, now, b2, layer_scale, resid, out, norows,
+            0ll);
+    };
+    if (C == 96) return launch(std::integral_constant<int, 96>{});
+    if (C == 192) return launch(std::integral_constant<int, 192>{});
+    return launch(std::integral_constant<int, 384>{});
 }
 
 int agp_cnx_downsample_f16_fwd(const float* x, int n, int h, int w, int C, const float* ln_w, const float* ln_b, float eps,
@@ -613,16 +608,13 @@ int agp_cnx_downsample_f16_fwd(const float* x, int n, int h, int w, int C, const
     const dim3 grid((unsigned)((P + CNX_TP - 1) / CNX_TP));
     hipStream_t s = (hipStream_t)stream;
     const bf16x8 *a = (const bf16x8*)wt, *none = nullptr;
-    if (uint32_t* const rf = agp_range_flag_get()) {
-#define CNX_DS_G(CC) AGP_LAUNCH((cnx_downsample_kernel<CC, 4, uint32_t*>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out, rf)
-        if (C == 96) { CNX_DS_G(96); } else if (C == 192) { CNX_DS_G(192); } else { CNX_DS_G(384); }
-#undef CNX_DS_G
-    }
-    else if (C == 96) { AGP_LAUNCH((cnx_downsample_kernel<96, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
-    else if (C == 192) { AGP_LAUNCH((cnx_downsample_kernel<192, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
-    else { AGP_LAUNCH((cnx_downsample_kernel<384, 4>), grid, dim3(256), 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out); }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    auto launch = [&](auto cc) {
+        return agp_launch_rg<AGP_RG_TWINS(cnx_downsample_kernel, decltype(cc)::value, 4)>(
+            agp_range_flag_get(), grid, dim3(256), 0, 0, s, x, h, w, ho, wo, P, ln_w, ln_b, eps, a, none, bias, out);
+    };
+    if (C == 96) return launch(std::integral_constant<int, 96>{});
+    if (C == 192) return launch(std::integral_constant<int, 192>{});
+    return launch(std::integral_constant<int, 384>{});
 }
 
 }  // extern "C"

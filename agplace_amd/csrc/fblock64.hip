@@ -560,24 +560,14 @@ extern "C" int agp_bblock64_fwd_grouped(const agp_bblock64_desc* descs, int n, v
         g.wg_end[i] = wg;
     }
     const int form = descs[0].form == 0 ? 1 : 0;                // kernel template argument M16 (agp_bblock64_desc::form)
-    static std::atomic<uint64_t> attr_done[2][2][2];
-    uint32_t* const rflag = agp_range_flag_get();
-    // (RF...: the guarded instantiations take the word as one more argument, see common.hpp rg_word)
-    auto launch = [&](auto... rf) {
-        constexpr bool RG = sizeof...(rf) != 0;
-        const void* fn = pool ? (form ? (const void*)fblock64_kernel<true, true, decltype(rf)...> : (const void*)fblock64_kernel<true, false, decltype(rf)...>)
-                              : (form ? (const void*)fblock64_kernel<false, true, decltype(rf)...> : (const void*)fblock64_kernel<false, false, decltype(rf)...>);
-        const int lds = pool ? lds_bytes<true>() : lds_bytes<false>();
-        if (!agp_lds_attr(fn, lds, attr_done[RG][pool][form])) return AGP_E_LAUNCH;
-        (void)hipGetLastError();
-        if (pool && form) hipLaunchKernelGGL((fblock64_kernel<true, true, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
-        else if (pool) hipLaunchKernelGGL((fblock64_kernel<true, false, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
-        else if (form) hipLaunchKernelGGL((fblock64_kernel<false, true, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
-        else hipLaunchKernelGGL((fblock64_kernel<false, false, decltype(rf)...>), dim3(wg), dim3(512), lds, (hipStream_t)stream, g, rf...);
-        AGP_CHECK_LAUNCH();
-        return AGP_OK;
+    // the (pool, form) pair of twins (common.hpp agp_launch_rg), its dynamic LDS raised to what it uses
+    auto launch = [&](auto po, auto m16) {
+        constexpr int lds = lds_bytes<decltype(po)::value>();
+        return agp_launch_rg<AGP_RG_TWINS(fblock64_kernel, decltype(po)::value, decltype(m16)::value)>(
+            agp_range_flag_get(), dim3(wg), dim3(512), lds, lds, (hipStream_t)stream, g);
     };
-    return rflag ? launch(rflag) : launch();
+    if (pool) return form ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
+    return form ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
 }
 
 // mean_out[i][c] = (sum of image i's pair sums [pair][strip][c]) / (h w), fixed order: 16 slices of the entries per channel

@@ -684,27 +684,23 @@ template <int BM, int BN, int WM, int WN, int NPREC, int RING, bool LDS_EPI = fa
 int launch_kxr(IgemmParams& p, hipStream_t s, TilePlan* plan) {
     constexpr int lds = kxr_lds_bytes<BM, BN, WM, WN, NPREC, RING>();
     static_assert(lds <= (kxr_min_blocks<BM, BN, WM, WN, RING, NPREC>() == 3 ? 53 : 80) * 1024, "LDS budget of the intended workgroups per CU");
-    static std::atomic<uint64_t> attr_done{0}, attr_done_rg{0};
     const XcdGrid xg = xcd_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
     if (plan) return plan_xcd(plan, AGP_CONV_KERNEL_KXR, BM, BN, xg);
     p.MT = xg.MT;
     p.NT = xg.NT;
     p.mt_chunk = xg.mt_chunk;
-    // fp16 maps (modes 2 / 4): the guarded twin while a range-guard word is bound (common.hpp RangeTrack)
+    // fp16 maps (modes 2 / 4): the guarded twin while a range-guard word is bound (common.hpp agp_launch_rg); the other modes
+    // have no twin (it is not instantiated) and never read the word
     if constexpr (PrecT<NPREC>::F16) {
-        if (uint32_t* const rflag = agp_range_flag_get()) {
-            if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8, uint32_t*>, lds, attr_done_rg))
-                return AGP_E_LAUNCH;
-            AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8, uint32_t*>), dim3(xg.blocks),
-                       dim3(WM * WN * 64), lds, s, p, rflag);
-            AGP_CHECK_LAUNCH();
-            return AGP_OK;
-        }
+        return agp_launch_rg<AGP_RG_TWINS(igemm_kxr_kernel, BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8)>(
+            agp_range_flag_get(), dim3(xg.blocks), dim3(WM * WN * 64), lds, lds, s, p);
+    } else {
+        static std::atomic<uint64_t> attr_done{0};
+        if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
+        AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8>), dim3(xg.blocks), dim3(WM * WN * 64), lds, s, p);
+        AGP_CHECK_LAUNCH();
+        return AGP_OK;
     }
-    if (!agp_lds_attr((const void*)igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8>, lds, attr_done)) return AGP_E_LAUNCH;
-    AGP_LAUNCH((igemm_kxr_kernel<BM, BN, WM, WN, NPREC, RING, LDS_EPI, Q8>), dim3(xg.blocks), dim3(WM * WN * 64), lds, s, p);
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
 }
 
 }  // namespace agp_igemm

@@ -495,11 +495,11 @@ __global__ void __launch_bounds__(256, KXR2_MINB) igemm_kxr2_kernel(Kxr2Group g,
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <bool POOL, bool RG>
-int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
+// rf: the entry point's one read of the range guard's word (NULL: the plain kernel)
+template <bool POOL>
+int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan, uint32_t* rf) {
     constexpr int BM = KXR2_BM, lds = kxr2_lds_bytes();
     static_assert(lds * KXR2_MINB <= 160 * 1024, "LDS budget of the intended workgroups per CU");
-    static std::atomic<uint64_t> attr_done{0};
     int mt = 0;
     for (int i = 0; i < g.nprob; ++i) {
         mt += (g.p[i].M + BM - 1) / BM;
@@ -510,14 +510,7 @@ int launch_kxr2(Kxr2Group& g, hipStream_t s, TilePlan* plan) {
     g.MT = xg.MT;
     g.NT = xg.NT;
     g.mt_chunk = xg.mt_chunk;
-    if (!agp_lds_attr(RG ? (const void*)igemm_kxr2_kernel<POOL, uint32_t*> : (const void*)igemm_kxr2_kernel<POOL>, lds, attr_done)) return AGP_E_LAUNCH;
-    if constexpr (RG) {
-        AGP_LAUNCH((igemm_kxr2_kernel<POOL, uint32_t*>), dim3(xg.blocks), dim3(256), lds, s, g, agp_range_flag_get());
-    } else {
-        AGP_LAUNCH((igemm_kxr2_kernel<POOL>), dim3(xg.blocks), dim3(256), lds, s, g);
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<AGP_RG_TWINS(igemm_kxr2_kernel, POOL)>(rf, dim3(xg.blocks), dim3(256), lds, lds, s, g);
 }
 
 }  // namespace agp_igemm
@@ -536,9 +529,7 @@ int agp_internal_conv_kxr2(agp_igemm::IgemmParams* ps, int n, hipStream_t s, agp
     }
     bool pool = false;
     for (int i = 0; i < n; ++i) pool = pool || ps[i].pool_partial != nullptr;
-    return agp_rg_dispatch(agp_range_flag_get(), [&](auto rg) {
-        constexpr bool RG = decltype(rg)::value;
-        if (pool) return launch_kxr2<true, RG>(g, s, plan);     // (agp_conv2d_pool_blocks promises this tile shape)
-        return launch_kxr2<false, RG>(g, s, plan);
-    });
+    uint32_t* const rf = agp_range_flag_get();
+    if (pool) return launch_kxr2<true>(g, s, plan, rf);     // (agp_conv2d_pool_blocks promises this tile shape)
+    return launch_kxr2<false>(g, s, plan, rf);
 }

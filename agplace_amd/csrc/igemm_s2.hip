@@ -385,29 +385,20 @@ int agp_internal_conv_s2(agp_igemm::IgemmParams* ps, const agp_conv_desc* descs,
     g.MT = mt;
     g.mt_chunk = (g.MT + 7) / 8;
     const int wide = AGP_TUNE("S2_WIDE", 1);            // development build, 0: 64-channel tiles for every width
-    auto launch = [&](auto kern, int lds, std::atomic<uint64_t>& attr, auto... rf) -> int {
-        if (!agp_lds_attr((const void*)kern, lds, attr)) return AGP_E_LAUNCH;
-        AGP_LAUNCH(kern, dim3(g.mt_chunk * 8 * g.NT), dim3(256), lds, s, g, rf...);
-        return AGP_OK;
-    };
-    static std::atomic<uint64_t> a4s{0}, a2s{0}, a4g{0}, a2g{0};
-    uint32_t* const rflag = agp_range_flag_get();
     const bool w4 = wide && ps[0].N % 128 == 0;
     g.NT = w4 ? ps[0].N / 128 : (ps[0].N + 63) / 64;
     if (plan) {
         *plan = TilePlan{AGP_CONV_KERNEL_S2, S2_BM, w4 ? 128 : 64, g.MT, g.NT, g.MT, 0, g.mt_chunk * 8 * g.NT};
         return AGP_OK;
     }
-    int rc;
-    if (nods) {
-        static std::atomic<uint64_t> n4s{0}, n2s{0}, n4g{0}, n2g{0};
-        if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, true, uint32_t*>, s2_lds<4, true>(), n4g, rflag)
-                           : launch(igemm_s2_kernel<2, true, uint32_t*>, s2_lds<2, true>(), n2g, rflag);
-        else rc = w4 ? launch(igemm_s2_kernel<4, true>, s2_lds<4, true>(), n4s) : launch(igemm_s2_kernel<2, true>, s2_lds<2, true>(), n2s);
-    } else if (rflag) rc = w4 ? launch(igemm_s2_kernel<4, false, uint32_t*>, s2_lds<4>(), a4g, rflag)
-                              : launch(igemm_s2_kernel<2, false, uint32_t*>, s2_lds<2>(), a2g, rflag);
-    else rc = w4 ? launch(igemm_s2_kernel<4, false>, s2_lds<4>(), a4s) : launch(igemm_s2_kernel<2, false>, s2_lds<2>(), a2s);
-    if (rc != AGP_OK) return rc;
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    // the (w4, nods) pair of twins (common.hpp agp_launch_rg), its dynamic LDS raised to what it uses
+    auto launch = [&](auto tn, auto nd) {
+        constexpr int TN = decltype(tn)::value, lds = s2_lds<TN, decltype(nd)::value>();
+        return agp_launch_rg<AGP_RG_TWINS(igemm_s2_kernel, TN, decltype(nd)::value)>(
+            agp_range_flag_get(), dim3(g.mt_chunk * 8 * g.NT), dim3(256), lds, lds, s, g);
+    };
+    using T4 = std::integral_constant<int, 4>;
+    using T2 = std::integral_constant<int, 2>;
+    if (nods) return w4 ? launch(T4{}, std::true_type{}) : launch(T2{}, std::true_type{});
+    return w4 ? launch(T4{}, std::false_type{}) : launch(T2{}, std::false_type{});
 }

@@ -432,16 +432,9 @@ extern "C" int agp_pack_f32_to_nhwc4_h16(const float* x, int64_t sn, int64_t sc,
           (int64_t)n * h * (w / 4) < (1ll << 31)))
         return AGP_E_UNSUPPORTED;
     const int64_t threads = (int64_t)n * h * (w / 4);
-    if (uint32_t* const rf = agp_range_flag_get()) {
-        AGP_LAUNCH((pack_nchw4_kernel<uint32_t*>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc,
-                   sh, n, c, h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)h16,
-                   rf);
-    } else {
-        AGP_LAUNCH((pack_nchw4_kernel<>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, n, c,
-                   h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)h16);
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<pack_nchw4_kernel<>, pack_nchw4_kernel<uint32_t*>>(
+        agp_range_flag_get(), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, x, sn, sc, sh, n, c, h, w,
+        pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)h16);
 }
 
 extern "C" int agp_pack_f32_to_nhwc(const float* x, int64_t sn, int64_t sc, int64_t sh, int64_t sw,
@@ -452,38 +445,19 @@ extern "C" int agp_pack_f32_to_nhwc(const float* x, int64_t sn, int64_t sc, int6
     if (cpad == 4 && sw == 1 && c <= 4 && w % 4 == 0 && ((uintptr_t)x % 16) == 0 && sn % 4 == 0 && sc % 4 == 0 && sh % 4 == 0 &&
         (int64_t)n * h * (w / 4) < (1ll << 31)) {
         const int64_t threads = (int64_t)n * h * (w / 4);
-        if (rf) {
-            AGP_LAUNCH((pack_nchw4_kernel<uint32_t*>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn,
-                       sc, sh, n, c, h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo,
-                       (bf16_t*)nullptr, rf);
-        } else {
-            AGP_LAUNCH((pack_nchw4_kernel<>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh,
-                       n, c, h, w, pad, make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo,
-                       (bf16_t*)nullptr);
-        }
-    } else if (cpad == 4) {
-        if (rf) {
-            AGP_LAUNCH((pack_kernel<4, uint32_t*>), dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0, (hipStream_t)stream, x, sn, sc,
-                       sh, sw, n, c, h, w, cpad, pad, (bf16_t*)hi, (bf16_t*)lo, rf);
-        } else {
-            AGP_LAUNCH(pack_kernel<4>, dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0,
-                               (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad, pad,
-                               (bf16_t*)hi, (bf16_t*)lo);
-        }
-    } else if (cpad % 8 == 0) {
-        if (rf) {
-            AGP_LAUNCH((pack_kernel<8, uint32_t*>), dim3(grid_for((int64_t)n * h * w * (cpad / 8), 256)), dim3(256), 0, (hipStream_t)stream,
-                       x, sn, sc, sh, sw, n, c, h, w, cpad, pad, (bf16_t*)hi, (bf16_t*)lo, rf);
-        } else {
-            AGP_LAUNCH(pack_kernel<8>, dim3(grid_for((int64_t)n * h * w * (cpad / 8), 256)),
-                               dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad,
-                               pad, (bf16_t*)hi, (bf16_t*)lo);
-        }
-    } else {
-        return AGP_E_BADARG;
+        return agp_launch_rg<pack_nchw4_kernel<>, pack_nchw4_kernel<uint32_t*>>(
+            rf, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, (hipStream_t)stream, x, sn, sc, sh, n, c, h, w, pad,
+            make_fastdiv((uint32_t)(w / 4)), make_fastdiv((uint32_t)h), (bf16_t*)hi, (bf16_t*)lo, (bf16_t*)nullptr);
     }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    if (cpad == 4)
+        return agp_launch_rg<AGP_RG_TWINS(pack_kernel, 4)>(rf, dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0, 0,
+                                                           (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad, pad, (bf16_t*)hi,
+                                                           (bf16_t*)lo);
+    if (cpad % 8 == 0)
+        return agp_launch_rg<AGP_RG_TWINS(pack_kernel, 8)>(rf, dim3(grid_for((int64_t)n * h * w * (cpad / 8), 256)), dim3(256), 0, 0,
+                                                           (hipStream_t)stream, x, sn, sc, sh, sw, n, c, h, w, cpad, pad, (bf16_t*)hi,
+                                                           (bf16_t*)lo);
+    return AGP_E_BADARG;
 }
 
 extern "C" int agp_pack_u8_cams_to_nhwc(const uint8_t* img, int n, int ncam, int h, int w, const float* mean3,
@@ -543,14 +517,7 @@ extern "C" int agp_bcast_add_fwd(const void* in_hi, const void* in_lo, const flo
                                  int w, int c, int pin, void* out_hi, void* out_lo, int pout,
                                  void* stream) {
     if (!in_hi || !out_hi || !vec || c % 8 || n <= 0) return AGP_E_BADARG;
-    if (uint32_t* const rf = agp_range_flag_get()) {
-        AGP_LAUNCH((bcast_add_kernel<uint32_t*>), dim3(grid_for((int64_t)n * h * w * (c / 8), 256)), dim3(256), 0, (hipStream_t)stream,
-                   (const bf16_t*)in_hi, (const bf16_t*)in_lo, vec, n, h, w, c, pin, (bf16_t*)out_hi, (bf16_t*)out_lo, pout, rf);
-    } else {
-        AGP_LAUNCH((bcast_add_kernel<>), dim3(grid_for((int64_t)n * h * w * (c / 8), 256)), dim3(256),
-                           0, (hipStream_t)stream, (const bf16_t*)in_hi, (const bf16_t*)in_lo, vec, n, h,
-                           w, c, pin, (bf16_t*)out_hi, (bf16_t*)out_lo, pout);
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<bcast_add_kernel<>, bcast_add_kernel<uint32_t*>>(
+        agp_range_flag_get(), dim3(grid_for((int64_t)n * h * w * (c / 8), 256)), dim3(256), 0, 0, (hipStream_t)stream,
+        (const bf16_t*)in_hi, (const bf16_t*)in_lo, vec, n, h, w, c, pin, (bf16_t*)out_hi, (bf16_t*)out_lo, pout);
 }

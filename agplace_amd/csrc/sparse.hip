@@ -673,15 +673,9 @@ extern "C" int agp_sparse_conv_cin1_fwd(const float* f, int64_t n_in, const int3
                                         int cout, const float* scale, const float* shift, int relu, void* out_hi, void* out_lo,
                                         const int64_t* n_dev, void* stream) {
     if (!f || !nbr || !w || !out_hi || n_out <= 0 || cout % 8 || ntaps <= 0) return AGP_E_BADARG;
-    if (uint32_t* const rf = agp_range_flag_get()) {
-        AGP_LAUNCH((conv_cin1_kernel<uint32_t*>), dim3(grid_for(n_out * (cout / 8))), dim3(256), 0, (hipStream_t)stream, f, nbr, n_in,
-                   n_out, ntaps, w, cout, scale, shift, relu, BF(out_hi), BF(out_lo), n_dev, rf);
-    } else {
-        AGP_LAUNCH((conv_cin1_kernel<>), dim3(grid_for(n_out * (cout / 8))), dim3(256), 0, (hipStream_t)stream, f, nbr, n_in, n_out,
-                   ntaps, w, cout, scale, shift, relu, BF(out_hi), BF(out_lo), n_dev);
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<conv_cin1_kernel<>, conv_cin1_kernel<uint32_t*>>(
+        agp_range_flag_get(), dim3(grid_for(n_out * (cout / 8))), dim3(256), 0, 0, (hipStream_t)stream, f, nbr, n_in, n_out, ntaps, w,
+        cout, scale, shift, relu, BF(out_hi), BF(out_lo), n_dev);
 }
 
 extern "C" int agp_sparse_conv0_fwd(const int64_t* keys, int64_t cap, const int64_t* n_dev, const float* f, int ksize, int stride,
@@ -696,50 +690,25 @@ extern "C" int agp_sparse_conv0_fwd(const int64_t* keys, int64_t cap, const int6
         const int lds = (C0_ROWS + cout) * (KP * 2 + 16) + C0_WK * 12;
         const int tiles = (int)((cap + C0_ROWS - 1) / C0_ROWS);
         const int grid = tiles < 1024 ? tiles : 1024;
-        uint32_t* const rf = agp_range_flag_get();
-        if (cout == 32) {
-            if (rf) {
-                AGP_LAUNCH((conv0_mfma_kernel<32, uint32_t*>), dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale,
-                               shift, relu, BF(out_hi), seg_off, KP, rf);
-            } else {
-                AGP_LAUNCH(conv0_mfma_kernel<32>, dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
-                            BF(out_hi), seg_off, KP);
-            }
-        } else {
-            static std::atomic<uint64_t> attr_done{0}, attr_done_rg{0};
-            if (rf) {
-                if (!agp_lds_attr((const void*)conv0_mfma_kernel<64, uint32_t*>, 96 * 1024, attr_done_rg)) return AGP_E_LAUNCH;
-                AGP_LAUNCH((conv0_mfma_kernel<64, uint32_t*>), dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale,
-                           shift, relu, BF(out_hi), seg_off, KP, rf);
-            } else {
-                if (!agp_lds_attr((const void*)conv0_mfma_kernel<64>, 96 * 1024, attr_done)) return AGP_E_LAUNCH;
-                AGP_LAUNCH(conv0_mfma_kernel<64>, dim3(grid), dim3(256), lds, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
-                           BF(out_hi), seg_off, KP);
-            }
-        }
-        AGP_CHECK_LAUNCH();
-        return AGP_OK;
-    }
-    uint32_t* const rf = agp_range_flag_get();
-    if (cout == 32) {
-        if (rf) {
-            AGP_LAUNCH((conv0_search_kernel<32, uint32_t*>), dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w,
-                           scale, shift, relu, BF(out_hi), BF(out_lo), seg_off, rf);
-        } else {
-            AGP_LAUNCH(conv0_search_kernel<32>, dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift,
-                        relu, BF(out_hi), BF(out_lo), seg_off);
-        }
-    } else {
-        if (rf) {
-            AGP_LAUNCH((conv0_search_kernel<64, uint32_t*>), dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w,
-                           scale, shift, relu, BF(out_hi), BF(out_lo), seg_off, rf);
-        } else {
-            AGP_LAUNCH(conv0_search_kernel<64>, dim3(grid_for(cap)), dim3(256), 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift,
-                        relu, BF(out_hi), BF(out_lo), seg_off);
+        auto launch = [&](auto co, int lds_attr) {
+            return agp_launch_rg<AGP_RG_TWINS(conv0_mfma_kernel, decltype(co)::value)>(
+                agp_range_flag_get(), dim3(grid), dim3(256), lds, lds_attr, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
+                BF(out_hi), seg_off, KP);
+        };
+        switch (cout) {
+            case 32: return launch(std::integral_constant<int, 32>{}, 0);
+            default: return launch(std::integral_constant<int, 64>{}, 96 * 1024);
         }
     }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    auto launch = [&](auto co) {
+        return agp_launch_rg<AGP_RG_TWINS(conv0_search_kernel, decltype(co)::value)>(
+            agp_range_flag_get(), dim3(grid_for(cap)), dim3(256), 0, 0, s, keys, cap, n_dev, f, ksize, stride, w, scale, shift, relu,
+            BF(out_hi), BF(out_lo), seg_off);
+    };
+    switch (cout) {
+        case 32: return launch(std::integral_constant<int, 32>{});
+        default: return launch(std::integral_constant<int, 64>{});
+    }
 }
 
 extern "C" int agp_sparse_kernel_map(const int64_t* in_keys, int64_t n_in, const int64_t* out_keys, int64_t n_out,
@@ -782,15 +751,9 @@ extern "C" int agp_seg_affine_fwd(const void* y_hi, const void* y_lo, const int3
                                   const void* r_hi, const void* r_lo, int64_t n, int c, int relu, void* o_hi, void* o_lo,
                                   const int64_t* n_dev, void* stream) {
     if (!y_hi || !bidx || !o_hi || n <= 0 || c % 8) return AGP_E_BADARG;
-    if (uint32_t* const rf = agp_range_flag_get()) {
-        AGP_LAUNCH((seg_affine_kernel<uint32_t*>), dim3(grid_for(n * (c / 8))), dim3(256), 0, (hipStream_t)stream, CBF(y_hi), CBF(y_lo),
-                   bidx, scale, add, CBF(r_hi), CBF(r_lo), n, c, relu, BF(o_hi), BF(o_lo), n_dev, rf);
-    } else {
-        AGP_LAUNCH((seg_affine_kernel<>), dim3(grid_for(n * (c / 8))), dim3(256), 0, (hipStream_t)stream, CBF(y_hi), CBF(y_lo), bidx,
-                   scale, add, CBF(r_hi), CBF(r_lo), n, c, relu, BF(o_hi), BF(o_lo), n_dev);
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<seg_affine_kernel<>, seg_affine_kernel<uint32_t*>>(
+        agp_range_flag_get(), dim3(grid_for(n * (c / 8))), dim3(256), 0, 0, (hipStream_t)stream, CBF(y_hi), CBF(y_lo), bidx, scale, add,
+        CBF(r_hi), CBF(r_lo), n, c, relu, BF(o_hi), BF(o_lo), n_dev);
 }
 
 extern "C" int agp_seg_dot_fwd(const void* a_hi, const void* a_lo, const void* b_hi, const void* b_lo, const int64_t* seg_off,

@@ -955,15 +955,9 @@ extern "C" int agp_map_affine(const void* a_hi, const void* a_lo, const float* s
     if (!geo_fits(n, h, w, c)) return AGP_E_BADARG;
     // the guarded form only when a word is bound AND this call stores fp16 at all (a bf16 pair without the operand plane does not)
     uint32_t* const rf = (!o_lo || o_h16) ? agp_range_flag_get() : nullptr;
-    if (rf) {
-        AGP_LAUNCH((affine_kernel<uint32_t*>), dim3(grid_for((int64_t)n * h * w * (c / 8))), dim3(256), 0, (hipStream_t)stream, g,
-                   CBF(a_hi), CBF(a_lo), scale, shift, CBF(r_hi), CBF(r_lo), relu, BF(o_hi), BF(o_lo), BF(o_h16), rf);
-    } else {
-        AGP_LAUNCH((affine_kernel<>), dim3(grid_for((int64_t)n * h * w * (c / 8))), dim3(256), 0, (hipStream_t)stream, g, CBF(a_hi),
-                   CBF(a_lo), scale, shift, CBF(r_hi), CBF(r_lo), relu, BF(o_hi), BF(o_lo), BF(o_h16));
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<affine_kernel<>, affine_kernel<uint32_t*>>(rf, dim3(grid_for((int64_t)n * h * w * (c / 8))), dim3(256), 0, 0,
+                                                                    (hipStream_t)stream, g, CBF(a_hi), CBF(a_lo), scale, shift, CBF(r_hi),
+                                                                    CBF(r_lo), relu, BF(o_hi), BF(o_lo), BF(o_h16));
 }
 
 // frozen: the statistics are constants (eval-mode BatchNorm): gz = gamma*rstd*g, no mean / projection terms
@@ -1203,16 +1197,9 @@ extern "C" int agp_affine_maxpool3x3s2_fwd(const void* z_hi, const void* z_lo, c
     const MapGeo g = geo_of(n, h, w, c, pad);
     if (!geo_fits(n, h, w, c)) return AGP_E_BADARG;
     uint32_t* const rf = (!out_lo || out_h16) ? agp_range_flag_get() : nullptr;       // (as agp_map_affine)
-    if (rf) {
-        AGP_LAUNCH((affine_maxpool_kernel<uint32_t*>), dim3(grid_for((int64_t)n * hout * wout * (c / 8))), dim3(256), 0,
-                   (hipStream_t)stream, g, CBF(z_hi), CBF(z_lo), scale, shift, BF(out_hi), BF(out_lo), hout, wout, pout, argmax,
-                   BF(out_h16), rf);
-    } else {
-        AGP_LAUNCH((affine_maxpool_kernel<>), dim3(grid_for((int64_t)n * hout * wout * (c / 8))), dim3(256), 0, (hipStream_t)stream, g,
-                   CBF(z_hi), CBF(z_lo), scale, shift, BF(out_hi), BF(out_lo), hout, wout, pout, argmax, BF(out_h16));
-    }
-    AGP_CHECK_LAUNCH();
-    return AGP_OK;
+    return agp_launch_rg<affine_maxpool_kernel<>, affine_maxpool_kernel<uint32_t*>>(
+        rf, dim3(grid_for((int64_t)n * hout * wout * (c / 8))), dim3(256), 0, 0, (hipStream_t)stream, g, CBF(z_hi), CBF(z_lo), scale,
+        shift, BF(out_hi), BF(out_lo), hout, wout, pout, argmax, BF(out_h16));
 }
 
 extern "C" int agp_pool_bwd(const void* x_hi, const void* x_lo, const float* gmean, const float* ggem, const float* gem_y,

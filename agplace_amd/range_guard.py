@@ -234,56 +234,44 @@ def model_device(model):
 
 
 @contextlib.contextmanager
-def guarded(model, opt, prec, train):
-    """Around a model's inference work: bind its guard when active(opt, prec, train), publish behind the work on exit."""
-    if not active(opt, prec, train):
-        yield
-        return
-    g, dev = guard_of(model), model_device(model)
-    with g.bind(dev):
-        yield
-    g.publish(dev, prec)
-
-
-@contextlib.contextmanager
-def guarded_cnx(model, tag):
-    """Around inference work that runs a ConvNeXt trunk at precision 4 (`tag` from cnx_tag; None: nothing is bound): bind the model's
-    one guard, publish behind the work under `tag` -- the same word, mirrors and capture rules as guarded()."""
+def _guarded(model, tag, publish=True):
+    """The one body of the context managers below.  `tag` None: nothing is bound.  Otherwise bind the model's one guard around the
+    work and, when `publish`, publish behind it under `tag` (not if the work raised)."""
     if tag is None:
         yield
         return
     g, dev = guard_of(model), model_device(model)
     with g.bind(dev):
         yield
-    g.publish(dev, tag)
+    if publish:
+        g.publish(dev, tag)
 
 
-@contextlib.contextmanager
+def guarded(model, opt, prec, train):
+    """Around a model's inference work: bind its guard when active(opt, prec, train), publish behind the work on exit."""
+    return _guarded(model, prec if active(opt, prec, train) else None)
+
+
+def guarded_cnx(model, tag):
+    """Around inference work that runs a ConvNeXt trunk at precision 4 (`tag` from cnx_tag; None: nothing is bound): bind the model's
+    one guard, publish behind the work under `tag` -- the same word, mirrors and capture rules as guarded()."""
+    return _guarded(model, tag)
+
+
 def bound(model, on):
     """Bind the model's guard around a PART of its forward when `on`, publishing nothing: the caller publishes behind the whole
     forward (publish_tag), once its side streams have joined."""
-    if not on:
-        yield
-        return
-    with guard_of(model).bind(model_device(model)):
-        yield
+    return _guarded(model, True if on else None, publish=False)
 
 
 def publish_tag(model, tag):
     guard_of(model).publish(model_device(model), tag)
 
 
-@contextlib.contextmanager
 def guarded_train(model, opt):
     """Around a model's forward on the TRAINING graph (not its backward, which stores no fp16 map): bind the model's one guard
     when active_train(opt), publish behind the forward on exit -- the same word, mirrors and capture rules as guarded()."""
-    if not active_train(opt):
-        yield
-        return
-    g, dev = guard_of(model), model_device(model)
-    with g.bind(dev):
-        yield
-    g.publish(dev, train_tag(opt))
+    return _guarded(model, train_tag(opt) if active_train(opt) else None)
 
 
 def poll(model):

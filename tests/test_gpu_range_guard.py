@@ -436,6 +436,32 @@ def test_sparse_first_conv(dev, mode):
         assert torch.equal(hi, plain)
 
 
+@pytest.mark.parametrize("cout", [32, 64])
+def test_sparse_first_conv_search_form(dev, cout):
+    """agp_sparse_conv0_fwd's other route (conv0_search_kernel: every precision but AGP_PREC_F16; mode 2 stores fp16): 40 voxels
+    too far apart to be neighbours and unit weights, so a voxel's output is its own feature.  One feature of 70000 sets the word,
+    60000 leaves it at 0, and the stored bits are the same with and without the binding."""
+    from agplace_amd import ops
+    from agplace_amd.sparse import SparseTensor
+    from agplace_amd.sparse.modules import MinkowskiConvolution
+    ij = torch.arange(20)
+    coords = torch.cat([torch.stack([torch.full((20,), float(b)), 8.0 * (ij % 5), 8.0 * (ij // 5), torch.zeros(20)], 1) for b in range(2)], 0)
+    conv = MinkowskiConvolution(1, cout, kernel_size=5).to(dev)
+    conv.kernel.data.fill_(1.0)
+    for planted in (60000.0, 70000.0):
+        f = torch.ones(40, 1)
+        f[17] = planted
+
+        def run():
+            sp = SparseTensor.from_coords_capacity(f.to(dev), coords.to(dev), 2, ops.Workspace())
+            return conv(sp, None, relu=True, prec=2).hi[:int(sp.n_dev.item())].clone()
+        plain = run()
+        hi, flag = _guarded(dev, run)
+        assert flag == int(planted > 65504.0), (cout, planted)
+        assert torch.equal(hi, plain)
+        assert float(hi.float().max()) == min(planted, 65504.0) and float(hi.float().min()) == 1.0
+
+
 def test_bcast_add_and_input_packs(dev):
     """agp_bcast_add_fwd (the image branch's stage-2 fusion map) and the fp32 input packs (agp_pack_f32_to_nhwc: the 4-channel
     stem form and the generic form; agp_pack_f32_to_nhwc4_h16 of the fast training stem)."""
