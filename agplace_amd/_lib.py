@@ -67,6 +67,20 @@ class BBlock64Desc(C.Structure):
                 ("pool_partial", C.c_void_p), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("form", C.c_int32)]
 
 
+class CnxGroup(C.Structure):
+    """struct agp_cnx_group (include/agplace_hip.h): one problem of a grouped ConvNeXt launch."""
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("sn", C.c_int64), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64),
+                ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("ncam", C.c_int32),
+                ("mean3", C.c_float * 3), ("std3", C.c_float * 3),
+                ("wt", C.c_void_p), ("bias", C.c_void_p), ("ln_w", C.c_void_p), ("ln_b", C.c_void_p),
+                ("w1_hi", C.c_void_p), ("w1_lo", C.c_void_p), ("w2_hi", C.c_void_p), ("w2_lo", C.c_void_p),
+                ("b1", C.c_void_p), ("b2", C.c_void_p), ("layer_scale", C.c_void_p)]
+
+
+CNX_MAX_GROUPS = 4            # AGP_CNX_MAX_GROUPS
+
+
 class VecProgOp(C.Structure):
     """struct agp_vecprog_op (include/agplace_hip.h)."""
     _fields_ = [("op", C.c_int32), ("dst", C.c_int32), ("r", C.c_int32 * 6), ("k", C.c_int32), ("act", C.c_int32),
@@ -240,6 +254,14 @@ SIGNATURES = {
     "agp_normalize_u8_cams": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P]),
     "agp_cnx_stem_u8_fwd": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _P, _F, _P, _P]),
     "agp_cnx_stem_u8_bwd": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "agp_cnx_stem_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _F, _P]),
+    "agp_cnx_stem_u8_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _F, _P]),
+    "agp_cnx_dwconv_ln_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _I, _F, _P]),
+    "agp_cnx_mlp_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _I, _P]),
+    "agp_cnx_downsample_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _I, _F, _P]),
+    "agp_cnx_dwconv_ln_f16_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _I, _F, _P]),
+    "agp_cnx_mlp_f16_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _I, _P]),
+    "agp_cnx_downsample_f16_fwd_grouped": (_I, [C.POINTER(CnxGroup), _I, _I, _F, _P]),
 }
 
 _lib = None

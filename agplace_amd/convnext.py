@@ -39,6 +39,11 @@ twins that report a LayerNorm or GELU output beyond +-65504 into the bound word 
 same stored bits), and `forward_maps` hands the weight planes' clamp flag (prep_block / prep_down "sat", _half_clamped) to the
 bound guard on every forward.  The ops know nothing of Options: no binding, no twin, no flag.
 
+Lock-step trunks (`ConvNeXt.forward_maps_multi`, what pair.embed_pair runs behind Options.convnext_pair): the inference path of up to
+MAX_GROUPS trunks of equal block counts and precision, every step ONE grouped launch of the same kernels (`*_fwd_grouped` below,
+agp_cnx_*_fwd_grouped): a workgroup finds its trunk from the prefix sums of the per-trunk grids and does what the plain launch gives
+that block index there, so each trunk's maps are bit for bit those of `forward_maps`.
+
 Stochastic depth restates torchvision's StochasticDepth(p, "row") (torchvision is not a dependency): block k of the FULL
 18-block network has p_k = stochastic_depth_prob * k / 17 (the truncation happens after construction, so a kept block keeps its
 k); in .train() each image draws scale = bernoulli(1 - p_k) / (1 - p_k) and out = x + scale[n] * layer_scale * branch(x);
@@ -359,6 +364,102 @@ def downsample_fwd(x, p, prec=3):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------- grouped launches
+# One launch per step over 1 .. MAX_GROUPS independent problems (csrc/convnext.hip: the same kernel bodies, a workgroup finds its
+# problem from the prefix sums of the per-problem grids): bit for bit what the per-problem ops above write.  The problems of a
+# launch share C and the precision.  No guarded twins: under a bound fp16 range guard use the per-problem ops.
+MAX_GROUPS = _lib.CNX_MAX_GROUPS
+
+
+def _group_table(descs, what):
+    if not 1 <= len(descs) <= MAX_GROUPS:
+        raise ValueError(f"ConvNeXt.{what}: 1 .. {MAX_GROUPS} problems per launch, got {len(descs)}")
+    return (_lib.CnxGroup * len(descs))(*descs), len(descs)
+
+
+def _stem_desc(p, out):
+    return dict(wt=ptr(p["w"]), bias=ptr(p["bias"]), ln_w=ptr(p["g"]), ln_b=ptr(p["b"]), out=ptr(out))
+
+
+def stem_fwd_grouped(xs, ps, norms=None):
+    """[stem_fwd(x, p)] (fp32 images) or [stem_u8_fwd(tiles, mean, std, p)] (uint8 tiles, norms = [(mean, std)]) for the problems
+    zip(xs, ps) as ONE launch; the xs are all fp32 or all uint8."""
+    u8 = xs[0].dtype == torch.uint8
+    outs, descs = [], []
+    for i, (x, p) in enumerate(zip(xs, ps)):
+        if (x.dtype == torch.uint8) != u8:
+            raise ValueError("ConvNeXt.stem_fwd_grouped: one launch takes fp32 images or uint8 tiles, not both")
+        if u8:
+            _tiles_ok(x, "stem_fwd_grouped")
+            n, ncam, h, w, _ = x.shape
+            if h < 4 or ncam * w < 4:
+                raise ValueError(f"ConvNeXt.stem_fwd_grouped: a {h}x{ncam * w} panorama is smaller than the 4x4 stem")
+            out = torch.empty((n, (h - 4) // 4 + 1, (ncam * w - 4) // 4 + 1, DIMS[0]), dtype=torch.float32, device=x.device)
+            mean, std = norms[i]
+            descs.append(_lib.CnxGroup(x=ptr(x), n=n, ncam=ncam, h=h, w=w, mean3=_norm3(mean), std3=_norm3(std), **_stem_desc(p, out)))
+        else:
+            n, _, H, W = x.shape
+            out = torch.empty((n, (H - 4) // 4 + 1, (W - 4) // 4 + 1, DIMS[0]), dtype=torch.float32, device=x.device)
+            sn, sc, sh, sw = x.stride()
+            descs.append(_lib.CnxGroup(x=ptr(x), sn=sn, sc=sc, sh=sh, sw=sw, n=n, h=H, w=W, **_stem_desc(p, out)))
+        outs.append(out)
+    name = "agp_cnx_stem_u8_fwd_grouped" if u8 else "agp_cnx_stem_fwd_grouped"
+    check(getattr(_lib.load(), name)(*_group_table(descs, "stem_fwd_grouped"), LN_EPS, _lib.stream()), name)
+    return outs
+
+
+def dwconv_ln_fwd_grouped(xs, ps, wss, prec=3):
+    """dwconv_ln_fwd(x, p, ws, prec) for the problems zip(xs, ps, wss) as ONE launch (the streams share C)."""
+    if prec not in (3, 4):
+        raise ValueError(f"ConvNeXt.dwconv_ln_fwd_grouped: prec {prec!r}: 3 | 4")
+    c = ps[0]["c"]
+    descs = []
+    for x, p, ws in zip(xs, ps, wss):
+        _stream_ok(x, c)
+        n, h, w, _ = x.shape
+        descs.append(_lib.CnxGroup(x=ptr(x), n=n, h=h, w=w, wt=ptr(p["dw"]), bias=ptr(p["dwb"]), ln_w=ptr(p["g"]), ln_b=ptr(p["b"]),
+                                   workspace=ptr(ws), workspace_bytes=ws.numel()))
+    name = "agp_cnx_dwconv_ln_f16_fwd_grouped" if prec == 4 else "agp_cnx_dwconv_ln_fwd_grouped"
+    check(getattr(_lib.load(), name)(*_group_table(descs, "dwconv_ln_fwd_grouped"), c, LN_EPS, _lib.stream()), name)
+
+
+def mlp_fwd_grouped(wss, ps, resids, outs, prec=3):
+    """mlp_fwd(ws, p, resid, out, prec) for the problems zip(wss, ps, resids, outs) as ONE launch."""
+    c = ps[0]["c"]
+    descs = []
+    for ws, p, resid, out in zip(wss, ps, resids, outs):
+        _stream_ok(resid, c)
+        _stream_ok(out, c)
+        if out.shape != resid.shape:
+            raise ValueError("ConvNeXt.mlp_fwd_grouped: out and resid differ in shape")
+        _planes_ok(p["w1"], prec, "mlp_fwd_grouped")
+        n, h, w, _ = resid.shape
+        descs.append(_lib.CnxGroup(x=ptr(resid), out=ptr(out), n=n, h=h, w=w, workspace=ptr(ws), workspace_bytes=ws.numel(),
+                                   w1_hi=ptr(p["w1"][0]), w1_lo=ptr(p["w1"][-1]) if prec == 3 else None, b1=ptr(p["b1"]),
+                                   w2_hi=ptr(p["w2"][0]), w2_lo=ptr(p["w2"][-1]) if prec == 3 else None, b2=ptr(p["b2"]),
+                                   layer_scale=ptr(p["ls"])))
+    name = "agp_cnx_mlp_f16_fwd_grouped" if prec == 4 else "agp_cnx_mlp_fwd_grouped"
+    check(getattr(_lib.load(), name)(*_group_table(descs, "mlp_fwd_grouped"), c, _lib.stream()), name)
+    return outs
+
+
+def downsample_fwd_grouped(xs, ps, prec=3):
+    """[downsample_fwd(x, p, prec)] for the problems zip(xs, ps) as ONE launch."""
+    c = ps[0]["c"]
+    outs, descs = [], []
+    for x, p in zip(xs, ps):
+        _stream_ok(x, c)
+        _planes_ok(p["w"], prec, "downsample_fwd_grouped")
+        n, h, w, _ = x.shape
+        out = torch.empty((n, h // 2, w // 2, 2 * c), dtype=torch.float32, device=x.device)
+        descs.append(_lib.CnxGroup(x=ptr(x), out=ptr(out), n=n, h=h, w=w, ln_w=ptr(p["g"]), ln_b=ptr(p["b"]), w1_hi=ptr(p["w"][0]),
+                                   w1_lo=ptr(p["w"][-1]) if prec == 3 else None, bias=ptr(p["bias"])))
+        outs.append(out)
+    name = "agp_cnx_downsample_f16_fwd_grouped" if prec == 4 else "agp_cnx_downsample_fwd_grouped"
+    check(getattr(_lib.load(), name)(*_group_table(descs, "downsample_fwd_grouped"), c, LN_EPS, _lib.stream()), name)
+    return outs
+
+
 class _TrunkFn(torch.autograd.Function):
     """The training forward of the whole trunk as one node.  Inputs: the trunk, the input image, the per-block scales, then every
     parameter of `features` (so that autograd accumulates into their .grad: a trunk applied twice adds up).  Outputs: the three
@@ -528,6 +629,10 @@ class ConvNeXt(nn.Module):
             raise ValueError(f"ConvNeXt: a {h}x{w} input is too small for three stages (map sizes {sizes})")
         return sizes
 
+    def block_counts(self):
+        """The blocks each of the three stages keeps (`layers` capped at convnext_tiny's depths)."""
+        return [len(self.features[1 + 2 * s]) for s in range(3)]
+
     def takes_training_path(self):
         """Whether `forward_maps` would hand this call to `forward_maps_train` (mode 3, no fp16: nothing for the range guard)."""
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters())
@@ -570,6 +675,64 @@ class ConvNeXt(nn.Module):
                 dwconv_ln_fwd(cur, p, ws, prec)
                 mlp_fwd(ws, p, cur, cur, prec)
             maps.append(cur.permute(0, 3, 1, 2))
+        return maps
+
+    @staticmethod
+    def forward_maps_multi(nets, xs):
+        """[net.forward_maps(x) for net, x in zip(nets, xs)] -- the inference path only -- with the 1 .. MAX_GROUPS trunks advancing in
+        lock-step: the stem, every block's depthwise conv + LayerNorm and MLP, and every downsample are ONE grouped launch over all
+        trunks (stem_fwd_grouped ...; trunks given fp32 images and trunks given uint8 tiles / frames take one stem launch per kind).
+        The trunks have the same block counts and precision; sizes, weights (each trunk's own prepared planes) and operand workspaces
+        (each trunk's own, keyed by the launch stream) are their own, and each x follows its trunk's enable_u8_inputs rule.  The maps
+        are bit for bit those of forward_maps.  Launches on the current stream, never synchronises, capturable after one eager call.
+        While the caller has bound an fp16 range guard at precision 4 the grouped launches, which have no guarded twins, are not
+        used: every trunk then runs its own forward_maps, guarded as there."""
+        nets, xs = list(nets), list(xs)
+        if not 1 <= len(nets) <= MAX_GROUPS or len(xs) != len(nets):
+            raise ValueError(f"ConvNeXt.forward_maps_multi: 1 .. {MAX_GROUPS} trunks and one input each, got {len(nets)} and {len(xs)}")
+        counts = [net.block_counts() for net in nets]
+        if any(c != counts[0] for c in counts) or any(net.precision != nets[0].precision for net in nets):
+            raise ValueError("ConvNeXt.forward_maps_multi: the trunks must have the same block counts and precision, got "
+                             f"{[(c, net.precision) for c, net in zip(counts, nets)]}")
+        for net in nets:
+            if net.training or net.takes_training_path():
+                raise NotImplementedError("ConvNeXt.forward_maps_multi: the inference path only (.eval() under torch.no_grad(), or a "
+                                          "frozen trunk); training forwards run per trunk (forward_maps)")
+            if torch.is_grad_enabled() and any(p.requires_grad for p in net.features.parameters()):
+                raise NotImplementedError("ConvNeXt.forward_maps_multi: gradients into the trunk are not enabled (inference only): run "
+                                          "under torch.no_grad() or freeze the trunks")
+        prec = nets[0].precision
+        if prec == 4 and range_guard.bound_word() is not None:
+            return [net.forward_maps(x) for net, x in zip(nets, xs)]
+        xs = [net._input(x, "forward_maps_multi") for net, x in zip(nets, xs)]
+        if torch.is_grad_enabled() and any(getattr(x, "requires_grad", False) for x in xs):
+            raise NotImplementedError("ConvNeXt.forward_maps_multi: the gradient of an input image is not built")
+        preps = [net._prepared(prec) for net in nets]
+        wss, seen = [], {}
+        for net, x in zip(nets, xs):
+            n, H, W = net._geometry(x)
+            sizes = net.map_sizes(H, W)
+            k = seen[id(net)] = seen.get(id(net), -1) + 1         # (one trunk given twice: an operand workspace per use)
+            wss.append(net._ws.tensor("cnx_ws" if k == 0 else f"cnx_ws_multi{k}",
+                                      (max(workspace_bytes(n, h, w, DIMS[s]) for s, (h, w) in enumerate(sizes)),), torch.uint8, x.device))
+        maps, curs = [[] for _ in nets], [None] * len(nets)
+        for s in range(3):
+            if s == 0:
+                for u8 in (False, True):
+                    idx = [i for i, x in enumerate(xs) if (x.dtype == torch.uint8) == u8]
+                    if idx:
+                        outs = stem_fwd_grouped([xs[i] for i in idx], [preps[i]["stem"] for i in idx],
+                                                [(nets[i].image_mean, nets[i].image_std) for i in idx])
+                        for i, o in zip(idx, outs):
+                            curs[i] = o
+            else:
+                curs = downsample_fwd_grouped(curs, [p[("down", s - 1)] for p in preps], prec)
+            for b in range(counts[0][s]):
+                ps = [p[("blocks", s)][b] for p in preps]
+                dwconv_ln_fwd_grouped(curs, ps, wss, prec)
+                mlp_fwd_grouped(wss, ps, curs, curs, prec)
+            for m, cur in zip(maps, curs):
+                m.append(cur.permute(0, 3, 1, 2))
         return maps
 
     # ------------------------------------------------------------------ training

@@ -21,17 +21,87 @@
 
 namespace {
 
+// ---------------------------------------------------------------------------------------------------------- grouped launches
+// Up to CNX_MAXG independent problems (the trunks of a query / database pair advancing in lock-step, agplace_amd/pair.py) as ONE
+// launch of the SAME kernel template: the trailing argument pack of the four forward kernels is empty (one problem, the arguments),
+// the range guard's word (the guarded twin), or a CnxTable by value.  With a table the grid is the problems' own grids one behind
+// the other, start[i] the first block of problem i (0xffffffff for an unused slot): a workgroup finds its problem from those prefix
+// sums (wave-uniform: scalar compares), takes that problem's pointers and geometry in place of its arguments and runs the body at
+// the block index it has INSIDE the problem -- so tiles, partial last tiles, arithmetic and summation order are the plain launch's,
+// problem by problem, and nothing is shared across a problem boundary.  The problems share C, the precision and eps.  Every
+// difference sits behind `if constexpr`: the instantiations without a table are the code they were.  Unguarded only (the pair falls
+// back to the separate, guarded forwards while a ConvNeXt range guard would bind).
+constexpr int CNX_MAXG = AGP_CNX_MAX_GROUPS;
+template <class LOAD> struct CnxStemGroup {
+    LOAD ld;
+    int ho, wo;
+    long long P;
+    const float *wt, *bias, *g, *b;
+    float* out;
+};
+struct CnxDwGroup {
+    const float* x;
+    int h, w, ty, tx;
+    const float *wt, *bias, *g, *b;
+    bf16_t *o_hi, *o_lo;
+};
+struct CnxMlpGroup {
+    const bf16_t *x_hi, *x_lo;
+    long long P;
+    const bf16x8 *w1_hi, *w1_lo, *w2_hi, *w2_lo;
+    const float *b1, *b2, *ls, *resid;
+    float* out;
+};
+struct CnxDownGroup {
+    const float* x;
+    int h, w, ho, wo;
+    long long P;
+    const float *g, *b, *bias;
+    const bf16x8 *w_hi, *w_lo;
+    float* out;
+};
+template <class G> struct CnxTable {
+    unsigned start[CNX_MAXG];
+    G g[CNX_MAXG];
+};
+// what a kernel's trailing pack says
+template <class... EX> struct CnxPack {
+    static constexpr bool grouped = false, guarded = sizeof...(EX) != 0;
+};
+template <class G> struct CnxPack<CnxTable<G>> {
+    static constexpr bool grouped = true, guarded = false;
+};
+// the problem of block `bid`; bid becomes the block index inside it
+template <class B, class G> __device__ __forceinline__ const G& cnx_group(B& bid, const CnxTable<G>& tab) {
+    int gi = 0;
+#pragma unroll
+    for (int i = 1; i < CNX_MAXG; ++i)
+        if ((unsigned)bid >= tab.start[i]) gi = i;
+    bid -= (B)tab.start[gi];
+    return tab.g[gi];
+}
+using ::rg_word;               // (common.hpp) the range guard's word of a trailing pack: none for a table
+template <class G> __device__ __forceinline__ uint32_t* rg_word(const CnxTable<G>&) { return nullptr; }
+
 // ------------------------------------------------------------------------------------------------------------------ stem
 // Conv2d(3, 96, k=4, s=4, bias) + LayerNorm over the 96 channels.  32 output pixels per block; a thread owns 3 channels
 // (cl, cl + 32, cl + 64) of 4 pixels, the 32 lanes of a half wave hold one pixel's 96 channels.  wt: [48][96], 48 = (ci, ky, kx).
 // LOAD: the image source (convnext_common.hpp: CnxLoadF32 strided fp32, CnxLoadU8 uint8 camera tiles normalised on the fly).
-template <class LOAD>
-__global__ __launch_bounds__(256) void cnx_stem_kernel(const LOAD ld, int ho, int wo, long long P, const float* __restrict__ wt,
+// gr: empty, or the table of a grouped launch (CnxTable above; the leading arguments but eps are then unused).
+template <class LOAD, class... GR>
+__global__ __launch_bounds__(256) void cnx_stem_kernel(const LOAD ld0, int ho, int wo, long long P, const float* __restrict__ wt,
                                                        const float* __restrict__ bias, const float* __restrict__ g,
-                                                       const float* __restrict__ b, float eps, float* __restrict__ out) {
+                                                       const float* __restrict__ b, float eps, float* __restrict__ out, GR... gr) {
     __shared__ float xin[32][48];
     const int t = threadIdx.x, cl = t & 31, pg = t >> 5;
-    const long long p0 = (long long)blockIdx.x * 32;
+    unsigned bid = blockIdx.x;
+    const LOAD* lp = &ld0;
+    if constexpr (CnxPack<GR...>::grouped) {
+        const CnxStemGroup<LOAD>& d = cnx_group(bid, gr...);
+        lp = &d.ld, ho = d.ho, wo = d.wo, P = d.P, wt = d.wt, bias = d.bias, g = d.g, b = d.b, out = d.out;
+    }
+    const LOAD& ld = *lp;
+    const long long p0 = (long long)bid * 32;
     for (int e = t; e < 32 * 48; e += 256) {
         const int px = e / 48, idx = e % 48;
         const long long p = p0 + px;
@@ -106,19 +176,23 @@ __global__ void cnx_normalize_u8_kernel(const CnxLoadU8 ld, int W, long long tot
 // registers; the 32 lanes of a half wave then hold one pixel's C channels for the LayerNorm.  wt: [49][C].
 // PREC: 3 = the operand as bf16 (hi, lo) planes; 4 = as ONE fp16 plane in o_hi (cnx_h1: nearest even, saturating), o_lo unused.
 // rf (here, in cnx_mlp_kernel and in cnx_downsample_kernel; PREC = 4 only): the fp16 range guard's word in the guarded instantiation
-// (common.hpp rg_word), absent otherwise.  Tracked: the fp32 values handed to cnx_h1 / cnx_h2, before the clamp, of REAL pixels only.
+// (common.hpp rg_word), the table of a grouped launch (CnxTable above), absent otherwise.  Tracked: the fp32 values handed to cnx_h1 / cnx_h2, before the clamp, of REAL pixels only.
 template <int C, int PREC = 3, class... RF>
 __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restrict__ x, int h, int w, int tiles_y, int tiles_x,
                                                             const float* __restrict__ wt, const float* __restrict__ bias,
                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                             bf16_t* __restrict__ o_hi, bf16_t* __restrict__ o_lo, RF... rf) {
-    static_assert(sizeof...(RF) == 0 || PREC == 4, "the range guard covers the fp16 instantiations only");
+    static_assert(!CnxPack<RF...>::guarded || PREC == 4, "the range guard covers the fp16 instantiations only");
     constexpr int NK = C / 32;
-    RangeTrack<sizeof...(RF) != 0> rg;
+    RangeTrack<CnxPack<RF...>::guarded> rg;
     __shared__ __attribute__((aligned(16))) float tile[10][14][32];
     __shared__ float wl[49][32];
     const int t = threadIdx.x, cl = t & 31, col = t >> 5;
     int bid = blockIdx.x;
+    if constexpr (CnxPack<RF...>::grouped) {
+        const CnxDwGroup& d = cnx_group(bid, rf...);
+        x = d.x, h = d.h, w = d.w, tiles_y = d.ty, tiles_x = d.tx, wt = d.wt, bias = d.bias, g = d.g, b = d.b, o_hi = d.o_hi, o_lo = d.o_lo;
+    }
     const int tx = bid % tiles_x;
     bid /= tiles_x;
     const int ty = bid % tiles_y, img = bid / tiles_y;
@@ -181,7 +255,7 @@ __global__ __launch_bounds__(256) void cnx_dwconv_ln_kernel(const float* __restr
                     o_hi[p * C + c] = cnx_h1(xn);
                     // (the twin only: without it the scheduler hoists every channel's gamma / beta load above the running maximum
                     // and C = 384 needs 100 VGPRs instead of 86 -- 4 waves per SIMD instead of the unguarded form's 5)
-                    if constexpr (sizeof...(RF) != 0) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (CnxPack<RF...>::guarded) __builtin_amdgcn_sched_barrier(0);
                 } else {
                     bf16_t hi, lo;
                     split_bf16(fmaf(conv[i][k] * rstd, g[c], b[c]), hi, lo);
@@ -217,15 +291,22 @@ __global__ __launch_bounds__(256) void cnx_mlp_kernel(const bf16_t* __restrict__
                                                       const bf16x8* __restrict__ w2_lo, const float* __restrict__ b2,
                                                       const float* __restrict__ ls, const float* resid, float* out,
                                                       const float* __restrict__ row_scale, long long ppi, RF... rf) {
-    static_assert(sizeof...(RF) == 0 || (PREC == 4 && !ROWS), "the range guard covers the fp16 instantiations only");
+    static_assert(!CnxPack<RF...>::guarded || (PREC == 4 && !ROWS), "the range guard covers the fp16 instantiations only");
+    static_assert(!CnxPack<RF...>::grouped || !ROWS, "grouped launches are the inference kernel's");
     constexpr int LD = C + CNX_KPAD, KK = C / 16, CT = C / 32, JB = C / 8, VR = C / 8;
-    RangeTrack<sizeof...(RF) != 0> rg;
+    RangeTrack<CnxPack<RF...>::guarded> rg;
     constexpr int XBYTES = (PREC == 4 ? 1 : 2) * CNX_TP * LD * 2, RBYTES = 4 * 32 * 36 * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem[XBYTES > RBYTES ? XBYTES : RBYTES];
     bf16_t* const sx_hi = (bf16_t*)smem;
     bf16_t* const sx_lo = sx_hi + CNX_TP * LD;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, r = lane & 31, h = lane >> 5;
-    const long long p0 = (long long)blockIdx.x * CNX_TP;
+    unsigned bid = blockIdx.x;
+    if constexpr (CnxPack<RF...>::grouped) {
+        const CnxMlpGroup& d = cnx_group(bid, rf...);
+        x_hi = d.x_hi, x_lo = d.x_lo, P = d.P, w1_hi = d.w1_hi, w1_lo = d.w1_lo, b1 = d.b1, w2_hi = d.w2_hi, w2_lo = d.w2_lo, b2 = d.b2;
+        ls = d.ls, resid = d.resid, out = d.out;
+    }
+    const long long p0 = (long long)bid * CNX_TP;
     for (int e = t; e < CNX_TP * VR; e += 256) {
         const int row = e / VR, v = e - row * VR;
         u32x4 vh = {0u, 0u, 0u, 0u}, vl = {0u, 0u, 0u, 0u};
@@ -335,14 +416,19 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
                                                              const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                              const bf16x8* __restrict__ w_hi, const bf16x8* __restrict__ w_lo,
                                                              const float* __restrict__ bias, float* __restrict__ out, RF... rf) {
-    static_assert(sizeof...(RF) == 0 || PREC == 4, "the range guard covers the fp16 instantiations only");
-    RangeTrack<sizeof...(RF) != 0> rg;
+    static_assert(!CnxPack<RF...>::guarded || PREC == 4, "the range guard covers the fp16 instantiations only");
+    RangeTrack<CnxPack<RF...>::guarded> rg;
     constexpr int KC = 384, LD = KC + CNX_KPAD, IPP = KC / C, NCH = 4 * C / KC, NT = 2 * C / 32, NTW = (NT + 3) / 4, KKT = 4 * C / 16;
     constexpr int NV = C / 32;             // float4 per lane of a pixel's eight
     __shared__ __attribute__((aligned(16))) bf16_t sx_hi[CNX_TP * LD];
     __shared__ __attribute__((aligned(16))) bf16_t sx_lo[PREC == 4 ? 8 : CNX_TP * LD];     // (precision 4: one plane, unused)
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, r = lane & 31, hh = lane >> 5;
-    const long long p0 = (long long)blockIdx.x * CNX_TP;
+    unsigned bid = blockIdx.x;
+    if constexpr (CnxPack<RF...>::grouped) {
+        const CnxDownGroup& d = cnx_group(bid, rf...);
+        x = d.x, h = d.h, w = d.w, ho = d.ho, wo = d.wo, P = d.P, g = d.g, b = d.b, w_hi = d.w_hi, w_lo = d.w_lo, bias = d.bias, out = d.out;
+    }
+    const long long p0 = (long long)bid * CNX_TP;
     const int lpx = t >> 3, sl = t & 7;
     const long long lp = p0 + lpx;
     long long img = 0;
@@ -442,6 +528,23 @@ __global__ __launch_bounds__(256) void cnx_downsample_kernel(const float* __rest
         }
     }
 }
+
+// Host side of a grouped launch: an empty table; append a problem of `blocks` workgroups (false when the launch would leave the
+// 2^31 - 1 blocks of a grid).
+template <class G> inline void cnx_table_init(CnxTable<G>& tab) {
+    for (int i = 0; i < CNX_MAXG; ++i) {
+        tab.start[i] = 0xffffffffu;
+        tab.g[i] = G{};
+    }
+}
+template <class G> inline bool cnx_table_add(CnxTable<G>& tab, int i, long long& total, long long blocks, const G& g) {
+    if (blocks <= 0 || total + blocks >= (1ll << 31)) return false;
+    tab.start[i] = (unsigned)total;
+    tab.g[i] = g;
+    total += blocks;
+    return true;
+}
+inline bool cnx_groups_ok(const agp_cnx_group* groups, int ngroups) { return groups && ngroups >= 1 && ngroups <= CNX_MAXG; }
 
 }  // namespace
 
@@ -615,6 +718,182 @@ int agp_cnx_downsample_f16_fwd(const float* x, int n, int h, int w, int C, const
     if (C == 96) return launch(std::integral_constant<int, 96>{});
     if (C == 192) return launch(std::integral_constant<int, 192>{});
     return launch(std::integral_constant<int, 384>{});
+}
+
+// ---- grouped launches (include/agplace_hip.h: agp_cnx_group): 1 .. AGP_CNX_MAX_GROUPS problems per launch, each validated as by its
+// plain entry above; the kernels' leading arguments are unused (the table replaces them) except eps.
+int agp_cnx_stem_fwd_grouped(const agp_cnx_group* groups, int ngroups, float eps, void* stream) {
+    if (!cnx_groups_ok(groups, ngroups)) return AGP_E_BADARG;
+    using T = CnxTable<CnxStemGroup<CnxLoadF32>>;
+    T tab;
+    cnx_table_init(tab);
+    long long total = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const agp_cnx_group& q = groups[i];
+        if (!q.x || !q.wt || !q.bias || !q.ln_w || !q.ln_b || !q.out || q.n <= 0 || q.h < 4 || q.w < 4) return AGP_E_BADARG;
+        const int ho = (q.h - 4) / 4 + 1, wo = (q.w - 4) / 4 + 1;
+        if (!cnx_map_ok(q.n, ho, wo)) return AGP_E_BADARG;
+        const long long P = (long long)q.n * ho * wo;
+        const CnxLoadF32 ld = {(const float*)q.x, (long long)q.sn, (long long)q.sc, (long long)q.sh, (long long)q.sw};
+        if (!cnx_table_add(tab, i, total, (P + 31) / 32, {ld, ho, wo, P, q.wt, q.bias, q.ln_w, q.ln_b, (float*)q.out})) return AGP_E_BADARG;
+    }
+    const float* const nof = nullptr;
+    float* const noo = nullptr;
+    AGP_LAUNCH((cnx_stem_kernel<CnxLoadF32, T>), dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, CnxLoadF32{}, 0, 0, 0ll, nof,
+               nof, nof, nof, eps, noo, tab);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_stem_u8_fwd_grouped(const agp_cnx_group* groups, int ngroups, float eps, void* stream) {
+    if (!cnx_groups_ok(groups, ngroups)) return AGP_E_BADARG;
+    using T = CnxTable<CnxStemGroup<CnxLoadU8>>;
+    T tab;
+    cnx_table_init(tab);
+    long long total = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const agp_cnx_group& q = groups[i];
+        if (!q.x || !q.wt || !q.bias || !q.ln_w || !q.ln_b || !q.out || q.n <= 0 || q.ncam <= 0 || q.h < 4 || q.w <= 0) return AGP_E_BADARG;
+        const long long W = (long long)q.ncam * q.w;
+        if (W < 4 || W >= (1ll << 31)) return AGP_E_BADARG;
+        const int ho = (q.h - 4) / 4 + 1, wo = (int)((W - 4) / 4 + 1);
+        if (!cnx_map_ok(q.n, ho, wo)) return AGP_E_BADARG;
+        const long long P = (long long)q.n * ho * wo;
+        const CnxLoadU8 ld = {(const uint8_t*)q.x, q.ncam, q.h, q.w, q.mean3[0], q.mean3[1], q.mean3[2], q.std3[0], q.std3[1], q.std3[2]};
+        if (!cnx_table_add(tab, i, total, (P + 31) / 32, {ld, ho, wo, P, q.wt, q.bias, q.ln_w, q.ln_b, (float*)q.out})) return AGP_E_BADARG;
+    }
+    const float* const nof = nullptr;
+    float* const noo = nullptr;
+    AGP_LAUNCH((cnx_stem_kernel<CnxLoadU8, T>), dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, CnxLoadU8{}, 0, 0, 0ll, nof, nof,
+               nof, nof, eps, noo, tab);
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+// planes: operand / weight planes per tensor, 2 = bf16 (hi, lo), 1 = fp16 (the PREC = 4 instantiations)
+static int cnx_dwconv_ln_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, int planes, void* stream) {
+    if (!cnx_groups_ok(groups, ngroups) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    using T = CnxTable<CnxDwGroup>;
+    T tab;
+    cnx_table_init(tab);
+    long long total = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const agp_cnx_group& q = groups[i];
+        if (!q.x || !q.wt || !q.bias || !q.ln_w || !q.ln_b || !q.workspace || !cnx_map_ok(q.n, q.h, q.w)) return AGP_E_BADARG;
+        const long long plane = cnx_pad((long long)q.n * q.h * q.w) * C;
+        if (q.workspace_bytes < planes * plane * 2 || ((uintptr_t)q.workspace & 15)) return AGP_E_BADARG;
+        bf16_t* const hi = (bf16_t*)q.workspace;
+        bf16_t* const lo = planes == 2 ? hi + plane : nullptr;
+        const int ty = (q.h + 3) / 4, tx = (q.w + 7) / 8;
+        if (!cnx_table_add(tab, i, total, (long long)q.n * ty * tx, {(const float*)q.x, q.h, q.w, ty, tx, q.wt, q.bias, q.ln_w, q.ln_b, hi, lo}))
+            return AGP_E_BADARG;
+    }
+    const dim3 grid((unsigned)total);
+    hipStream_t s = (hipStream_t)stream;
+    const float* const nof = nullptr;
+    bf16_t* const nob = nullptr;
+#define CNX_DWG(CC, PP) AGP_LAUNCH((cnx_dwconv_ln_kernel<CC, PP, T>), grid, dim3(256), 0, s, nof, 0, 0, 0, 0, nof, nof, nof, nof, eps, nob, nob, tab)
+    if (planes == 2) {
+        if (C == 96) { CNX_DWG(96, 3); } else if (C == 192) { CNX_DWG(192, 3); } else { CNX_DWG(384, 3); }
+    } else {
+        if (C == 96) { CNX_DWG(96, 4); } else if (C == 192) { CNX_DWG(192, 4); } else { CNX_DWG(384, 4); }
+    }
+#undef CNX_DWG
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+static int cnx_mlp_grouped(const agp_cnx_group* groups, int ngroups, int C, int planes, void* stream) {
+    if (!cnx_groups_ok(groups, ngroups) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    using T = CnxTable<CnxMlpGroup>;
+    T tab;
+    cnx_table_init(tab);
+    long long total = 0;
+    const bool two = planes == 2;
+    for (int i = 0; i < ngroups; ++i) {
+        const agp_cnx_group& q = groups[i];
+        if (!q.workspace || !q.w1_hi || !q.b1 || !q.w2_hi || !q.b2 || !q.layer_scale || !q.x || !q.out) return AGP_E_BADARG;
+        if (two && (!q.w1_lo || !q.w2_lo)) return AGP_E_BADARG;
+        if (!cnx_map_ok(q.n, q.h, q.w)) return AGP_E_BADARG;
+        const long long P = (long long)q.n * q.h * q.w, plane = cnx_pad(P) * C;
+        if (q.workspace_bytes < planes * plane * 2 || ((uintptr_t)q.workspace & 15)) return AGP_E_BADARG;
+        const bf16_t* const hi = (const bf16_t*)q.workspace;
+        const bf16_t* const lo = two ? hi + plane : nullptr;
+        if (!cnx_table_add(tab, i, total, (P + CNX_TP - 1) / CNX_TP,
+                           {hi, lo, P, (const bf16x8*)q.w1_hi, two ? (const bf16x8*)q.w1_lo : nullptr, (const bf16x8*)q.w2_hi,
+                            two ? (const bf16x8*)q.w2_lo : nullptr, q.b1, q.b2, q.layer_scale, (const float*)q.x, (float*)q.out}))
+            return AGP_E_BADARG;
+    }
+    const dim3 grid((unsigned)total);
+    hipStream_t s = (hipStream_t)stream;
+    const bf16_t* const nox = nullptr;
+    const bf16x8* const now = nullptr;
+    const float* const nof = nullptr;
+    float* const noo = nullptr;
+#define CNX_MLPG(CC, PP) \
+    AGP_LAUNCH((cnx_mlp_kernel<CC, false, PP, T>), grid, dim3(256), 0, s, nox, nox, 0ll, now, now, nof, now, now, nof, nof, nof, noo, nof, 0ll, tab)
+    if (two) {
+        if (C == 96) { CNX_MLPG(96, 3); } else if (C == 192) { CNX_MLPG(192, 3); } else { CNX_MLPG(384, 3); }
+    } else {
+        if (C == 96) { CNX_MLPG(96, 4); } else if (C == 192) { CNX_MLPG(192, 4); } else { CNX_MLPG(384, 4); }
+    }
+#undef CNX_MLPG
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+static int cnx_downsample_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, int planes, void* stream) {
+    if (!cnx_groups_ok(groups, ngroups) || !cnx_c_host_ok(C)) return AGP_E_BADARG;
+    using T = CnxTable<CnxDownGroup>;
+    T tab;
+    cnx_table_init(tab);
+    long long total = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const agp_cnx_group& q = groups[i];
+        if (!q.x || !q.ln_w || !q.ln_b || !q.w1_hi || !q.bias || !q.out || !cnx_map_ok(q.n, q.h, q.w)) return AGP_E_BADARG;
+        if (planes == 2 && !q.w1_lo) return AGP_E_BADARG;
+        const int ho = q.h / 2, wo = q.w / 2;
+        if (ho < 1 || wo < 1) return AGP_E_BADARG;
+        const long long P = (long long)q.n * ho * wo;
+        if (!cnx_table_add(tab, i, total, (P + CNX_TP - 1) / CNX_TP,
+                           {(const float*)q.x, q.h, q.w, ho, wo, P, q.ln_w, q.ln_b, q.bias, (const bf16x8*)q.w1_hi,
+                            planes == 2 ? (const bf16x8*)q.w1_lo : nullptr, (float*)q.out}))
+            return AGP_E_BADARG;
+    }
+    const dim3 grid((unsigned)total);
+    hipStream_t s = (hipStream_t)stream;
+    const float* const nof = nullptr;
+    const bf16x8* const now = nullptr;
+    float* const noo = nullptr;
+#define CNX_DOWNG(CC, PP) \
+    AGP_LAUNCH((cnx_downsample_kernel<CC, PP, T>), grid, dim3(256), 0, s, nof, 0, 0, 0, 0, 0ll, nof, nof, eps, now, now, nof, noo, tab)
+    if (planes == 2) {
+        if (C == 96) { CNX_DOWNG(96, 3); } else if (C == 192) { CNX_DOWNG(192, 3); } else { CNX_DOWNG(384, 3); }
+    } else {
+        if (C == 96) { CNX_DOWNG(96, 4); } else if (C == 192) { CNX_DOWNG(192, 4); } else { CNX_DOWNG(384, 4); }
+    }
+#undef CNX_DOWNG
+    AGP_CHECK_LAUNCH();
+    return AGP_OK;
+}
+
+int agp_cnx_dwconv_ln_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream) {
+    return cnx_dwconv_ln_grouped(groups, ngroups, C, eps, 2, stream);
+}
+int agp_cnx_dwconv_ln_f16_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream) {
+    return cnx_dwconv_ln_grouped(groups, ngroups, C, eps, 1, stream);
+}
+int agp_cnx_mlp_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, void* stream) {
+    return cnx_mlp_grouped(groups, ngroups, C, 2, stream);
+}
+int agp_cnx_mlp_f16_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, void* stream) {
+    return cnx_mlp_grouped(groups, ngroups, C, 1, stream);
+}
+int agp_cnx_downsample_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream) {
+    return cnx_downsample_grouped(groups, ngroups, C, eps, 2, stream);
+}
+int agp_cnx_downsample_f16_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream) {
+    return cnx_downsample_grouped(groups, ngroups, C, eps, 1, stream);
 }
 
 }  // extern "C"

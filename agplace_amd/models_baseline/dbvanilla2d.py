@@ -88,7 +88,8 @@ class DBVanilla2D(nn.Module):
 
     def forward_db(self, data_dict, trunk_maps=None, out_rows=None, defer_head=None):
         """trunk_maps: optional {map index: (stage maps, filled final PoolReq)} of the tiles computed by the caller
-        (agplace_amd.pair runs a trunk in lock-step with the query network's).
+        (agplace_amd.pair runs a trunk in lock-step with the query network's); with dbimage_fe='convnext_tiny' the entries are
+        (the trunk's three fp32 maps, None) and need Options.convnext_pair (_forward_db_convnext).
         out_rows: optional preallocated fp32 [b * ndb, 256] tensor the fused inference head writes the embedding rows to.
         defer_head: optional list; the fused inference head (one vector program) is then NOT launched but appended to it: the
         caller lets it ride in another program's launch (VecProgram.run(rider=...), agplace_amd.pair) -- the returned embedding
@@ -281,7 +282,10 @@ class DBVanilla2D(nn.Module):
         u8_on = all(e.fe._u8_enabled for e in self.dbimage_fes)       # Options.convnext_u8
         if not u8_on and ('db_frames' in data_dict or 'db_jitter' in data_dict):
             raise NotImplementedError(f"{what}: `db_frames` (decoded uint8 frames) is not built; pass fp32 `db_map`")
-        if trunk_maps is not None:
+        # Options.convnext_pair: trunk_maps = {map index: (the trunk's three fp32 maps of that map type's tiles, None)} computed by
+        # the caller (pair.embed_pair: ConvNeXt.forward_maps_multi, in lock-step with the query trunk); GeM, heads and the mean over
+        # map types are this forward, unchanged.  Without the switch the argument stays refused.
+        if trunk_maps is not None and not opt.convnext_pair:
             raise NotImplementedError(f"{what}: lock-step trunks (pair.embed_pair) are not built")
         if not u8_on and data_dict['db_map'].dtype == torch.uint8:
             raise NotImplementedError(f"{what}: uint8 `db_map` is not built; pass fp32 tiles")
@@ -298,14 +302,23 @@ class DBVanilla2D(nn.Module):
         tag = None
         if not any(e.fe.takes_training_path() for e in self.dbimage_fes):
             tag = range_guard.cnx_tag(opt, self.dbimage_fes[0].fe.precision)
+        if trunk_maps:
+            if self.training or any(e.fe.takes_training_path() for e in self.dbimage_fes):
+                raise ValueError(f"{what}: `trunk_maps` is an inference argument (.eval() under torch.no_grad())")
+            if tag is not None:
+                raise ValueError(f"{what}: `trunk_maps` while Options.convnext_range_guard binds this model's guard around its trunks: "
+                                 "maps computed outside the forward would skip the guard; call forward_db without them")
         with range_guard.guarded_cnx(self, tag):
             vecs = []
             for i in range(nmap):
                 j = 0 if opt.share_dbfe is True else i
-                x = self._db_tile_input(i, frames, jitter, crop, db_map, u8, dims)
-                if torch.is_tensor(x) and not u8:
-                    x = x.float()
-                last, _ = self.dbimage_fes[j](x)
+                if trunk_maps and i in trunk_maps:
+                    last = trunk_maps[i][0][-1]
+                else:
+                    x = self._db_tile_input(i, frames, jitter, crop, db_map, u8, dims)
+                    if torch.is_tensor(x) and not u8:
+                        x = x.float()
+                    last, _ = self.dbimage_fes[j](x)
                 v = gem_op(last, self.dbimage_pools[j].p, self.dbimage_pools[j].eps)
                 v = self.dbimage_mlps[j](v)
                 if opt.output_l2 is True:

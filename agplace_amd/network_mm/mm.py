@@ -240,7 +240,8 @@ class MM(nn.Module):
 
     def forward_q(self, data_dict, image_maps=None, out_rows=None, rider=None):
         """image_maps: optional (stage maps, level means, final PoolReq) of `query_image(data_dict)` computed by the
-        caller -- agplace_amd.pair runs this trunk in lock-step with the database network's (grouped conv launches).
+        caller -- agplace_amd.pair runs this trunk in lock-step with the database network's (grouped conv launches).  With
+        mm_imgfe='convnext_tiny' it is the trunk's list of three fp32 maps and needs Options.convnext_pair (_forward_q_convnext).
         out_rows: optional {output key: preallocated fp32 [b, 256] tensor}: the inference path writes those outputs there
         (a sub-batch's row slice of the whole batch's output: the sub-batches then need no concatenation).
         rider: optional list holding ONE deferred vector program of another network (DBVanilla2D.forward_db(defer_head=...)): the
@@ -295,17 +296,28 @@ class MM(nn.Module):
             raise NotImplementedError(f"{what}: `query_frames` (decoded uint8 frames) is not built; pass the fp32 `query_image`")
         if not u8_on and data_dict['query_image'].dtype == torch.uint8:
             raise NotImplementedError(f"{what}: uint8 `query_image` is not built; pass the normalised fp32 panorama")
-        if image_maps is not None or out_rows:
+        # Options.convnext_pair: `image_maps` = the trunk's three fp32 maps of query_image(data_dict), computed by the caller
+        # (pair.embed_pair: ConvNeXt.forward_maps_multi, in lock-step with the database trunks); everything behind the trunk is
+        # this forward, unchanged.  Row-sliced outputs stay refused, and so does the argument without the switch.
+        if out_rows or (image_maps is not None and not self.opt.convnext_pair):
             raise NotImplementedError(f"{what}: lock-step trunks and row-sliced outputs (pair.embed_pair, query sub-streams) are "
                                       "not built")
         train = enabled and (self.training or (torch.is_grad_enabled() and not getattr(self, "_frozen_backbone", False)
                                                and any(p.requires_grad for p in self.parameters())))
+        if train and image_maps is not None:
+            raise ValueError(f"{what}: `image_maps` is an inference argument (.eval() under torch.no_grad())")
         if not train:
             # Options.convnext_range_guard at trunk precision 4: with fp16_range_guard also binding (mfma_precision 2 / 4) the
             # whole-forward binding below covers the trunk too -- ONE word over the trunk, stage 2 and the voxel branch, published
             # under a tag that names both sources; alone, _forward_q binds around the trunk call only (stage 2 and the voxel branch
             # follow fp16_range_guard as before) and the word is published behind the forward, side streams joined
             tag = range_guard.cnx_tag(self.opt, self.image_fe.fe.precision, self.opt.mfma_precision)
+            if image_maps is not None:
+                if tag is not None:
+                    raise ValueError(f"{what}: `image_maps` while Options.convnext_range_guard binds this model's guard around its "
+                                     "trunk: maps computed outside the forward would skip the guard; call forward_q without them")
+                with range_guard.guarded(self, self.opt, self.opt.mfma_precision, False):
+                    return self._forward_q(data_dict, False, image_maps, None, None)
             if tag is not None:
                 if tag != "cnx4":
                     with range_guard.guarded_cnx(self, tag):
@@ -407,8 +419,11 @@ class MM(nn.Module):
                 fpool = None
                 if self._convnext:
                     # fp32 maps, no conv epilogue to pool in: one pass over each map, the last one for both of its poolings
-                    with range_guard.bound(self, cnx_guard):
-                        maps = self.image_fe.fe.forward_maps(image)
+                    if image_maps is not None:      # (Options.convnext_pair: the caller's lock-step trunk, the same bits)
+                        maps = list(image_maps)
+                    else:
+                        with range_guard.bound(self, cnx_guard):
+                            maps = self.image_fe.fe.forward_maps(image)
                     levels = [_Pooled(ops.pool_f32(m, None, want_mean=True, want_gem=False)[0]) for m in maps[:-1]]
                     mean3, imagefeatvec = ops.pool_f32(maps[-1], self.image_pool.p, want_mean=True, want_gem=True, eps=self.image_pool.eps)
                     levels.append(_Pooled(mean3))

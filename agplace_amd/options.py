@@ -165,6 +165,15 @@ class Options:
     # trunks and on every training forward (mode 3 whatever is set) it is accepted and binds nothing.  Not a reference option:
     # from_reference_opt leaves it False.
     convnext_range_guard: bool = False
+    # Opt-in lock-step ConvNeXt trunks in agplace_amd.pair.embed_pair / pair.CapturedPair: with the switch on in BOTH models' Options
+    # (mm_imgfe = dbimage_fe = "convnext_tiny", the same three block counts and convnext_precision, at most 4 trunks, no ConvNeXt
+    # range-guard tag binding on either model) the query trunk and the map-type trunks advance together and every step -- stem, a
+    # block's depthwise conv + LayerNorm, its MLP, a downsample -- is ONE grouped launch (ConvNeXt.forward_maps_multi ->
+    # agp_cnx_*_fwd_grouped); MM.forward_q(image_maps=...) and DBVanilla2D.forward_db(trunk_maps=...) then take the maps.  Outputs are
+    # bit for bit those of the two separate forwards, which embed_pair still returns for a pair that does not qualify (a guarded,
+    # mixed or unequal pair).  Query sub-streams stay refused for this trunk.  False (default): embed_pair and both arguments refuse
+    # a ConvNeXt model as before, text for text.  Not a reference option: from_reference_opt leaves it False.
+    convnext_pair: bool = False
     # Opt-in one-launch routes of FCODE(384) (the Neural-ODE blocks of MM on the ConvNeXt-tiny trunk): with a gradient wanted a
     # fixed-grid solve records its trajectory in the one-launch kernel and differentiates through agp_fcode_wide_bwd instead of
     # the any-width sequence of launches, and odeint_method = "dopri5" runs on the adaptive kernels at 384 columns instead of
@@ -249,6 +258,8 @@ class Options:
             raise ValueError(f"train_range_guard {self.train_range_guard!r}: True | False")
         if not isinstance(self.convnext_range_guard, bool):
             raise ValueError(f"convnext_range_guard {self.convnext_range_guard!r}: True | False")
+        if not isinstance(self.convnext_pair, bool):
+            raise ValueError(f"convnext_pair {self.convnext_pair!r}: True | False")
         v = self.voxel_capacity
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < (1 << 30)):
             raise ValueError(f"voxel_capacity {v!r}: None or an integer in 1 .. 2^30 - 1 (rows of every level from raw points)")
@@ -263,7 +274,7 @@ def from_reference_opt(ns) -> Options:
     """Adapt a reference argparse namespace (tools/options.py) to Options."""
     o = Options()
     for f in fields(Options):
-        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity", "train_range_guard", "convnext_range_guard"):      # (not reference options: stay at their defaults)
+        if hasattr(ns, f.name) and f.name not in ("convnext_u8", "convnext_precision", "fcode_wide", "odeint_adaptive_family", "voxel_capacity", "train_range_guard", "convnext_range_guard", "convnext_pair"):      # (not reference options: stay at their defaults)
             v = getattr(ns, f.name)
             if f.name in ("output_type", "final_type") and isinstance(v, str):
                 v = v.split("_")

@@ -8,11 +8,14 @@ expensive ones (a 3x3 conv over 64 aerial tiles fills a third of the chip for on
 `embed_pair` advances the two trunks in lock-step and issues every layer as ONE grouped launch
 (resnet.forward_maps_multi -> agp_conv2d_fwd_grouped); everything behind the trunks is the models' own forward.
 Outputs are bit-identical to calling the two models separately (tests/test_gpu_models.py).
+ConvNeXt models (mm_imgfe = dbimage_fe = 'convnext_tiny') pair behind Options.convnext_pair: their trunks are 15 small launches each
+for '2_2_2', and the lock-step form issues every stem / depthwise + LayerNorm / MLP / downsample step as one grouped launch
+(convnext.ConvNeXt.forward_maps_multi -> agp_cnx_*_fwd_grouped; tests/test_gpu_convnext_pair.py).
 """
 import torch
 
 
-from . import ops, range_guard, resnet
+from . import convnext, ops, range_guard, resnet
 
 RIDER = True      # False: the database head as a launch of its own behind the query network's tail
 
@@ -23,11 +26,37 @@ def can_pair(modelq, modeldb, qdata, dbdata):
     fq, fdbs = modelq.image_fe.fe, [m.fe for m in modeldb.dbimage_fes]
     db_map = dbdata['db_map']
     nmap = db_map.shape[-4]                     # [..., nmap, 3, h, w] and uint8 [..., nmap, h, w, 3] alike
+    cnx = [isinstance(f, convnext.ConvNeXt) for f in [fq] + fdbs[:max(nmap, 1)]]
+    if any(cnx):                                # ConvNeXt trunks pair among themselves only, and only with Options.convnext_pair
+        return all(cnx) and _can_pair_convnext(modelq, modeldb, fq, fdbs, qdata, db_map, nmap)
     if modelq.opt.mfma_precision != modeldb.opt.mfma_precision or db_map.dim() not in (5, 6):
         return False
     if modeldb.opt.share_dbfe is True and nmap > 1:
         return False
     return all((f.fe_type, f.nstages) == (fq.fe_type, fq.nstages) for f in fdbs[:nmap])
+
+
+def _can_pair_convnext(modelq, modeldb, fq, fdbs, qdata, db_map, nmap):
+    """The ConvNeXt rule of can_pair (every trunk is a ConvNeXt; eval under no_grad already holds): Options.convnext_pair on in BOTH
+    models, the same three block counts and precision in every trunk, at most convnext.MAX_GROUPS trunks, `db_map` 5-D or 6-D, the
+    share_dbfe / nmap rule of the ResNet pair, uint8 inputs only where Options.convnext_u8 enabled them, and NO ConvNeXt range-guard
+    tag binding on either model: the grouped launches have no guarded twins, so a guarded pair runs the separate forwards, in which
+    each model guards itself."""
+    if not (modelq.opt.convnext_pair and modeldb.opt.convnext_pair) or db_map.dim() not in (5, 6):
+        return False
+    if (modeldb.opt.share_dbfe is True and nmap > 1) or not 1 <= nmap <= len(fdbs) or 1 + nmap > convnext.MAX_GROUPS:
+        return False
+    trunks = [fq] + fdbs[:nmap]
+    if any((f.block_counts(), f.precision) != (fq.block_counts(), fq.precision) or f.takes_training_path() for f in trunks):
+        return False
+    if range_guard.cnx_tag(modelq.opt, fq.precision, modelq.opt.mfma_precision) is not None \
+            or range_guard.cnx_tag(modeldb.opt, fdbs[0].precision) is not None:
+        return False
+    img = qdata.get('query_image')
+    if (torch.is_tensor(img) and img.dtype == torch.uint8 and not fq._u8_enabled) \
+            or (db_map.dtype == torch.uint8 and not all(f._u8_enabled for f in fdbs[:nmap])):
+        return False                           # (the separate forwards refuse such an input by name)
+    return True
 
 
 def _resized_tiles(modelq, modeldb, qdata, dbdata):
@@ -71,13 +100,23 @@ def embed_pair(modelq, modeldb, qdata, dbdata):
     Decoded frames (`query_frames`, `db_frames`) are resized to uint8 tiles first (_resized_tiles) and continue as tiles.
     fp16 range guard (Options.fp16_range_guard): the lock-step trunks of BOTH models report through the query model's word when
     its guard is on (else the database model's): a saturated database tile then shows in modelq.fp16_range_ok() /
-    poll_fp16_range(), whose message names the database trunks as a possible source."""
-    if any(getattr(e, "fe_type", None) == "convnext_tiny" for e in getattr(modeldb, "dbimage_fes", ())):
+    poll_fp16_range(), whose message names the database trunks as a possible source.
+    ConvNeXt models (Options.convnext_pair on in the ConvNeXt models, else refused): lock-step through ConvNeXt.forward_maps_multi
+    when _can_pair_convnext holds -- one grouped launch per stem / depthwise + LayerNorm / MLP / downsample step over the query
+    trunk and the map-type trunks, bit-identical to the separate forwards -- and the two separate forwards otherwise (a ResNet on
+    the other side, unequal block counts or precisions, more than four trunks, or a ConvNeXt range-guard tag binding on either
+    model: each model then guards itself as always, a guard is never skipped).  Everything behind the trunks, each model's
+    fp16_range_guard binding included, is the model's own forward.  query_substreams > 1 is refused for a ConvNeXt query model."""
+    cnx_db = any(getattr(e, "fe_type", None) == "convnext_tiny" for e in getattr(modeldb, "dbimage_fes", ()))
+    cnx_q = getattr(modelq, "_convnext", False)
+    if cnx_db and not modeldb.opt.convnext_pair:
         raise NotImplementedError("pair.embed_pair with a ConvNeXt database model (dbimage_fe='convnext_tiny') is not built; call "
                                   "modelq(qdata, 'q') and modeldb(dbdata, 'db') separately")
-    if getattr(modelq, "_convnext", False):
+    if cnx_q and not modelq.opt.convnext_pair:
         raise NotImplementedError("pair.embed_pair with a ConvNeXt query model (mm_imgfe='convnext_tiny') is not built; call "
                                   "modelq(qdata, 'q') and modeldb(dbdata, 'db') separately")
+    if cnx_q or cnx_db:
+        return _embed_pair_convnext(modelq, modeldb, qdata, dbdata, cnx_q, cnx_db)
     qdata, dbdata = _resized_tiles(modelq, modeldb, qdata, dbdata)
     if not can_pair(modelq, modeldb, qdata, dbdata):
         return modelq(qdata, mode='q'), modeldb(dbdata, mode='db')
@@ -91,6 +130,43 @@ def embed_pair(modelq, modeldb, qdata, dbdata):
             with g.bind(range_guard.model_device(m)):
                 return _embed_pair_dispatch(modelq, modeldb, qdata, dbdata)
     return _embed_pair_dispatch(modelq, modeldb, qdata, dbdata)
+
+
+def _embed_pair_convnext(modelq, modeldb, qdata, dbdata, cnx_q, cnx_db):
+    """embed_pair with a ConvNeXt model on at least one side (Options.convnext_pair on in every ConvNeXt model)."""
+    if cnx_q and modelq.opt.query_substreams > 1:
+        raise NotImplementedError("pair.embed_pair with a ConvNeXt query model (mm_imgfe='convnext_tiny') and Options.query_substreams "
+                                  f"= {modelq.opt.query_substreams}: row-sliced outputs are not built for this trunk; set "
+                                  "query_substreams = 1")
+    separate = lambda: (modelq(qdata, mode='q'), modeldb(dbdata, mode='db'))
+    # decoded frames become uint8 tiles, which a ConvNeXt model takes only with Options.convnext_u8: without it the model's own
+    # forward refuses the frames by name
+    if cnx_q and not modelq.image_fe.fe._u8_enabled and ('query_frames' in qdata or 'query_jitter' in qdata):
+        return separate()
+    if cnx_db and not all(e.fe._u8_enabled for e in modeldb.dbimage_fes) and ('db_frames' in dbdata or 'db_jitter' in dbdata):
+        return separate()
+    qdata, dbdata = _resized_tiles(modelq, modeldb, qdata, dbdata)
+    if not (cnx_q and cnx_db) or not can_pair(modelq, modeldb, qdata, dbdata):
+        return modelq(qdata, mode='q'), modeldb(dbdata, mode='db')
+    image = modelq.query_image(qdata)
+    db_map = dbdata['db_map']
+    u8 = db_map.dtype == torch.uint8            # decoded tiles [b,(ndb,)nmap,h,w,3]: normalised by the stem as it reads
+    if db_map.dim() == 5:
+        db_map = db_map.unsqueeze(1)
+    nets, xs = [modelq.image_fe.fe], [image]
+    nmap = db_map.shape[2]
+    for i in range(nmap):
+        nets.append(modeldb.dbimage_fes[i].fe)
+        if u8:
+            bb, ndb, _, h, w, _ = db_map.shape
+            xs.append(db_map[:, :, i].reshape(bb * ndb, 1, h, w, 3))
+        else:
+            bb, ndb, _, c, h, w = db_map.shape
+            xs.append(db_map[:, :, i].reshape(bb * ndb, c, h, w).float())
+    maps = convnext.ConvNeXt.forward_maps_multi(nets, xs)
+    out_db = modeldb.forward_db(dbdata, trunk_maps={i: (maps[1 + i], None) for i in range(nmap)})
+    out_q = modelq.forward_q(qdata, image_maps=maps[0])
+    return out_q, out_db
 
 
 def _embed_pair_dispatch(modelq, modeldb, qdata, dbdata):

@@ -1278,6 +1278,46 @@ int agp_cnx_stem_u8_bwd(const uint8_t* tiles, int n, int ncam, int h, int w, con
                         const float* bias, const float* ln_w, float eps, const float* gout, float* g_w, float* g_bias, float* g_ln_w,
                         float* g_ln_b, void* bwd_workspace, int64_t bwd_workspace_bytes, void* stream);
 
+/* ---- ConvNeXt-tiny trunk, grouped inference launches (csrc/convnext.hip; agplace_amd/convnext.py forward_maps_multi;
+ * Options.convnext_pair).  One launch runs the kernel of a plain forward entry above over 1 .. AGP_CNX_MAX_GROUPS independent
+ * problems ("groups": the query trunk and the database trunks of a pair, advancing in lock-step).  The groups of a launch share C
+ * and the precision; sizes, weights, maps and workspaces are each group's own.  The grid is the groups' own grids one behind the
+ * other: a workgroup finds its group from the prefix sums of the per-group grid sizes and does exactly the work the plain entry
+ * gives that block index inside that group (the same 4x8 depthwise tile, the same 32-pixel tile of the stem / MLP / downsample; a
+ * group's partial last tile is its own), so every group's output is bit for bit what the plain entry writes.  The descriptors are
+ * read on the host during the call and travel to the kernel by value.  No allocation, no synchronisation; every group is validated
+ * as by its plain entry, AGP_E_BADARG otherwise (also for ngroups outside 1 .. AGP_CNX_MAX_GROUPS and a total grid of 2^31 blocks or
+ * more).  There are no range-guarded twins: a caller with an fp16 range guard bound uses the plain entries.
+ * Fields by entry (others ignored):
+ *   stem_fwd_grouped         x fp32 image with strides sn, sc, sh, sw; n, h, w its size; wt, bias, ln_w, ln_b; out
+ *   stem_u8_fwd_grouped      x uint8 tiles [n][ncam][h][w][3]; n, ncam, h, w; mean3, std3; wt, bias, ln_w, ln_b; out
+ *   dwconv_ln(_f16)          x the stream [n][h][w][C]; wt, bias, ln_w, ln_b; workspace, workspace_bytes (written)
+ *   mlp(_f16)                workspace, workspace_bytes (read); n, h, w (P = n h w); w1_hi, w1_lo, b1, w2_hi, w2_lo, b2, layer_scale;
+ *                            x = resid, out (may alias x); _f16: one plane per weight in w1_hi / w2_hi, the _lo fields ignored
+ *   downsample(_f16)         x the stream [n][h][w][C]; ln_w, ln_b; w1_hi, w1_lo = the weight planes (_f16: w1_hi alone); bias; out */
+#define AGP_CNX_MAX_GROUPS 4
+typedef struct agp_cnx_group {
+    const void* x;
+    void* out;
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t sn, sc, sh, sw;
+    int32_t n, h, w, ncam;
+    float mean3[3], std3[3];
+    const float *wt, *bias, *ln_w, *ln_b;
+    const void *w1_hi, *w1_lo, *w2_hi, *w2_lo;
+    const float *b1, *b2, *layer_scale;
+} agp_cnx_group;
+int agp_cnx_stem_fwd_grouped(const agp_cnx_group* groups, int ngroups, float eps, void* stream);
+int agp_cnx_stem_u8_fwd_grouped(const agp_cnx_group* groups, int ngroups, float eps, void* stream);
+int agp_cnx_dwconv_ln_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream);
+int agp_cnx_mlp_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, void* stream);
+int agp_cnx_downsample_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream);
+/* precision 4 (agp_cnx_*_f16_fwd): one fp16 operand plane at the start of each workspace, one fp16 plane per weight */
+int agp_cnx_dwconv_ln_f16_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream);
+int agp_cnx_mlp_f16_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, void* stream);
+int agp_cnx_downsample_f16_fwd_grouped(const agp_cnx_group* groups, int ngroups, int C, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@ the same batch for context; then one training forward + backward of '2_2_2' (the
 no stochastic depth) and each backward entry alone.
 
 python tools/convnext_bench.py [--batch 64] [--size 256] [--reps 10] [--windows 5] [--json out.json] [--train-only]
-                               [--precision {3,4}] [--infer-only] [--range-guard]
+                               [--precision {3,4}] [--infer-only] [--range-guard] [--pair]
+--pair measures nothing of the above: it times a ConvNeXt query / database pair (Options.convnext_pair) as two separate forwards,
+as pair.embed_pair with the trunks in lock-step, and as two pair.CapturedPair in flight, at 16 + 64 and at 2 + 8 (pair_leg).
 --precision 4 times the inference legs in the opt-in one-product fp16 mode (Options.convnext_precision = 4); the training leg runs
 in mode 3 whatever the precision and is skipped then.  --range-guard (with --precision 4 only) turns Options.convnext_range_guard on
 for the measured trunks -- each eager forward then binds the module's fp16 range guard and publishes behind it -- and binds a guard's
@@ -124,6 +126,89 @@ def train_leg(a, dev, x, report, rows):
         del cur, g, ws, bws
 
 
+def timed_alternating(fns, reps, windows):
+    """timed() for several legs in ONE run, their windows alternating (leg 0, leg 1, ..., leg 0, ...), so that a drift of the clock
+    or of the neighbours on the host reaches every leg alike.  Returns [(median, min, max) ms per call]."""
+    for fn in fns:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for _ in range(windows):
+        for k, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / reps)
+    return [(statistics.median(m), min(m), max(m)) for m in ms]
+
+
+def pair_leg(a, dev, rows):
+    """--pair: MM and DBVanilla2D on '2_2_2' ConvNeXt trunks with Options.convnext_pair, dense voxel stand-ins, at the serving shape
+    (16 panoramas 224 x 1344 + 64 tiles 256 x 256) and at batch 2 + 8, where the launches are smallest.  Per shape, windows
+    alternating in one run: (a) the two separate forwards back to back on one stream (the only route without the switch), (b)
+    pair.embed_pair eager (the trunks in lock-step, grouped launches), (c) two pair.CapturedPair on two streams replayed
+    alternately, both in flight (time per pair); and the trunks alone, per trunk and in lock-step."""
+    from agplace_amd import pair
+    from agplace_amd.models_baseline.dbvanilla2d import DBVanilla2D
+    from agplace_amd.network_mm.mm import MM
+    from oracle import nets
+    prec = a.precision
+    qopt = Options(mm_imgfe="convnext_tiny", mm_imgfe_layers="2_2_2", mm_imgfe_planes="96_192_384", mm_imgfe_dim=384,
+                   mm_stg2fuse_dim=384, mm_voxfe_planes="64_128_384", mm_voxfe_dim=384, convnext_pair=True, convnext_precision=prec)
+    dopt = Options(dbimage_fe="convnext_tiny", dbimage_fe_layers="2_2_2", features_dim=384, convnext_pair=True, convnext_precision=prec)
+    torch.manual_seed(0)
+    mq, mdb = MM(opt=qopt), DBVanilla2D("db", 384, opt=dopt)
+    randomize(mq.image_fe.fe, 0)
+    for i, e in enumerate(mdb.dbimage_fes):
+        randomize(e.fe, 1 + i)
+    mq, mdb = mq.to(dev).eval(), mdb.to(dev).eval()
+    for bq, bd in ((16, 64), (2, 8)):
+        def inputs(seed):
+            qd = {k: ([t.to(dev) for t in v] if isinstance(v, list) else v.to(dev))
+                  for k, v in nets.synth_query(bq, 224, 1344, qopt, seed=seed).items()}
+            return qd, {"db_map": torch.randn(bd, 1, 3, 256, 256, generator=torch.Generator().manual_seed(seed + 1)).to(dev)}
+        qd, dd = inputs(1)
+        assert pair.can_pair(mq, mdb, qd, dd)
+        want = mq(qd, mode="q"), mdb(dd, mode="db")
+        got = pair.embed_pair(mq, mdb, qd, dd)
+        torch.cuda.synchronize()
+        same = all(torch.equal(got[0][k], want[0][k]) for k in want[0]) and torch.equal(got[1]["embedding"], want[1]["embedding"])
+        if not same:
+            raise SystemExit("pair.embed_pair differs from the separate forwards")
+        cps = [pair.CapturedPair(mq, mdb, *inputs(10 + i), stream=torch.cuda.Stream(device=dev)) for i in range(2)]
+        turn = [0]
+
+        def captured():
+            cps[turn[0] & 1].replay()
+            turn[0] += 1
+
+        def captured_window():        # (the replays run on the captures' own streams: join them before the window's end event)
+            captured()
+            captured()
+            cur = torch.cuda.current_stream(dev)
+            for cp in cps:
+                cur.wait_stream(cp.stream)
+        fq, fdb, x, tiles = mq.image_fe.fe, mdb.dbimage_fes[0].fe, qd["query_image"], dd["db_map"][:, 0]
+        legs = [("(a) separate forwards, one stream", lambda: (mq(qd, mode="q"), mdb(dd, mode="db"))),
+                ("(b) embed_pair eager, lock-step", lambda: pair.embed_pair(mq, mdb, qd, dd)),
+                ("(c) two CapturedPair in flight, per pair", captured_window),
+                ("trunks alone, one after the other", lambda: (fq.forward_maps(x), fdb.forward_maps(tiles))),
+                ("trunks alone, lock-step", lambda: cnx.ConvNeXt.forward_maps_multi([fq, fdb], [x, tiles]))]
+        res = timed_alternating([fn for _, fn in legs], max(2, a.reps // 2), a.windows)
+        for cp in cps:
+            cp.finish()
+        for (name, _), (med, lo, hi) in zip(legs, res):
+            div = 2.0 if name.startswith("(c)") else 1.0
+            med, lo, hi = med / div, lo / div, hi / div
+            rows.append({"name": f"pair {bq}+{bd} prec {prec}: {name}", "ms": med, "ms_min": lo, "ms_max": hi})
+            print(f"pair {bq:2d} x [3,224,1344] + {bd:2d} x [3,256,256], prec {prec}: {name:42s} {med:9.3f} ms (min {lo:.3f} max {hi:.3f})")
+        del cps
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -135,7 +220,19 @@ def main():
     ap.add_argument("--infer-only", action="store_true", help="skip the training leg")
     ap.add_argument("--precision", type=int, choices=(3, 4), default=3, help="ConvNeXt inference precision (Options.convnext_precision)")
     ap.add_argument("--range-guard", action="store_true", help="Options.convnext_range_guard on the measured model (--precision 4 only)")
+    ap.add_argument("--pair", action="store_true", help="only the lock-step pair measurement (Options.convnext_pair): see pair_leg")
     a = ap.parse_args()
+    if a.pair:
+        if a.range_guard:
+            ap.error("--pair with --range-guard: a guarded pair is not run in lock-step")
+        torch.set_grad_enabled(False)
+        rows = []
+        pair_leg(a, torch.device("cuda:0"), rows)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, "w") as f:
+                json.dump({"pair": True, "reps": max(2, a.reps // 2), "windows": a.windows, "precision": a.precision, "rows": rows}, f, indent=1)
+        return
     prec = a.precision
     if a.range_guard and prec != 4:
         ap.error("--range-guard needs --precision 4 (the guard covers the fp16 operands of that mode only)")
